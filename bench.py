@@ -19,11 +19,19 @@ ids that are the same for every question, 18 question ids that differ.  Weights:
 N(0, 0.02^2) from the repo PRNG (no checkpoint offline), generated on rank 0 and broadcast once (RCCL over xGMI) to the
 other ranks -- the path's only collective.  Control flow is scripted (random weights emit neither EOS nor a bbox).
 
-At N = 1 the same line carries, as named sub-objects with their own rooflines: `configs1` (BASELINE configs[1]: one
-chain, batch 1, the single-chain GEMV decode path), `batch64` (BASELINE configs[2]: 64 chain slots) and `cpu_baseline`
-(the reference's own transformers CPU path on this box's host cores).  `--batch 1` makes configs[1] the line's value,
-`--batch B` configs[2] with B chains.  `--gpus N` without a torchrun environment spawns the N ranks itself (before
-anything touches the GPU).
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the outputs (`--dump-outputs DIR`)
+and the line.  `--full` adds the annexes, each measured after the timed region: the roofline objects of the line, the
+`reuse_sensitivity` streams and, at N = 1, the named sub-objects `configs1` (BASELINE configs[1]: one chain, batch 1, the
+single-chain GEMV decode path), `batch64` (BASELINE configs[2]: 64 chain slots) and `cpu_baseline` (the reference's own
+transformers CPU path on this box's host cores).  `--batch 1` makes configs[1] the line's value, `--batch B` configs[2] with
+B chains.  `--gpus N` without a torchrun environment spawns the N ranks itself (before anything touches the GPU).
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path handed its caller in its LAST step, for rank 0's
+questions of that step (all of them at N = 1), in question order: `question.npy` (float64 [n], the question numbers the
+inputs are generated from), `stage1_tokens.npy` / `stage2_tokens.npy` (float32 [n, longest], the generated token ids of
+the two stages, padded with -1) and `lengths.npy` (float32 [n, 4]: stage-1 prompt, stage-1 output, stage-2 prompt and
+stage-2 output lengths).  The inputs (weights, tiles, question table, prompts) are seeded: the same arguments give the same
+inputs on every run.
 """
 from __future__ import annotations
 
@@ -273,11 +281,12 @@ class TileFeeder:
 REUSE_GENERATED = True   # ChainScheduler.reuse_generated of the streams below (the `reuse_sensitivity` annex runs one stream with it off)
 
 
-def run_stream(engine, table, q0: int, slots: int, stats=None, use_graph=None):
+def run_stream(engine, table, q0: int, slots: int, stats=None, use_graph=None, outputs=None):
     """The questions `table` = [(question number offset, tile DeviceImage, view key)] through the continuous-batching
     scheduler and the host code of src/eval/infer.py (hostloop: views, crops, prompts); the "parsed" box is scripted,
     lengths are ragged and EOS is ignored (random weights emit neither).  Every question of a (tile, view key) looks at
-    the same <=512-px view, encoded once."""
+    the same <=512-px view, encoded once.  `outputs` (a dict) receives question number -> (stage-1 tokens, stage-2 tokens,
+    the four lengths of `done`)."""
     from zoomearth_amd import hostloop as H
     from zoomearth_amd.scheduler import ChainScheduler, Request
 
@@ -311,6 +320,8 @@ def run_stream(engine, table, q0: int, slots: int, stats=None, use_graph=None):
 
             def stage2(req2, toks2, out2, q=q, n_p1=req.n_prompt, n_o1=len(toks)):
                 done[q] = (n_p1, n_o1, req2.n_prompt, len(toks2))
+                if outputs is not None:
+                    outputs[q] = (list(toks), list(toks2), done[q])
             return Request(prompt=H.stage2_prompt(text, out1), images=[view, crop], max_new_tokens=n2, on_done=stage2)
 
         sched.submit(Request(prompt=text, images=[views[vkey][0]], max_new_tokens=n1, on_done=stage1))
@@ -322,7 +333,7 @@ def run_stream(engine, table, q0: int, slots: int, stats=None, use_graph=None):
     return done
 
 
-def run_stream_lanes(engines, table, q0: int, slots: int, stats=None, use_graph=None, host_pool=None):
+def run_stream_lanes(engines, table, q0: int, slots: int, stats=None, use_graph=None, host_pool=None, outputs=None):
     """The same stream on several LANES of one GPU: every lane is an engine of its own (weights, KV cache, workspaces) with
     its own scheduler, host thread and HIP stream; tiles are dealt to the lanes whole (a tile's questions share its view and
     its prompt prefix).  While one lane is in a prefill / ViT round (matrix-bound) the other one decodes (bandwidth- and
@@ -357,7 +368,7 @@ def run_stream_lanes(engines, table, q0: int, slots: int, stats=None, use_graph=
         return [(b, feeders[ln].tile(tile), vkey) for b, tile, vkey in parts[ln]]
 
     if len(engines) == 1:
-        done = run_stream(engines[0], lane_table(0), q0, slots, stats, use_graph)
+        done = run_stream(engines[0], lane_table(0), q0, slots, stats, use_graph, outputs)
         if stats is not None and feeders[0] is not None:
             torch.cuda.synchronize()
             stats["tile_upload_ms_total"], stats["tiles_uploaded"] = feeders[0].upload_ms()
@@ -372,7 +383,7 @@ def run_stream_lanes(engines, table, q0: int, slots: int, stats=None, use_graph=
                 prof = cProfile.Profile()
                 prof.enable()
             with torch.cuda.stream(torch.cuda.Stream(device=e.device)):
-                outs[ln] = run_stream(e, lane_table(ln), q0, slots, sts[ln], use_graph)
+                outs[ln] = run_stream(e, lane_table(ln), q0, slots, sts[ln], use_graph, outputs)
                 torch.cuda.current_stream().synchronize()
             if prof is not None:
                 import io
@@ -408,13 +419,13 @@ def run_stream_lanes(engines, table, q0: int, slots: int, stats=None, use_graph=
     return done
 
 
-def batch_step(engine, tiles, q0: int, B: int, stats=None, use_graph=None, slots=None):
+def batch_step(engine, tiles, q0: int, B: int, stats=None, use_graph=None, slots=None, outputs=None):
     """B questions about len(tiles) tiles (6 : 64 as LRS-GRO's 908 : 9734), passes of 64 questions over the tiles."""
     table = []
     for b in range(B):
         t = b * len(tiles) // min(B, 64) if B <= 64 else (b // 64) * len(tiles) + (b % 64) * len(tiles) // 64
         table.append((b, tiles[t % len(tiles)], t))
-    return run_stream(engine, table, q0, slots or B, stats, use_graph)
+    return run_stream(engine, table, q0, slots or B, stats, use_graph, outputs)
 
 
 # ----------------------------------------------------------------------------- CPU baseline (rank 0, N = 1 only)
@@ -665,7 +676,25 @@ def spawn_ranks(n: int) -> int:
     return rc
 
 
+def dump_outputs(out_dir: str, questions, stage1, stage2, lengths) -> None:
+    """What the timed path handed its caller in its last step, as .npy files (see the module docstring)."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def padded(rows):
+        a = np.full((len(rows), max([len(r) for r in rows] + [1])), -1.0, dtype=np.float32)
+        for i, r in enumerate(rows):
+            a[i, :len(r)] = r
+        return a
+
+    arrays = {"question": np.asarray(questions, dtype=np.float64), "stage1_tokens": padded(stage1), "stage2_tokens": padded(stage2),
+              "lengths": np.asarray(lengths, dtype=np.float32).reshape(len(questions), 4)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
+    t_start = time.perf_counter()
     if "--hf-baseline-child" in sys.argv:
         print(json.dumps(cpu_baseline_hf(full_depth=sys.argv[-1] != "sample")), flush=True)
         return 0
@@ -697,9 +726,14 @@ def main():
                     help="engines per GPU of the stream workload, each with its own scheduler thread and HIP stream (prefill of one "
                          "overlaps decode of the other; `src/eval/infer.py --lanes`); --slots chain slots EACH.  Measured on the "
                          "1280-question stream: 1 x 512 slots 57.7, 1 x 1024 60.3, 2 x 256 62.9, 2 x 512 66.2, 2 x 768 67.6, 3 x 512 65.4 questions/s")
-    ap.add_argument("--no-batch64", action="store_true", help="skip the batch64 object of the default N = 1 line")
-    ap.add_argument("--no-configs1", action="store_true", help="skip the configs1 object of the default N = 1 line")
-    ap.add_argument("--no-reuse-sensitivity", action="store_true", help="skip the two short streams behind `value_without_generated_row_reuse`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the annexes after the timed region: rooflines, reuse_sensitivity and, at N = 1, configs1, "
+                         "batch64 and cpu_baseline (a plain run measures the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (token ids and lengths, float32)")
+    ap.add_argument("--no-batch64", action="store_true", help="skip the batch64 object of the --full N = 1 line")
+    ap.add_argument("--no-configs1", action="store_true", help="skip the configs1 object of the --full N = 1 line")
+    ap.add_argument("--no-reuse-sensitivity", action="store_true", help="skip the two short streams behind `value_without_generated_row_reuse` (--full)")
     ap.add_argument("--spawn-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     args.fp8 = args.fp8 or args.fp8_act
@@ -748,11 +782,13 @@ def main():
 
     B = max(1, args.batch)
     SLOTS = max(1, args.slots)
-    want1 = stream and world == 1 and args.model == "3b" and not args.fp8 and not args.no_configs1
-    want64 = stream and world == 1 and args.model == "3b" and not args.fp8 and not args.no_batch64
+    # (the engine is sized for the batch64 annex whether or not --full runs it: a plain run times the same engine)
+    sized64 = stream and world == 1 and args.model == "3b" and not args.fp8 and not args.no_batch64
+    want1 = args.full and stream and world == 1 and args.model == "3b" and not args.fp8 and not args.no_configs1
+    want64 = args.full and sized64
     cfg = ModelConfig.zoomearth_3b() if args.model == "3b" else ModelConfig.qwen25vl_7b()
     chains = SLOTS if stream else B
-    e = Engine(cfg, device=local, max_seqs=chains, max_ctx=2048, max_patches=max(4096, 1400 * min(max(chains, 64 if want64 else 1), 40)),
+    e = Engine(cfg, device=local, max_seqs=chains, max_ctx=2048, max_patches=max(4096, 1400 * min(max(chains, 64 if sized64 else 1), 40)),
                max_prefill_rows=(int(os.environ.get("ZE_PREFILL_ROWS", str(32 * 832 if chains > 64 else 16 * 832))) if chains > 1 else 0),
                max_tile_side=max(args.tile, 1024))
     filled_here = rank == 0 or os.environ.get("ZE_BENCH_EVERY_RANK_FILLS") == "1"
@@ -790,7 +826,7 @@ def main():
     # ---- the workload's tiles: a small pool of distinct synthetic host tiles (generating one takes ~1 s of host time),
     # every logical tile of the rank uploaded from the pool to its own HBM buffer (pinned host memory -> HBM through the C
     # ABI, timed on its own, never inside `value`: tiles are resident when the timed region starts)
-    n_pool = 6 if (stream or B > 1 or want64) else 1
+    n_pool = 6 if (stream or B > 1 or sized64) else 1
     host_pool = [torch.from_numpy(synthetic_tile(1000 + rank * 16 + t, args.tile, args.tile)).pin_memory() for t in range(n_pool)]
 
     upload_stats = {"n": 0, "s": 0.0}
@@ -806,6 +842,8 @@ def main():
 
     line = {}
     bstats = {}
+    outs = {} if args.dump_outputs else None   # question number -> (stage-1 tokens, stage-2 tokens, lengths) of the timed path
+    dump = None                                # (question numbers, stage-1 tokens, stage-2 tokens, lengths) of the last step
     use_graph = not args.no_graph
     sched_graph = False if args.no_graph else None  # (None: the scheduler's own choice -- graphs up to 64 chain slots only)
     if stream:
@@ -825,20 +863,26 @@ def main():
         else:
             table = [(i, tile_of[i], tile_of[i]) for i in mine]
         warm_table = [(i, ("w", t), ("w", t)) for i, t in enumerate(warm_tile_of)]
+        t_warm = time.perf_counter()
         if warm_table:
             run_stream_lanes(engines, warm_table, 9_000_000 + rank * 100_000, SLOTS, use_graph=sched_graph, host_pool=host_pool)
         for en in engines:
             en.phase_timers(enable=True, reset=True)
         barrier()
         t0 = time.perf_counter()
-        run_stream_lanes(engines, table, 1_000_000, SLOTS, bstats, use_graph=sched_graph, host_pool=None if resident else host_pool)
+        run_stream_lanes(engines, table, 1_000_000, SLOTS, bstats, use_graph=sched_graph, host_pool=None if resident else host_pool,
+                         outputs=outs)
         torch.cuda.synchronize()
         my_dt = time.perf_counter() - t0
         barrier()
         dt = time.perf_counter() - t0
-        if not resident:  # (the annexes below look at one resident tile)
+        if outs is not None:   # the last step: the questions of the table's last Q_STEP x world rows that this rank answered
+            qs = [1_000_000 + i for i in sorted(mine) if i >= (args.steps - 1) * Q_STEP * world]
+            dump = (qs, [outs[q][0] for q in qs], [outs[q][1] for q in qs], [outs[q][2] for q in qs])
+        if not resident:
             upload_stats["n"], upload_stats["s"] = int(bstats.pop("tiles_uploaded", 0)), bstats.pop("tile_upload_ms_total", 0.0) / 1000.0
-            dev = {t: DeviceImage(e.tile_upload(host_pool[t % n_pool]), e) for t in my_tiles[:6]}
+            if args.full:  # (the annexes below look at one resident tile)
+                dev = {t: DeviceImage(e.tile_upload(host_pool[t % n_pool]), e) for t in my_tiles[:6]}
         n_questions = n_total
         lens_all = bstats.pop("lens")
         # how much of `value` rests on the synthetic tokenizer's identity round trip.  The stream keeps the K/V
@@ -848,7 +892,7 @@ def main():
         # prompt prefilled from the end of the cached stage-1 PROMPT: bit-identical to a full prefill): their ratio scales `value` to
         # the figure without any generated-row reuse -- the lower bound for any tokenizer.
         reuse_sens = None
-        if world == 1 and not args.no_reuse_sensitivity and args.warmup > 0:
+        if args.full and world == 1 and not args.no_reuse_sensitivity and args.warmup > 0:
             global REUSE_GENERATED
             n_short = max(4, args.warmup) * Q_STEP
             short_of = question_table(n_short, seed=3)
@@ -878,13 +922,14 @@ def main():
         chain = Chain(e, dev_tiles[0], use_graph=use_graph)
         q0 = rank * 100000
 
-        def run_step(q):
+        def run_step(q, outputs=None):
             if B == 1:
                 return chain.question(q)
-            d = batch_step(e, tiles64, q * B, B, bstats, use_graph=sched_graph)
+            d = batch_step(e, tiles64, q * B, B, bstats, use_graph=sched_graph, outputs=outputs)
             l = d[q * B]
             return [0] * l[1], [0] * l[3], l[0], l[2]
 
+        t_warm = time.perf_counter()
         for i in range(args.warmup):
             run_step(q0 + i)
         e.phase_timers(enable=True, reset=True)
@@ -892,7 +937,7 @@ def main():
         t0 = time.perf_counter()
         lens = None
         for i in range(args.steps):
-            out1, out2, l1, l2 = run_step(q0 + args.warmup + i)
+            out1, out2, l1, l2 = run_step(q0 + args.warmup + i, outs if i == args.steps - 1 else None)
             lens = (l1, l2, len(out1), len(out2))
         torch.cuda.synchronize()
         my_dt = time.perf_counter() - t0
@@ -900,6 +945,14 @@ def main():
         dt = time.perf_counter() - t0
         n_questions = world * args.steps * B
         mine = list(range(args.steps * B))
+        if outs is not None and args.steps > 0:
+            ql = q0 + args.warmup + args.steps - 1
+            if B == 1:   # (the loop's last question: out1 / out2 are its token lists)
+                dump = ([ql], [list(out1)], [list(out2)], [(l1, len(out1), l2, len(out2))])
+            else:
+                qs = sorted(outs)
+                dump = (qs, [outs[q][0] for q in qs], [outs[q][1] for q in qs], [outs[q][2] for q in qs])
+    timing = (t_warm - t_start, t0 - t_warm, dt, t0 + dt)   # (set-up, warm-up, timed region, its end) for the note on stderr
     phases = e.phase_timers(enable=False)
     for en in engines[1:]:
         for k, v in en.phase_timers(enable=False).items():
@@ -1281,9 +1334,9 @@ def main():
             if reuse_sens is not None:
                 line["reuse_sensitivity"] = reuse_sens
                 line["value_without_generated_row_reuse"] = round(line["value"] * reuse_sens["ratio"], 3)
-            if len(engines) > 1:
+            if len(engines) > 1 and args.full:
                 e.lib.ze_tune(4, 2)   # the annexes below run ONE engine's kernels alone: the persistent form (restored to 0 = by live-engine count below)
-            if args.model == "3b" and not args.fp8:
+            if args.full and args.model == "3b" and not args.fp8:
                 live = int(min(SLOTS, max(1, round(line["mean_chains_per_step"]))))
                 mean_ctx = live_like_contexts(live)
                 line["roofline"] = batch_roofline(live, shared=(10, 347))
@@ -1309,7 +1362,7 @@ def main():
                         rows: round(sum(ent[tk["form_in_stream"]]["layer_us"].values()) / int(rows), 4) for rows, ent in tk.get("by_rows", {}).items()}
                 except Exception:
                     pass
-        if args.model == "3b" and not args.fp8 and not stream:
+        if args.full and args.model == "3b" and not args.fp8 and not stream:
             if B == 1:
                 pm = line["phase_ms_per_question"]
                 line.update(decode_rooflines(pm, lens, chain.kept_generated, line["ms_per_step"]))
@@ -1317,7 +1370,7 @@ def main():
             else:
                 line["roofline"] = batch_roofline(B)
                 line["scheduler"] = {k: v for k, v in bstats.items() if k != "lens"}
-        elif B == 1 and not stream:
+        elif args.full and B == 1 and not stream:
             # configs[4] shapes (7B backbone and / or FP8 decoder weights): the same object for this configuration's own
             # dominant kernel -- the decode gate/up weight stream at this shape and weight width -- measured the same way
             us, by = e.profile_decode_kernel(2, iters=144)
@@ -1369,9 +1422,13 @@ def main():
             }
         if want1:
             line["configs1"] = configs1_object(4, 1)
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             line["cpu_baseline"] = measure_cpu_baseline(args.cpu_baseline)
         e.lib.ze_tune(4, 0)   # (back to the library's own rule: by live-engine count)
+        if dump is not None:
+            dump_outputs(args.dump_outputs, *dump)
+        print(f"[bench] set-up {timing[0]:.1f} s, warm-up {timing[1]:.1f} s, timed {timing[2]:.1f} s, after {time.perf_counter() - timing[3]:.1f} s",
+              file=sys.stderr, flush=True)
         print(json.dumps(line), flush=True)
     for en in engines:
         en.close()

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -39,8 +40,8 @@ def check_roofline(r, lo=0.05):
 def test_bench_line_contract():
     """The default workload: BASELINE configs[3], the question stream (here 12 timed steps of 64 questions: enough live chains for
     the decode attention to be the step's dominant kernel, so that the line takes the branch the driver's line takes -- the
-    shared-prefix measurement), with the configs[1] / configs[2] / cpu_baseline sub-objects of an N = 1 run."""
-    d = run_bench("--gpus", "1", "--steps", "12", "--warmup", "1")
+    shared-prefix measurement), with the configs[1] / configs[2] / cpu_baseline sub-objects of an N = 1 `--full` run."""
+    d = run_bench("--gpus", "1", "--steps", "12", "--warmup", "1", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "per_rank"):
         assert k in d, k
@@ -128,11 +129,35 @@ def test_bench_line_contract():
 
 def test_bench_batch1_is_configs1():
     """`--batch 1`: BASELINE configs[1] as the line's own value (one question per step), no sub-objects."""
-    d = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1", "--no-cpu-baseline")
+    d = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1", "--no-cpu-baseline", "--full")
     assert "configs[1]" in d["config"]["workload"] and d["config"]["questions_per_step_per_gpu"] == 1
     assert abs(d["value"] - 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"] and 0.5 < d["value"] < 10.0
     check_roofline(d["roofline"], lo=0.3)
     assert "batch64" not in d and "configs1" not in d and "cpu_baseline" not in d
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the stream and prints the headline line without the annexes; --dump-outputs writes the token ids
+    and lengths of the last timed step's questions, and a second run with the same arguments gets the same inputs (same questions,
+    same prompt lengths)."""
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        d = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "bf16" and d["higher_is_better"] is True
+        assert abs(d["value"] - 64 * 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+        for key in ("roofline", "roofline_phases", "reuse_sensitivity", "configs1", "batch64", "cpu_baseline"):
+            assert key not in d, key
+        arrays = {n: np.load(out / f"{n}.npy") for n in ("question", "stage1_tokens", "stage2_tokens", "lengths")}
+        q, t1, t2, ln = arrays["question"], arrays["stage1_tokens"], arrays["stage2_tokens"], arrays["lengths"]
+        assert q.dtype == np.float64 and t1.dtype == t2.dtype == ln.dtype == np.float32
+        assert q.tolist() == [1_000_000 + i for i in range(64, 128)] and ln.shape == (64, 4) and len(t1) == len(t2) == 64
+        assert (ln[:, 0] == 802).all() and ((t1 >= 0).sum(axis=1) == ln[:, 1]).all() and ((t2 >= 0).sum(axis=1) == ln[:, 3]).all()
+        assert 0.75 * 192 - 1 <= ln[:, 1].min() and ln[:, 1].max() <= 1.25 * 192 + 1
+        runs.append(arrays)
+    assert np.array_equal(runs[0]["question"], runs[1]["question"]) and np.array_equal(runs[0]["lengths"][:, 1], runs[1]["lengths"][:, 1])
 
 
 def test_bench_runs_the_collective_path_on_one_rank():

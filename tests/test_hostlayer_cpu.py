@@ -421,6 +421,20 @@ def test_bench_gpus_flag_spawns_the_ranks():
     assert r.returncode == 0 and r.stdout.strip() == ""  # a torchrun rank 1: no spawn, no line
 
 
+def test_bench_dump_outputs_writes_padded_float_arrays(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last step's questions, their token ids padded with -1 and their lengths, as float
+    arrays that two builds can be compared with."""
+    import numpy as np
+
+    import bench
+    bench.dump_outputs(str(tmp_path / "o"), [7, 9], [[5, 150000, 3], [4]], [[8], [151935, 2]], [(802, 3, 1320, 1), (802, 1, 1319, 2)])
+    got = {n: np.load(tmp_path / "o" / f"{n}.npy") for n in ("question", "stage1_tokens", "stage2_tokens", "lengths")}
+    assert got["question"].dtype == np.float64 and got["question"].tolist() == [7.0, 9.0]
+    assert got["stage1_tokens"].dtype == np.float32 and got["stage1_tokens"].tolist() == [[5, 150000, 3], [4, -1, -1]]
+    assert got["stage2_tokens"].tolist() == [[8, -1], [151935, 2]]          # vocabulary ids are exact in float32
+    assert got["lengths"].dtype == np.float32 and got["lengths"].tolist() == [[802, 3, 1320, 1], [802, 1, 1319, 2]]
+
+
 def test_decode_rgb_reads_uncompressed_tiff_strips_directly(tmp_path):
     """zoomearth_amd/image.py decode_rgb: an uncompressed 8-bit RGB TIFF is read strip by strip straight into the array (no
     interpreter lock held: the decode threads of the tile prefetcher must not starve the threads that drive the GPU); every

@@ -10,7 +10,7 @@ cp zoomearth_amd/libzoomearth_hip.so /tmp/swz_new.so
 for rep in 1 2; do
   for v in old new; do
     if [ $v = old ]; then cp zoomearth_amd/libzoomearth_hip_oldswz.so zoomearth_amd/libzoomearth_hip.so; else cp /tmp/swz_new.so zoomearth_amd/libzoomearth_hip.so; fi
-    python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-batch64 --no-configs1 2>/dev/null | python -c "
+    python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-batch64 --no-configs1 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
