@@ -299,6 +299,31 @@ int ze_op_sample_greedy(ze_engine* e, int seq, const float* logits, float repeti
 int ze_op_sample_temperature(ze_engine* e, int seq, const float* logits, float repetition_penalty, float temperature,
                              uint64_t seed, int index, int32_t* out_token, void* stream);
 
+/* Sampling filters of one chain (replaces: TopKLogitsWarper / TopPLogitsWarper / MinPLogitsWarper, HF:generation/
+ * logits_process.py, in HF's order temperature -> top-k -> top-p -> min-p, as model.generate(do_sample=True) applies a
+ * checkpoint's generation_config and as the GRPO rollout configures them, src/train/RL/src/open-r1-multimodal/src/open_r1/
+ * trainer/grpo_config.py:62-70).  With z_i = score_i / T and e_i = expf(z_i - z_max):
+ *   top-k: keep z_i >= the k-th largest z (ties at that value all kept);
+ *   top-p (over the survivors of top-k): keep i iff the mass of the survivors with z_j > z_i is < top_p x their total mass
+ *          (equal scores together; the arg-max always);
+ *   min-p: keep e_i >= min_p.
+ * The three collapse into one fp32 cut per chain and step, found on the device inside the (captured) step by a selection
+ * kernel (ze_sample_filter.hip: the mass is integer fixed point, so the cut is a function of the chain's row alone); the draw
+ * treats z_i < cut as e_i = 0 and is otherwise the draw of ze_op_sample_temperature.  top_k = 0, top_p = 1, min_p = 0 mean off;
+ * ZE_ERR_INVALID for top_k < 0, top_p outside (0, 1], min_p outside [0, 1].  The values travel as kernel arguments on `stream`
+ * into a per-slot device table: chains with different filters share one burst and one captured graph.  Honoured by
+ * ze_op_sample_temperature, ze_generate, ze_generate_batch, ze_chain_begin and ze_decode_burst* when p->do_sample is set
+ * (greedy ignores it); cleared wherever the chain's repetition-penalty set is (ze_seq_reset, ze_seq_truncate,
+ * ze_seq_copy_prefix into the slot).  While no chain of the engine has a filter, every sampling step launches exactly what
+ * it launches without this entry. */
+int ze_seq_set_sampling_filter(ze_engine* e, int seq, int top_k, float top_p, float min_p, void* stream);
+/* The selection alone on caller-supplied rows: logits f32 [rows, ld] device (ld >= vocab), host arrays of length `rows` for
+ * temperature / top_k / top_p / min_p, out_cut f32 [rows] device, out_kept int32 [rows] device (may be NULL): row r keeps the
+ * out_kept[r] tokens with logits[r, i] / temperature[r] >= out_cut[r].  No repetition penalty.  Waits for `stream`. */
+int ze_op_sample_filter(ze_engine* e, const float* logits, int rows, int vocab, int ld, const float* temperature,
+                        const int32_t* top_k, const float* top_p, const float* min_p, float* out_cut, int32_t* out_kept,
+                        void* stream);
+
 /* FP8 decode weights (BASELINE.json configs[4], "fp8 weights"): quantises the decoder's linear layers (and an untied
  * lm_head) to OCP E4M3 with one power-of-two scale per output row, REPLACES the bf16 copies by the dequantised
  * values (exactly representable) so that prefill and decode compute with identical weights, and switches the batch-1

@@ -118,6 +118,15 @@ struct ze_engine {
     int* pfx_dev = nullptr;
     std::vector<hipEvent_t> pfx_copy_ev;
     bool prefix_hints = true;      // the hint fits its 16 + 16 bits (ze_tune knob 17 = 1: every chain reads its own rows)
+    // Sampling filters (ze_seq_set_sampling_filter): filt_host is the truth, filt_dev the per-slot table the selection kernel reads
+    // ((top_k bits, top_p, min_p, 0) per slot; all zero = off), written in stream order by the setter; n_filters = slots with a
+    // filter.  While it is 0 no sampling launch knows about filters at all.  cut_dev: [max_seqs] cuts of a batched step (one per
+    // row of the launch), then [max_seqs] for the single-chain launches (one per slot).
+    struct filter_host { int top_k = 0; float top_p = 1.f, min_p = 0.f; bool on() const { return top_k > 0 || top_p < 1.f || min_p > 0.f; } };
+    std::vector<filter_host> filt_host;
+    int n_filters = 0;
+    float *filt_dev = nullptr, *cut_dev = nullptr;
+    std::vector<int> graph_filters;  // whether the chain's graph was captured with the selection kernel in it
     std::vector<hipGraphExec_t> graphs;
     std::vector<float> graph_penalty;
     std::vector<int> graph_ignore_eos;
@@ -189,7 +198,7 @@ struct ze_engine {
     int* bseq = nullptr;
     float *blogits = nullptr, *bpartial = nullptr, *bsample = nullptr;
     ze_seq_dev* bstate_host = nullptr;  // pinned
-    std::map<std::tuple<int, float, int, float, unsigned long long, int>, hipGraphExec_t> bgraphs;  // captured batched decode step per batch size (and attention grid)
+    std::map<std::tuple<int, float, int, float, unsigned long long, int, int>, hipGraphExec_t> bgraphs;  // captured batched decode step per batch size (and attention grid)
     int live_parts = 0;  // 192-key parts the longest chain of the current batch needs (the attention grid's extent); 0 = all
 
     // timers

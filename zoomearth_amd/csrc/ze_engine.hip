@@ -227,7 +227,7 @@ static int init_tables(ze_engine* e) {
     return 0;
 }
 
-extern "C" int ze_version(void) { return 100; }
+extern "C" int ze_version(void) { return 101; }
 
 extern "C" const char* ze_last_error(const ze_engine* e) { return e ? e->err.c_str() : ze_global_error.c_str(); }
 
@@ -301,6 +301,10 @@ extern "C" int ze_engine_create(const ze_config* cfg, int device_id, ze_engine**
     e->graph_variant.assign(c.max_seqs, 0);
     e->graph_temperature.assign(c.max_seqs, 0.f);
     e->graph_seed.assign(c.max_seqs, 0ull);
+    e->graph_filters.assign(c.max_seqs, 0);
+    e->filt_host.assign(c.max_seqs, ze_engine::filter_host{});
+    chk(dev_alloc(e, &e->filt_dev, (size_t)c.max_seqs * 4));
+    chk(dev_alloc(e, &e->cut_dev, (size_t)c.max_seqs * 2));
 
     // front-end workspace: horizontal-pass image (box_h x out_w) and resized image
     const size_t side = (size_t)std::max(c.max_tile_side, 1024);
@@ -460,7 +464,7 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
                    e->vo, e->va, e->vz, e->vz2, e->vcos, e->vsin, e->vperm, e->vinv, e->vtiles_win, e->vtiles_full,
                    e->th, e->ty, e->tqkv, e->to, e->ta, e->tsrc, e->tpos, e->ttiles, e->ttile_aux, e->trow_aux, e->dh, e->dq, e->dattn, e->dact,
                    e->dlogits, e->dpartial, e->dsample, e->atickets, e->gslab, e->gtickets, e->pslab, e->ptickets, e->bh, e->by, e->bqkv, e->bo, e->ba, e->bseq, e->bmate, e->blogits, e->bpartial, e->bsample, e->arena8, e->arena_f, e->arena_f8,
-                   e->ty8, e->ty8_scale, e->damax, e->ty8p, e->ty8p_scale};
+                   e->ty8, e->ty8_scale, e->damax, e->ty8p, e->ty8p_scale, e->filt_dev, e->cut_dev};
     for (void* p : dev)
         if (p) hipFree(p);
     if (e->pfx_dev) hipFree(e->pfx_dev);

@@ -395,6 +395,32 @@ static int push_state(ze_engine* e, int seq, hipStream_t s, int token, int n_gen
     return ZE_OK;
 }
 
+// ---- sampling filters (top-k / top-p / min-p per chain; ze_engine::filt_host is the truth, ze_sample_filter.hip the kernel)
+static void write_filter(ze_engine* e, int seq, int top_k, float top_p, float min_p, hipStream_t s) {
+    ze_engine::filter_host& f = e->filt_host[seq];
+    const bool was = f.on();
+    f.top_k = top_k, f.top_p = top_p, f.min_p = min_p;
+    e->n_filters += (int)f.on() - (int)was;
+    // the table keeps all zeros for "off" (a zero top_p is no legal value)
+    if (was || f.on()) ze_launch_set_filter(e->filt_dev, seq, top_k, f.on() ? top_p : 0.f, min_p, 0.f, s);
+}
+// the slot goes to another chain (wherever its seen-set is cleared): it never inherits a filter.  Nothing is launched for a
+// slot that has none.
+static void clear_filter(ze_engine* e, int seq, hipStream_t s) {
+    if (e->filt_host[seq].on()) write_filter(e, seq, 0, 1.f, 0.f, s);
+}
+
+extern "C" int ze_seq_set_sampling_filter(ze_engine* e, int seq, int top_k, float top_p, float min_p, void* stream) {
+    ZE_TRY(check_seq(e, seq));
+    if (top_k < 0) return ze_fail(e, ZE_ERR_INVALID, "top_k must be >= 0 (0 = off)");
+    if (!(top_p > 0.f && top_p <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "top_p must be in (0, 1] (1 = off)");
+    if (!(min_p >= 0.f && min_p <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "min_p must be in [0, 1] (0 = off)");
+    hipSetDevice(e->device);
+    write_filter(e, seq, top_k, top_p, min_p, (hipStream_t)stream);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
 extern "C" int ze_seq_reset(ze_engine* e, int seq, void* stream) {
     ZE_TRY(check_seq(e, seq));
     hipSetDevice(e->device);
@@ -405,6 +431,7 @@ extern "C" int ze_seq_reset(ze_engine* e, int seq, void* stream) {
     prefix_source_gone(e, seq, 0);
     e->pfx_host[seq] = 0;
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)seq * e->cfg.vocab, 0, e->cfg.vocab, s));
+    clear_filter(e, seq, s);
     return push_state(e, seq, s, 0, 0, 0);
 }
 
@@ -464,6 +491,7 @@ extern "C" int ze_seq_truncate(ze_engine* e, int seq, int keep_len, void* stream
     if ((e->pfx_host[seq] & 0xffff) > keep_len) e->pfx_host[seq] = 0;
     // the seen-set belongs to the dropped continuation: the caller re-marks the (new) prompt
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)seq * e->cfg.vocab, 0, e->cfg.vocab, (hipStream_t)stream));
+    clear_filter(e, seq, (hipStream_t)stream);
     return push_state(e, seq, (hipStream_t)stream, 0, 0, 0);
 }
 
@@ -496,6 +524,7 @@ extern "C" int ze_seq_copy_prefix(ze_engine* e, int dst_seq, int src_seq, int n_
         e->pfx_host[dst_seq] = (e->prefix_hints && n_tokens < 65536 && src != dst_seq) ? ((src << 16) | n_tokens) : 0;
     }
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)dst_seq * c.vocab, 0, c.vocab, s));
+    clear_filter(e, dst_seq, s);
     return push_state(e, dst_seq, s, 0, 0, 0);
 }
 
@@ -1034,6 +1063,46 @@ extern "C" int ze_decode_step(ze_engine* e, int seq, int token, float* out_logit
     return ZE_OK;
 }
 
+// A sampled launch learns about filters only while some chain of the engine has one: with none set it is today's launch
+// sequence.  `batch`: the cuts of a batched step (one per row) -- otherwise the slot's own word.
+static void attach_filters(ze_engine* e, ze_sample_opts& so, bool batch) {
+    if (so.temperature > 0.f && e->n_filters > 0) {
+        so.filt = e->filt_dev;
+        so.cuts = batch ? e->cut_dev : e->cut_dev + e->cfg.max_seqs + so.slot;
+    }
+}
+
+// The selection alone, on caller-supplied rows (unit op: any vocab / ld, a filter and a temperature per row, no repetition penalty)
+extern "C" int ze_op_sample_filter(ze_engine* e, const float* logits, int rows, int vocab, int ld, const float* temperature,
+                                   const int32_t* top_k, const float* top_p, const float* min_p, float* out_cut,
+                                   int32_t* out_kept, void* stream) {
+    if (!e || !logits || !temperature || !top_k || !top_p || !min_p || !out_cut) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    if (rows <= 0 || vocab <= 0 || ld < vocab) return ze_fail(e, ZE_ERR_INVALID, "rows and vocab must be positive, ld >= vocab");
+    std::vector<float> table((size_t)rows * 4);
+    for (int r = 0; r < rows; ++r) {
+        if (!(temperature[r] > 0.f)) return ze_fail(e, ZE_ERR_INVALID, "temperature must be positive");
+        if (top_k[r] < 0) return ze_fail(e, ZE_ERR_INVALID, "top_k must be >= 0 (0 = off)");
+        if (!(top_p[r] > 0.f && top_p[r] <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "top_p must be in (0, 1] (1 = off)");
+        if (!(min_p[r] >= 0.f && min_p[r] <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "min_p must be in [0, 1] (0 = off)");
+        memcpy(&table[4 * r], &top_k[r], sizeof(int));
+        table[4 * r + 1] = top_p[r];
+        table[4 * r + 2] = min_p[r];
+        table[4 * r + 3] = temperature[r];
+    }
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    float* dev = nullptr;
+    ZE_HIP(hipMalloc((void**)&dev, table.size() * sizeof(float)));
+    int r = ZE_OK;
+    if (hipMemcpyAsync(dev, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)
+        r = ze_fail(e, ZE_ERR_HIP, "hipMemcpyAsync failed");
+    if (r == ZE_OK) ze_launch_sample_filter(logits, vocab, ld, nullptr, nullptr, 0, rows, 1.0f, 1.0f, dev, out_cut, out_kept, s);
+    if (r == ZE_OK && hipGetLastError() != hipSuccess) r = ze_fail(e, ZE_ERR_HIP, "selection kernel launch failed");
+    if (hipStreamSynchronize(s) != hipSuccess && r == ZE_OK) r = ze_fail(e, ZE_ERR_HIP, "hipStreamSynchronize failed");
+    hipFree(dev);
+    return r;
+}
+
 // one sampling step on caller-supplied logits; `index` plays the role of the generated-token index of the draw
 static int op_sample(ze_engine* e, int seq, const float* logits, float repetition_penalty, const ze_sample_opts& so,
                      int index, int32_t* out_token, hipStream_t s) {
@@ -1065,16 +1134,18 @@ extern "C" int ze_op_sample_temperature(ze_engine* e, int seq, const float* logi
     so.temperature = temperature;
     so.seed = seed;
     so.slot = seq;
+    if (check_seq(e, seq) == 0) attach_filters(e, so, false);
     return op_sample(e, seq, logits, repetition_penalty, so, index, out_token, (hipStream_t)stream);
 }
 
-static ze_sample_opts sample_opts_of(const ze_gen_params* p, int slot) {
+static ze_sample_opts sample_opts_of(ze_engine* e, const ze_gen_params* p, int slot, bool batch = false) {
     ze_sample_opts so;
     if (p->do_sample && p->temperature > 0.f) {
         so.temperature = p->temperature;
         so.seed = p->seed;
     }
     so.slot = slot;
+    attach_filters(e, so, batch);
     return so;
 }
 
@@ -1100,7 +1171,7 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
 
     const int t_s = ze_timer_begin(e, 4, s);
     // first token from the prefill logits (no cache growth)
-    const ze_sample_opts so = sample_opts_of(p, seq);
+    const ze_sample_opts so = sample_opts_of(e, p, seq);
     ze_launch_sample(e->dlogits + (size_t)seq * c.vocab, c.vocab, e->seen + (size_t)seq * c.vocab, pen, st, e->eos_dev,
                      c.n_eos, c.pad_token_id, ign, 0, dev_out, e->dsample, so, s);
     ze_timer_end(e, t_s, s);
@@ -1111,7 +1182,7 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
     if (p->use_graph && max_new > 1) {
         if (!e->graphs[seq] || e->graph_penalty[seq] != pen || e->graph_ignore_eos[seq] != ign ||
             e->graph_variant[seq] != (int)ze_tune_epoch || e->graph_temperature[seq] != so.temperature ||
-            e->graph_seed[seq] != so.seed) {
+            e->graph_seed[seq] != so.seed || e->graph_filters[seq] != (int)(so.filt != nullptr)) {
             if (e->graphs[seq]) {
                 hipGraphExecDestroy(e->graphs[seq]);
                 e->graphs[seq] = nullptr;
@@ -1135,6 +1206,7 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
             e->graph_variant[seq] = (int)ze_tune_epoch;
             e->graph_temperature[seq] = so.temperature;
             e->graph_seed[seq] = so.seed;
+            e->graph_filters[seq] = so.filt != nullptr;
         }
         gexec = e->graphs[seq];
     }
@@ -1501,7 +1573,7 @@ extern "C" int ze_decode_batch(ze_engine* e, const int32_t* seqs, int n, const i
 // The captured batched decode step for `na` chains (chain ids / positions live in device memory, so one graph per
 // batch size and sampling setting serves every composition); nullptr in *out = run eagerly.
 static int batch_step_graph(ze_engine* e, int na, float pen, int ign, const ze_sample_opts& bso, hipGraphExec_t* out) {
-    auto key = std::make_tuple(na, pen, ign, bso.temperature, bso.seed, e->live_parts * 64 + e->live_parts_long);
+    auto key = std::make_tuple(na, pen, ign, bso.temperature, bso.seed, e->live_parts * 64 + e->live_parts_long, (int)(bso.filt != nullptr));
     if (e->bgraph_epoch != ze_tune_epoch) {
         for (auto& kv : e->bgraphs) hipGraphExecDestroy(kv.second);
         e->bgraphs.clear();
@@ -1551,7 +1623,7 @@ static int run_burst(ze_engine* e, const std::vector<int>& active, int steps, co
 // first token of a chain from the logits its prefill left behind; `sample_stream` = the chain's random stream
 static int begin_chain(ze_engine* e, int q, const ze_gen_params* p, float pen, int ign, int sample_stream, hipStream_t s) {
     const ze_config& c = e->cfg;
-    ze_sample_opts so = sample_opts_of(p, q);
+    ze_sample_opts so = sample_opts_of(e, p, q);
     if (so.temperature > 0.f) ze_launch_set_ints(&(e->st_dev + q)->stream, &sample_stream, 1, s);
     ze_launch_sample(e->dlogits + (size_t)q * c.vocab, c.vocab, e->seen + (size_t)q * c.vocab, pen, e->st_dev + q, e->eos_dev,
                      c.n_eos, c.pad_token_id, ign, 0, e->out_tokens + (size_t)q * c.max_ctx, e->dsample, so, s);
@@ -1581,7 +1653,7 @@ extern "C" int ze_generate_batch(ze_engine* e, const int32_t* seqs, int n, const
     }
     const float pen = p->repetition_penalty > 0.f ? p->repetition_penalty : 1.0f;
     const int ign = p->ignore_eos ? 1 : 0;
-    const ze_sample_opts bso = sample_opts_of(p, 0);
+    const ze_sample_opts bso = sample_opts_of(e, p, 0, true);
     // sampling stream of a chain = its row in this call (reproducible per request)
     for (int i = 0; i < n; ++i) ZE_TRY(begin_chain(e, seqs[i], p, pen, ign, i, s));
     std::vector<int> active;
@@ -1667,7 +1739,7 @@ extern "C" int ze_decode_burst_begin(ze_engine* e, const int32_t* seqs, int n, i
     const float pen = p->repetition_penalty > 0.f ? p->repetition_penalty : 1.0f;
     const int ign = p->ignore_eos ? 1 : 0;
     const int td = ze_timer_begin(e, 3, s);
-    if (steps > 0) ZE_TRY(run_burst(e, active, steps, p, pen, ign, sample_opts_of(p, 0), s));
+    if (steps > 0) ZE_TRY(run_burst(e, active, steps, p, pen, ign, sample_opts_of(e, p, 0, true), s));
     ze_timer_end(e, td, s);
     return steps;
 }

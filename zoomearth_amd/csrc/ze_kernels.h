@@ -292,8 +292,18 @@ void ze_launch_kv_copy_prefix(bf16_t* kcache, bf16_t* vcache, size_t layer_strid
 struct ze_sample_opts {
     float temperature = 0.f;      // 0: greedy arg-max; > 0: multinomial draw from softmax(score / temperature)
     unsigned long long seed = 0;  // draw = f(seed, ze_seq_dev::stream of the chain, index of the generated token)
-    int slot = 0;                 // unused (kept for layout)
+    int slot = 0;                 // single-chain launches: the chain's slot (row of the filter table)
+    // sampling filters: the per-slot table (top_k bits, top_p, min_p, 0) and where the step's cuts go (one per chain of the
+    // launch); both null unless some chain of the engine has a filter -- then the draw launches exactly what it always did
+    const float* filt = nullptr;
+    float* cuts = nullptr;
 };
+// The cut of each of n rows (ze_sample_filter.hip): row b reads filt[seq_ids ? seq_ids[b] : slot0 + b]; seen_base is per slot
+// when seq_ids is given, the chain's own set (or null) otherwise; out_kept may be null.
+void ze_launch_sample_filter(const float* logits, int vocab, int ld, const uint8_t* seen_base, const int* seq_ids, int slot0,
+                             int n, float penalty, float temperature, const float* filt, float* out_cut, int* out_kept,
+                             hipStream_t s);
+void ze_launch_set_filter(float* filt, int slot, int top_k, float top_p, float min_p, float temperature, hipStream_t s);
 // ws: 2 * 128 arg-max partials + 64 spare + 128 chunk sums (floats)
 void ze_launch_sample(const float* logits, int vocab, uint8_t* seen, float penalty, ze_seq_dev* st,
                       const int* eos_ids, int n_eos, int pad_id, int ignore_eos, int advance_ctx,

@@ -120,7 +120,8 @@ __device__ __forceinline__ void accept_token(int bi, uint8_t* __restrict__ seen,
 
 void ze_launch_multinomial(const float* logits, int vocab, const uint8_t* seen_base, const ze_seq_dev* st,
                            const int* seq_ids, int slot0, int n, float penalty, float temperature,
-                           unsigned long long seed, float* ws_part, float* ws_sum, hipStream_t s);
+                           unsigned long long seed, float* ws_part, float* ws_sum, const float* filt, float* cuts,
+                           hipStream_t s);
 
 void ze_launch_sample(const float* logits, int vocab, uint8_t* seen, float penalty, ze_seq_dev* st,
                       const int* eos_ids, int n_eos, int pad_id, int ignore_eos, int advance_ctx,
@@ -128,7 +129,7 @@ void ze_launch_sample(const float* logits, int vocab, uint8_t* seen, float penal
     k_argmax_partial<<<SAMPLE_BLOCKS, 256, 0, s>>>(logits, vocab, seen, penalty, ws);
     if (so.temperature > 0.f)
         ze_launch_multinomial(logits, vocab, seen, st, nullptr, so.slot, 1, penalty, so.temperature, so.seed, ws,
-                              ws + 2 * SAMPLE_BLOCKS + 64, s);
+                              ws + 2 * SAMPLE_BLOCKS + 64, so.filt, so.cuts, s);
     k_argmax_final<<<1, 64, 0, s>>>(ws, seen, st, eos_ids, n_eos, pad_id, ignore_eos, advance_ctx, out_tokens, vocab);
 }
 
@@ -268,7 +269,7 @@ void ze_launch_sample_batch(const float* logits, int vocab, uint8_t* seen_base, 
         k_argmax_partial_batch<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, seen_base, seq_ids, penalty, ws);
         if (so.temperature > 0.f)
             ze_launch_multinomial(logits, vocab, seen_base, st, seq_ids, 0, n, penalty, so.temperature, so.seed, ws,
-                                  ws_sum, s);
+                                  ws_sum, so.filt, so.cuts, s);
     }
     k_argmax_final_batch<<<n, 64, 0, s>>>(ws, seen_base, st, seq_ids, vocab, eos_ids, n_eos, pad_id, ignore_eos,
                                           advance_ctx, sample, out_tokens_base, max_gen);
@@ -285,12 +286,21 @@ void ze_launch_sample_batch(const float* logits, int vocab, uint8_t* seen_base, 
 //     token = first i (ascending) whose running sum of e exceeds u * sum(e)
 // Summation order (fp32), which the oracle (oracle/qwen25vl.py:sample_temperature) restates: the vocabulary is cut
 // into SAMPLE_BLOCKS contiguous chunks, a chunk into 256 contiguous runs; run sums, then the 256 run sums in order,
-// then the chunk sums in order.  Two extra launches per token after the arg-max partials; the pick is handed to
+// then the chunk sums in order.  A token under the chain's filter cut (top-k / top-p / min-p: ze_sample_filter.hip writes one
+// fp32 cut per chain, launched only when some chain of the engine has a filter) counts as e = 0, in the same order.
+// Two extra launches per token after the arg-max partials; the pick is handed to
 // the arg-max final kernels as an unbeatable partial (+inf, token), so EOS / pad / state bookkeeping is shared.
 __device__ __forceinline__ float sample_score(const float* lg, const uint8_t* seen, float penalty, int i) {
     float v = lg[i];
     if (penalty != 1.0f && seen[i]) v = v < 0.f ? v * penalty : v / penalty;
     return v;
+}
+
+// e of one token; a token under the chain's filter cut (ze_sample_filter.hip) has none.  cut = -inf: today's value, bit for bit
+__device__ __forceinline__ float sample_e(const float* lg, const uint8_t* seen, float penalty, float temperature, float zmax,
+                                          float cut, int i) {
+    const float z = sample_score(lg, seen, penalty, i) / temperature;
+    return z < cut ? 0.f : expf(z - zmax);
 }
 
 __device__ __forceinline__ float sample_zmax(const float* part, float temperature) {
@@ -304,12 +314,13 @@ __device__ __forceinline__ float sample_zmax(const float* part, float temperatur
 // sum of e over this thread's contiguous run, then the 256 run sums in thread order (by thread 0) -> *total;
 // sRun[t] keeps the run sums for the caller
 __device__ __forceinline__ void sample_chunk_sums(const float* lg, const uint8_t* seen, float penalty, float temperature,
-                                                  float zmax, int start, int end, int run, float* sRun, float* total) {
+                                                  float zmax, float cut, int start, int end, int run, float* sRun,
+                                                  float* total) {
     const int t = threadIdx.x;
     float acc = 0.f;
     for (int j = 0; j < run; ++j) {
         const int i = start + t * run + j;
-        if (i < end) acc += expf(sample_score(lg, seen, penalty, i) / temperature - zmax);
+        if (i < end) acc += sample_e(lg, seen, penalty, temperature, zmax, cut, i);
     }
     sRun[t] = acc;
     __syncthreads();
@@ -325,7 +336,7 @@ __global__ void __launch_bounds__(256) k_softmax_partial(const float* __restrict
                                                          const uint8_t* __restrict__ seen_base,
                                                          const int* __restrict__ seq_ids, float penalty,
                                                          float temperature, const float* __restrict__ ws_part,
-                                                         float* __restrict__ ws_sum) {
+                                                         float* __restrict__ ws_sum, const float* __restrict__ cuts) {
     const int b = blockIdx.y;
     const float* lg = logits + (size_t)b * vocab;
     const uint8_t* seen = seen_base + (seq_ids ? (size_t)seq_ids[b] * vocab : 0);
@@ -334,7 +345,7 @@ __global__ void __launch_bounds__(256) k_softmax_partial(const float* __restrict
     const int start = blockIdx.x * chunk, end = min(vocab, start + chunk);
     __shared__ float sRun[256];
     __shared__ float sTot;
-    sample_chunk_sums(lg, seen, penalty, temperature, zmax, start, end, run, sRun, &sTot);
+    sample_chunk_sums(lg, seen, penalty, temperature, zmax, cuts ? cuts[b] : -INFINITY, start, end, run, sRun, &sTot);
     if (threadIdx.x == 0) ws_sum[(size_t)b * SAMPLE_BLOCKS + blockIdx.x] = sTot;
 }
 
@@ -344,13 +355,15 @@ __global__ void __launch_bounds__(256) k_multinomial_pick(const float* __restric
                                                           const int* __restrict__ seq_ids, int slot0, float penalty,
                                                           float temperature, unsigned long long seed,
                                                           float* __restrict__ ws_part,
-                                                          const float* __restrict__ ws_sum) {
+                                                          const float* __restrict__ ws_sum,
+                                                          const float* __restrict__ cuts) {
     const int b = blockIdx.x, slot = seq_ids ? seq_ids[b] : slot0;
     const ze_seq_dev* st = seq_ids ? st_base + slot : st_base;
     const float* lg = logits + (size_t)b * vocab;
     const uint8_t* seen = seen_base + (seq_ids ? (size_t)slot * vocab : 0);
     float* part = ws_part + (size_t)b * 2 * SAMPLE_BLOCKS;
     const float zmax = sample_zmax(part, temperature);
+    const float cut = cuts ? cuts[b] : -INFINITY;
     const int chunk = (vocab + SAMPLE_BLOCKS - 1) / SAMPLE_BLOCKS, run = (chunk + 255) / 256;
     __shared__ float sRun[256];
     __shared__ float sTot;
@@ -386,7 +399,7 @@ __global__ void __launch_bounds__(256) k_multinomial_pick(const float* __restric
     const int blk = sBlk;
     const float target = sTarget;
     const int start = blk * chunk, end = min(vocab, start + chunk);
-    sample_chunk_sums(lg, seen, penalty, temperature, zmax, start, end, run, sRun, &sTot);
+    sample_chunk_sums(lg, seen, penalty, temperature, zmax, cut, start, end, run, sRun, &sTot);
     if (threadIdx.x == 0) {
         int tok = -1, last_nz = start;
         float cum = 0.f;
@@ -395,7 +408,7 @@ __global__ void __launch_bounds__(256) k_multinomial_pick(const float* __restric
                 for (int j = 0; j < run; ++j) {
                     const int i = start + t * run + j;
                     if (i >= end) break;
-                    const float e = expf(sample_score(lg, seen, penalty, i) / temperature - zmax);
+                    const float e = sample_e(lg, seen, penalty, temperature, zmax, cut, i);
                     cum += e;
                     if (cum > target) {
                         tok = i;
@@ -410,7 +423,7 @@ __global__ void __launch_bounds__(256) k_multinomial_pick(const float* __restric
         }
         if (tok < 0) {  // rounding at the very end (or target = -inf): last element of the chunk that carries mass
             tok = last_nz;
-            while (tok > start && !(expf(sample_score(lg, seen, penalty, tok) / temperature - zmax) > 0.f)) --tok;
+            while (tok > start && !(sample_e(lg, seen, penalty, temperature, zmax, cut, tok) > 0.f)) --tok;
         }
         part[0] = INFINITY;  // unbeatable arg-max partial: the final kernel adopts the pick
         reinterpret_cast<int*>(part)[1] = tok;
@@ -419,12 +432,17 @@ __global__ void __launch_bounds__(256) k_multinomial_pick(const float* __restric
 
 void ze_launch_multinomial(const float* logits, int vocab, const uint8_t* seen_base, const ze_seq_dev* st,
                            const int* seq_ids, int slot0, int n, float penalty, float temperature,
-                           unsigned long long seed, float* ws_part, float* ws_sum, hipStream_t s) {
+                           unsigned long long seed, float* ws_part, float* ws_sum, const float* filt, float* cuts,
+                           hipStream_t s) {
     if (n <= 0) return;
+    // filt = null (no chain of the engine has a filter): the two launches of the plain draw, nothing else
+    if (!filt) cuts = nullptr;
+    if (cuts)
+        ze_launch_sample_filter(logits, vocab, vocab, seen_base, seq_ids, slot0, n, penalty, temperature, filt, cuts, nullptr, s);
     k_softmax_partial<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, seen_base, seq_ids, penalty, temperature,
-                                                             ws_part, ws_sum);
+                                                             ws_part, ws_sum, cuts);
     k_multinomial_pick<<<n, 256, 0, s>>>(logits, vocab, seen_base, st, seq_ids, slot0, penalty, temperature, seed,
-                                         ws_part, ws_sum);
+                                         ws_part, ws_sum, cuts);
 }
 
 // ----------------------------------------------------------------------------------------------------------------

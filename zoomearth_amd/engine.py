@@ -247,6 +247,38 @@ class Engine:
             self._check(h)
         return (h >> 16, h & 0xffff) if h else (seq, 0)
 
+    def set_sampling_filter(self, seq: int, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+        """Top-k / top-p / min-p of chain `seq` (HF's warpers in HF's order, applied on the device inside the sampled step;
+        0 / 1.0 / 0.0 = off; None counts as off).  Sampled draws of the chain honour it until the slot is reset, truncated or
+        copied into; greedy decoding ignores it.  Chains with different filters share bursts and graphs."""
+        self._check(self.lib.ze_seq_set_sampling_filter(self.h, int(seq), int(top_k or 0), float(1.0 if top_p is None else top_p),
+                                                        float(min_p or 0.0), self._stream()))
+
+    def _apply_filter(self, seqs, top_k, top_p, min_p):
+        if top_k is None and top_p is None and min_p is None:
+            return  # (whatever set_sampling_filter left on the chains stays)
+        for q in seqs:
+            self.set_sampling_filter(int(q), top_k, top_p, min_p)
+
+    def sample_filter(self, logits: torch.Tensor, temperature, top_k, top_p, min_p):
+        """The selection kernel alone (ze_op_sample_filter): logits f32 [rows, vocab] (row stride >= vocab), one temperature /
+        top_k / top_p / min_p per row (scalars broadcast).  Returns (cut f32 [rows], kept int32 [rows]): row r keeps the
+        kept[r] tokens with logits[r] / temperature[r] >= cut[r]."""
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+        rows = int(logits.shape[0])
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, dtype=np.float32), (rows,)))
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(top_k, dtype=np.int32), (rows,)))
+        p = np.ascontiguousarray(np.broadcast_to(np.asarray(top_p, dtype=np.float32), (rows,)))
+        m = np.ascontiguousarray(np.broadcast_to(np.asarray(min_p, dtype=np.float32), (rows,)))
+        cut = torch.empty(rows, dtype=torch.float32, device=self.device)
+        kept = torch.empty(rows, dtype=torch.int32, device=self.device)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        ld = int(logits.stride(0)) if rows > 1 else int(logits.shape[1])   # (the stride of a one-row tensor means nothing)
+        self._check(self.lib.ze_op_sample_filter(self.h, _ptr(logits), rows, int(logits.shape[1]), ld,
+                                                 t.ctypes.data_as(fp), k.ctypes.data_as(ip), p.ctypes.data_as(fp),
+                                                 m.ctypes.data_as(fp), _ptr(cut), _ptr(kept), self._stream()))
+        return cut, kept
+
     def seq_truncate(self, seq: int, keep: int):
         self._check(self.lib.ze_seq_truncate(self.h, seq, keep, self._stream()))
 
@@ -343,9 +375,10 @@ class Engine:
 
     def generate(self, seq: int, max_new_tokens: int, repetition_penalty: float = 1.0, ignore_eos: bool = False,
                  use_graph: bool = True, sync_every: int = 16, do_sample: bool = False, temperature: float = 1.0,
-                 seed: int = 0):
+                 seed: int = 0, top_k=None, top_p=None, min_p=None):
         p = self._gen_params(max_new_tokens, repetition_penalty, ignore_eos, use_graph, sync_every, do_sample,
                              temperature, seed)
+        self._apply_filter([seq], top_k, top_p, min_p)
         out = (C.c_int32 * max(max_new_tokens, 1))()
         n = C.c_int()
         self._check(self.lib.ze_generate(self.h, seq, C.byref(p), out, C.byref(n), self._stream()))
@@ -365,9 +398,11 @@ class Engine:
 
     def generate_batch(self, seqs, max_new_tokens: int, repetition_penalty: float = 1.0, ignore_eos: bool = False,
                        sync_every: int = 16, use_graph: bool = True, do_sample: bool = False, temperature: float = 1.0,
-                       seed: int = 0):
-        """Generation for several prefilled chains at once; returns one token list per chain."""
+                       seed: int = 0, top_k=None, top_p=None, min_p=None):
+        """Generation for several prefilled chains at once; returns one token list per chain.  top_k / top_p / min_p, when
+        given, are set on every chain of the call (set_sampling_filter beforehand for a filter per chain)."""
         sq, sp = _i32(seqs)
+        self._apply_filter(sq, top_k, top_p, min_p)
         p = self._gen_params(max_new_tokens, repetition_penalty, ignore_eos, use_graph, sync_every, do_sample,
                              temperature, seed)
         out = (C.c_int32 * (len(sq) * max_new_tokens))()

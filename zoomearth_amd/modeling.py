@@ -8,8 +8,10 @@ replaces: `Qwen2_5_VLForConditionalGeneration.from_pretrained(model_name, torch_
 
 Documented deviations: arithmetic is bf16 (the reference runs fp16 weights under a bf16 autocast
 wrapper); `do_sample=True, temperature=T` draws from softmax(logits / T) with the engine's counter-based
-random stream (`seed=` kwarg or `generation_config.seed`); `top_k` / `top_p` other than None (or top_k=1, which is
-greedy) raise NotImplementedError, as the reference sets both to None; `num_beams` must be 1.
+random stream (`seed=` kwarg or `generation_config.seed`); `top_k` / `top_p` / `min_p` (kwargs, then
+`generation_config`) are HF's warpers in HF's order, applied per chain on the device (`Engine.set_sampling_filter`;
+None, `top_k=0`, `top_p=1.0` mean off, `top_k=1` is greedy, out-of-range values raise ValueError as HF does);
+`num_beams` must be 1.
 """
 from __future__ import annotations
 
@@ -211,13 +213,22 @@ class ZoomEarthForConditionalGeneration:
         temperature = temperature if temperature is not None else getattr(gc, "temperature", None)
         if do_sample and top_k == 1:
             do_sample = False  # a one-token nucleus is the arg-max
-        if do_sample and ((top_k not in (None, 0)) or (top_p not in (None, 1.0))):
-            raise NotImplementedError("top_k / top_p filtering is not part of the ZoomEarth path "
-                                      "(src/eval/infer.py sets both to None)")
+        min_p = kw.get("min_p") if kw.get("min_p") is not None else getattr(gc, "min_p", None)
+        filt_kw = {}
+        if do_sample:  # HF's warpers in HF's order, on the device (Engine.set_sampling_filter); HF's "off" values and HF's errors
+            if top_k not in (None, 0) and (not isinstance(top_k, (int, np.integer)) or top_k < 0):
+                raise ValueError(f"`top_k` has to be a strictly positive integer, but is {top_k}")
+            if top_p is not None and not (0.0 <= float(top_p) <= 1.0):
+                raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+            if min_p is not None and not (0.0 <= float(min_p) <= 1.0):
+                raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
+            # (top_p = 0 keeps HF's min_tokens_to_keep = 1, the arg-max: the smallest positive value does the same)
+            filt_kw = dict(top_k=int(top_k or 0), top_p=1.0 if top_p is None else max(float(top_p), 1e-37),
+                           min_p=float(min_p or 0.0))
         if do_sample and temperature is None:
             temperature = 1.0
         sample_kw = dict(do_sample=bool(do_sample), temperature=float(temperature or 1.0),
-                         seed=int(kw.get("seed", getattr(gc, "seed", 0) or 0)))
+                         seed=int(kw.get("seed", getattr(gc, "seed", 0) or 0)), **filt_kw)
         gi = 0
         outs = []
         nrows = ids_cpu.shape[0]

@@ -44,11 +44,15 @@ class Rollout:
 
 def rollout_two_stage(model, processor, samples, num_generations: int = 4, temperature: float = 0.7,
                       max_new_tokens: int = 800, seed: int = 0, max_view: int = 512, with_logps: bool = True,
-                      burst: int = 8) -> List[Rollout]:
+                      burst: int = 8, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                      min_p: Optional[float] = None) -> List[Rollout]:
     """samples: dicts with `prompt` (the stage-1 prompt text, one `<|vision_start|><|image_pad|><|vision_end|>` block),
     `image` (the tile: DeviceImage or PIL) and `bbox` (the dataset's reference box; empty = non-cropping question).
+    top_k / top_p / min_p: the sampling filters of the reference's generation step (GRPOConfig top_k / top_p / min_p,
+    open_r1/trainer/grpo_config.py:62-70), applied to every chain of both stages; None = off.
     Returns len(samples) * num_generations rollouts, sample-major."""
-    sched = ChainScheduler(model, processor, do_sample=True, temperature=temperature, seed=seed, burst=burst)
+    sched = ChainScheduler(model, processor, do_sample=True, temperature=temperature, seed=seed, burst=burst,
+                           top_k=top_k, top_p=top_p, min_p=min_p)
     n, G = len(samples), int(num_generations)
     out = [Rollout(sample=i, generation=g, prompt1=samples[i]["prompt"]) for i in range(n) for g in range(G)]
     views = {}

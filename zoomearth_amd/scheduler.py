@@ -38,6 +38,10 @@ class Request:
     on_done: Optional[Callable[["Request", List[int], str], Optional["Request"]]] = None
     on_error: Optional[Callable[["Request", Exception], None]] = None
     tag: Any = None
+    # sampling filters of this request (None = the scheduler's default; 0 / 1.0 / 0.0 = off); used by a sampling scheduler only
+    top_k: Optional[int] = None
+    top_p: Optional[float] = None
+    min_p: Optional[float] = None
     # filled by the scheduler
     slot: int = -1
     n_prompt: int = 0
@@ -60,8 +64,14 @@ class ChainScheduler:
                  burst: int = 8, max_batch: Optional[int] = None, ignore_eos: bool = False, use_graph: Optional[bool] = None,
                  feature_cache: int = 64, min_admit: int = 1, max_wait_bursts: int = 2, share_prefix: bool = True,
                  min_shared: int = 64, reuse_generated: bool = True, overlap: Optional[bool] = None, hold_below: int = 0,
-                 admit_chunk_rows: int = 0):
+                 admit_chunk_rows: int = 0, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                 min_p: Optional[float] = None):
         self.model, self.processor, self.engine = model, processor, model.engine
+        # Sampling filters (top-k / top-p / min-p): the defaults of requests that name none; settable between requests.  A request's
+        # filter is written into its slot's row of the engine's table right before its first draw, so requests with different
+        # filters share the same bursts.  A greedy scheduler never touches the table.
+        self.do_sample = bool(do_sample)
+        self.top_k, self.top_p, self.min_p = top_k, top_p, min_p
         gc = model.generation_config
         pen = repetition_penalty if repetition_penalty is not None else (getattr(gc, "repetition_penalty", 1.0) or 1.0)
         if do_sample and temperature is None:
@@ -515,6 +525,18 @@ class ChainScheduler:
             req.n_prompt = len(ids)
             self._ready.append((req, tuple(ids), tuple(keys)))
 
+    def _set_filter(self, req) -> None:
+        """The request's own filter into its slot (the slot's reset / truncate / prefix copy cleared the previous chain's), before
+        its first draw."""
+        if not self.do_sample:
+            return
+        top_k = req.top_k if req.top_k is not None else self.top_k
+        top_p = req.top_p if req.top_p is not None else self.top_p
+        min_p = req.min_p if req.min_p is not None else self.min_p
+        top_k, top_p, min_p = int(top_k or 0), float(1.0 if top_p is None else top_p), float(min_p or 0.0)
+        if top_k > 0 or top_p < 1.0 or min_p > 0.0:
+            self.engine.set_sampling_filter(req.slot, top_k, top_p, min_p)
+
     def _join_ready(self, wait: bool = False) -> None:
         """The prefilled newcomers draw their first token (from the logits their pass left) and join the live set.  When
         overlapping, a pass that is still running does not hold the live chains up: they go into their next burst, the
@@ -534,6 +556,7 @@ class ChainScheduler:
                     keep_from = i
                     break
         for req, ids, keys in self._ready[:keep_from]:
+            self._set_filter(req)
             self.engine.chain_begin(req.slot, self.params, req.stream_id)
             self.live[req.slot] = _Live(req, ids, keys)
             self.stats["admitted"] += 1

@@ -5,7 +5,8 @@
 
 Request: the subset that client sends -- `messages` with `role` in {system, user, assistant} and `content` either a
 string or a list of `{"type": "text", "text": ...}` / `{"type": "image_url", "image_url": {"url": "data:image/...;
-base64,..."}}` items, plus `max_tokens`, `temperature`, `seed` (`n` must be 1, `stream` is not offered).
+base64,..."}}` items, plus `max_tokens`, `temperature`, `seed`, `top_p` and the vLLM extensions `top_k` (-1 / 0 = off) and
+`min_p` (`n` must be 1, `stream` is not offered); the three filters apply to sampled requests, each request its own.
 Prompt: the Qwen2.5-VL chat template (`<|im_start|>role\\n ... <|im_end|>\\n`, an image item becomes
 `<|vision_start|><|image_pad|><|vision_end|>`, a default system turn when the conversation has none, then the
 generation prompt `<|im_start|>assistant\\n`).  temperature 0 / absent -> greedy, else temperature sampling.
@@ -81,7 +82,8 @@ def build_prompt(messages):
 
 
 class _Parsed:
-    __slots__ = ("req", "prompt", "pil_images", "max_tokens", "sample", "temperature", "seed", "future")
+    __slots__ = ("req", "prompt", "pil_images", "max_tokens", "sample", "temperature", "seed", "future", "top_k", "top_p",
+                 "min_p")
 
 
 class ChatServer:
@@ -113,6 +115,20 @@ class ChatServer:
         p.sample = t is not None and float(t) > 0.0
         p.temperature = float(t) if p.sample else None
         p.seed = int(req.get("seed") or 0)
+        # sampling filters (OpenAI `top_p`; vLLM's `top_k`, -1 = off, and `min_p`): 0 / 1.0 / 0.0 = off
+        try:
+            p.top_p = 1.0 if req.get("top_p") is None else float(req["top_p"])
+            p.top_k = 0 if req.get("top_k") is None else int(req["top_k"])
+            p.min_p = 0.0 if req.get("min_p") is None else float(req["min_p"])
+        except (TypeError, ValueError) as ex:
+            raise BadRequest(f"top_p / top_k / min_p must be numbers: {ex}") from ex
+        if not (0.0 < p.top_p <= 1.0):
+            raise BadRequest(f"top_p must be in (0, 1], got {p.top_p}")
+        if p.top_k < -1:
+            raise BadRequest(f"top_k must be -1 (off) or >= 0, got {p.top_k}")
+        if not (0.0 <= p.min_p <= 1.0):
+            raise BadRequest(f"min_p must be in [0, 1], got {p.min_p}")
+        p.top_k = max(p.top_k, 0)
         p.future = None
         return p
 
@@ -147,7 +163,7 @@ class ChatServer:
             p0 = batch[0]
             kw = dict(max_new_tokens=max(p.max_tokens for p in batch), num_beams=1, do_sample=p0.sample)
             if p0.sample:
-                kw.update(temperature=p0.temperature, top_k=None, top_p=None, seed=p0.seed)
+                kw.update(temperature=p0.temperature, top_k=p0.top_k, top_p=p0.top_p, min_p=p0.min_p, seed=p0.seed)
             out = self.model.generate(**inputs, **kw)[:, width:].tolist()
         return [self._response(p, row, int(n)) for p, row, n in zip(batch, out, n_in)]
 
@@ -249,7 +265,8 @@ class ChatServer:
                 # The running (greedy) batch has drained.  Temperature and seed are baked into the captured decode step, so
                 # the sampled requests that share both run TOGETHER on a scheduler of their own (continuous batching, a
                 # request's random stream = stream 0 of its seed: what it would draw running alone, so a request's tokens
-                # do not depend on its company); other sampling configurations follow in turn.
+                # do not depend on its company); other sampling configurations follow in turn.  top_p / top_k / min_p are
+                # per chain on the device, so requests with different filters still share the group.
                 key = (sampled[0].temperature, sampled[0].seed)
                 group = [p for p in sampled if (p.temperature, p.seed) == key]
                 sampled = [p for p in sampled if (p.temperature, p.seed) != key]
@@ -268,7 +285,8 @@ class ChatServer:
                         try:
                             imgs = [DeviceImage.from_pil(im, self.model.engine) for im in p.pil_images]
                             ss.submit(Request(prompt=p.prompt, images=imgs, max_new_tokens=max(1, min(p.max_tokens, self.model.engine.max_ctx)),
-                                              stream_id=0, on_done=done, on_error=failed))
+                                              stream_id=0, on_done=done, on_error=failed, top_k=p.top_k, top_p=p.top_p,
+                                              min_p=p.min_p))
                         except Exception as ex:
                             failed(None, ex)
                     try:
