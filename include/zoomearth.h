@@ -324,6 +324,42 @@ int ze_op_sample_filter(ze_engine* e, const float* logits, int rows, int vocab, 
                         const int32_t* top_k, const float* top_p, const float* min_p, float* out_cut, int32_t* out_kept,
                         void* stream);
 
+/* Log-probabilities of the generated tokens (replaces: the `logprobs` / `top_logprobs` the OpenAI-compatible back-end of
+ * src/eval/infer_vllm.py:244-271 can return with a sampled token, and the completion positions of `old_per_token_logps`,
+ * src/train/RL/src/open-r1-multimodal/src/open_r1/trainer/grpo_trainer.py:660-683, which the reference gets from one more
+ * forward pass).  For a token t drawn at a step whose lm_head row is l (fp32, BEFORE repetition penalty, temperature and
+ * filters -- the model's own distribution, what ze_score computes):
+ *   logprob(t) = l[t] - max(l) - logf(sum_i expf(l[i] - max(l)))          fp32, fixed summation order
+ * and the top-N alternatives are the N entries with the largest l (ties to the lower id; order: value descending, id
+ * ascending), each with its logprob by the same formula; the sampled token need not be among them; places a row cannot fill
+ * with finite entries carry id -1 and logprob -inf.  top_n: -1 = off (default), 0 = the chosen token only, 1 ..
+ * ZE_MAX_TOP_LOGPROBS; ZE_ERR_INVALID outside.  Set it after the chain's prefill and before its first draw.  The request
+ * travels as a kernel argument on `stream` into a per-slot device table, so chains with and without a request share one burst
+ * and one captured graph; one more kernel per step (ze_logprobs.hip, one workgroup per chain, so the entry is a function of the
+ * chain's row alone: bit-identical whatever the batch, the slot, graph or eager) runs after the token is accepted in ze_generate,
+ * ze_generate_batch, ze_chain_begin and ze_decode_burst*, only while some chain of the engine has a request.  Cleared wherever
+ * the sampling filter is (ze_seq_reset, ze_seq_truncate, ze_seq_copy_prefix into the slot).  The history buffers are allocated
+ * by the first request that needs them (chosen token: max_seqs x max_ctx x 4 B; alternatives: max_seqs x max_ctx x 20 x 8 B);
+ * ZE_ERR_NOMEM if that fails, and the engine stays usable. */
+#define ZE_MAX_TOP_LOGPROBS 20
+int ze_seq_set_logprobs(ze_engine* e, int seq, int top_n, void* stream);
+/* The entries of the tokens ze_chain_tokens returns (trimmed after the first EOS; pad steps of a finished chain are never
+ * reported), replaces: CompletionOutput.logprobs.  Host arrays: out_logprobs f32 [capacity], out_top_ids int32 / out_top_logprobs
+ * f32 [capacity, top_n of the chain] (both may be NULL); *n_out entries, *top_n (may be NULL) the chain's request.
+ * ZE_ERR_INVALID for a chain without a request. */
+int ze_chain_logprobs(ze_engine* e, int seq, float* out_logprobs, int32_t* out_top_ids, float* out_top_logprobs,
+                      int capacity, int* n_out, int* top_n, void* stream);
+/* replaces: the same for the n chains a burst retires, as ze_chain_tokens_batch: one gather launch, one device -> host copy,
+ * one wait.  out_logprobs [n, capacity]; out_top_ids / out_top_logprobs [n, capacity, top_n_stride] (may be NULL; places beyond a
+ * chain's own top_n are -1 / -inf); n_out [n]. */
+int ze_chain_logprobs_batch(ze_engine* e, const int32_t* seqs, int n, float* out_logprobs, int32_t* out_top_ids,
+                            float* out_top_logprobs, int capacity, int top_n_stride, int32_t* n_out, void* stream);
+/* The kernel alone on device arrays (replaces: logits.log_softmax(-1) + gather + topk on one step's rows): logits f32
+ * [rows, ld] (ld >= vocab), targets int32 [rows], out_logprob f32 [rows], out_top_ids int32 / out_top_logprobs f32
+ * [rows, top_n] (unused for top_n = 0).  ZE_ERR_INVALID for top_n outside [0, ZE_MAX_TOP_LOGPROBS]. */
+int ze_op_token_logprobs(ze_engine* e, const float* logits, int rows, int vocab, int ld, const int32_t* targets,
+                         int top_n, float* out_logprob, int32_t* out_top_ids, float* out_top_logprobs, void* stream);
+
 /* FP8 decode weights (BASELINE.json configs[4], "fp8 weights"): quantises the decoder's linear layers (and an untied
  * lm_head) to OCP E4M3 with one power-of-two scale per output row, REPLACES the bf16 copies by the dequantised
  * values (exactly representable) so that prefill and decode compute with identical weights, and switches the batch-1

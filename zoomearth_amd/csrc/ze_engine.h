@@ -127,6 +127,22 @@ struct ze_engine {
     int n_filters = 0;
     float *filt_dev = nullptr, *cut_dev = nullptr;
     std::vector<int> graph_filters;  // whether the chain's graph was captured with the selection kernel in it
+    // Log-probabilities of generated tokens (ze_seq_set_logprobs): lp_host is the truth (-1 off, 0 chosen token only, 1..20
+    // alternatives), lp_dev the per-slot table the kernel reads, written in stream order by the setter; n_logprobs = slots with
+    // a request.  While it is 0 no step launches the kernel.  History, allocated by the first request that needs it: lp_tok f32
+    // [max_seqs, max_ctx]; lp_top_ids int32 / lp_top_lps f32 [max_seqs, max_ctx, 20].
+    std::vector<int> lp_host;
+    int n_logprobs = 0;
+    int* lp_dev = nullptr;
+    float* lp_tok = nullptr;
+    int* lp_top_ids = nullptr;
+    float* lp_top_lps = nullptr;
+    // what a captured step must have been captured with: 0 = no kernel, 1 = chosen-token history only, 2 = alternatives too
+    int lp_mode() const { return n_logprobs > 0 ? (lp_top_ids ? 2 : 1) : 0; }
+    ze_logprob_bufs lp_bufs() const { return ze_logprob_bufs{lp_dev, lp_tok, lp_top_ids, lp_top_lps}; }
+    std::vector<int> graph_logprobs;  // lp_mode() the chain's graph was captured under
+    int *xl_host = nullptr, *xl_dev = nullptr;  // gather scratch of ze_chain_logprobs* (pinned + device, grown on demand)
+    size_t xl_cap = 0;
     std::vector<hipGraphExec_t> graphs;
     std::vector<float> graph_penalty;
     std::vector<int> graph_ignore_eos;
@@ -198,7 +214,7 @@ struct ze_engine {
     int* bseq = nullptr;
     float *blogits = nullptr, *bpartial = nullptr, *bsample = nullptr;
     ze_seq_dev* bstate_host = nullptr;  // pinned
-    std::map<std::tuple<int, float, int, float, unsigned long long, int, int>, hipGraphExec_t> bgraphs;  // captured batched decode step per batch size (and attention grid)
+    std::map<std::tuple<int, float, int, float, unsigned long long, int, int, int>, hipGraphExec_t> bgraphs;  // captured batched decode step per batch size (and attention grid)
     int live_parts = 0;  // 192-key parts the longest chain of the current batch needs (the attention grid's extent); 0 = all
 
     // timers

@@ -227,7 +227,7 @@ static int init_tables(ze_engine* e) {
     return 0;
 }
 
-extern "C" int ze_version(void) { return 101; }
+extern "C" int ze_version(void) { return 102; }
 
 extern "C" const char* ze_last_error(const ze_engine* e) { return e ? e->err.c_str() : ze_global_error.c_str(); }
 
@@ -305,6 +305,10 @@ extern "C" int ze_engine_create(const ze_config* cfg, int device_id, ze_engine**
     e->filt_host.assign(c.max_seqs, ze_engine::filter_host{});
     chk(dev_alloc(e, &e->filt_dev, (size_t)c.max_seqs * 4));
     chk(dev_alloc(e, &e->cut_dev, (size_t)c.max_seqs * 2));
+    e->graph_logprobs.assign(c.max_seqs, 0);
+    e->lp_host.assign(c.max_seqs, -1);
+    chk(dev_alloc(e, &e->lp_dev, (size_t)c.max_seqs, false));
+    if (e->lp_dev && hipMemset(e->lp_dev, 0xff, (size_t)c.max_seqs * sizeof(int)) != hipSuccess) chk(ZE_ERR_HIP);  // every slot -1 = off
 
     // front-end workspace: horizontal-pass image (box_h x out_w) and resized image
     const size_t side = (size_t)std::max(c.max_tile_side, 1024);
@@ -464,7 +468,8 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
                    e->vo, e->va, e->vz, e->vz2, e->vcos, e->vsin, e->vperm, e->vinv, e->vtiles_win, e->vtiles_full,
                    e->th, e->ty, e->tqkv, e->to, e->ta, e->tsrc, e->tpos, e->ttiles, e->ttile_aux, e->trow_aux, e->dh, e->dq, e->dattn, e->dact,
                    e->dlogits, e->dpartial, e->dsample, e->atickets, e->gslab, e->gtickets, e->pslab, e->ptickets, e->bh, e->by, e->bqkv, e->bo, e->ba, e->bseq, e->bmate, e->blogits, e->bpartial, e->bsample, e->arena8, e->arena_f, e->arena_f8,
-                   e->ty8, e->ty8_scale, e->damax, e->ty8p, e->ty8p_scale, e->filt_dev, e->cut_dev};
+                   e->ty8, e->ty8_scale, e->damax, e->ty8p, e->ty8p_scale, e->filt_dev, e->cut_dev,
+                   e->lp_dev, e->lp_tok, e->lp_top_ids, e->lp_top_lps, e->xl_dev};
     for (void* p : dev)
         if (p) hipFree(p);
     if (e->pfx_dev) hipFree(e->pfx_dev);
@@ -478,7 +483,7 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
     if (e->xs_staged) hipEventDestroy(e->xs_staged);
     if (e->xs_dev) hipFree(e->xs_dev);
     if (e->xt_dev) hipFree(e->xt_dev);
-    void* host[] = {e->fe_coef_host, e->v_host_ints, e->v_host_f32, e->t_host_ints, e->d_host_ints, e->bstate_host, e->xs_host, e->xt_host};
+    void* host[] = {e->fe_coef_host, e->v_host_ints, e->v_host_f32, e->t_host_ints, e->d_host_ints, e->bstate_host, e->xs_host, e->xt_host, e->xl_host};
     for (void* p : host)
         if (p) hipHostFree(p);
     delete e;

@@ -421,6 +421,57 @@ extern "C" int ze_seq_set_sampling_filter(ze_engine* e, int seq, int top_k, floa
     return ZE_OK;
 }
 
+// ---- log-probabilities of generated tokens (ze_engine::lp_host is the truth, ze_logprobs.hip the kernel)
+static void write_logprobs(ze_engine* e, int seq, int top_n, hipStream_t s) {
+    const int was = e->lp_host[seq];
+    if (was == top_n) return;
+    e->lp_host[seq] = top_n;
+    e->n_logprobs += (int)(top_n >= 0) - (int)(was >= 0);
+    ze_launch_set_logprobs(e->lp_dev, seq, top_n, s);
+}
+// the slot goes to another chain (wherever its filter is cleared): it never inherits a request.  Nothing is launched for a slot
+// that has none.
+static void clear_logprobs(ze_engine* e, int seq, hipStream_t s) { write_logprobs(e, seq, -1, s); }
+
+extern "C" int ze_seq_set_logprobs(ze_engine* e, int seq, int top_n, void* stream) {
+    ZE_TRY(check_seq(e, seq));
+    if (top_n < -1 || top_n > ZE_MAX_TOP_LOGPROBS) return ze_fail(e, ZE_ERR_INVALID, "top_n must be in [-1, 20] (-1 = off)");
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t entries = (size_t)e->cfg.max_seqs * e->cfg.max_ctx;
+    // history, on first use: a failed allocation leaves the engine as it was
+    if (top_n >= 0 && !e->lp_tok) {
+        float* t = nullptr;
+        if (hipMalloc((void**)&t, entries * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the log-probability history failed");
+        }
+        e->lp_tok = t;
+    }
+    if (top_n >= 1 && !e->lp_top_ids) {
+        int* ids = nullptr;
+        float* lps = nullptr;
+        if (hipMalloc((void**)&ids, entries * ZE_MAX_TOP_LOGPROBS * sizeof(int)) != hipSuccess ||
+            hipMalloc((void**)&lps, entries * ZE_MAX_TOP_LOGPROBS * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (ids) hipFree(ids);
+            return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the top-logprobs history failed");
+        }
+        e->lp_top_ids = ids;
+        e->lp_top_lps = lps;
+    }
+    write_logprobs(e, seq, top_n, s);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
+// after the token of a step was accepted: the chains' entries (only while some chain of the engine has a request -- without one
+// the step launches what it always did).  seq_ids = null: the one chain `slot0`, whose row `logits` is.
+static void launch_logprobs(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s) {
+    if (e->n_logprobs > 0)
+        ze_launch_chain_logprobs(logits, e->cfg.vocab, e->cfg.vocab, e->st_dev, seq_ids, slot0, n, e->lp_bufs(), e->cfg.max_ctx, s);
+}
+
 extern "C" int ze_seq_reset(ze_engine* e, int seq, void* stream) {
     ZE_TRY(check_seq(e, seq));
     hipSetDevice(e->device);
@@ -432,6 +483,7 @@ extern "C" int ze_seq_reset(ze_engine* e, int seq, void* stream) {
     e->pfx_host[seq] = 0;
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)seq * e->cfg.vocab, 0, e->cfg.vocab, s));
     clear_filter(e, seq, s);
+    clear_logprobs(e, seq, s);
     return push_state(e, seq, s, 0, 0, 0);
 }
 
@@ -492,6 +544,7 @@ extern "C" int ze_seq_truncate(ze_engine* e, int seq, int keep_len, void* stream
     // the seen-set belongs to the dropped continuation: the caller re-marks the (new) prompt
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)seq * e->cfg.vocab, 0, e->cfg.vocab, (hipStream_t)stream));
     clear_filter(e, seq, (hipStream_t)stream);
+    clear_logprobs(e, seq, (hipStream_t)stream);
     return push_state(e, seq, (hipStream_t)stream, 0, 0, 0);
 }
 
@@ -525,6 +578,7 @@ extern "C" int ze_seq_copy_prefix(ze_engine* e, int dst_seq, int src_seq, int n_
     }
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)dst_seq * c.vocab, 0, c.vocab, s));
     clear_filter(e, dst_seq, s);
+    clear_logprobs(e, dst_seq, s);
     return push_state(e, dst_seq, s, 0, 0, 0);
 }
 
@@ -1041,6 +1095,7 @@ int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int ignore_eos,
                          e->out_tokens + (size_t)seq * c.max_ctx, e->dsample, so, s);
     else
         ze_launch_advance_ctx(e->st_dev + seq, s);  // teacher forcing: the caller chooses the next token
+    if (sample) launch_logprobs(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s);
     ZE_KCHECK();
     return ZE_OK;
 }
@@ -1116,6 +1171,7 @@ static int op_sample(ze_engine* e, int seq, const float* logits, float repetitio
     if (index) ze_launch_set_ints(&(e->st_dev + seq)->n_gen, &index, 1, s);
     ze_launch_sample(logits, c.vocab, e->seen + (size_t)seq * c.vocab, repetition_penalty, e->st_dev + seq, e->eos_dev,
                      c.n_eos, c.pad_token_id, 1, 0, e->out_tokens + (size_t)seq * c.max_ctx, e->dsample, so, s);
+    launch_logprobs(e, logits, nullptr, seq, 1, s);
     ZE_KCHECK();
     ZE_HIP(hipMemcpyAsync(out_token, e->out_tokens + (size_t)seq * c.max_ctx + index, sizeof(int), hipMemcpyDeviceToHost, s));
     ZE_HIP(hipStreamSynchronize(s));
@@ -1174,6 +1230,7 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
     const ze_sample_opts so = sample_opts_of(e, p, seq);
     ze_launch_sample(e->dlogits + (size_t)seq * c.vocab, c.vocab, e->seen + (size_t)seq * c.vocab, pen, st, e->eos_dev,
                      c.n_eos, c.pad_token_id, ign, 0, dev_out, e->dsample, so, s);
+    launch_logprobs(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s);
     ze_timer_end(e, t_s, s);
     ZE_KCHECK();
 
@@ -1182,7 +1239,8 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
     if (p->use_graph && max_new > 1) {
         if (!e->graphs[seq] || e->graph_penalty[seq] != pen || e->graph_ignore_eos[seq] != ign ||
             e->graph_variant[seq] != (int)ze_tune_epoch || e->graph_temperature[seq] != so.temperature ||
-            e->graph_seed[seq] != so.seed || e->graph_filters[seq] != (int)(so.filt != nullptr)) {
+            e->graph_seed[seq] != so.seed || e->graph_filters[seq] != (int)(so.filt != nullptr) ||
+            e->graph_logprobs[seq] != e->lp_mode()) {
             if (e->graphs[seq]) {
                 hipGraphExecDestroy(e->graphs[seq]);
                 e->graphs[seq] = nullptr;
@@ -1207,6 +1265,7 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
             e->graph_temperature[seq] = so.temperature;
             e->graph_seed[seq] = so.seed;
             e->graph_filters[seq] = so.filt != nullptr;
+            e->graph_logprobs[seq] = e->lp_mode();
         }
         gexec = e->graphs[seq];
     }
@@ -1542,6 +1601,7 @@ static int enqueue_decode_batch(ze_engine* e, int n, float penalty, int ignore_e
     ze_launch_sample_batch(e->blogits, c.vocab, e->seen, penalty, e->st_dev, e->bseq, n, e->eos_dev, c.n_eos,
                            c.pad_token_id, ignore_eos, 1, sample, e->out_tokens, c.max_ctx, e->bsample,
                            e->bsample + (size_t)c.max_seqs * 2 * 128, so, s);
+    if (sample) launch_logprobs(e, e->blogits, e->bseq, 0, n, s);
     ZE_KCHECK();
     return ZE_OK;
 }
@@ -1573,7 +1633,8 @@ extern "C" int ze_decode_batch(ze_engine* e, const int32_t* seqs, int n, const i
 // The captured batched decode step for `na` chains (chain ids / positions live in device memory, so one graph per
 // batch size and sampling setting serves every composition); nullptr in *out = run eagerly.
 static int batch_step_graph(ze_engine* e, int na, float pen, int ign, const ze_sample_opts& bso, hipGraphExec_t* out) {
-    auto key = std::make_tuple(na, pen, ign, bso.temperature, bso.seed, e->live_parts * 64 + e->live_parts_long, (int)(bso.filt != nullptr));
+    auto key = std::make_tuple(na, pen, ign, bso.temperature, bso.seed, e->live_parts * 64 + e->live_parts_long, (int)(bso.filt != nullptr),
+                               e->lp_mode());
     if (e->bgraph_epoch != ze_tune_epoch) {
         for (auto& kv : e->bgraphs) hipGraphExecDestroy(kv.second);
         e->bgraphs.clear();
@@ -1627,6 +1688,7 @@ static int begin_chain(ze_engine* e, int q, const ze_gen_params* p, float pen, i
     if (so.temperature > 0.f) ze_launch_set_ints(&(e->st_dev + q)->stream, &sample_stream, 1, s);
     ze_launch_sample(e->dlogits + (size_t)q * c.vocab, c.vocab, e->seen + (size_t)q * c.vocab, pen, e->st_dev + q, e->eos_dev,
                      c.n_eos, c.pad_token_id, ign, 0, e->out_tokens + (size_t)q * c.max_ctx, e->dsample, so, s);
+    launch_logprobs(e, e->dlogits + (size_t)q * c.vocab, nullptr, q, 1, s);
     ZE_KCHECK();
     return ZE_OK;
 }
@@ -1834,7 +1896,86 @@ extern "C" int ze_chain_tokens_batch(ze_engine* e, const int32_t* seqs, int n, i
     return ZE_OK;
 }
 
+// The log-probability entries of the tokens ze_chain_tokens_batch returns, the same way: one gather launch (tokens, for the
+// EOS trim, and entries), one device -> host copy, one wait.
+extern "C" int ze_chain_logprobs_batch(ze_engine* e, const int32_t* seqs, int n, float* out_logprobs, int32_t* out_top_ids,
+                                       float* out_top_logprobs, int cap, int top_n_stride, int32_t* n_out, void* stream) {
+    if (!e || n < 0 || cap < 0 || (n > 0 && (!seqs || !out_logprobs || !n_out))) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    if (n == 0) return ZE_OK;
+    if (n > e->cfg.max_seqs) return ze_fail(e, ZE_ERR_INVALID, "more chains than slots");
+    if (top_n_stride < 0 || top_n_stride > ZE_MAX_TOP_LOGPROBS) return ze_fail(e, ZE_ERR_INVALID, "top_n_stride must be in [0, 20]");
+    const ze_config& c = e->cfg;
+    for (int i = 0; i < n; ++i) {
+        ZE_TRY(check_seq(e, seqs[i]));
+        if (e->lp_host[seqs[i]] < 0) return ze_fail(e, ZE_ERR_INVALID, "the chain has no log-probability request (ze_seq_set_logprobs)");
+    }
+    cap = std::min(cap, c.max_ctx);
+    const int stride = (out_top_ids && out_top_logprobs) ? top_n_stride : 0;
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t rows = (size_t)n * cap, words = 3 * (size_t)n + 2 * rows + 2 * rows * stride;
+    ZE_TRY(xfer_reserve(e, e->xl_host, e->xl_dev, e->xl_cap, words + (size_t)n, nullptr, s));
+    // (the call waits for the stream before it returns, so the scratch is free again by the next call)
+    int* slots_dev = e->xl_dev + words;
+    memcpy(e->xl_host + words, seqs, (size_t)n * sizeof(int));
+    ZE_HIP(hipMemcpyAsync(slots_dev, e->xl_host + words, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    ze_launch_gather_chain_logprobs(e->st_dev, e->out_tokens, e->lp_bufs(), c.max_ctx, slots_dev, n, cap, stride, e->xl_dev, s);
+    ZE_KCHECK();
+    ZE_HIP(hipMemcpyAsync(e->xl_host, e->xl_dev, words * sizeof(int), hipMemcpyDeviceToHost, s));
+    ZE_HIP(hipStreamSynchronize(s));
+    const int* h_tok = e->xl_host + 3 * (size_t)n;
+    const float* h_lp = reinterpret_cast<const float*>(e->xl_host + 3 * (size_t)n + rows);
+    const int* h_ids = e->xl_host + 3 * (size_t)n + 2 * rows;
+    const float* h_tlp = reinterpret_cast<const float*>(e->xl_host + 3 * (size_t)n + 2 * rows + rows * stride);
+    for (int i = 0; i < n; ++i) {
+        int m = e->xl_host[3 * i];
+        const bool finished = e->xl_host[3 * i + 1] != 0;
+        for (int t = 0; t < m; ++t) {  // trim at the first EOS, as ze_chain_tokens
+            bool is_eos = false;
+            for (int k = 0; k < c.n_eos; ++k) is_eos |= h_tok[(size_t)i * cap + t] == c.eos_token_ids[k];
+            if (is_eos && finished) {
+                m = t + 1;
+                break;
+            }
+        }
+        memcpy(out_logprobs + (size_t)i * cap, h_lp + (size_t)i * cap, (size_t)m * sizeof(float));
+        if (stride) {
+            memcpy(out_top_ids + (size_t)i * cap * stride, h_ids + (size_t)i * cap * stride, (size_t)m * stride * sizeof(int));
+            memcpy(out_top_logprobs + (size_t)i * cap * stride, h_tlp + (size_t)i * cap * stride, (size_t)m * stride * sizeof(float));
+        }
+        n_out[i] = m;
+    }
+    return ZE_OK;
+}
+
+extern "C" int ze_chain_logprobs(ze_engine* e, int seq, float* out_logprobs, int32_t* out_top_ids, float* out_top_logprobs,
+                                 int cap, int* n_out, int* top_n, void* stream) {
+    ZE_TRY(check_seq(e, seq));
+    if (!out_logprobs || !n_out || cap < 0) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    const int tn = e->lp_host[seq];
+    if (tn < 0) return ze_fail(e, ZE_ERR_INVALID, "the chain has no log-probability request (ze_seq_set_logprobs)");
+    if (top_n) *top_n = tn;
+    const int32_t sq = seq;
+    int32_t m = 0;
+    ZE_TRY(ze_chain_logprobs_batch(e, &sq, 1, out_logprobs, tn > 0 ? out_top_ids : nullptr, tn > 0 ? out_top_logprobs : nullptr, cap,
+                                   tn, &m, stream));
+    *n_out = m;
+    return ZE_OK;
+}
+
 // ================================================================== unit ops
+extern "C" int ze_op_token_logprobs(ze_engine* e, const float* logits, int rows, int vocab, int ld, const int32_t* targets,
+                                    int top_n, float* out_logprob, int32_t* out_top_ids, float* out_top_logprobs, void* stream) {
+    if (!e || !logits || !targets || !out_logprob || rows < 0 || vocab <= 0 || ld < vocab)
+        return ze_fail(e, ZE_ERR_INVALID, "bad token_logprobs arguments");
+    if (top_n < 0 || top_n > ZE_MAX_TOP_LOGPROBS) return ze_fail(e, ZE_ERR_INVALID, "top_n must be in [0, 20]");
+    if (top_n > 0 && (!out_top_ids || !out_top_logprobs)) return ze_fail(e, ZE_ERR_INVALID, "null top arrays");
+    hipSetDevice(e->device);
+    ze_launch_token_logprobs(logits, rows, vocab, ld, targets, top_n, out_logprob, out_top_ids, out_top_logprobs, (hipStream_t)stream);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
 extern "C" int ze_op_linear(ze_engine* e, const void* a, const void* w, const void* bias, void* cmat, int M, int N,
                             int K, int act, void* stream) {
     if (!e || !a || !w || !cmat) return ze_fail(e, ZE_ERR_INVALID, "null argument");

@@ -333,4 +333,23 @@ void ze_launch_mark_seen(uint8_t* seen, const int* ids, int n, hipStream_t s);
 void ze_launch_mark_seen_batch(uint8_t* seen, int vocab, const int* hdr, const int* ids, int n, int max_count, hipStream_t s);
 void ze_launch_gather_chain_tokens(const ze_seq_dev* st, const int* out_tokens, int max_ctx, const int* slots, int n, int cap, int* out,
                                    hipStream_t s);
+// ---- log-probabilities of generated tokens (ze_logprobs.hip)
+// the engine's per-slot request table and history buffers (null until the first request that needs them)
+struct ze_logprob_bufs {
+    const int* want = nullptr;  // [slots] -1 off, 0 chosen token only, 1..ZE_MAX_TOP_LOGPROBS alternatives
+    float* tok = nullptr;       // [slots, max_ctx]
+    int* top_ids = nullptr;     // [slots, max_ctx, ZE_MAX_TOP_LOGPROBS]
+    float* top_lps = nullptr;
+};
+// unit form: logits f32 [rows, ld], targets [rows]; out_lp [rows], out_ids / out_tlp [rows, top_n] (unused for top_n = 0)
+void ze_launch_token_logprobs(const float* logits, int rows, int vocab, int ld, const int* targets, int top_n, float* out_lp,
+                              int* out_ids, float* out_tlp, hipStream_t s);
+// chain form, after the token of a step was accepted: row b of logits is chain slot seq_ids ? seq_ids[b] : slot0; a chain whose
+// slot wants nothing leaves at once; the entry goes to history index st[slot].n_gen - 1
+void ze_launch_chain_logprobs(const float* logits, int vocab, int ld, const ze_seq_dev* st, const int* seq_ids, int slot0, int n,
+                              const ze_logprob_bufs& lp, int max_gen, hipStream_t s);
+void ze_launch_set_logprobs(int* want, int slot, int top_n, hipStream_t s);
+// out (ints): [n_gen, finished, top_n per chain (3n) | n x cap ids | n x cap f32 | n x cap x stride ids | n x cap x stride f32]
+void ze_launch_gather_chain_logprobs(const ze_seq_dev* st, const int* out_tokens, const ze_logprob_bufs& lp, int max_ctx,
+                                     const int* slots, int n, int cap, int stride, int* out, hipStream_t s);
 void ze_launch_numeric_helpers(const float* x, const float* y, uint32_t* out, uint32_t* out2, int n, hipStream_t s);

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Iterable, Sequence
+from typing import Iterable, Optional, Sequence
 
 import numpy as np
 import torch
@@ -15,6 +15,7 @@ import torch
 from . import _lib
 from .config import ModelConfig
 
+MAX_TOP_LOGPROBS = 20  # ZE_MAX_TOP_LOGPROBS (OpenAI's cap on top_logprobs)
 _NP2ZE = {np.dtype(np.float32): _lib.ZE_F32, np.dtype(np.float16): _lib.ZE_F16}
 
 
@@ -278,6 +279,63 @@ class Engine:
                                                  t.ctypes.data_as(fp), k.ctypes.data_as(ip), p.ctypes.data_as(fp),
                                                  m.ctypes.data_as(fp), _ptr(cut), _ptr(kept), self._stream()))
         return cut, kept
+
+    def set_logprobs(self, seq: int, top_n: Optional[int] = 0):
+        """Log-probabilities of the tokens chain `seq` generates from now on (ze_seq_set_logprobs): None / -1 = off, 0 = the chosen
+        token only, 1 .. MAX_TOP_LOGPROBS = that many best alternatives too.  Computed on the device from the step's own fp32
+        logits (before repetition penalty, temperature and filters); held until the slot is reset, truncated or copied into.
+        Chains with and without a request share bursts and graphs."""
+        self._check(self.lib.ze_seq_set_logprobs(self.h, int(seq), -1 if top_n is None else int(top_n), self._stream()))
+
+    def chain_logprobs(self, seq: int, capacity: int = 0, stream=None):
+        """The entries of the tokens chain_tokens(seq) returns: (logprobs f32 [n], top_ids int32 [n, N], top_logprobs f32 [n, N]),
+        N the chain's own request; places a row could not fill are (-1, -inf).  Raises for a chain without a request."""
+        cap = max(1, min(int(capacity) if capacity else self.max_ctx, self.max_ctx))
+        lp = np.empty(cap, dtype=np.float32)
+        ids = np.empty((cap, MAX_TOP_LOGPROBS), dtype=np.int32)
+        tlp = np.empty((cap, MAX_TOP_LOGPROBS), dtype=np.float32)
+        n, tn = C.c_int(), C.c_int()
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else self._stream()
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        self._check(self.lib.ze_chain_logprobs(self.h, int(seq), lp.ctypes.data_as(fp), ids.ctypes.data_as(ip),
+                                               tlp.ctypes.data_as(fp), cap, C.byref(n), C.byref(tn), st))
+        m, N = n.value, tn.value  # (the C arrays are [capacity, N] packed)
+        return (lp[:m].copy(), ids.reshape(-1)[:m * N].reshape(m, N).copy(), tlp.reshape(-1)[:m * N].reshape(m, N).copy())
+
+    def chain_logprobs_batch(self, seqs, top_n: int = 0, capacity: int = 0, stream=None):
+        """chain_logprobs for several chains in one device -> host copy and one wait: a list of (logprobs [n_i], top_ids
+        [n_i, top_n], top_logprobs [n_i, top_n]); places beyond a chain's own request are (-1, -inf)."""
+        if not len(seqs):
+            return []
+        cap = max(1, min(int(capacity) if capacity else self.max_ctx, self.max_ctx))
+        N = int(top_n)
+        sq, sp = _i32(seqs)
+        lp = np.empty((len(sq), cap), dtype=np.float32)
+        ids = np.empty((len(sq), cap, max(N, 1)), dtype=np.int32)
+        tlp = np.empty((len(sq), cap, max(N, 1)), dtype=np.float32)
+        n = (C.c_int32 * len(sq))()
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else self._stream()
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        self._check(self.lib.ze_chain_logprobs_batch(self.h, sp, len(sq), lp.ctypes.data_as(fp),
+                                                     ids.ctypes.data_as(ip) if N else None, tlp.ctypes.data_as(fp) if N else None,
+                                                     cap, N, n, st))
+        return [(lp[i, :n[i]].copy(), ids[i, :n[i], :N].copy(), tlp[i, :n[i], :N].copy()) for i in range(len(sq))]
+
+    def op_token_logprobs(self, logits: torch.Tensor, targets: torch.Tensor, top_n: int = 0):
+        """The kernel alone (ze_op_token_logprobs): logits f32 [rows, vocab] (row stride >= vocab), targets int32 [rows].  Returns
+        (logprob f32 [rows], top_ids int32 [rows, top_n], top_logprobs f32 [rows, top_n]): log_softmax(logits)[target] and the
+        top_n largest entries in (value descending, id ascending) order."""
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+        assert targets.dtype == torch.int32 and targets.is_contiguous()
+        rows = int(logits.shape[0])
+        out = torch.empty(rows, dtype=torch.float32, device=self.device)
+        ids = torch.empty((rows, max(int(top_n), 0)), dtype=torch.int32, device=self.device)
+        tlp = torch.empty((rows, max(int(top_n), 0)), dtype=torch.float32, device=self.device)
+        ld = int(logits.stride(0)) if rows > 1 else int(logits.shape[1])   # (the stride of a one-row tensor means nothing)
+        self._check(self.lib.ze_op_token_logprobs(self.h, _ptr(logits), rows, int(logits.shape[1]), ld, _ptr(targets),
+                                                  int(top_n), _ptr(out), _ptr(ids) if top_n > 0 else None,
+                                                  _ptr(tlp) if top_n > 0 else None, self._stream()))
+        return out, ids, tlp
 
     def seq_truncate(self, seq: int, keep: int):
         self._check(self.lib.ze_seq_truncate(self.h, seq, keep, self._stream()))

@@ -18,7 +18,9 @@ from __future__ import annotations
 import json
 import os
 from collections import OrderedDict
+from dataclasses import dataclass
 from types import SimpleNamespace
+from typing import Optional
 
 import numpy as np
 import torch
@@ -26,7 +28,18 @@ import torch
 from . import processor as _processor
 from .checkpoint import iter_checkpoint
 from .config import ModelConfig
-from .engine import Engine
+from .engine import MAX_TOP_LOGPROBS, Engine
+
+
+@dataclass
+class GenerateOutput:
+    """What generate(logprobs=N) returns.  sequences: the id tensor generate returns without it; logprobs f32 [rows, new]: the
+    log-probability of every generated token (0 past a row's end); top_ids int32 / top_logprobs f32 [rows, new, N]: the step's N
+    best tokens, best first (-1 / -inf past a row's end and where a step had fewer finite logits)."""
+    sequences: torch.Tensor
+    logprobs: torch.Tensor
+    top_ids: torch.Tensor
+    top_logprobs: torch.Tensor
 
 
 class ZoomEarthForConditionalGeneration:
@@ -196,9 +209,16 @@ class ZoomEarthForConditionalGeneration:
     def generate(self, input_ids=None, attention_mask=None, pixel_values=None, image_grid_thw=None,
                  mm_token_type_ids=None, image_keys=None, max_new_tokens: int = 20, do_sample: bool = False,
                  num_beams: int = 1, temperature=None, top_p=None, top_k=None, repetition_penalty=None,
-                 ignore_eos: bool = False, **kw):
+                 ignore_eos: bool = False, logprobs: Optional[int] = None, **kw):
+        """`logprobs`: None returns the id tensor; an int in 0 .. 20 returns a GenerateOutput with the log-probability of every
+        generated token under the model's own distribution (the step's fp32 logits, before repetition penalty, temperature
+        and filters) and that many best alternatives per step, computed on the device inside the decode step."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not part of the ZoomEarth path (num_beams=1 everywhere)")
+        if logprobs is not None:
+            if isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer)) or not (0 <= logprobs <= MAX_TOP_LOGPROBS):
+                raise ValueError(f"`logprobs` has to be None or an integer in [0, {MAX_TOP_LOGPROBS}], but is {logprobs}")
+            logprobs = int(logprobs)
         e, cfg = self.engine, self.config
         ids_cpu = input_ids.cpu().numpy()
         mask = attention_mask.cpu().numpy().astype(bool) if attention_mask is not None else np.ones_like(ids_cpu, bool)
@@ -241,6 +261,7 @@ class ZoomEarthForConditionalGeneration:
             e.set_decode_regime(-1)  # (a scheduler may have pinned the family to its own capacity)
         slots = []
         pending = []
+        lps = []
         for b in range(nrows):
             ids = ids_cpu[b][mask[b]].astype(np.int64).tolist()
             is_img = np.asarray(ids) == cfg.image_token_id
@@ -273,7 +294,11 @@ class ZoomEarthForConditionalGeneration:
             if not batched:
                 self._chains[slot] = (tuple(ids), tuple(my_keys))
                 self._chains.move_to_end(slot)
+                if logprobs is not None:
+                    e.set_logprobs(slot, logprobs)  # (the reset / truncate above cleared the slot's previous request)
                 outs.append(e.generate(slot, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw))
+                if logprobs is not None:
+                    lps.append(e.chain_logprobs(slot, max_new_tokens))
             slots.append(slot)
         if batched:
             group, rows = [], 0
@@ -288,11 +313,26 @@ class ZoomEarthForConditionalGeneration:
             if pen != 1.0:
                 for slot, _, _, _, _, ids in pending:
                     e.mark_seen(slot, ids)
+            if logprobs is not None:
+                for slot in slots:
+                    e.set_logprobs(slot, logprobs)
             outs = e.generate_batch(slots, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw)
+            if logprobs is not None:
+                lps = e.chain_logprobs_batch(slots, logprobs, max_new_tokens)
         width = max(len(t) for t in outs)
         pad = cfg.pad_token_id
         res = torch.full((ids_cpu.shape[0], ids_cpu.shape[1] + width), pad, dtype=torch.long)
         res[:, : ids_cpu.shape[1]] = torch.from_numpy(ids_cpu)
         for b, t in enumerate(outs):
             res[b, ids_cpu.shape[1]: ids_cpu.shape[1] + len(t)] = torch.tensor(t, dtype=torch.long)
-        return res.to(input_ids.device)
+        if logprobs is None:
+            return res.to(input_ids.device)
+        out = GenerateOutput(sequences=res.to(input_ids.device), logprobs=torch.zeros((nrows, width), dtype=torch.float32),
+                             top_ids=torch.full((nrows, width, logprobs), -1, dtype=torch.int32),
+                             top_logprobs=torch.full((nrows, width, logprobs), float("-inf"), dtype=torch.float32))
+        for b, (lp, ids, tlp) in enumerate(lps):
+            n = min(len(outs[b]), len(lp))
+            out.logprobs[b, :n] = torch.from_numpy(lp[:n])
+            out.top_ids[b, :n] = torch.from_numpy(ids[:n, :logprobs])
+            out.top_logprobs[b, :n] = torch.from_numpy(tlp[:n, :logprobs])
+        return out

@@ -39,20 +39,27 @@ class Rollout:
     n_prompt1: int = 0               # stage-1 prompt length in tokens
     images: list = field(default_factory=list)   # images of the FINAL prompt, in order
     logps: Optional[object] = None   # f32 tensor: log p of every token of the final sequence from position n_prompt1 on
+    # sampled_logps: the decode-time log-probability of every sampled id of the stage (the policy's own `old_per_token_logps` of
+    # the completion positions, grpo_trainer.py:660-683), from the step that drew it -- no extra pass
+    completion1_logps: List[float] = field(default_factory=list)
+    completion2_logps: List[float] = field(default_factory=list)
     error: Optional[str] = None
 
 
 def rollout_two_stage(model, processor, samples, num_generations: int = 4, temperature: float = 0.7,
                       max_new_tokens: int = 800, seed: int = 0, max_view: int = 512, with_logps: bool = True,
                       burst: int = 8, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                      min_p: Optional[float] = None) -> List[Rollout]:
+                      min_p: Optional[float] = None, sampled_logps: bool = False) -> List[Rollout]:
     """samples: dicts with `prompt` (the stage-1 prompt text, one `<|vision_start|><|image_pad|><|vision_end|>` block),
     `image` (the tile: DeviceImage or PIL) and `bbox` (the dataset's reference box; empty = non-cropping question).
     top_k / top_p / min_p: the sampling filters of the reference's generation step (GRPOConfig top_k / top_p / min_p,
     open_r1/trainer/grpo_config.py:62-70), applied to every chain of both stages; None = off.
+    sampled_logps: fill completion1_logps / completion2_logps with the log-probabilities the decode steps computed for their own
+    samples (the model's distribution, before temperature and filters); independent of with_logps, which scores the final
+    sequence with one more pass per chain.
     Returns len(samples) * num_generations rollouts, sample-major."""
     sched = ChainScheduler(model, processor, do_sample=True, temperature=temperature, seed=seed, burst=burst,
-                           top_k=top_k, top_p=top_p, min_p=min_p)
+                           top_k=top_k, top_p=top_p, min_p=min_p, logprobs=0 if sampled_logps else None)
     n, G = len(samples), int(num_generations)
     out = [Rollout(sample=i, generation=g, prompt1=samples[i]["prompt"]) for i in range(n) for g in range(G)]
     views = {}
@@ -69,6 +76,7 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
     def stage1_done(ro):
         def done(req, tokens, text):
             ro.completion1, ro.completion1_ids, ro.n_prompt1 = text, list(tokens), req.n_prompt
+            ro.completion1_logps = list(req.token_logprobs)
             img, view, scale = views[ro.sample]
             ro.images = [view]
             if not samples[ro.sample].get("bbox"):             # non-cropping question: the chain ends here
@@ -85,6 +93,7 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
 
             def done2(req2, tokens2, text2):
                 ro.completion2, ro.completion2_ids = text2, list(tokens2)
+                ro.completion2_logps = list(req2.token_logprobs)
                 return None
             return Request(prompt=ro.prompt2, images=[view, crop], max_new_tokens=max_new_tokens,
                            stream_id=n * G + ro.sample * G + ro.generation, on_done=done2, on_error=fail(ro))

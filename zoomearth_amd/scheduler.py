@@ -42,11 +42,18 @@ class Request:
     top_k: Optional[int] = None
     top_p: Optional[float] = None
     min_p: Optional[float] = None
+    # log-probabilities of the generated tokens (None = the scheduler's default, which is off; 0 = the chosen token only; 1..20 =
+    # that many best alternatives as well)
+    logprobs: Optional[int] = None
     # filled by the scheduler
     slot: int = -1
     n_prompt: int = 0
     tokens: List[int] = field(default_factory=list)
     text: str = ""
+    # with `logprobs`: one entry per token of `tokens`, there before on_done runs -- the log-probability of the token under the
+    # model's own distribution at its step, and the step's best alternatives as (id, logprob), best first
+    token_logprobs: List[float] = field(default_factory=list)
+    top_logprobs: List[list] = field(default_factory=list)
 
 
 class _Live:
@@ -65,8 +72,11 @@ class ChainScheduler:
                  feature_cache: int = 64, min_admit: int = 1, max_wait_bursts: int = 2, share_prefix: bool = True,
                  min_shared: int = 64, reuse_generated: bool = True, overlap: Optional[bool] = None, hold_below: int = 0,
                  admit_chunk_rows: int = 0, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                 min_p: Optional[float] = None):
+                 min_p: Optional[float] = None, logprobs: Optional[int] = None):
         self.model, self.processor, self.engine = model, processor, model.engine
+        # Log-probabilities of generated tokens: the default of requests that name none (None = off).  Written into the slot's row
+        # of the engine's table next to the filter; requests with and without them share the same bursts.
+        self.logprobs = logprobs
         # Sampling filters (top-k / top-p / min-p): the defaults of requests that name none; settable between requests.  A request's
         # filter is written into its slot's row of the engine's table right before its first draw, so requests with different
         # filters share the same bursts.  A greedy scheduler never touches the table.
@@ -537,6 +547,25 @@ class ChainScheduler:
         if top_k > 0 or top_p < 1.0 or min_p > 0.0:
             self.engine.set_sampling_filter(req.slot, top_k, top_p, min_p)
 
+    def _want_logprobs(self, req) -> Optional[int]:
+        n = getattr(req, "logprobs", None)
+        n = self.logprobs if n is None else n
+        return None if n is None else int(n)
+
+    def _set_logprobs(self, req) -> None:
+        """The request's log-probability request into its slot (cleared, like the filter, by the slot's reset / truncate / prefix
+        copy), before its first draw."""
+        n = self._want_logprobs(req)
+        if n is not None:
+            self.engine.set_logprobs(req.slot, n)
+
+    @staticmethod
+    def _attach_logprobs(req, lp, n: int) -> None:
+        logps, ids, tlps = lp
+        m = len(req.tokens)
+        req.token_logprobs = [float(x) for x in logps[:m]]
+        req.top_logprobs = [[(int(i), float(v)) for i, v in zip(ids[t][:n], tlps[t][:n]) if int(i) >= 0] for t in range(m)]
+
     def _join_ready(self, wait: bool = False) -> None:
         """The prefilled newcomers draw their first token (from the logits their pass left) and join the live set.  When
         overlapping, a pass that is still running does not hold the live chains up: they go into their next burst, the
@@ -557,6 +586,7 @@ class ChainScheduler:
                     break
         for req, ids, keys in self._ready[:keep_from]:
             self._set_filter(req)
+            self._set_logprobs(req)
             self.engine.chain_begin(req.slot, self.params, req.stream_id)
             self.live[req.slot] = _Live(req, ids, keys)
             self.stats["admitted"] += 1
@@ -606,8 +636,16 @@ class ChainScheduler:
             ds = getattr(self, "_decode_stream", None)
             cap = max(self.live[s].req.max_new_tokens for s in out)
             toks = e.chain_tokens_batch(out, cap, stream=ds) if ds is not None else e.chain_tokens_batch(out, cap)
+        lps = {}
+        want = [s for s in out if self._want_logprobs(self.live[s].req) is not None]
+        if len(want) > 1 and hasattr(e, "chain_logprobs_batch") and not _PER_CHAIN:   # the same for their log-probabilities
+            ds = getattr(self, "_decode_stream", None)
+            cap = max(self.live[s].req.max_new_tokens for s in want)
+            top = max(self._want_logprobs(self.live[s].req) for s in want)
+            lps = dict(zip(want, e.chain_logprobs_batch(want, top, cap, stream=ds) if ds is not None
+                           else e.chain_logprobs_batch(want, top, cap)))
         for i, slot in enumerate(out):
-            self._retire(slot, None if toks is None else toks[i][:self.live[slot].req.max_new_tokens])
+            self._retire(slot, None if toks is None else toks[i][:self.live[slot].req.max_new_tokens], lps.get(slot))
 
     def _burst_steps(self) -> int:
         """Steps of the next burst: never past the chain with the fewest tokens left.  (Letting chains overrun their budget by
@@ -639,7 +677,7 @@ class ChainScheduler:
         with self._side_stream():   # (the callbacks of finished chains crop / resize on the front-end's stream)
             self._retire_finished(slots, n_gen, fin)
 
-    def _retire(self, slot: int, tokens=None) -> None:
+    def _retire(self, slot: int, tokens=None, logprobs=None) -> None:
         l = self.live.pop(slot)
         req = l.req
         ds = getattr(self, "_decode_stream", None)
@@ -649,6 +687,12 @@ class ChainScheduler:
             req.tokens = (self.engine.chain_tokens(slot, req.max_new_tokens, stream=ds) if ds is not None
                           else self.engine.chain_tokens(slot, req.max_new_tokens))
         req.text = self.processor.tokenizer.decode(req.tokens, skip_special_tokens=True).strip()
+        n_lp = self._want_logprobs(req)
+        if n_lp is not None:
+            if logprobs is None:
+                logprobs = (self.engine.chain_logprobs(slot, req.max_new_tokens, stream=ds) if ds is not None
+                            else self.engine.chain_logprobs(slot, req.max_new_tokens))
+            self._attach_logprobs(req, logprobs, n_lp)
         follow = None
         try:
             follow = req.on_done(req, req.tokens, req.text) if req.on_done else None

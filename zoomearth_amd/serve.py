@@ -7,6 +7,8 @@ Request: the subset that client sends -- `messages` with `role` in {system, user
 string or a list of `{"type": "text", "text": ...}` / `{"type": "image_url", "image_url": {"url": "data:image/...;
 base64,..."}}` items, plus `max_tokens`, `temperature`, `seed`, `top_p` and the vLLM extensions `top_k` (-1 / 0 = off) and
 `min_p` (`n` must be 1, `stream` is not offered); the three filters apply to sampled requests, each request its own.
+`logprobs: true` (with `top_logprobs: 0..20`) adds `choices[0].logprobs.content`, one entry per completion token, from the
+decode step's own logits (the model's distribution, before repetition penalty, temperature and filters).
 Prompt: the Qwen2.5-VL chat template (`<|im_start|>role\\n ... <|im_end|>\\n`, an image item becomes
 `<|vision_start|><|image_pad|><|vision_end|>`, a default system turn when the conversation has none, then the
 generation prompt `<|im_start|>assistant\\n`).  temperature 0 / absent -> greedy, else temperature sampling.
@@ -83,7 +85,7 @@ def build_prompt(messages):
 
 class _Parsed:
     __slots__ = ("req", "prompt", "pil_images", "max_tokens", "sample", "temperature", "seed", "future", "top_k", "top_p",
-                 "min_p")
+                 "min_p", "logprobs")
 
 
 class ChatServer:
@@ -129,10 +131,37 @@ class ChatServer:
         if not (0.0 <= p.min_p <= 1.0):
             raise BadRequest(f"min_p must be in [0, 1], got {p.min_p}")
         p.top_k = max(p.top_k, 0)
+        # OpenAI's `logprobs` (bool) and `top_logprobs` (0 .. 20, only with logprobs): None = no block in the response
+        lp, top = req.get("logprobs"), req.get("top_logprobs")
+        if lp is not None and not isinstance(lp, bool):
+            raise BadRequest(f"logprobs must be a boolean, got {lp!r}")
+        if top is not None:
+            if isinstance(top, bool) or not isinstance(top, int):
+                raise BadRequest(f"top_logprobs must be an integer, got {top!r}")
+            if not lp:
+                raise BadRequest("top_logprobs needs logprobs = true")
+            if not (0 <= top <= 20):
+                raise BadRequest(f"top_logprobs must be in [0, 20], got {top}")
+        p.logprobs = (int(top or 0) if lp else None)
         p.future = None
         return p
 
-    def _response(self, p: _Parsed, out, n_in: int) -> dict:
+    def _logprobs_block(self, p: _Parsed, ids, lp) -> dict:
+        """OpenAI's `choices[0].logprobs`: lp = (log-probability per token, [(id, logprob), ...] best first per token)."""
+        tok = self.processor.tokenizer
+
+        def entry(i, v):
+            s = tok.decode([int(i)], skip_special_tokens=False)
+            return {"token": s, "logprob": float(v), "bytes": list(s.encode("utf-8"))}
+
+        content = []
+        for t, i in enumerate(ids):
+            item = entry(i, lp[0][t])
+            item["top_logprobs"] = [entry(j, v) for j, v in lp[1][t][: p.logprobs]]
+            content.append(item)
+        return {"content": content}
+
+    def _response(self, p: _Parsed, out, n_in: int, lp=None) -> dict:
         eos = set(self.model.config.eos_token_ids)
         pad = self.model.config.pad_token_id
         out = out[: p.max_tokens]
@@ -141,13 +170,18 @@ class ChatServer:
         while stop is None and ids and ids[-1] == pad:
             ids = ids[:-1]
         text = self.processor.tokenizer.decode(ids, skip_special_tokens=True).strip()
-        return {
+        res = {
             "id": "chatcmpl-" + uuid.uuid4().hex[:24], "object": "chat.completion", "created": int(time.time()),
             "model": p.req.get("model") or self.model_id,
             "choices": [{"index": 0, "message": {"role": "assistant", "content": text},
                          "finish_reason": "stop" if stop is not None else "length"}],
             "usage": {"prompt_tokens": n_in, "completion_tokens": len(ids), "total_tokens": n_in + len(ids)},
         }
+        if p.logprobs is not None and lp is not None:  # (between message and finish_reason, where OpenAI has it)
+            c = res["choices"][0]
+            res["choices"][0] = {"index": c["index"], "message": c["message"], "logprobs": self._logprobs_block(p, ids, lp),
+                                 "finish_reason": c["finish_reason"]}
+        return res
 
     def _run(self, batch):
         """One processor + generate call for the parsed requests of `batch` (all greedy, or a single request)."""
@@ -164,8 +198,16 @@ class ChatServer:
             kw = dict(max_new_tokens=max(p.max_tokens for p in batch), num_beams=1, do_sample=p0.sample)
             if p0.sample:
                 kw.update(temperature=p0.temperature, top_k=p0.top_k, top_p=p0.top_p, min_p=p0.min_p, seed=p0.seed)
-            out = self.model.generate(**inputs, **kw)[:, width:].tolist()
-        return [self._response(p, row, int(n)) for p, row, n in zip(batch, out, n_in)]
+            want = [p.logprobs for p in batch if p.logprobs is not None]
+            if not want:
+                out = self.model.generate(**inputs, **kw)[:, width:].tolist()
+                return [self._response(p, row, int(n)) for p, row, n in zip(batch, out, n_in)]
+            g = self.model.generate(**inputs, logprobs=max(want), **kw)
+            out = g.sequences[:, width:].tolist()
+            lps = [(g.logprobs[b].tolist(),
+                    [[(i, v) for i, v in zip(ids, vals) if i >= 0] for ids, vals in zip(g.top_ids[b].tolist(), g.top_logprobs[b].tolist())])
+                   for b in range(len(batch))]
+        return [self._response(p, row, int(n), lp) for p, row, n, lp in zip(batch, out, n_in, lps)]
 
     # ------------------------------------------------------------------ entry points
     def complete(self, req: dict) -> dict:
@@ -238,7 +280,7 @@ class ChatServer:
                         continue
 
                     def done(req, tokens, text, p=p):
-                        p.future.set_result(self._response(p, tokens, req.n_prompt))
+                        p.future.set_result(self._response(p, tokens, req.n_prompt, (req.token_logprobs, req.top_logprobs)))
                         return None
 
                     def failed(req, ex, p=p):
@@ -249,7 +291,7 @@ class ChatServer:
                         imgs = [DeviceImage.from_pil(im, self.model.engine) for im in p.pil_images]
                         budget = max(1, min(p.max_tokens, self.model.engine.max_ctx))  # per request: never fails its batch
                         sched.submit(Request(prompt=p.prompt, images=imgs, max_new_tokens=budget, on_done=done,
-                                             on_error=failed))
+                                             on_error=failed, logprobs=p.logprobs))
                     except Exception as ex:
                         failed(None, ex)
                 if sched.busy():
@@ -275,7 +317,7 @@ class ChatServer:
                                         max_batch=self.max_batch, burst=8)
                     for p in group:
                         def done(req, tokens, text, p=p):
-                            p.future.set_result(self._response(p, tokens, req.n_prompt))
+                            p.future.set_result(self._response(p, tokens, req.n_prompt, (req.token_logprobs, req.top_logprobs)))
                             return None
 
                         def failed(req, ex, p=p):
@@ -286,7 +328,7 @@ class ChatServer:
                             imgs = [DeviceImage.from_pil(im, self.model.engine) for im in p.pil_images]
                             ss.submit(Request(prompt=p.prompt, images=imgs, max_new_tokens=max(1, min(p.max_tokens, self.model.engine.max_ctx)),
                                               stream_id=0, on_done=done, on_error=failed, top_k=p.top_k, top_p=p.top_p,
-                                              min_p=p.min_p))
+                                              min_p=p.min_p, logprobs=p.logprobs))
                         except Exception as ex:
                             failed(None, ex)
                     try:
