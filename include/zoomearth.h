@@ -360,6 +360,48 @@ int ze_chain_logprobs_batch(ze_engine* e, const int32_t* seqs, int n, float* out
 int ze_op_token_logprobs(ze_engine* e, const float* logits, int rows, int vocab, int ld, const int32_t* targets,
                          int top_n, float* out_logprob, int32_t* out_top_ids, float* out_top_logprobs, void* stream);
 
+/* Additive logit adjustments of one chain (replaces: `presence_penalty` / `frequency_penalty` / `logit_bias` of the
+ * OpenAI-compatible back-end src/eval/infer_vllm.py talks to, vLLM's `min_tokens`, and HF's SequenceBiasLogitsProcessor
+ * (single-token keys), SuppressTokensLogitsProcessor and MinNewTokensLengthLogitsProcessor, HF:generation/logits_process.py).
+ * For a chain with a request, a step's raw fp32 lm_head row l becomes the row a the sampler reads instead:
+ *   c_i = number of times token i was GENERATED by this chain since the request was set (prompt tokens do not count;
+ *         saturating at 65535)
+ *   t_i = frequency_penalty * (float)c_i                 ; if c_i > 0:  t_i = t_i + presence_penalty
+ *   a_i = (l_i + bias_i) - t_i                           ; bias_i = 0 for ids not in the chain's list
+ *   a_i = -inf for every EOS id of the config while fewer than min_new_tokens were generated   (applied last: wins over any bias)
+ * every operation rounded to fp32 on its own (no fused multiply-add), so a is bit for bit the numpy float32 restatement.
+ * A bias is finite or -inf (-inf: the token is banned).  Everything downstream acts on a exactly as it acts on l without a
+ * request: the repetition penalty, temperature, the filters' cut and the draw.  That order is this library's own -- additive
+ * adjustments first, the multiplicative repetition penalty after them; vLLM applies them the other way round.  Greedy
+ * decoding honours the request too (it changes the arg-max).  Log-probabilities (ze_seq_set_logprobs) keep reporting the raw
+ * row l, as their definition says.
+ * ZE_ERR_INVALID for a token id outside the vocabulary or listed twice, more than ZE_MAX_LOGIT_BIAS pairs, a penalty that is
+ * not finite, a bias that is NaN or +inf, min_new_tokens < 0 -- the chain's request is then unchanged.  All-off values (0, 0,
+ * 0, no pairs) clear the request.  Setting a request zeroes the chain's counts; like the log-probability request it is set
+ * after the chain's prefill and before its first draw.  bias_ids / bias_vals are host arrays; they and the parameters travel as
+ * kernel arguments on `stream` into per-slot device tables (no stream synchronisation), so chains with and without a request
+ * share one burst and one captured graph: ze_logit_adjust.hip writes the adjusted copy of the step's rows (a chain without a
+ * request gets its row copied unchanged, so its tokens are what they are without this entry), one more one-thread-per-chain
+ * kernel counts the accepted token (pad steps of a finished chain are not counted).  Honoured by ze_generate,
+ * ze_generate_batch, ze_chain_begin and ze_decode_burst*; a chain with a request stays off the folded arg-max of the
+ * single-chain greedy step, which never sees the row.  Cleared wherever the sampling filter is (ze_seq_reset, ze_seq_truncate,
+ * ze_seq_copy_prefix into the slot).  While no chain of the engine has a request every step launches exactly what it launches
+ * without this entry.  The buffers are allocated by the first request that needs them (adjusted rows: (max_seqs + 1) x vocab
+ * x 4 B, bias lists: max_seqs x 512 x 8 B; with a penalty, counts: max_seqs x vocab x 2 B); ZE_ERR_NOMEM if that fails, and
+ * the engine stays usable. */
+#define ZE_MAX_LOGIT_BIAS 512
+int ze_seq_set_logit_adjust(ze_engine* e, int seq, float presence_penalty, float frequency_penalty, int min_new_tokens,
+                            const int32_t* bias_ids, const float* bias_vals, int n_bias, void* stream);
+/* The kernel alone on caller rows, every array on the device: logits / out f32 [rows, ld] (ld >= vocab, out != logits; the
+ * columns beyond vocab are left alone), counts uint16 [rows, vocab] or NULL (all zero), presence / frequency f32 [rows],
+ * eos_masked int32 [rows] (non-zero: the engine's EOS ids below vocab become -inf), the bias pairs of row r at
+ * bias_offsets[r] .. bias_offsets[r + 1] (int32 [rows + 1]) of bias_ids int32 / bias_vals f32 (distinct ids per row; ids
+ * outside [0, vocab) are skipped).  A row whose values are all off (penalties 0, not masked, no pairs) is a row without a
+ * request: copied unchanged.  Asynchronous on `stream`. */
+int ze_op_logit_adjust(ze_engine* e, const float* logits, int rows, int vocab, int ld, const uint16_t* counts,
+                       const float* presence, const float* frequency, const int32_t* eos_masked, const int32_t* bias_offsets,
+                       const int32_t* bias_ids, const float* bias_vals, float* out, void* stream);
+
 /* FP8 decode weights (BASELINE.json configs[4], "fp8 weights"): quantises the decoder's linear layers (and an untied
  * lm_head) to OCP E4M3 with one power-of-two scale per output row, REPLACES the bf16 copies by the dequantised
  * values (exactly representable) so that prefill and decode compute with identical weights, and switches the batch-1

@@ -143,6 +143,31 @@ struct ze_engine {
     std::vector<int> graph_logprobs;  // lp_mode() the chain's graph was captured under
     int *xl_host = nullptr, *xl_dev = nullptr;  // gather scratch of ze_chain_logprobs* (pinned + device, grown on demand)
     size_t xl_cap = 0;
+    // Logit adjustments (ze_seq_set_logit_adjust): la_host is the truth, la_dev the per-slot table the kernels read (ZE_LA_WORDS
+    // ints per slot, all zero = off), written in stream order by the setter; n_adjust = slots with a request.  While it is 0 no
+    // step launches anything for them.  Allocated by the first request: la_bias_ids / la_bias_vals [max_seqs, ZE_MAX_LOGIT_BIAS]
+    // and la_rows f32 [max_seqs + 1, vocab], the adjusted rows the sampler reads (row b of a batched step; the last row serves
+    // the single-chain launches, which share one workspace as it is); by the first request with a penalty: la_counts u16
+    // [max_seqs, vocab].
+    struct adjust_host {
+        float presence = 0.f, frequency = 0.f;
+        int min_new = 0, n_bias = 0;
+        bool penalties() const { return presence != 0.f || frequency != 0.f; }
+        bool on() const { return penalties() || min_new > 0 || n_bias > 0; }
+    };
+    std::vector<adjust_host> la_host;
+    int n_adjust = 0;
+    int* la_dev = nullptr;
+    int* la_bias_ids = nullptr;
+    float* la_bias_vals = nullptr;
+    float* la_rows = nullptr;
+    uint16_t* la_counts = nullptr;
+    // what a captured step must have been captured with: 0 = nothing, 1 = the adjust kernel, 2 = the count kernel too
+    int la_mode() const { return n_adjust > 0 ? (la_counts ? 2 : 1) : 0; }
+    // (of a single-chain step, which serves one chain: nothing while THAT chain has no request -- it then reads its raw row)
+    int la_mode(int seq) const { return la_host[seq].on() ? la_mode() : 0; }
+    ze_logit_adjust_bufs la_bufs() const { return ze_logit_adjust_bufs{la_dev, la_bias_ids, la_bias_vals, la_counts}; }
+    std::vector<int> graph_adjust;  // la_mode(seq) the chain's graph was captured under
     std::vector<hipGraphExec_t> graphs;
     std::vector<float> graph_penalty;
     std::vector<int> graph_ignore_eos;
@@ -214,7 +239,7 @@ struct ze_engine {
     int* bseq = nullptr;
     float *blogits = nullptr, *bpartial = nullptr, *bsample = nullptr;
     ze_seq_dev* bstate_host = nullptr;  // pinned
-    std::map<std::tuple<int, float, int, float, unsigned long long, int, int, int>, hipGraphExec_t> bgraphs;  // captured batched decode step per batch size (and attention grid)
+    std::map<std::tuple<int, float, int, float, unsigned long long, int, int, int, int>, hipGraphExec_t> bgraphs;  // captured batched decode step per batch size (and attention grid)
     int live_parts = 0;  // 192-key parts the longest chain of the current batch needs (the attention grid's extent); 0 = all
 
     // timers

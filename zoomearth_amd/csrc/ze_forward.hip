@@ -1,6 +1,7 @@
 // Forward passes of the engine: image front-end, ViT, LLM prefill, decode step (eager or hipGraph), greedy
 // generation, plus the unit ops and the measurement hooks of the C ABI.
 #include <math.h>
+#include <cmath>
 #include <string.h>
 
 #include <algorithm>
@@ -472,6 +473,98 @@ static void launch_logprobs(ze_engine* e, const float* logits, const int* seq_id
         ze_launch_chain_logprobs(logits, e->cfg.vocab, e->cfg.vocab, e->st_dev, seq_ids, slot0, n, e->lp_bufs(), e->cfg.max_ctx, s);
 }
 
+// ---- logit adjustments (ze_engine::la_host is the truth, ze_logit_adjust.hip the kernels)
+static void write_adjust(ze_engine* e, int seq, const ze_engine::adjust_host& h, const int32_t* ids, const float* vals, hipStream_t s) {
+    const bool was = e->la_host[seq].on();
+    e->la_host[seq] = h;
+    e->n_adjust += (int)h.on() - (int)was;
+    if (!was && !h.on()) return;
+    if (h.n_bias > 0) {  // the list travels as kernel arguments, 128 words a launch
+        ze_launch_set_ints(e->la_bias_ids + (size_t)seq * ZE_MAX_LOGIT_BIAS, ids, h.n_bias, s);
+        ze_launch_set_ints(reinterpret_cast<int*>(e->la_bias_vals + (size_t)seq * ZE_MAX_LOGIT_BIAS), reinterpret_cast<const int*>(vals),
+                           h.n_bias, s);
+    }
+    // (also the word that remembers a finished chain: every request starts from a live chain with zero counts)
+    ze_launch_set_logit_adjust(e->la_dev, seq, h.presence, h.frequency, h.min_new, h.n_bias, s);
+}
+// the slot goes to another chain (wherever its filter is cleared): it never inherits a request.  Nothing is launched for a slot
+// that has none.
+static void clear_adjust(ze_engine* e, int seq, hipStream_t s) {
+    if (e->la_host[seq].on()) write_adjust(e, seq, ze_engine::adjust_host{}, nullptr, nullptr, s);
+}
+
+template <typename T>
+static bool la_alloc(T** p, size_t count) {
+    if (hipMalloc((void**)p, count * sizeof(T)) == hipSuccess) return true;
+    (void)hipGetLastError();
+    *p = nullptr;
+    return false;
+}
+
+extern "C" int ze_seq_set_logit_adjust(ze_engine* e, int seq, float presence_penalty, float frequency_penalty, int min_new_tokens,
+                                       const int32_t* bias_ids, const float* bias_vals, int n_bias, void* stream) {
+    ZE_TRY(check_seq(e, seq));
+    const ze_config& c = e->cfg;
+    if (!std::isfinite(presence_penalty) || !std::isfinite(frequency_penalty))
+        return ze_fail(e, ZE_ERR_INVALID, "presence_penalty and frequency_penalty must be finite (0 = off)");
+    if (min_new_tokens < 0) return ze_fail(e, ZE_ERR_INVALID, "min_new_tokens must be >= 0 (0 = off)");
+    if (n_bias < 0 || n_bias > ZE_MAX_LOGIT_BIAS) return ze_fail(e, ZE_ERR_INVALID, "n_bias must be in [0, 512]");
+    if (n_bias > 0 && (!bias_ids || !bias_vals)) return ze_fail(e, ZE_ERR_INVALID, "null bias arrays");
+    for (int i = 0; i < n_bias; ++i) {
+        if (bias_ids[i] < 0 || bias_ids[i] >= c.vocab) return ze_fail(e, ZE_ERR_INVALID, "bias token id out of range");
+        if (std::isnan(bias_vals[i]) || bias_vals[i] == INFINITY)
+            return ze_fail(e, ZE_ERR_INVALID, "a bias must be finite or -inf (-inf = the token is banned)");
+    }
+    if (n_bias > 1) {
+        std::vector<int32_t> sorted(bias_ids, bias_ids + n_bias);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return ze_fail(e, ZE_ERR_INVALID, "duplicate bias token id");
+    }
+    ze_engine::adjust_host h;
+    h.presence = presence_penalty + 0.f;  // (-0 -> +0: "no penalty" has one spelling)
+    h.frequency = frequency_penalty + 0.f;
+    h.min_new = min_new_tokens;
+    h.n_bias = n_bias;
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    // buffers, on first use: a failed allocation leaves the engine as it was
+    if (h.on() && !e->la_rows) {
+        int* ids = nullptr;
+        float *vals = nullptr, *rows = nullptr;
+        if (!la_alloc(&ids, (size_t)c.max_seqs * ZE_MAX_LOGIT_BIAS) || !la_alloc(&vals, (size_t)c.max_seqs * ZE_MAX_LOGIT_BIAS) ||
+            !la_alloc(&rows, ((size_t)c.max_seqs + 1) * c.vocab)) {
+            if (ids) hipFree(ids);
+            if (vals) hipFree(vals);
+            return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the adjusted-row buffer failed");
+        }
+        e->la_bias_ids = ids, e->la_bias_vals = vals, e->la_rows = rows;
+    }
+    if (h.penalties() && !e->la_counts) {
+        uint16_t* counts = nullptr;
+        if (!la_alloc(&counts, (size_t)c.max_seqs * c.vocab)) return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the token counts failed");
+        e->la_counts = counts;
+    }
+    if (h.penalties()) ZE_HIP(hipMemsetAsync(e->la_counts + (size_t)seq * c.vocab, 0, (size_t)c.vocab * sizeof(uint16_t), s));
+    write_adjust(e, seq, h, bias_ids, bias_vals, s);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
+// The rows the sampler of a step reads: the step's own while no chain of it has a request (the step then launches what it always
+// did), else their adjusted copy.  seq_ids = null: the one chain `slot0`, whose row `logits` is.
+static const float* adjusted_rows(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s) {
+    if (seq_ids ? e->n_adjust == 0 : !e->la_host[slot0].on()) return logits;
+    float* out = seq_ids ? e->la_rows : e->la_rows + (size_t)e->cfg.max_seqs * e->cfg.vocab;
+    ze_launch_chain_logit_adjust(logits, e->cfg.vocab, e->st_dev, seq_ids, slot0, n, e->la_bufs(), e->eos_dev, e->cfg.n_eos, out, s);
+    return out;
+}
+// after the token of a step was accepted, next to launch_logprobs: the chains' counts
+static void launch_counts(ze_engine* e, const int* seq_ids, int slot0, int n, hipStream_t s) {
+    if (seq_ids ? e->n_adjust == 0 : !e->la_host[slot0].on()) return;
+    ze_launch_count_tokens(e->st_dev, seq_ids, slot0, n, e->la_bufs(), e->cfg.vocab, s);
+}
+
 extern "C" int ze_seq_reset(ze_engine* e, int seq, void* stream) {
     ZE_TRY(check_seq(e, seq));
     hipSetDevice(e->device);
@@ -484,6 +577,7 @@ extern "C" int ze_seq_reset(ze_engine* e, int seq, void* stream) {
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)seq * e->cfg.vocab, 0, e->cfg.vocab, s));
     clear_filter(e, seq, s);
     clear_logprobs(e, seq, s);
+    clear_adjust(e, seq, s);
     return push_state(e, seq, s, 0, 0, 0);
 }
 
@@ -545,6 +639,7 @@ extern "C" int ze_seq_truncate(ze_engine* e, int seq, int keep_len, void* stream
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)seq * e->cfg.vocab, 0, e->cfg.vocab, (hipStream_t)stream));
     clear_filter(e, seq, (hipStream_t)stream);
     clear_logprobs(e, seq, (hipStream_t)stream);
+    clear_adjust(e, seq, (hipStream_t)stream);
     return push_state(e, seq, (hipStream_t)stream, 0, 0, 0);
 }
 
@@ -579,6 +674,7 @@ extern "C" int ze_seq_copy_prefix(ze_engine* e, int dst_seq, int src_seq, int n_
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)dst_seq * c.vocab, 0, c.vocab, s));
     clear_filter(e, dst_seq, s);
     clear_logprobs(e, dst_seq, s);
+    clear_adjust(e, dst_seq, s);
     return push_state(e, dst_seq, s, 0, 0, 0);
 }
 
@@ -1079,7 +1175,8 @@ int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int ignore_eos,
     a.out_f32 = e->dlogits + (size_t)seq * c.vocab;
     a.D = hd;
     // greedy: the arg-max partials come out of the lm_head launch itself (knob 14 = 1: the separate partial kernel)
-    const bool folded = sample && so.temperature <= 0.f && ze_gemv_knobs[14] != 1;
+    // (a chain with a logit-adjust request keeps off it: the folded arg-max never sees the row)
+    const bool folded = sample && so.temperature <= 0.f && ze_gemv_knobs[14] != 1 && !e->la_host[seq].on();
     if (folded) {
         a.seen = e->seen + (size_t)seq * c.vocab;
         a.penalty = penalty;
@@ -1090,12 +1187,15 @@ int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int ignore_eos,
         ze_launch_sample_folded(e->damax, c.vocab, e->seen + (size_t)seq * c.vocab, e->st_dev + seq, e->eos_dev, c.n_eos,
                                 c.pad_token_id, ignore_eos, /*advance_ctx=*/1, e->out_tokens + (size_t)seq * c.max_ctx, s);
     else if (sample)
-        ze_launch_sample(e->dlogits + (size_t)seq * c.vocab, c.vocab, e->seen + (size_t)seq * c.vocab, penalty, e->st_dev + seq, e->eos_dev,
-                         c.n_eos, c.pad_token_id, ignore_eos, /*advance_ctx=*/1,
+        ze_launch_sample(adjusted_rows(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s), c.vocab, e->seen + (size_t)seq * c.vocab,
+                         penalty, e->st_dev + seq, e->eos_dev, c.n_eos, c.pad_token_id, ignore_eos, /*advance_ctx=*/1,
                          e->out_tokens + (size_t)seq * c.max_ctx, e->dsample, so, s);
     else
         ze_launch_advance_ctx(e->st_dev + seq, s);  // teacher forcing: the caller chooses the next token
-    if (sample) launch_logprobs(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s);
+    if (sample) {
+        launch_logprobs(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s);
+        launch_counts(e, nullptr, seq, 1, s);
+    }
     ZE_KCHECK();
     return ZE_OK;
 }
@@ -1228,9 +1328,10 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
     const int t_s = ze_timer_begin(e, 4, s);
     // first token from the prefill logits (no cache growth)
     const ze_sample_opts so = sample_opts_of(e, p, seq);
-    ze_launch_sample(e->dlogits + (size_t)seq * c.vocab, c.vocab, e->seen + (size_t)seq * c.vocab, pen, st, e->eos_dev,
-                     c.n_eos, c.pad_token_id, ign, 0, dev_out, e->dsample, so, s);
+    ze_launch_sample(adjusted_rows(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s), c.vocab, e->seen + (size_t)seq * c.vocab,
+                     pen, st, e->eos_dev, c.n_eos, c.pad_token_id, ign, 0, dev_out, e->dsample, so, s);
     launch_logprobs(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s);
+    launch_counts(e, nullptr, seq, 1, s);
     ze_timer_end(e, t_s, s);
     ZE_KCHECK();
 
@@ -1240,7 +1341,7 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
         if (!e->graphs[seq] || e->graph_penalty[seq] != pen || e->graph_ignore_eos[seq] != ign ||
             e->graph_variant[seq] != (int)ze_tune_epoch || e->graph_temperature[seq] != so.temperature ||
             e->graph_seed[seq] != so.seed || e->graph_filters[seq] != (int)(so.filt != nullptr) ||
-            e->graph_logprobs[seq] != e->lp_mode()) {
+            e->graph_logprobs[seq] != e->lp_mode() || e->graph_adjust[seq] != e->la_mode(seq)) {
             if (e->graphs[seq]) {
                 hipGraphExecDestroy(e->graphs[seq]);
                 e->graphs[seq] = nullptr;
@@ -1266,6 +1367,7 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
             e->graph_seed[seq] = so.seed;
             e->graph_filters[seq] = so.filt != nullptr;
             e->graph_logprobs[seq] = e->lp_mode();
+            e->graph_adjust[seq] = e->la_mode(seq);
         }
         gexec = e->graphs[seq];
     }
@@ -1598,10 +1700,13 @@ static int enqueue_decode_batch(ze_engine* e, int n, float penalty, int ignore_e
     else
         ze_launch_gemm_stream(ZE_EPI_F32, e->by, H, e->lm_head, H, nullptr, nullptr, 0, (bf16_t*)e->blogits, c.vocab, n,
                               c.vocab, H, e->gemm_ws(), s);
-    ze_launch_sample_batch(e->blogits, c.vocab, e->seen, penalty, e->st_dev, e->bseq, n, e->eos_dev, c.n_eos,
-                           c.pad_token_id, ignore_eos, 1, sample, e->out_tokens, c.max_ctx, e->bsample,
+    ze_launch_sample_batch(sample ? adjusted_rows(e, e->blogits, e->bseq, 0, n, s) : e->blogits, c.vocab, e->seen, penalty, e->st_dev,
+                           e->bseq, n, e->eos_dev, c.n_eos, c.pad_token_id, ignore_eos, 1, sample, e->out_tokens, c.max_ctx, e->bsample,
                            e->bsample + (size_t)c.max_seqs * 2 * 128, so, s);
-    if (sample) launch_logprobs(e, e->blogits, e->bseq, 0, n, s);
+    if (sample) {
+        launch_logprobs(e, e->blogits, e->bseq, 0, n, s);
+        launch_counts(e, e->bseq, 0, n, s);
+    }
     ZE_KCHECK();
     return ZE_OK;
 }
@@ -1634,7 +1739,7 @@ extern "C" int ze_decode_batch(ze_engine* e, const int32_t* seqs, int n, const i
 // batch size and sampling setting serves every composition); nullptr in *out = run eagerly.
 static int batch_step_graph(ze_engine* e, int na, float pen, int ign, const ze_sample_opts& bso, hipGraphExec_t* out) {
     auto key = std::make_tuple(na, pen, ign, bso.temperature, bso.seed, e->live_parts * 64 + e->live_parts_long, (int)(bso.filt != nullptr),
-                               e->lp_mode());
+                               e->lp_mode(), e->la_mode());
     if (e->bgraph_epoch != ze_tune_epoch) {
         for (auto& kv : e->bgraphs) hipGraphExecDestroy(kv.second);
         e->bgraphs.clear();
@@ -1686,9 +1791,10 @@ static int begin_chain(ze_engine* e, int q, const ze_gen_params* p, float pen, i
     const ze_config& c = e->cfg;
     ze_sample_opts so = sample_opts_of(e, p, q);
     if (so.temperature > 0.f) ze_launch_set_ints(&(e->st_dev + q)->stream, &sample_stream, 1, s);
-    ze_launch_sample(e->dlogits + (size_t)q * c.vocab, c.vocab, e->seen + (size_t)q * c.vocab, pen, e->st_dev + q, e->eos_dev,
-                     c.n_eos, c.pad_token_id, ign, 0, e->out_tokens + (size_t)q * c.max_ctx, e->dsample, so, s);
+    ze_launch_sample(adjusted_rows(e, e->dlogits + (size_t)q * c.vocab, nullptr, q, 1, s), c.vocab, e->seen + (size_t)q * c.vocab, pen,
+                     e->st_dev + q, e->eos_dev, c.n_eos, c.pad_token_id, ign, 0, e->out_tokens + (size_t)q * c.max_ctx, e->dsample, so, s);
     launch_logprobs(e, e->dlogits + (size_t)q * c.vocab, nullptr, q, 1, s);
+    launch_counts(e, nullptr, q, 1, s);
     ZE_KCHECK();
     return ZE_OK;
 }
@@ -1964,6 +2070,19 @@ extern "C" int ze_chain_logprobs(ze_engine* e, int seq, float* out_logprobs, int
 }
 
 // ================================================================== unit ops
+extern "C" int ze_op_logit_adjust(ze_engine* e, const float* logits, int rows, int vocab, int ld, const uint16_t* counts,
+                                  const float* presence, const float* frequency, const int32_t* eos_masked, const int32_t* bias_offsets,
+                                  const int32_t* bias_ids, const float* bias_vals, float* out, void* stream) {
+    if (!e || !logits || !presence || !frequency || !eos_masked || !bias_offsets || !out || out == logits)
+        return ze_fail(e, ZE_ERR_INVALID, "bad logit_adjust arguments");
+    if (rows < 0 || vocab <= 0 || ld < vocab) return ze_fail(e, ZE_ERR_INVALID, "rows >= 0, vocab > 0 and ld >= vocab");
+    hipSetDevice(e->device);
+    ze_launch_logit_adjust(logits, rows, vocab, ld, counts, presence, frequency, eos_masked, bias_offsets, bias_ids, bias_vals, e->eos_dev,
+                           e->cfg.n_eos, out, (hipStream_t)stream);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
 extern "C" int ze_op_token_logprobs(ze_engine* e, const float* logits, int rows, int vocab, int ld, const int32_t* targets,
                                     int top_n, float* out_logprob, int32_t* out_top_ids, float* out_top_logprobs, void* stream) {
     if (!e || !logits || !targets || !out_logprob || rows < 0 || vocab <= 0 || ld < vocab)

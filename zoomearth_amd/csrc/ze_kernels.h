@@ -352,4 +352,29 @@ void ze_launch_set_logprobs(int* want, int slot, int top_n, hipStream_t s);
 // out (ints): [n_gen, finished, top_n per chain (3n) | n x cap ids | n x cap f32 | n x cap x stride ids | n x cap x stride f32]
 void ze_launch_gather_chain_logprobs(const ze_seq_dev* st, const int* out_tokens, const ze_logprob_bufs& lp, int max_ctx,
                                      const int* slots, int n, int cap, int stride, int* out, hipStream_t s);
+// ---- per-chain logit adjustments (ze_logit_adjust.hip)
+#define ZE_LA_WORDS 8  // ints per slot of the request table: presence bits, frequency bits, min_new_tokens, n_bias, done, 0, 0, 0
+// the engine's per-slot request table, bias lists and count rows (counts: null until the first request with a penalty)
+struct ze_logit_adjust_bufs {
+    int* table = nullptr;          // [slots, ZE_LA_WORDS]
+    const int* bias_ids = nullptr;  // [slots, ZE_MAX_LOGIT_BIAS]
+    const float* bias_vals = nullptr;
+    uint16_t* counts = nullptr;    // [slots, vocab], saturating
+};
+// unit form, everything on the device: logits / out f32 [rows, ld]; counts u16 [rows, vocab] or null; presence / frequency /
+// eos_masked [rows]; bias entries of row r = bias_off[r] .. bias_off[r + 1] of bias_ids / bias_vals (ids outside [0, vocab) are
+// skipped); eos_ids [n_eos]
+void ze_launch_logit_adjust(const float* logits, int rows, int vocab, int ld, const uint16_t* counts, const float* presence,
+                            const float* frequency, const int* eos_masked, const int* bias_off, const int* bias_ids,
+                            const float* bias_vals, const int* eos_ids, int n_eos, float* out, hipStream_t s);
+// chain form, before the sampler of a step: row b of logits ([n, vocab]) is chain slot seq_ids ? seq_ids[b] : slot0, whose
+// request is read from the table; EOS ids are masked while st[slot].n_gen < min_new_tokens; a chain without a request gets
+// its row copied
+void ze_launch_chain_logit_adjust(const float* logits, int vocab, const ze_seq_dev* st, const int* seq_ids, int slot0, int n,
+                                  const ze_logit_adjust_bufs& la, const int* eos_ids, int n_eos, float* out, hipStream_t s);
+// after the token of a step was accepted: counts[slot, st[slot].token] += 1 for chains with a penalty (not for pad steps)
+void ze_launch_count_tokens(const ze_seq_dev* st, const int* seq_ids, int slot0, int n, const ze_logit_adjust_bufs& la, int vocab,
+                            hipStream_t s);
+void ze_launch_set_logit_adjust(int* table, int slot, float presence, float frequency, int min_new_tokens, int n_bias,
+                                hipStream_t s);
 void ze_launch_numeric_helpers(const float* x, const float* y, uint32_t* out, uint32_t* out2, int n, hipStream_t s);

@@ -16,6 +16,7 @@ from . import _lib
 from .config import ModelConfig
 
 MAX_TOP_LOGPROBS = 20  # ZE_MAX_TOP_LOGPROBS (OpenAI's cap on top_logprobs)
+MAX_LOGIT_BIAS = 512   # ZE_MAX_LOGIT_BIAS (pairs of one chain's bias list)
 _NP2ZE = {np.dtype(np.float32): _lib.ZE_F32, np.dtype(np.float16): _lib.ZE_F16}
 
 
@@ -336,6 +337,56 @@ class Engine:
                                                   int(top_n), _ptr(out), _ptr(ids) if top_n > 0 else None,
                                                   _ptr(tlp) if top_n > 0 else None, self._stream()))
         return out, ids, tlp
+
+    def seq_set_logit_adjust(self, seq: int, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                             min_new_tokens: int = 0, logit_bias=None):
+        """Additive logit adjustments of chain `seq` (ze_seq_set_logit_adjust), applied on the device to every step's row before
+        the repetition penalty, temperature, filters and the draw -- greedy decoding included: `logit_bias` {token id: bias} (or
+        (id, bias) pairs; at most MAX_LOGIT_BIAS, -inf bans the token), OpenAI's presence / frequency penalties over the counts
+        of the tokens the chain generates from now on, and the EOS ids banned until min_new_tokens were generated.  Set after the
+        chain's prefill and before its first draw; all-off values clear the request; held until the slot is reset, truncated or
+        copied into.  Chains with and without a request share bursts and graphs."""
+        pairs = list(logit_bias.items()) if hasattr(logit_bias, "items") else list(logit_bias or ())
+        ids = np.ascontiguousarray([int(k) for k, _ in pairs], dtype=np.int32)
+        vals = np.ascontiguousarray([float(v) for _, v in pairs], dtype=np.float32)
+        self._check(self.lib.ze_seq_set_logit_adjust(self.h, int(seq), float(presence_penalty or 0.0), float(frequency_penalty or 0.0),
+                                                     int(min_new_tokens or 0), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     vals.ctypes.data_as(C.POINTER(C.c_float)), len(pairs), self._stream()))
+
+    def op_logit_adjust(self, logits: torch.Tensor, counts=None, presence=0.0, frequency=0.0, eos_masked=0, bias=None,
+                        out: Optional[torch.Tensor] = None):
+        """The kernel alone (ze_op_logit_adjust): logits f32 [rows, vocab] (row stride >= vocab), counts uint16-valued [rows, vocab]
+        (a torch.int16 tensor holding the bit patterns, or a numpy uint16 array) or None, presence / frequency / eos_masked per row
+        (scalars broadcast), bias: per row a list of (id, value) pairs (or a dict), or None.  Returns the adjusted rows, f32 with the
+        stride of `logits` (columns beyond vocab are not written)."""
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+        rows, vocab = int(logits.shape[0]), int(logits.shape[1])
+        ld = int(logits.stride(0)) if rows > 1 else vocab   # (the stride of a one-row tensor means nothing)
+        dev = self.device
+
+        def per_row(x, dt):
+            return torch.from_numpy(np.broadcast_to(np.asarray(x, dtype=dt), (rows,)).copy()).to(dev)
+
+        pr, fr, em = per_row(presence, np.float32), per_row(frequency, np.float32), per_row(eos_masked, np.int32)
+        lists = [list(b.items()) if hasattr(b, "items") else list(b or ()) for b in (bias if bias is not None else [None] * rows)]
+        assert len(lists) == rows
+        off = np.zeros(rows + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(b) for b in lists])
+        ids = np.asarray([int(k) for b in lists for k, _ in b] + [0], dtype=np.int32)   # (+ one entry: never an empty tensor)
+        vals = np.asarray([float(v) for b in lists for _, v in b] + [0.0], dtype=np.float32)
+        off_d, ids_d, vals_d = (torch.from_numpy(x).to(dev) for x in (off, ids, vals))
+        if counts is not None:
+            if isinstance(counts, np.ndarray):
+                counts = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.uint16).view(np.int16)).to(dev)
+            assert counts.dtype == torch.int16 and counts.is_contiguous() and tuple(counts.shape) == (rows, vocab)
+        if out is None:
+            out = torch.empty_strided((rows, vocab), (ld, 1), dtype=torch.float32, device=dev)
+        assert out.dtype == torch.float32 and out.stride(1) == 1 and (rows <= 1 or int(out.stride(0)) == ld)
+        self._check(self.lib.ze_op_logit_adjust(self.h, _ptr(logits), rows, vocab, ld, _ptr(counts) if counts is not None else None,
+                                                _ptr(pr), _ptr(fr), _ptr(em), _ptr(off_d), _ptr(ids_d), _ptr(vals_d), _ptr(out),
+                                                self._stream()))
+        self._keep = (pr, fr, em, off_d, ids_d, vals_d, counts)   # (the launch is asynchronous: alive until the next one)
+        return out
 
     def seq_truncate(self, seq: int, keep: int):
         self._check(self.lib.ze_seq_truncate(self.h, seq, keep, self._stream()))

@@ -28,7 +28,7 @@ import torch
 from . import processor as _processor
 from .checkpoint import iter_checkpoint
 from .config import ModelConfig
-from .engine import MAX_TOP_LOGPROBS, Engine
+from .engine import MAX_LOGIT_BIAS, MAX_TOP_LOGPROBS, Engine
 
 
 @dataclass
@@ -205,6 +205,61 @@ class ZoomEarthForConditionalGeneration:
         return out.to(input_ids.device) if input_ids.device.type != "cpu" else out.cpu()
 
     # ------------------------------------------------------------------ generate
+    @staticmethod
+    def _logit_adjust_request(kw):
+        """(presence_penalty, frequency_penalty, min_new_tokens, {id: bias}) from generate's keyword arguments, or None when all
+        are off (nothing is launched then).  HF's `min_new_tokens`, `sequence_bias` (single-token keys) and `suppress_tokens`
+        with HF's ValueErrors (MinNewTokensLengthLogitsProcessor, SequenceBiasLogitsProcessor, SuppressTokensLogitsProcessor);
+        `presence_penalty`, `frequency_penalty` and `logit_bias` {id: bias} as the OpenAI API names them."""
+        min_new = kw.get("min_new_tokens")
+        if min_new is not None and (isinstance(min_new, bool) or not isinstance(min_new, (int, np.integer)) or min_new < 0):
+            raise ValueError(f"`min_new_tokens` has to be a positive integer, but is {min_new}")
+        bias = {}
+        lb = kw.get("logit_bias")
+        if lb is not None:
+            if not isinstance(lb, dict):
+                raise ValueError(f"`logit_bias` has to be a dictionary of token id -> bias, but is {lb}")
+            for k, v in lb.items():
+                if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                    raise ValueError(f"`logit_bias` has to be a dict with floats as values, but is {lb}")
+                bias[int(k)] = float(v)
+        sb = kw.get("sequence_bias")
+        if sb is not None:
+            if (not isinstance(sb, (dict, list))) or len(sb) == 0:
+                raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {sb}.")
+            items = list(sb.items()) if isinstance(sb, dict) else [(tuple(x[0]) if isinstance(x, (list, tuple)) and len(x) == 2
+                                                                      and isinstance(x[0], (list, tuple)) else None, x[1] if
+                                                                     isinstance(x, (list, tuple)) and len(x) == 2 else None) for x in sb]
+            if any(not isinstance(k, tuple) for k, _ in items):
+                raise ValueError(f"`sequence_bias` has to be a dict with tuples as keys, but is {sb}.")
+            if any(len(k) == 0 or any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) or t < 0 for t in k) for k, _ in items):
+                raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {sb}.")
+            if any(isinstance(v, bool) or not isinstance(v, (float, np.floating)) for _, v in items):
+                raise ValueError(f"`sequence_bias` has to be a dict with floats as values, but is {sb}.")
+            for k, v in items:
+                if len(k) != 1:
+                    raise ValueError(f"`sequence_bias` keys are limited to a single token here (multi-token sequences are not "
+                                     f"supported), but {k} has {len(k)}")
+                bias[int(k[0])] = bias.get(int(k[0]), 0.0) + float(v)
+        st = kw.get("suppress_tokens")
+        if st is not None:
+            for t in list(st):
+                if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or t < 0:
+                    raise ValueError(f"`suppress_tokens` has to be a list of positive integers, but is {st}")
+                bias[int(t)] = float("-inf")
+        pens = []
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = kw.get(name)
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v)):
+                raise ValueError(f"`{name}` has to be a finite float, but is {v}")
+            pens.append(float(v or 0.0))
+        bias = {k: v for k, v in bias.items() if v != 0.0}
+        if len(bias) > MAX_LOGIT_BIAS:
+            raise ValueError(f"at most {MAX_LOGIT_BIAS} tokens can carry a bias, but {len(bias)} do")
+        if pens[0] == 0.0 and pens[1] == 0.0 and not min_new and not bias:
+            return None
+        return pens[0], pens[1], int(min_new or 0), bias
+
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, pixel_values=None, image_grid_thw=None,
                  mm_token_type_ids=None, image_keys=None, max_new_tokens: int = 20, do_sample: bool = False,
@@ -245,6 +300,7 @@ class ZoomEarthForConditionalGeneration:
             # (top_p = 0 keeps HF's min_tokens_to_keep = 1, the arg-max: the smallest positive value does the same)
             filt_kw = dict(top_k=int(top_k or 0), top_p=1.0 if top_p is None else max(float(top_p), 1e-37),
                            min_p=float(min_p or 0.0))
+        adjust = self._logit_adjust_request(kw)
         if do_sample and temperature is None:
             temperature = 1.0
         sample_kw = dict(do_sample=bool(do_sample), temperature=float(temperature or 1.0),
@@ -296,6 +352,8 @@ class ZoomEarthForConditionalGeneration:
                 self._chains.move_to_end(slot)
                 if logprobs is not None:
                     e.set_logprobs(slot, logprobs)  # (the reset / truncate above cleared the slot's previous request)
+                if adjust is not None:
+                    e.seq_set_logit_adjust(slot, *adjust)
                 outs.append(e.generate(slot, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw))
                 if logprobs is not None:
                     lps.append(e.chain_logprobs(slot, max_new_tokens))
@@ -316,6 +374,9 @@ class ZoomEarthForConditionalGeneration:
             if logprobs is not None:
                 for slot in slots:
                     e.set_logprobs(slot, logprobs)
+            if adjust is not None:
+                for slot in slots:
+                    e.seq_set_logit_adjust(slot, *adjust)
             outs = e.generate_batch(slots, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw)
             if logprobs is not None:
                 lps = e.chain_logprobs_batch(slots, logprobs, max_new_tokens)

@@ -45,6 +45,13 @@ class Request:
     # log-probabilities of the generated tokens (None = the scheduler's default, which is off; 0 = the chosen token only; 1..20 =
     # that many best alternatives as well)
     logprobs: Optional[int] = None
+    # logit adjustments of this request (None = the scheduler's default, which is off): OpenAI's presence / frequency penalties
+    # over the tokens the request generates, `logit_bias` {token id: bias} (-inf bans the token), and the EOS ids banned until
+    # min_new_tokens were generated; greedy schedulers honour them too
+    presence_penalty: Optional[float] = None
+    frequency_penalty: Optional[float] = None
+    logit_bias: Optional[dict] = None
+    min_new_tokens: Optional[int] = None
     # filled by the scheduler
     slot: int = -1
     n_prompt: int = 0
@@ -72,8 +79,14 @@ class ChainScheduler:
                  feature_cache: int = 64, min_admit: int = 1, max_wait_bursts: int = 2, share_prefix: bool = True,
                  min_shared: int = 64, reuse_generated: bool = True, overlap: Optional[bool] = None, hold_below: int = 0,
                  admit_chunk_rows: int = 0, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                 min_p: Optional[float] = None, logprobs: Optional[int] = None):
+                 min_p: Optional[float] = None, logprobs: Optional[int] = None, presence_penalty: Optional[float] = None,
+                 frequency_penalty: Optional[float] = None, logit_bias: Optional[dict] = None, min_new_tokens: Optional[int] = None):
         self.model, self.processor, self.engine = model, processor, model.engine
+        # Logit adjustments: the defaults of requests that name none (None = off).  Written into the slot's rows of the engine's
+        # tables next to the filter, with zero counts, for fresh slots and for follow-ups on a parked slot alike; requests with and
+        # without them share the same bursts.
+        self.presence_penalty, self.frequency_penalty = presence_penalty, frequency_penalty
+        self.logit_bias, self.min_new_tokens = logit_bias, min_new_tokens
         # Log-probabilities of generated tokens: the default of requests that name none (None = off).  Written into the slot's row
         # of the engine's table next to the filter; requests with and without them share the same bursts.
         self.logprobs = logprobs
@@ -559,6 +572,17 @@ class ChainScheduler:
         if n is not None:
             self.engine.set_logprobs(req.slot, n)
 
+    def _set_logit_adjust(self, req) -> None:
+        """The request's logit adjustments into its slot (cleared, like the filter, by the slot's reset / truncate / prefix copy),
+        before its first draw; off values launch nothing."""
+        def pick(name):
+            v = getattr(req, name, None)
+            return getattr(self, name) if v is None else v
+        presence, frequency = float(pick("presence_penalty") or 0.0), float(pick("frequency_penalty") or 0.0)
+        bias, min_new = pick("logit_bias") or {}, int(pick("min_new_tokens") or 0)
+        if presence != 0.0 or frequency != 0.0 or bias or min_new > 0:
+            self.engine.seq_set_logit_adjust(req.slot, presence, frequency, min_new, bias)
+
     @staticmethod
     def _attach_logprobs(req, lp, n: int) -> None:
         logps, ids, tlps = lp
@@ -587,6 +611,7 @@ class ChainScheduler:
         for req, ids, keys in self._ready[:keep_from]:
             self._set_filter(req)
             self._set_logprobs(req)
+            self._set_logit_adjust(req)
             self.engine.chain_begin(req.slot, self.params, req.stream_id)
             self.live[req.slot] = _Live(req, ids, keys)
             self.stats["admitted"] += 1

@@ -7,6 +7,8 @@ Request: the subset that client sends -- `messages` with `role` in {system, user
 string or a list of `{"type": "text", "text": ...}` / `{"type": "image_url", "image_url": {"url": "data:image/...;
 base64,..."}}` items, plus `max_tokens`, `temperature`, `seed`, `top_p` and the vLLM extensions `top_k` (-1 / 0 = off) and
 `min_p` (`n` must be 1, `stream` is not offered); the three filters apply to sampled requests, each request its own.
+`presence_penalty` / `frequency_penalty` ([-2, 2]), `logit_bias` (at most 300 `"id": bias` entries in [-100, 100]) and vLLM's
+`min_tokens` adjust every step's logits on the device, each request its own values, greedy requests included.
 `logprobs: true` (with `top_logprobs: 0..20`) adds `choices[0].logprobs.content`, one entry per completion token, from the
 decode step's own logits (the model's distribution, before repetition penalty, temperature and filters).
 Prompt: the Qwen2.5-VL chat template (`<|im_start|>role\\n ... <|im_end|>\\n`, an image item becomes
@@ -85,7 +87,15 @@ def build_prompt(messages):
 
 class _Parsed:
     __slots__ = ("req", "prompt", "pil_images", "max_tokens", "sample", "temperature", "seed", "future", "top_k", "top_p",
-                 "min_p", "logprobs")
+                 "min_p", "logprobs", "presence_penalty", "frequency_penalty", "logit_bias", "min_tokens")
+
+    def adjusts(self) -> bool:
+        return bool(self.presence_penalty or self.frequency_penalty or self.logit_bias or self.min_tokens)
+
+    def adjust_kw(self) -> dict:
+        """generate()'s keyword arguments of the request's logit adjustments (none when they are all off)."""
+        return dict(presence_penalty=self.presence_penalty, frequency_penalty=self.frequency_penalty, logit_bias=self.logit_bias,
+                    min_new_tokens=self.min_tokens) if self.adjusts() else {}
 
 
 class ChatServer:
@@ -143,6 +153,44 @@ class ChatServer:
             if not (0 <= top <= 20):
                 raise BadRequest(f"top_logprobs must be in [0, 20], got {top}")
         p.logprobs = (int(top or 0) if lp else None)
+        # OpenAI's `presence_penalty` / `frequency_penalty` ([-2, 2]) and `logit_bias` ({"id": bias in [-100, 100]}, at most 300
+        # entries), vLLM's `min_tokens`: applied on the device to every step's logits, greedy requests included
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = req.get(name)
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float))):
+                raise BadRequest(f"{name} must be a number, got {v!r}")
+            v = 0.0 if v is None else float(v)
+            if not (-2.0 <= v <= 2.0):
+                raise BadRequest(f"{name} must be in [-2, 2], got {v}")
+            setattr(p, name, v)
+        lb = req.get("logit_bias")
+        p.logit_bias = {}
+        if lb is not None:
+            if not isinstance(lb, dict):
+                raise BadRequest(f"logit_bias must be an object of token id -> bias, got {lb!r}")
+            if len(lb) > 300:
+                raise BadRequest(f"logit_bias must have at most 300 entries, got {len(lb)}")
+            vocab = int(self.model.config.text.vocab_size)
+            for k, v in lb.items():
+                try:
+                    tid = int(k)
+                except (TypeError, ValueError) as ex:
+                    raise BadRequest(f"logit_bias keys must be token ids, got {k!r}") from ex
+                if not (0 <= tid < vocab):
+                    raise BadRequest(f"logit_bias token id must be in [0, {vocab}), got {tid}")
+                if isinstance(v, bool) or not isinstance(v, (int, float)):
+                    raise BadRequest(f"logit_bias values must be numbers, got {v!r}")
+                if not (-100.0 <= float(v) <= 100.0):
+                    raise BadRequest(f"logit_bias values must be in [-100, 100], got {v}")
+                if tid in p.logit_bias:
+                    raise BadRequest(f"logit_bias names token id {tid} twice")
+                p.logit_bias[tid] = float(v)
+        mt = req.get("min_tokens")
+        if mt is not None and (isinstance(mt, bool) or not isinstance(mt, int)):
+            raise BadRequest(f"min_tokens must be an integer, got {mt!r}")
+        if mt is not None and mt < 0:
+            raise BadRequest(f"min_tokens must be >= 0, got {mt}")
+        p.min_tokens = int(mt or 0)
         p.future = None
         return p
 
@@ -184,7 +232,8 @@ class ChatServer:
         return res
 
     def _run(self, batch):
-        """One processor + generate call for the parsed requests of `batch` (all greedy, or a single request)."""
+        """One processor + generate call for the parsed requests of `batch` (all greedy without logit adjustments, or a single
+        request: generate() gives every row of a call the same sampling settings and adjustments)."""
         from .image import DeviceImage
 
         with self._lock:
@@ -198,6 +247,7 @@ class ChatServer:
             kw = dict(max_new_tokens=max(p.max_tokens for p in batch), num_beams=1, do_sample=p0.sample)
             if p0.sample:
                 kw.update(temperature=p0.temperature, top_k=p0.top_k, top_p=p0.top_p, min_p=p0.min_p, seed=p0.seed)
+            kw.update(p0.adjust_kw())
             want = [p.logprobs for p in batch if p.logprobs is not None]
             if not want:
                 out = self.model.generate(**inputs, **kw)[:, width:].tolist()
@@ -218,6 +268,8 @@ class ChatServer:
         batch = [self._parse(r) for r in reqs]
         if any(p.sample for p in batch) and len(batch) > 1:
             raise BadRequest("sampled requests are not batched")
+        if any(p.adjusts() for p in batch) and len(batch) > 1:
+            raise BadRequest("requests with presence_penalty / frequency_penalty / logit_bias / min_tokens are not batched")
         if len(batch) > self.max_batch:
             raise BadRequest(f"batch of {len(batch)} exceeds max_seqs = {self.max_batch}")
         return self._run(batch)
@@ -291,7 +343,9 @@ class ChatServer:
                         imgs = [DeviceImage.from_pil(im, self.model.engine) for im in p.pil_images]
                         budget = max(1, min(p.max_tokens, self.model.engine.max_ctx))  # per request: never fails its batch
                         sched.submit(Request(prompt=p.prompt, images=imgs, max_new_tokens=budget, on_done=done,
-                                             on_error=failed, logprobs=p.logprobs))
+                                             on_error=failed, logprobs=p.logprobs, presence_penalty=p.presence_penalty,
+                                             frequency_penalty=p.frequency_penalty, logit_bias=p.logit_bias,
+                                             min_new_tokens=p.min_tokens))
                     except Exception as ex:
                         failed(None, ex)
                 if sched.busy():
@@ -328,7 +382,9 @@ class ChatServer:
                             imgs = [DeviceImage.from_pil(im, self.model.engine) for im in p.pil_images]
                             ss.submit(Request(prompt=p.prompt, images=imgs, max_new_tokens=max(1, min(p.max_tokens, self.model.engine.max_ctx)),
                                               stream_id=0, on_done=done, on_error=failed, top_k=p.top_k, top_p=p.top_p,
-                                              min_p=p.min_p, logprobs=p.logprobs))
+                                              min_p=p.min_p, logprobs=p.logprobs, presence_penalty=p.presence_penalty,
+                                              frequency_penalty=p.frequency_penalty, logit_bias=p.logit_bias,
+                                              min_new_tokens=p.min_tokens))
                         except Exception as ex:
                             failed(None, ex)
                     try:
