@@ -402,6 +402,50 @@ int ze_op_logit_adjust(ze_engine* e, const float* logits, int rows, int vocab, i
                        const float* presence, const float* frequency, const int32_t* eos_masked, const int32_t* bias_offsets,
                        const int32_t* bias_ids, const float* bias_vals, float* out, void* stream);
 
+/* Token rules of one chain: the rules that depend on the SEQUENCE of its tokens (replaces: HF's NoRepeatNGramLogitsProcessor
+ * (`no_repeat_ngram_size`) and NoBadWordsLogitsProcessor (`bad_words_ids`), HF:generation/logits_process.py; HF's
+ * StopStringCriteria (`stop_strings`), HF:generation/stopping_criteria.py; `stop` of the OpenAI-compatible back-end
+ * src/eval/infer_vllm.py talks to and vLLM's `stop_token_ids`).  The HISTORY of a chain is context_ids (normally its prompt)
+ * followed by the ids it generated since its prefill.
+ *   no_repeat_ngram  0 = off; n in 1..ZE_MAX_RULE_LEN: before every draw, each id that followed an occurrence of the history's
+ *                    last n - 1 ids anywhere in the history is -inf (n = 1: every id of the history).
+ *   ban_seqs         packed records `len, id0 .. id(len-1)`: a one-id record is always -inf; a record of m ids has its last id
+ *                    -inf whenever the history's last m - 1 ids equal its first m - 1 (a prompt that ends in the prefix bans the
+ *                    first generated token).
+ *   stop_seqs        same packing: after a token was accepted, a whole record found at the tail of the GENERATED ids finishes
+ *                    the chain (st.finished, exactly as an EOS does: the matched ids stay, pad follows).  A match never reaches
+ *                    into the context, is ignored while fewer than the min_new_tokens of the chain's logit-adjust request were
+ *                    generated (vLLM's order), and is NOT switched off by ignore_eos.
+ * The bans are written into the adjusted copy of the step's row (ze_seq_set_logit_adjust: a chain with bans has one), behind the
+ * additive terms and before the repetition penalty, temperature, filters and the draw -- -inf commutes with all of them, so the
+ * order equals HF's; greedy decoding honours them (such a chain stays off the folded arg-max).  Log-probabilities keep reporting
+ * the raw row.  ZE_ERR_INVALID for no_repeat_ngram outside [0, ZE_MAX_RULE_LEN], a list of more than ZE_MAX_RULE_INTS ints or
+ * ZE_MAX_RULE_WORDS records, a record of fewer than 1 or more than ZE_MAX_RULE_LEN ids or one that overruns its list, an id
+ * outside the vocabulary, n_context outside [0, max_ctx] -- the chain's request is then unchanged.  All-off values clear the
+ * request.  Set after the chain's prefill and before its first draw.  The arrays are host arrays; the lists travel as kernel
+ * arguments and the context as one copy on `stream` into per-slot device tables, so chains with and without rules share one
+ * burst and one captured graph.  Honoured by ze_generate, ze_generate_batch, ze_chain_begin and ze_decode_burst*.  Cleared
+ * wherever the sampling filter is (ze_seq_reset, ze_seq_truncate, ze_seq_copy_prefix into the slot).  While no chain of the
+ * engine has a request every step launches exactly what it launches without this entry.  Buffers come with the first request
+ * (lists: 2 x max_seqs x ZE_MAX_RULE_INTS x 4 B; with bans the adjusted rows of ze_seq_set_logit_adjust; with a context:
+ * max_seqs x max_ctx x 4 B); ZE_ERR_NOMEM if that fails, and the engine stays as it was. */
+#define ZE_MAX_RULE_INTS 1024 /* ints of one packed list of one chain */
+#define ZE_MAX_RULE_WORDS 64  /* records of one list */
+#define ZE_MAX_RULE_LEN 16    /* ids of one record, and the largest no_repeat_ngram */
+int ze_seq_set_token_rules(ze_engine* e, int seq, int no_repeat_ngram, const int32_t* stop_seqs, int n_stop_words,
+                           const int32_t* ban_seqs, int n_ban_words, const int32_t* context_ids, int n_context, void* stream);
+/* The two kernels alone on caller rows, every array on the device: logits / out_rows f32 [rows, ld] (ld >= vocab, out_rows !=
+ * logits; the columns beyond vocab are left alone); the history of row r is hist_ids[hist_offsets[r] .. hist_offsets[r + 1])
+ * (int32 [rows + 1]), its first n_context[r] ids the context; no_repeat_ngram int32 [rows]; the packed ban / stop records of row
+ * r are ban_seqs[ban_offsets[r] .. ban_offsets[r + 1]) / stop_seqs[stop_offsets[r] .. ]; min_new int32 [rows].  out_rows = logits
+ * with -inf at the banned ids (a row with neither n-gram nor records comes back identical); out_stop int32 [rows] = 1 where a
+ * stop record ends the generated ids and at least min_new[r] ids were generated.  Ids outside [0, vocab) ban nothing; a
+ * malformed record ends its list.  Asynchronous on `stream`. */
+int ze_op_token_rules(ze_engine* e, const float* logits, int rows, int vocab, int ld, const int32_t* hist_ids,
+                      const int32_t* hist_offsets, const int32_t* n_context, const int32_t* no_repeat_ngram, const int32_t* ban_seqs,
+                      const int32_t* ban_offsets, const int32_t* stop_seqs, const int32_t* stop_offsets, const int32_t* min_new,
+                      float* out_rows, int32_t* out_stop, void* stream);
+
 /* FP8 decode weights (BASELINE.json configs[4], "fp8 weights"): quantises the decoder's linear layers (and an untied
  * lm_head) to OCP E4M3 with one power-of-two scale per output row, REPLACES the bf16 copies by the dequantised
  * values (exactly representable) so that prefill and decode compute with identical weights, and switches the batch-1

@@ -144,6 +144,9 @@ _SIGS = {
     "ze_seq_set_logit_adjust": (C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                           C.c_int, _P]),
     "ze_op_logit_adjust": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ze_seq_set_token_rules": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                         C.POINTER(C.c_int32), C.c_int, _P]),
+    "ze_op_token_rules": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ze_weights_quantize_fp8": (C.c_int, [_P, _P]),
     "ze_set_fp8_activations": (C.c_int, [_P, C.c_int]),
     "ze_op_quantize_fp8": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),

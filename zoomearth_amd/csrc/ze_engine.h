@@ -168,6 +168,27 @@ struct ze_engine {
     int la_mode(int seq) const { return la_host[seq].on() ? la_mode() : 0; }
     ze_logit_adjust_bufs la_bufs() const { return ze_logit_adjust_bufs{la_dev, la_bias_ids, la_bias_vals, la_counts}; }
     std::vector<int> graph_adjust;  // la_mode(seq) the chain's graph was captured under
+    // Token rules (ze_seq_set_token_rules): tr_host is the truth, tr_dev the per-slot table the kernels read (ZE_TR_WORDS ints per
+    // slot, all zero = off), written in stream order by the setter; n_bans / n_stops = slots with n-gram or ban records / with
+    // stop records.  While both are 0 no step launches anything for them.  Allocated by the first request: tr_stop / tr_ban
+    // [max_seqs, ZE_MAX_RULE_INTS] (and, with bans, the adjusted rows la_rows); by the first request with a context: tr_ctx
+    // [max_seqs, max_ctx].
+    struct rules_host {
+        int ngram = 0, n_stop_ints = 0, n_stop_words = 0, n_ban_ints = 0, n_ban_words = 0, n_context = 0;
+        bool bans() const { return ngram > 0 || n_ban_words > 0; }
+        bool stops() const { return n_stop_words > 0; }
+        bool on() const { return bans() || stops(); }
+    };
+    std::vector<rules_host> tr_host;
+    int n_bans = 0, n_stops = 0;
+    int *tr_dev = nullptr, *tr_stop = nullptr, *tr_ban = nullptr, *tr_ctx = nullptr;
+    // what a captured step must have been captured with: bit 0 = adjusted copy + ban pass, bit 1 = stop pass, bit 2 = the
+    // context history exists (a kernel argument)
+    int tr_mode() const { return n_bans + n_stops > 0 ? (n_bans > 0) | (n_stops > 0) << 1 | (tr_ctx != nullptr) << 2 : 0; }
+    // (of a single-chain step: by THAT chain's request)
+    int tr_mode(int seq) const { return tr_host[seq].on() ? (int)tr_host[seq].bans() | (int)tr_host[seq].stops() << 1 | (tr_ctx != nullptr) << 2 : 0; }
+    ze_token_rule_bufs tr_bufs() const { return ze_token_rule_bufs{tr_dev, tr_stop, tr_ban, tr_ctx}; }
+    std::vector<int> graph_rules;  // tr_mode(seq) the chain's graph was captured under
     std::vector<hipGraphExec_t> graphs;
     std::vector<float> graph_penalty;
     std::vector<int> graph_ignore_eos;
@@ -239,7 +260,7 @@ struct ze_engine {
     int* bseq = nullptr;
     float *blogits = nullptr, *bpartial = nullptr, *bsample = nullptr;
     ze_seq_dev* bstate_host = nullptr;  // pinned
-    std::map<std::tuple<int, float, int, float, unsigned long long, int, int, int, int>, hipGraphExec_t> bgraphs;  // captured batched decode step per batch size (and attention grid)
+    std::map<std::tuple<int, float, int, float, unsigned long long, int, int, int, int, int>, hipGraphExec_t> bgraphs;  // captured batched decode step per batch size (and attention grid)
     int live_parts = 0;  // 192-key parts the longest chain of the current batch needs (the attention grid's extent); 0 = all
 
     // timers

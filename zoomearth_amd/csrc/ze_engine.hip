@@ -227,7 +227,7 @@ static int init_tables(ze_engine* e) {
     return 0;
 }
 
-extern "C" int ze_version(void) { return 103; }
+extern "C" int ze_version(void) { return 104; }
 
 extern "C" const char* ze_last_error(const ze_engine* e) { return e ? e->err.c_str() : ze_global_error.c_str(); }
 
@@ -313,6 +313,9 @@ extern "C" int ze_engine_create(const ze_config* cfg, int device_id, ze_engine**
     e->graph_adjust.assign(c.max_seqs, 0);
     e->la_host.assign(c.max_seqs, ze_engine::adjust_host{});
     chk(dev_alloc(e, &e->la_dev, (size_t)c.max_seqs * ZE_LA_WORDS));  // all zero = off
+    e->graph_rules.assign(c.max_seqs, 0);
+    e->tr_host.assign(c.max_seqs, ze_engine::rules_host{});
+    chk(dev_alloc(e, &e->tr_dev, (size_t)c.max_seqs * ZE_TR_WORDS));  // all zero = off
 
     // front-end workspace: horizontal-pass image (box_h x out_w) and resized image
     const size_t side = (size_t)std::max(c.max_tile_side, 1024);
@@ -474,7 +477,8 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
                    e->dlogits, e->dpartial, e->dsample, e->atickets, e->gslab, e->gtickets, e->pslab, e->ptickets, e->bh, e->by, e->bqkv, e->bo, e->ba, e->bseq, e->bmate, e->blogits, e->bpartial, e->bsample, e->arena8, e->arena_f, e->arena_f8,
                    e->ty8, e->ty8_scale, e->damax, e->ty8p, e->ty8p_scale, e->filt_dev, e->cut_dev,
                    e->lp_dev, e->lp_tok, e->lp_top_ids, e->lp_top_lps, e->xl_dev,
-                   e->la_dev, e->la_bias_ids, e->la_bias_vals, e->la_rows, e->la_counts};
+                   e->la_dev, e->la_bias_ids, e->la_bias_vals, e->la_rows, e->la_counts,
+                   e->tr_dev, e->tr_stop, e->tr_ban, e->tr_ctx};
     for (void* p : dev)
         if (p) hipFree(p);
     if (e->pfx_dev) hipFree(e->pfx_dev);

@@ -501,6 +501,22 @@ static bool la_alloc(T** p, size_t count) {
     return false;
 }
 
+// the adjusted rows and the bias lists, on first use (a logit-adjust request, or token rules with bans)
+static int ensure_adjusted_rows(ze_engine* e) {
+    if (e->la_rows) return ZE_OK;
+    const ze_config& c = e->cfg;
+    int* ids = nullptr;
+    float *vals = nullptr, *rows = nullptr;
+    if (!la_alloc(&ids, (size_t)c.max_seqs * ZE_MAX_LOGIT_BIAS) || !la_alloc(&vals, (size_t)c.max_seqs * ZE_MAX_LOGIT_BIAS) ||
+        !la_alloc(&rows, ((size_t)c.max_seqs + 1) * c.vocab)) {
+        if (ids) hipFree(ids);
+        if (vals) hipFree(vals);
+        return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the adjusted-row buffer failed");
+    }
+    e->la_bias_ids = ids, e->la_bias_vals = vals, e->la_rows = rows;
+    return ZE_OK;
+}
+
 extern "C" int ze_seq_set_logit_adjust(ze_engine* e, int seq, float presence_penalty, float frequency_penalty, int min_new_tokens,
                                        const int32_t* bias_ids, const float* bias_vals, int n_bias, void* stream) {
     ZE_TRY(check_seq(e, seq));
@@ -529,17 +545,7 @@ extern "C" int ze_seq_set_logit_adjust(ze_engine* e, int seq, float presence_pen
     hipSetDevice(e->device);
     hipStream_t s = (hipStream_t)stream;
     // buffers, on first use: a failed allocation leaves the engine as it was
-    if (h.on() && !e->la_rows) {
-        int* ids = nullptr;
-        float *vals = nullptr, *rows = nullptr;
-        if (!la_alloc(&ids, (size_t)c.max_seqs * ZE_MAX_LOGIT_BIAS) || !la_alloc(&vals, (size_t)c.max_seqs * ZE_MAX_LOGIT_BIAS) ||
-            !la_alloc(&rows, ((size_t)c.max_seqs + 1) * c.vocab)) {
-            if (ids) hipFree(ids);
-            if (vals) hipFree(vals);
-            return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the adjusted-row buffer failed");
-        }
-        e->la_bias_ids = ids, e->la_bias_vals = vals, e->la_rows = rows;
-    }
+    if (h.on()) ZE_TRY(ensure_adjusted_rows(e));
     if (h.penalties() && !e->la_counts) {
         uint16_t* counts = nullptr;
         if (!la_alloc(&counts, (size_t)c.max_seqs * c.vocab)) return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the token counts failed");
@@ -553,16 +559,107 @@ extern "C" int ze_seq_set_logit_adjust(ze_engine* e, int seq, float presence_pen
 
 // The rows the sampler of a step reads: the step's own while no chain of it has a request (the step then launches what it always
 // did), else their adjusted copy.  seq_ids = null: the one chain `slot0`, whose row `logits` is.
+// A chain with bans (token rules) counts as adjusted: the ban pass writes -inf into its copy behind the adjust kernel, which
+// leaves the row of an all-zero request untouched.
 static const float* adjusted_rows(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s) {
-    if (seq_ids ? e->n_adjust == 0 : !e->la_host[slot0].on()) return logits;
+    const bool bans = seq_ids ? e->n_bans > 0 : e->tr_host[slot0].bans();
+    if (!bans && (seq_ids ? e->n_adjust == 0 : !e->la_host[slot0].on())) return logits;
     float* out = seq_ids ? e->la_rows : e->la_rows + (size_t)e->cfg.max_seqs * e->cfg.vocab;
     ze_launch_chain_logit_adjust(logits, e->cfg.vocab, e->st_dev, seq_ids, slot0, n, e->la_bufs(), e->eos_dev, e->cfg.n_eos, out, s);
+    if (bans) ze_launch_chain_token_ban(out, e->cfg.vocab, e->st_dev, seq_ids, slot0, n, e->tr_bufs(), e->out_tokens, e->cfg.max_ctx, s);
     return out;
 }
 // after the token of a step was accepted, next to launch_logprobs: the chains' counts
 static void launch_counts(ze_engine* e, const int* seq_ids, int slot0, int n, hipStream_t s) {
     if (seq_ids ? e->n_adjust == 0 : !e->la_host[slot0].on()) return;
     ze_launch_count_tokens(e->st_dev, seq_ids, slot0, n, e->la_bufs(), e->cfg.vocab, s);
+}
+
+// ---- token rules (ze_engine::tr_host is the truth, ze_token_rules.hip the kernels)
+static void write_rules(ze_engine* e, int seq, const ze_engine::rules_host& h, const int32_t* stop, const int32_t* ban, hipStream_t s) {
+    const ze_engine::rules_host was = e->tr_host[seq];
+    e->tr_host[seq] = h;
+    e->n_bans += (int)h.bans() - (int)was.bans();
+    e->n_stops += (int)h.stops() - (int)was.stops();
+    if (!was.on() && !h.on()) return;
+    // the lists travel as kernel arguments, 128 words a launch
+    if (h.n_stop_ints > 0) ze_launch_set_ints(e->tr_stop + (size_t)seq * ZE_MAX_RULE_INTS, stop, h.n_stop_ints, s);
+    if (h.n_ban_ints > 0) ze_launch_set_ints(e->tr_ban + (size_t)seq * ZE_MAX_RULE_INTS, ban, h.n_ban_ints, s);
+    ze_launch_set_token_rules(e->tr_dev, seq, h.ngram, h.n_stop_ints, h.n_stop_words, h.n_ban_ints, h.n_ban_words, h.n_context, s);
+}
+// the slot goes to another chain (wherever its filter is cleared): it never inherits a request.  Nothing is launched for a slot
+// that has none.
+static void clear_rules(ze_engine* e, int seq, hipStream_t s) {
+    if (e->tr_host[seq].on()) write_rules(e, seq, ze_engine::rules_host{}, nullptr, nullptr, s);
+}
+
+// ints of a packed list of n_words records (len, id0 .. id(len-1), ...), or -1 with the message set
+static int check_records(ze_engine* e, const int32_t* seqs, int n_words, const char* what) {
+    const auto bad = [&](const char* why) {
+        ze_fail(e, ZE_ERR_INVALID, (std::string(what) + ": " + why).c_str());
+        return -1;
+    };
+    if (n_words < 0 || n_words > ZE_MAX_RULE_WORDS) return bad("at most 64 records");
+    if (n_words > 0 && !seqs) return bad("null list");
+    int off = 0;
+    for (int w = 0; w < n_words; ++w) {
+        if (off >= ZE_MAX_RULE_INTS) return bad("a packed list holds at most 1024 ints");
+        const int len = seqs[off];
+        if (len < 1 || len > ZE_MAX_RULE_LEN) return bad("a record holds 1 to 16 token ids");
+        if (off + 1 + len > ZE_MAX_RULE_INTS) return bad("a packed list holds at most 1024 ints");
+        for (int i = 0; i < len; ++i)
+            if (seqs[off + 1 + i] < 0 || seqs[off + 1 + i] >= e->cfg.vocab) return bad("token id out of range");
+        off += 1 + len;
+    }
+    return off;
+}
+
+extern "C" int ze_seq_set_token_rules(ze_engine* e, int seq, int no_repeat_ngram, const int32_t* stop_seqs, int n_stop_words,
+                                      const int32_t* ban_seqs, int n_ban_words, const int32_t* context_ids, int n_context, void* stream) {
+    ZE_TRY(check_seq(e, seq));
+    const ze_config& c = e->cfg;
+    if (no_repeat_ngram < 0 || no_repeat_ngram > ZE_MAX_RULE_LEN) return ze_fail(e, ZE_ERR_INVALID, "no_repeat_ngram must be in [0, 16] (0 = off)");
+    const int stop_ints = check_records(e, stop_seqs, n_stop_words, "stop_seqs");
+    if (stop_ints < 0) return ZE_ERR_INVALID;
+    const int ban_ints = check_records(e, ban_seqs, n_ban_words, "ban_seqs");
+    if (ban_ints < 0) return ZE_ERR_INVALID;
+    if (n_context < 0 || n_context > c.max_ctx) return ze_fail(e, ZE_ERR_INVALID, "n_context must be in [0, max_ctx]");
+    if (n_context > 0 && !context_ids) return ze_fail(e, ZE_ERR_INVALID, "null context_ids");
+    for (int i = 0; i < n_context; ++i)
+        if (context_ids[i] < 0 || context_ids[i] >= c.vocab) return ze_fail(e, ZE_ERR_INVALID, "context token id out of range");
+    ze_engine::rules_host h;
+    h.ngram = no_repeat_ngram, h.n_stop_ints = stop_ints, h.n_stop_words = n_stop_words, h.n_ban_ints = ban_ints, h.n_ban_words = n_ban_words;
+    h.n_context = h.bans() ? n_context : 0;  // (stop records never look at the context)
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    // buffers, on first use: a failed allocation leaves the engine as it was
+    if (h.bans()) ZE_TRY(ensure_adjusted_rows(e));
+    if (h.on() && !e->tr_stop) {
+        int *st = nullptr, *bn = nullptr;
+        if (!la_alloc(&st, (size_t)c.max_seqs * ZE_MAX_RULE_INTS) || !la_alloc(&bn, (size_t)c.max_seqs * ZE_MAX_RULE_INTS)) {
+            if (st) hipFree(st);
+            return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the token-rule lists failed");
+        }
+        e->tr_stop = st, e->tr_ban = bn;
+    }
+    if (h.n_context > 0 && !e->tr_ctx) {
+        int* ctx = nullptr;
+        if (!la_alloc(&ctx, (size_t)c.max_seqs * c.max_ctx)) return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the context history failed");
+        e->tr_ctx = ctx;
+    }
+    // (a copy from pageable memory has left the caller's array when the call returns, and is ordered on the stream)
+    if (h.n_context > 0)
+        ZE_HIP(hipMemcpyAsync(e->tr_ctx + (size_t)seq * c.max_ctx, context_ids, (size_t)h.n_context * sizeof(int), hipMemcpyHostToDevice, s));
+    write_rules(e, seq, h, stop_seqs, ban_seqs, s);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
+// after the token of a step was accepted, next to launch_logprobs / launch_counts: a stop record at the tail of the generated ids
+// finishes its chain
+static void launch_stops(ze_engine* e, const int* seq_ids, int slot0, int n, hipStream_t s) {
+    if (seq_ids ? e->n_stops == 0 : !e->tr_host[slot0].stops()) return;
+    ze_launch_chain_token_stop(e->st_dev, seq_ids, slot0, n, e->tr_bufs(), e->la_dev, e->out_tokens, e->cfg.max_ctx, s);
 }
 
 extern "C" int ze_seq_reset(ze_engine* e, int seq, void* stream) {
@@ -578,6 +675,7 @@ extern "C" int ze_seq_reset(ze_engine* e, int seq, void* stream) {
     clear_filter(e, seq, s);
     clear_logprobs(e, seq, s);
     clear_adjust(e, seq, s);
+    clear_rules(e, seq, s);
     return push_state(e, seq, s, 0, 0, 0);
 }
 
@@ -640,6 +738,7 @@ extern "C" int ze_seq_truncate(ze_engine* e, int seq, int keep_len, void* stream
     clear_filter(e, seq, (hipStream_t)stream);
     clear_logprobs(e, seq, (hipStream_t)stream);
     clear_adjust(e, seq, (hipStream_t)stream);
+    clear_rules(e, seq, (hipStream_t)stream);
     return push_state(e, seq, (hipStream_t)stream, 0, 0, 0);
 }
 
@@ -675,6 +774,7 @@ extern "C" int ze_seq_copy_prefix(ze_engine* e, int dst_seq, int src_seq, int n_
     clear_filter(e, dst_seq, s);
     clear_logprobs(e, dst_seq, s);
     clear_adjust(e, dst_seq, s);
+    clear_rules(e, dst_seq, s);
     return push_state(e, dst_seq, s, 0, 0, 0);
 }
 
@@ -1176,7 +1276,7 @@ int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int ignore_eos,
     a.D = hd;
     // greedy: the arg-max partials come out of the lm_head launch itself (knob 14 = 1: the separate partial kernel)
     // (a chain with a logit-adjust request keeps off it: the folded arg-max never sees the row)
-    const bool folded = sample && so.temperature <= 0.f && ze_gemv_knobs[14] != 1 && !e->la_host[seq].on();
+    const bool folded = sample && so.temperature <= 0.f && ze_gemv_knobs[14] != 1 && !e->la_host[seq].on() && !e->tr_host[seq].bans();
     if (folded) {
         a.seen = e->seen + (size_t)seq * c.vocab;
         a.penalty = penalty;
@@ -1195,6 +1295,7 @@ int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int ignore_eos,
     if (sample) {
         launch_logprobs(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s);
         launch_counts(e, nullptr, seq, 1, s);
+        launch_stops(e, nullptr, seq, 1, s);
     }
     ZE_KCHECK();
     return ZE_OK;
@@ -1332,6 +1433,7 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
                      pen, st, e->eos_dev, c.n_eos, c.pad_token_id, ign, 0, dev_out, e->dsample, so, s);
     launch_logprobs(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s);
     launch_counts(e, nullptr, seq, 1, s);
+    launch_stops(e, nullptr, seq, 1, s);
     ze_timer_end(e, t_s, s);
     ZE_KCHECK();
 
@@ -1341,7 +1443,8 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
         if (!e->graphs[seq] || e->graph_penalty[seq] != pen || e->graph_ignore_eos[seq] != ign ||
             e->graph_variant[seq] != (int)ze_tune_epoch || e->graph_temperature[seq] != so.temperature ||
             e->graph_seed[seq] != so.seed || e->graph_filters[seq] != (int)(so.filt != nullptr) ||
-            e->graph_logprobs[seq] != e->lp_mode() || e->graph_adjust[seq] != e->la_mode(seq)) {
+            e->graph_logprobs[seq] != e->lp_mode() || e->graph_adjust[seq] != e->la_mode(seq) ||
+            e->graph_rules[seq] != e->tr_mode(seq)) {
             if (e->graphs[seq]) {
                 hipGraphExecDestroy(e->graphs[seq]);
                 e->graphs[seq] = nullptr;
@@ -1368,6 +1471,7 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
             e->graph_filters[seq] = so.filt != nullptr;
             e->graph_logprobs[seq] = e->lp_mode();
             e->graph_adjust[seq] = e->la_mode(seq);
+            e->graph_rules[seq] = e->tr_mode(seq);
         }
         gexec = e->graphs[seq];
     }
@@ -1706,6 +1810,7 @@ static int enqueue_decode_batch(ze_engine* e, int n, float penalty, int ignore_e
     if (sample) {
         launch_logprobs(e, e->blogits, e->bseq, 0, n, s);
         launch_counts(e, e->bseq, 0, n, s);
+        launch_stops(e, e->bseq, 0, n, s);
     }
     ZE_KCHECK();
     return ZE_OK;
@@ -1739,7 +1844,7 @@ extern "C" int ze_decode_batch(ze_engine* e, const int32_t* seqs, int n, const i
 // batch size and sampling setting serves every composition); nullptr in *out = run eagerly.
 static int batch_step_graph(ze_engine* e, int na, float pen, int ign, const ze_sample_opts& bso, hipGraphExec_t* out) {
     auto key = std::make_tuple(na, pen, ign, bso.temperature, bso.seed, e->live_parts * 64 + e->live_parts_long, (int)(bso.filt != nullptr),
-                               e->lp_mode(), e->la_mode());
+                               e->lp_mode(), e->la_mode(), e->tr_mode());
     if (e->bgraph_epoch != ze_tune_epoch) {
         for (auto& kv : e->bgraphs) hipGraphExecDestroy(kv.second);
         e->bgraphs.clear();
@@ -1795,6 +1900,7 @@ static int begin_chain(ze_engine* e, int q, const ze_gen_params* p, float pen, i
                      e->st_dev + q, e->eos_dev, c.n_eos, c.pad_token_id, ign, 0, e->out_tokens + (size_t)q * c.max_ctx, e->dsample, so, s);
     launch_logprobs(e, e->dlogits + (size_t)q * c.vocab, nullptr, q, 1, s);
     launch_counts(e, nullptr, q, 1, s);
+    launch_stops(e, nullptr, q, 1, s);
     ZE_KCHECK();
     return ZE_OK;
 }
@@ -2079,6 +2185,25 @@ extern "C" int ze_op_logit_adjust(ze_engine* e, const float* logits, int rows, i
     hipSetDevice(e->device);
     ze_launch_logit_adjust(logits, rows, vocab, ld, counts, presence, frequency, eos_masked, bias_offsets, bias_ids, bias_vals, e->eos_dev,
                            e->cfg.n_eos, out, (hipStream_t)stream);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
+extern "C" int ze_op_token_rules(ze_engine* e, const float* logits, int rows, int vocab, int ld, const int32_t* hist_ids,
+                                 const int32_t* hist_offsets, const int32_t* n_context, const int32_t* no_repeat_ngram,
+                                 const int32_t* ban_seqs, const int32_t* ban_offsets, const int32_t* stop_seqs, const int32_t* stop_offsets,
+                                 const int32_t* min_new, float* out_rows, int32_t* out_stop, void* stream) {
+    if (!e || !logits || !hist_ids || !hist_offsets || !n_context || !no_repeat_ngram || !ban_seqs || !ban_offsets || !stop_seqs ||
+        !stop_offsets || !min_new || !out_rows || !out_stop || out_rows == logits)
+        return ze_fail(e, ZE_ERR_INVALID, "bad token_rules arguments");
+    if (rows < 0 || vocab <= 0 || ld < vocab) return ze_fail(e, ZE_ERR_INVALID, "rows >= 0, vocab > 0 and ld >= vocab");
+    if (rows == 0) return ZE_OK;
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    ZE_HIP(hipMemcpy2DAsync(out_rows, (size_t)ld * sizeof(float), logits, (size_t)ld * sizeof(float), (size_t)vocab * sizeof(float), rows,
+                            hipMemcpyDeviceToDevice, s));
+    ze_launch_token_ban(out_rows, rows, vocab, ld, hist_ids, hist_offsets, n_context, no_repeat_ngram, ban_seqs, ban_offsets, s);
+    ze_launch_token_stop(rows, hist_ids, hist_offsets, n_context, stop_seqs, stop_offsets, min_new, out_stop, s);
     ZE_KCHECK();
     return ZE_OK;
 }

@@ -377,4 +377,29 @@ void ze_launch_count_tokens(const ze_seq_dev* st, const int* seq_ids, int slot0,
                             hipStream_t s);
 void ze_launch_set_logit_adjust(int* table, int slot, float presence, float frequency, int min_new_tokens, int n_bias,
                                 hipStream_t s);
+// ---- per-chain token rules (ze_token_rules.hip)
+#define ZE_TR_WORDS 8  // ints per slot of the request table: no_repeat_ngram, stop ints, stop records, ban ints, ban records, n_context, 0, 0
+// the engine's per-slot request table, packed record lists and context history (ctx: null until the first request with a context)
+struct ze_token_rule_bufs {
+    const int* table = nullptr;  // [slots, ZE_TR_WORDS]
+    const int* stop = nullptr;   // [slots, ZE_MAX_RULE_INTS] packed records: len, id0 .. id(len-1), ...
+    const int* ban = nullptr;    // [slots, ZE_MAX_RULE_INTS]
+    const int* ctx = nullptr;    // [slots, max_ctx]
+};
+// unit forms, everything on the device: the history of row r is hist[hist_off[r] .. hist_off[r + 1]), its first n_ctx[r] ids the
+// context; the packed records of row r are list[list_off[r] .. list_off[r + 1]).  Ban pass: -inf into rows [n, ld] in place.
+// Stop pass: out_stop[r] = 1 when a whole record ends the generated ids and at least min_new[r] were generated, else 0.
+void ze_launch_token_ban(float* rows, int n, int vocab, int ld, const int* hist, const int* hist_off, const int* n_ctx, const int* ngram,
+                         const int* ban, const int* ban_off, hipStream_t s);
+void ze_launch_token_stop(int n, const int* hist, const int* hist_off, const int* n_ctx, const int* stop, const int* stop_off,
+                          const int* min_new, int* out_stop, hipStream_t s);
+// chain forms: row b is chain slot seq_ids ? seq_ids[b] : slot0; the history is the slot's context, then out_tokens[slot, :n_gen].
+// Ban pass before the sampler of a step, on the rows it reads ([n, vocab]); chains without bans and finished chains are left
+// alone.  Stop pass after the token was accepted: sets st[slot].finished (never clears it; la_table word 2 = min_new_tokens).
+void ze_launch_chain_token_ban(float* rows, int vocab, ze_seq_dev* st, const int* seq_ids, int slot0, int n, const ze_token_rule_bufs& tr,
+                               const int* out_tokens, int max_ctx, hipStream_t s);
+void ze_launch_chain_token_stop(ze_seq_dev* st, const int* seq_ids, int slot0, int n, const ze_token_rule_bufs& tr, const int* la_table,
+                                const int* out_tokens, int max_ctx, hipStream_t s);
+void ze_launch_set_token_rules(int* table, int slot, int ngram, int n_stop_ints, int n_stop_words, int n_ban_ints, int n_ban_words,
+                               int n_context, hipStream_t s);
 void ze_launch_numeric_helpers(const float* x, const float* y, uint32_t* out, uint32_t* out2, int n, hipStream_t s);

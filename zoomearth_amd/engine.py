@@ -17,6 +17,17 @@ from .config import ModelConfig
 
 MAX_TOP_LOGPROBS = 20  # ZE_MAX_TOP_LOGPROBS (OpenAI's cap on top_logprobs)
 MAX_LOGIT_BIAS = 512   # ZE_MAX_LOGIT_BIAS (pairs of one chain's bias list)
+MAX_RULE_INTS, MAX_RULE_WORDS, MAX_RULE_LEN = 1024, 64, 16   # ZE_MAX_RULE_* (token rules: ints of a packed list, records, ids of a record)
+
+
+def pack_records(records) -> np.ndarray:
+    """Token-id sequences as the packed records of ze_seq_set_token_rules: len, id0 .. id(len-1), ..."""
+    out = []
+    for r in records:
+        r = [int(t) for t in r]
+        out.append(len(r))
+        out.extend(r)
+    return np.asarray(out, dtype=np.int32)
 _NP2ZE = {np.dtype(np.float32): _lib.ZE_F32, np.dtype(np.float16): _lib.ZE_F16}
 
 
@@ -387,6 +398,54 @@ class Engine:
                                                 self._stream()))
         self._keep = (pr, fr, em, off_d, ids_d, vals_d, counts)   # (the launch is asynchronous: alive until the next one)
         return out
+
+    def set_token_rules(self, seq: int, no_repeat_ngram_size: int = 0, stop=(), bad_words=(), context=None):
+        """Token rules of chain `seq` (ze_seq_set_token_rules), on the device inside every step: HF's `no_repeat_ngram_size` and
+        `bad_words_ids` (lists of token ids) over `context` (normally the prompt ids) + the generated ids, and `stop`: token-id
+        sequences that finish the chain, as an EOS does, when one ends the generated ids.  Set after the chain's prefill and before
+        its first draw; all-off values clear the request; held until the slot is reset, truncated or copied into.  Chains with and
+        without rules share bursts and graphs."""
+        stop, bad = [list(r) for r in (stop or ())], [list(r) for r in (bad_words or ())]
+        sp, bp = pack_records(stop), pack_records(bad)
+        ctx = np.ascontiguousarray([] if context is None else context, dtype=np.int32).reshape(-1)
+        i32 = C.POINTER(C.c_int32)
+        self._check(self.lib.ze_seq_set_token_rules(self.h, int(seq), int(no_repeat_ngram_size or 0), sp.ctypes.data_as(i32), len(stop),
+                                                    bp.ctypes.data_as(i32), len(bad), ctx.ctypes.data_as(i32), int(ctx.size),
+                                                    self._stream()))
+
+    def op_token_rules(self, logits: torch.Tensor, histories, n_context=0, no_repeat_ngram_size=0, bad_words=None, stop=None,
+                       min_new=0, out: Optional[torch.Tensor] = None):
+        """The kernels alone (ze_op_token_rules): logits f32 [rows, vocab] (row stride >= vocab), `histories` one id list per row
+        whose first n_context ids are the context, no_repeat_ngram_size / n_context / min_new per row (scalars broadcast),
+        bad_words / stop per row a list of id lists (or None).  Returns (rows with -inf at the banned ids, f32 with the stride of
+        `logits`, columns beyond vocab not written; stop flags int32 [rows])."""
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+        rows, vocab = int(logits.shape[0]), int(logits.shape[1])
+        ld = int(logits.stride(0)) if rows > 1 else vocab
+        dev = self.device
+        assert len(histories) == rows
+
+        def per_row(x):
+            return np.broadcast_to(np.asarray(x, dtype=np.int32), (rows,)).copy()
+
+        def flat(lists):
+            off = np.zeros(rows + 1, dtype=np.int32)
+            off[1:] = np.cumsum([len(x) for x in lists])
+            return np.concatenate([np.asarray(x, dtype=np.int32).reshape(-1) for x in lists] + [np.zeros(4, np.int32)]), off
+
+        hist, hoff = flat(histories)
+        ban, boff = flat([pack_records(b or ()) for b in (bad_words if bad_words is not None else [None] * rows)])
+        stp, soff = flat([pack_records(b or ()) for b in (stop if stop is not None else [None] * rows)])
+        host = (hist, hoff, per_row(n_context), per_row(no_repeat_ngram_size), ban, boff, stp, soff, per_row(min_new))
+        d = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in host]
+        if out is None:
+            out = torch.empty_strided((rows, vocab), (ld, 1), dtype=torch.float32, device=dev)
+        assert out.dtype == torch.float32 and out.stride(1) == 1 and (rows <= 1 or int(out.stride(0)) == ld)
+        hit = torch.zeros(rows, dtype=torch.int32, device=dev)
+        self._check(self.lib.ze_op_token_rules(self.h, _ptr(logits), rows, vocab, ld, *[_ptr(x) for x in d], _ptr(out), _ptr(hit),
+                                               self._stream()))
+        self._keep = d   # (the launch is asynchronous: alive until the next one)
+        return out, hit
 
     def seq_truncate(self, seq: int, keep: int):
         self._check(self.lib.ze_seq_truncate(self.h, seq, keep, self._stream()))

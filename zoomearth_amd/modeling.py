@@ -28,7 +28,7 @@ import torch
 from . import processor as _processor
 from .checkpoint import iter_checkpoint
 from .config import ModelConfig
-from .engine import MAX_LOGIT_BIAS, MAX_TOP_LOGPROBS, Engine
+from .engine import MAX_LOGIT_BIAS, MAX_RULE_INTS, MAX_RULE_LEN, MAX_RULE_WORDS, MAX_TOP_LOGPROBS, Engine
 
 
 @dataclass
@@ -260,6 +260,53 @@ class ZoomEarthForConditionalGeneration:
             return None
         return pens[0], pens[1], int(min_new or 0), bias
 
+    @staticmethod
+    def _token_rules_request(kw):
+        """(no_repeat_ngram_size, stop records, bad-word records, stop strings, tokenizer) from generate's keyword arguments, or
+        None when all are off (nothing is launched then).  HF's `no_repeat_ngram_size`, `bad_words_ids` and `stop_strings` (with
+        `tokenizer=`) with HF's ValueErrors (NoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor, GenerationMixin); vLLM's
+        `stop_token_ids`."""
+        def is_int(t):
+            return not isinstance(t, bool) and isinstance(t, (int, np.integer))
+
+        ngram = kw.get("no_repeat_ngram_size")
+        if ngram is not None and ngram != 0 and (not is_int(ngram) or ngram <= 0):
+            raise ValueError(f"`ngram_size` has to be a strictly positive integer, but is {ngram}")
+        if ngram and ngram > MAX_RULE_LEN:
+            raise ValueError(f"`no_repeat_ngram_size` is limited to {MAX_RULE_LEN} here, but is {ngram}")
+        bad = kw.get("bad_words_ids")
+        if bad is not None:
+            if not isinstance(bad, list) or len(bad) == 0:
+                raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad}.")
+            if any(not isinstance(b, list) for b in bad):
+                raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bad}.")
+            if any(len(b) == 0 or any(not is_int(t) or t < 0 for t in b) for b in bad):
+                raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bad}.")
+        bad = [[int(t) for t in b] for b in (bad or [])]
+        stop_ids = kw.get("stop_token_ids")
+        if stop_ids is not None and (not isinstance(stop_ids, (list, tuple)) or any(not is_int(t) or t < 0 for t in stop_ids)):
+            raise ValueError(f"`stop_token_ids` has to be a list of positive integers, but is {stop_ids}")
+        stop = [[int(t)] for t in (stop_ids or [])]
+        strings, tokenizer = kw.get("stop_strings"), kw.get("tokenizer")
+        if isinstance(strings, str):
+            strings = [strings]
+        strings = list(strings or [])
+        if strings:
+            if tokenizer is None:
+                raise ValueError("There are one or more stop strings, either in the arguments to `generate` or in the model's generation "
+                                 "config, but we could not locate a tokenizer. When generating with stop strings, you must pass the "
+                                 "model's tokenizer to the `tokenizer` argument of `generate`.")
+            if any(not isinstance(x, str) for x in strings):
+                raise ValueError(f"`stop_strings` has to be a string or a list of strings, but is {kw.get('stop_strings')}")
+            from .hostloop import stop_string_records
+            stop += [r for r in stop_string_records(tokenizer, strings) if len(r) <= MAX_RULE_LEN and r not in stop]
+        for name, recs in (("stop sequences", stop), ("bad_words_ids", bad)):
+            if len(recs) > MAX_RULE_WORDS or sum(1 + len(r) for r in recs) > MAX_RULE_INTS or any(len(r) > MAX_RULE_LEN for r in recs):
+                raise ValueError(f"{name}: at most {MAX_RULE_WORDS} sequences of at most {MAX_RULE_LEN} tokens, {MAX_RULE_INTS} ints packed")
+        if not ngram and not bad and not stop and not strings:
+            return None
+        return int(ngram or 0), stop, bad, strings, tokenizer
+
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, pixel_values=None, image_grid_thw=None,
                  mm_token_type_ids=None, image_keys=None, max_new_tokens: int = 20, do_sample: bool = False,
@@ -301,6 +348,7 @@ class ZoomEarthForConditionalGeneration:
             filt_kw = dict(top_k=int(top_k or 0), top_p=1.0 if top_p is None else max(float(top_p), 1e-37),
                            min_p=float(min_p or 0.0))
         adjust = self._logit_adjust_request(kw)
+        rules = self._token_rules_request(kw)
         if do_sample and temperature is None:
             temperature = 1.0
         sample_kw = dict(do_sample=bool(do_sample), temperature=float(temperature or 1.0),
@@ -354,6 +402,8 @@ class ZoomEarthForConditionalGeneration:
                     e.set_logprobs(slot, logprobs)  # (the reset / truncate above cleared the slot's previous request)
                 if adjust is not None:
                     e.seq_set_logit_adjust(slot, *adjust)
+                if rules is not None and (rules[0] or rules[1] or rules[2]):
+                    e.set_token_rules(slot, rules[0], rules[1], rules[2], context=ids if (rules[0] or rules[2]) else None)
                 outs.append(e.generate(slot, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw))
                 if logprobs is not None:
                     lps.append(e.chain_logprobs(slot, max_new_tokens))
@@ -377,9 +427,24 @@ class ZoomEarthForConditionalGeneration:
             if adjust is not None:
                 for slot in slots:
                     e.seq_set_logit_adjust(slot, *adjust)
+            if rules is not None and (rules[0] or rules[1] or rules[2]):
+                for slot, _, _, _, _, ids in pending:
+                    e.set_token_rules(slot, rules[0], rules[1], rules[2], context=ids if (rules[0] or rules[2]) else None)
             outs = e.generate_batch(slots, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw)
             if logprobs is not None:
                 lps = e.chain_logprobs_batch(slots, logprobs, max_new_tokens)
+        if rules is not None and (rules[1] or rules[3]):
+            # what follows a stop is pad (HF's finished rows): the ids behind a matched stop sequence are the device's own pads;
+            # a stop string is exact at text level, whatever tokenization carried it (hostloop.first_stop_cut)
+            from .hostloop import first_stop_cut, first_stop_hit
+            min_new = adjust[2] if adjust is not None else 0
+            for b, t in enumerate(outs):
+                cuts = [first_stop_hit(t, rules[1], min_new)]
+                hit = first_stop_cut(rules[4], t, rules[3], min_new) if rules[3] else None
+                cuts.append(hit[0] if hit else None)
+                cuts = [n for n in cuts if n is not None]
+                if cuts:
+                    outs[b] = list(t[:min(cuts)])
         width = max(len(t) for t in outs)
         pad = cfg.pad_token_id
         res = torch.full((ids_cpu.shape[0], ids_cpu.shape[1] + width), pad, dtype=torch.long)

@@ -52,6 +52,12 @@ class Request:
     frequency_penalty: Optional[float] = None
     logit_bias: Optional[dict] = None
     min_new_tokens: Optional[int] = None
+    # token rules of this request, on the device: `stop_ids` token-id sequences that end the chain as an EOS does (the request
+    # is retired in the burst that matched, its slot goes to a waiting one), HF's `bad_words_ids` and `no_repeat_ngram_size` over
+    # prompt + generated ids
+    stop_ids: Optional[list] = None
+    bad_words_ids: Optional[list] = None
+    no_repeat_ngram_size: Optional[int] = None
     # filled by the scheduler
     slot: int = -1
     n_prompt: int = 0
@@ -583,6 +589,14 @@ class ChainScheduler:
         if presence != 0.0 or frequency != 0.0 or bias or min_new > 0:
             self.engine.seq_set_logit_adjust(req.slot, presence, frequency, min_new, bias)
 
+    def _set_token_rules(self, req, prompt_ids) -> None:
+        """The request's token rules into its slot (cleared, like the filter, by the slot's reset / truncate / prefix copy), before
+        its first draw, with the prompt ids as the context of the bans; without rules nothing is launched."""
+        stop, bad = list(getattr(req, "stop_ids", None) or ()), list(getattr(req, "bad_words_ids", None) or ())
+        ngram = int(getattr(req, "no_repeat_ngram_size", None) or 0)
+        if stop or bad or ngram > 0:
+            self.engine.set_token_rules(req.slot, ngram, stop, bad, context=list(prompt_ids) if (bad or ngram > 0) else None)
+
     @staticmethod
     def _attach_logprobs(req, lp, n: int) -> None:
         logps, ids, tlps = lp
@@ -612,6 +626,7 @@ class ChainScheduler:
             self._set_filter(req)
             self._set_logprobs(req)
             self._set_logit_adjust(req)
+            self._set_token_rules(req, ids)
             self.engine.chain_begin(req.slot, self.params, req.stream_id)
             self.live[req.slot] = _Live(req, ids, keys)
             self.stats["admitted"] += 1
@@ -711,6 +726,12 @@ class ChainScheduler:
         else:
             req.tokens = (self.engine.chain_tokens(slot, req.max_new_tokens, stream=ds) if ds is not None
                           else self.engine.chain_tokens(slot, req.max_new_tokens))
+        if getattr(req, "stop_ids", None):   # the ids behind a stop sequence are the pads of a finished chain
+            from .hostloop import first_stop_hit
+            mn = getattr(req, "min_new_tokens", None)
+            n = first_stop_hit(req.tokens, req.stop_ids, int((self.min_new_tokens if mn is None else mn) or 0))
+            if n is not None:
+                req.tokens = list(req.tokens[:n])
         req.text = self.processor.tokenizer.decode(req.tokens, skip_special_tokens=True).strip()
         n_lp = self._want_logprobs(req)
         if n_lp is not None:

@@ -9,6 +9,9 @@ base64,..."}}` items, plus `max_tokens`, `temperature`, `seed`, `top_p` and the 
 `min_p` (`n` must be 1, `stream` is not offered); the three filters apply to sampled requests, each request its own.
 `presence_penalty` / `frequency_penalty` ([-2, 2]), `logit_bias` (at most 300 `"id": bias` entries in [-100, 100]) and vLLM's
 `min_tokens` adjust every step's logits on the device, each request its own values, greedy requests included.
+`stop` (a string or up to 4 strings), vLLM's `stop_token_ids` and `no_repeat_ngram_size` are token rules on the device: the chain
+ends in the step that completes a stop sequence (`finish_reason: "stop"`); the text is cut before a stop string, a stop token id
+is kept as an EOS is.
 `logprobs: true` (with `top_logprobs: 0..20`) adds `choices[0].logprobs.content`, one entry per completion token, from the
 decode step's own logits (the model's distribution, before repetition penalty, temperature and filters).
 Prompt: the Qwen2.5-VL chat template (`<|im_start|>role\\n ... <|im_end|>\\n`, an image item becomes
@@ -87,15 +90,30 @@ def build_prompt(messages):
 
 class _Parsed:
     __slots__ = ("req", "prompt", "pil_images", "max_tokens", "sample", "temperature", "seed", "future", "top_k", "top_p",
-                 "min_p", "logprobs", "presence_penalty", "frequency_penalty", "logit_bias", "min_tokens")
+                 "min_p", "logprobs", "presence_penalty", "frequency_penalty", "logit_bias", "min_tokens", "stop", "stop_token_ids",
+                 "no_repeat_ngram_size")
+
+    def rules(self) -> bool:
+        return bool(self.stop or self.stop_token_ids or self.no_repeat_ngram_size)
 
     def adjusts(self) -> bool:
-        return bool(self.presence_penalty or self.frequency_penalty or self.logit_bias or self.min_tokens)
+        """The request carries values generate() gives every row of a call alike: it runs alone, or through the dispatcher."""
+        return bool(self.presence_penalty or self.frequency_penalty or self.logit_bias or self.min_tokens) or self.rules()
 
-    def adjust_kw(self) -> dict:
-        """generate()'s keyword arguments of the request's logit adjustments (none when they are all off)."""
-        return dict(presence_penalty=self.presence_penalty, frequency_penalty=self.frequency_penalty, logit_bias=self.logit_bias,
-                    min_new_tokens=self.min_tokens) if self.adjusts() else {}
+    def adjust_kw(self, tokenizer=None) -> dict:
+        """generate()'s keyword arguments of the request's logit adjustments and token rules (none when they are all off)."""
+        kw = dict(presence_penalty=self.presence_penalty, frequency_penalty=self.frequency_penalty, logit_bias=self.logit_bias,
+                  min_new_tokens=self.min_tokens) if self.adjusts() else {}
+        if self.rules():
+            kw.update(stop_strings=list(self.stop) or None, tokenizer=tokenizer, stop_token_ids=list(self.stop_token_ids) or None,
+                      no_repeat_ngram_size=self.no_repeat_ngram_size or None)
+        return kw
+
+    def stop_records(self, tokenizer) -> list:
+        """What the device finishes the chain on: the stop token ids, and the tokenizer's own encoding of every stop string."""
+        from .engine import MAX_RULE_LEN
+        from .hostloop import stop_string_records
+        return [[t] for t in self.stop_token_ids] + [r for r in stop_string_records(tokenizer, self.stop) if len(r) <= MAX_RULE_LEN]
 
 
 class ChatServer:
@@ -191,6 +209,37 @@ class ChatServer:
         if mt is not None and mt < 0:
             raise BadRequest(f"min_tokens must be >= 0, got {mt}")
         p.min_tokens = int(mt or 0)
+        # OpenAI's `stop` (a string or up to 4 strings), vLLM's `stop_token_ids`, HF's `no_repeat_ngram_size`: token rules on the device
+        st = req.get("stop")
+        if st is None:
+            st = []
+        elif isinstance(st, str):
+            st = [st]
+        if not isinstance(st, list) or any(not isinstance(x, str) for x in st):
+            raise BadRequest(f"stop must be a string or a list of strings, got {req.get('stop')!r}")
+        if len(st) > 4:
+            raise BadRequest(f"stop must have at most 4 strings, got {len(st)}")
+        if any(x == "" for x in st):
+            raise BadRequest("stop strings must not be empty")
+        p.stop = st
+        sti = req.get("stop_token_ids")
+        if sti is None:
+            sti = []
+        if not isinstance(sti, list) or any(isinstance(t, bool) or not isinstance(t, int) for t in sti):
+            raise BadRequest(f"stop_token_ids must be a list of integers, got {req.get('stop_token_ids')!r}")
+        if sti:
+            vocab = int(self.model.config.text.vocab_size)
+            if any(not (0 <= t < vocab) for t in sti):
+                raise BadRequest(f"stop_token_ids must be in [0, {vocab}), got {sti}")
+        if len(sti) > 32:
+            raise BadRequest(f"stop_token_ids must have at most 32 entries, got {len(sti)}")
+        p.stop_token_ids = [int(t) for t in sti]
+        ng = req.get("no_repeat_ngram_size")
+        if ng is not None and (isinstance(ng, bool) or not isinstance(ng, int)):
+            raise BadRequest(f"no_repeat_ngram_size must be an integer, got {ng!r}")
+        if ng is not None and not (0 <= ng <= 16):
+            raise BadRequest(f"no_repeat_ngram_size must be in [0, 16], got {ng}")
+        p.no_repeat_ngram_size = int(ng or 0)
         p.future = None
         return p
 
@@ -217,7 +266,19 @@ class ChatServer:
         ids = out if stop is None else out[: stop + 1]
         while stop is None and ids and ids[-1] == pad:
             ids = ids[:-1]
-        text = self.processor.tokenizer.decode(ids, skip_special_tokens=True).strip()
+        text = None
+        if p.stop_token_ids or p.stop:
+            # the device ended the chain at the step that completed a stop sequence (pad follows); the text is cut here, exactly at
+            # text level, whatever tokenization carried a stop string (hostloop.first_stop_cut).  A stop token id is kept, as an EOS is.
+            from .hostloop import first_stop_cut, first_stop_hit
+            n_id = first_stop_hit(ids, [[t] for t in p.stop_token_ids], p.min_tokens)
+            cut = first_stop_cut(self.processor.tokenizer, ids, p.stop, p.min_tokens) if p.stop else None
+            if cut is not None and (n_id is None or cut[0] <= n_id):
+                ids, text, stop = ids[: cut[0]], cut[1].strip(), cut[0]
+            elif n_id is not None:
+                ids, stop = ids[:n_id], n_id
+        if text is None:
+            text = self.processor.tokenizer.decode(ids, skip_special_tokens=True).strip()
         res = {
             "id": "chatcmpl-" + uuid.uuid4().hex[:24], "object": "chat.completion", "created": int(time.time()),
             "model": p.req.get("model") or self.model_id,
@@ -247,7 +308,7 @@ class ChatServer:
             kw = dict(max_new_tokens=max(p.max_tokens for p in batch), num_beams=1, do_sample=p0.sample)
             if p0.sample:
                 kw.update(temperature=p0.temperature, top_k=p0.top_k, top_p=p0.top_p, min_p=p0.min_p, seed=p0.seed)
-            kw.update(p0.adjust_kw())
+            kw.update(p0.adjust_kw(self.processor.tokenizer))
             want = [p.logprobs for p in batch if p.logprobs is not None]
             if not want:
                 out = self.model.generate(**inputs, **kw)[:, width:].tolist()
@@ -269,7 +330,8 @@ class ChatServer:
         if any(p.sample for p in batch) and len(batch) > 1:
             raise BadRequest("sampled requests are not batched")
         if any(p.adjusts() for p in batch) and len(batch) > 1:
-            raise BadRequest("requests with presence_penalty / frequency_penalty / logit_bias / min_tokens are not batched")
+            raise BadRequest("requests with presence_penalty / frequency_penalty / logit_bias / min_tokens / stop / stop_token_ids / "
+                             "no_repeat_ngram_size are not batched")
         if len(batch) > self.max_batch:
             raise BadRequest(f"batch of {len(batch)} exceeds max_seqs = {self.max_batch}")
         return self._run(batch)
@@ -345,7 +407,8 @@ class ChatServer:
                         sched.submit(Request(prompt=p.prompt, images=imgs, max_new_tokens=budget, on_done=done,
                                              on_error=failed, logprobs=p.logprobs, presence_penalty=p.presence_penalty,
                                              frequency_penalty=p.frequency_penalty, logit_bias=p.logit_bias,
-                                             min_new_tokens=p.min_tokens))
+                                             min_new_tokens=p.min_tokens, stop_ids=p.stop_records(self.processor.tokenizer),
+                                             no_repeat_ngram_size=p.no_repeat_ngram_size))
                     except Exception as ex:
                         failed(None, ex)
                 if sched.busy():
@@ -384,7 +447,8 @@ class ChatServer:
                                               stream_id=0, on_done=done, on_error=failed, top_k=p.top_k, top_p=p.top_p,
                                               min_p=p.min_p, logprobs=p.logprobs, presence_penalty=p.presence_penalty,
                                               frequency_penalty=p.frequency_penalty, logit_bias=p.logit_bias,
-                                              min_new_tokens=p.min_tokens))
+                                              min_new_tokens=p.min_tokens, stop_ids=p.stop_records(self.processor.tokenizer),
+                                              no_repeat_ngram_size=p.no_repeat_ngram_size))
                         except Exception as ex:
                             failed(None, ex)
                     try:
