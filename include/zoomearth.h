@@ -521,6 +521,36 @@ int ze_op_kv_read(ze_engine* e, int seq, int layer, int start, int n, void* out_
  * qkv_bf16 [n, (heads + 2 kv_heads) x 128] = the chains' projections after ze_op_rope_kv_decode (their k / v are row ctx of the
  * cache); out_bf16 [n, heads x 128] = softmax(q K^T / sqrt(128)) V over rows 0 .. ctx, per head, with the step's own kernel. */
 int ze_op_attn_decode(ze_engine* e, const int32_t* seqs, int n, int layer, const void* qkv_bf16, void* out_bf16, void* stream);
+/* ONE launch of the single-chain decode GEMV family (K16-K22 at one token per step: the kernel that streams every decoder weight
+ * once per token), alone, on device operands: out[N] = W[N, K] . x[K] with the prologue and epilogue of the decode step.
+ *   W       w_bf16 [N, K] bf16, or -- w8 non-null -- the FP8 stream: w8 u8 [N, K] E4M3 bytes and scale8 f32 [N] as ze_op_quantize_fp8
+ *           writes them (K % 16 == 0)
+ *   x       x_bf16 [K]; norm_w non-null: RMSNorm prologue, bf16(bf16(x * rsqrt(mean(x^2) + eps)) * norm_w)
+ *           (HF:...modeling_qwen2_5_vl.py:64-79); act8 != 0 (FP8 stream + norm only): the normalised row replaced by its E4M3
+ *           quantisation (ze_set_fp8_activations); embed non-null: x = row `token` of embed [V, K] (HF:...:1206 embed_tokens),
+ *           also copied to embed_out [K]
+ *   bias    bias_bf16 [N] or null
+ *   epi     4 plain: out_bf16 [N] = bf16(W x + b) (HF:...:541-554 / 692-757: the q/k/v, o, gate/up, down Linear modules);
+ *           1 residual: out_bf16 [N] is the hidden row, updated in place to bf16(h + bf16(W x + b)) (HF:...:745-757);
+ *           2 SwiGLU on gate / up rows interleaved in blocks of 16 (as ze_op_linear act 4): out_bf16 [N / 2], N % 32 == 0 (HF:...:85-96);
+ *           3 logits: out_f32 [N] = the fp32 copy of bf16(W x + b) (HF:...:1386-1387, HF:generation/utils.py:2894); out_token
+ *             (host) non-null: the greedy arg-max folded into the launch -- repetition penalty on the ids flagged in seen u8 [N]
+ *             (logit < 0 ? logit * penalty : logit / penalty; seen may be null at penalty 1), lowest index on ties -- through the
+ *             engine's own partial slots and final reduction, as a greedy decode step takes its token;
+ *           0 qkv + M-RoPE + KV append (HF:...:557-599, 667-668): N = (heads + 2 kv_heads) x 128 of the engine; chain `seq`'s state,
+ *             the engine's cos / sin tables and `layer`'s cache: q heads roped to out_bf16 [heads x 128], roped k and plain v to row
+ *             ctx of the cache (read them with ze_op_kv_read).  The chain's length does not change.
+ * ZE_ERR_NOMEM when the launcher refuses the shape because x does not fit its LDS stage, ZE_ERR_INVALID for the FP8 stream with
+ * K % 16 != 0: outputs untouched, no other kernel runs in its place.  Unit-test entry: nothing in the product path calls it. */
+int ze_op_gemv(ze_engine* e, int epi, const void* w_bf16, const void* w8, const void* scale8, const void* x_bf16, const void* norm_w,
+               float eps, const void* bias_bf16, int act8, int N, int K, void* out_bf16, float* out_f32, const uint8_t* seen,
+               float penalty, int32_t* out_token, int seq, int layer, const void* embed, int token, void* embed_out, void* stream);
+/* The lm_head of the prefill paths, alone (final RMSNorm + lm_head on the kept positions + .float(), HF:...:1386-1387,
+ * HF:generation/utils.py:2894): w_bf16 [N, K], norm_w [K], x_bf16 [n, K] -> out_f32 [n, N], one pass over W per eight rows; row i is
+ * the same bits whatever n and wherever it stands.  K % 8 == 0; ZE_ERR_NOMEM for a K whose eight staged rows do not fit in LDS
+ * (K > 3072).  Unit-test entry. */
+int ze_op_logits_rows(ze_engine* e, const void* w_bf16, const void* norm_w, float eps, const void* x_bf16, float* out_f32, int n, int N,
+                      int K, void* stream);
 
 /* The numeric helpers every epilogue shares, alone (device pointers, n elements): out[i] = bf16(x[i]) | bf16(bf16(SiLU(x[i])) * y[i]) << 16
  * -- HF Qwen2MLP `act_fn(gate_proj(x)) * up_proj(x)` on bf16 modules, transformers/models/qwen2_5_vl/modeling_qwen2_5_vl.py:541-554 --

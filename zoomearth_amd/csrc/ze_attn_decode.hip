@@ -1,8 +1,10 @@
 // One-token (decode) GQA attention over the KV cache: flash-decoding slices merged in the same launch.
 // Own translation unit: it is compiled WITH hipcc's SLP vectoriser (11.5 vs 11.95 us per launch), which the rest of
-// the library is built without (see Makefile); every result of this kernel is pinned bit for bit against the fused
-// variant and within tolerance against the prefill attention and the oracle (tests/test_gpu_fused.py,
-// test_gpu_longctx.py, test_gpu_model.py).
+// the library is built without (see Makefile); this kernel is pinned within tolerance against the prefill attention at
+// contexts up to the cache's length (tests/test_gpu_longctx.py::test_decode_matches_prefill_at_context) and against the
+// oracle along teacher-forced chains (tests/test_gpu_model.py::test_two_stage_chain_teacher_forced, test_gpu_3b_shape.py,
+// test_gpu_7b_shape.py), and bit for bit between graph replay, eager steps and ze_decode_step
+// (tests/test_gpu_model.py::test_generate_graph_eager_and_stepwise_agree).
 #include "ze_kernels.h"
 
 // ------------------------------------------------------------------ decode attention (D = 128)

@@ -2502,6 +2502,118 @@ extern "C" int ze_op_kv_read(ze_engine* e, int seq, int layer, int start, int n,
     return ZE_OK;
 }
 
+// ONE launch of the single-chain decode GEMV family (ze_launch_gemv: k_gemv, bf16 or FP8 stream) on the caller's device operands,
+// every epilogue and prologue reachable -- the product path calls the launcher only from ze_enqueue_decode_step / ze_prefill, with
+// the model's own shapes.  epi = the ZE_GV_* code.  A shape the launcher refuses is an error, never another kernel.
+extern "C" int ze_op_gemv(ze_engine* e, int epi, const void* w_bf16, const void* w8, const void* scale8, const void* x_bf16,
+                          const void* norm_w, float eps, const void* bias_bf16, int act8, int N, int K, void* out_bf16,
+                          float* out_f32, const uint8_t* seen, float penalty, int32_t* out_token, int seq, int layer,
+                          const void* embed, int token, void* embed_out, void* stream) {
+    if (!e || (!w_bf16 && !w8) || (w8 && !scale8) || (!x_bf16 && !embed)) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    if (epi < ZE_GV_QKV_ROPE || epi > ZE_GV_PLAIN) return ze_fail(e, ZE_ERR_INVALID, "unknown epilogue");
+    if (N < 2 || N % 2 || K < 8 || K % 8) return ze_fail(e, ZE_ERR_INVALID, "N must be even, K a multiple of 8");
+    if (epi == ZE_GV_SWIGLU && N % 32) return ze_fail(e, ZE_ERR_INVALID, "SwiGLU: N = 2 * width with width % 16 == 0");
+    if (epi == ZE_GV_LOGITS ? !out_f32 : !out_bf16) return ze_fail(e, ZE_ERR_INVALID, "null output");
+    if (act8 && (!w8 || !norm_w)) return ze_fail(e, ZE_ERR_INVALID, "act8 goes with the FP8 stream and the norm prologue");
+    if (embed && (!embed_out || token < 0)) return ze_fail(e, ZE_ERR_INVALID, "embedding prologue: embed_out and a token");
+    if (out_token && epi != ZE_GV_LOGITS) return ze_fail(e, ZE_ERR_INVALID, "the folded arg-max belongs to the LOGITS epilogue");
+    if (out_token && penalty != 1.0f && !seen) return ze_fail(e, ZE_ERR_INVALID, "a penalty needs the seen flags");
+    const ze_config& c = e->cfg;
+    if (epi == ZE_GV_QKV_ROPE) {
+        ZE_TRY(check_seq(e, seq));
+        if (layer < 0 || layer >= c.layers || e->head_dim != 128 || N != (c.heads + 2 * c.kv_heads) * 128)
+            return ze_fail(e, ZE_ERR_INVALID, "QKV_ROPE: N = (heads + 2 kv_heads) x 128 of the engine, a layer of the engine");
+        if (e->ctx_host[seq] + 1 > c.max_ctx) return ze_fail(e, ZE_ERR_NOMEM, "sequence exceeds max_ctx");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipSetDevice(e->device);
+    // scratch: a chain state that carries `token` (embedding prologue), and what the arg-max reduction writes besides the token
+    ze_seq_dev* st_tmp = nullptr;
+    uint8_t* seen_tmp = nullptr;
+    if (embed || out_token) ZE_HIP(hipMalloc((void**)&st_tmp, sizeof(ze_seq_dev) + 2 * sizeof(int) + (out_token ? (size_t)N : 0)));
+    int32_t* tok_tmp = reinterpret_cast<int32_t*>(st_tmp + 1);
+    int r = ZE_OK;
+    const ze_seq_dev* st = epi == ZE_GV_QKV_ROPE ? e->st_dev + seq : nullptr;
+    if (embed) {
+        if (st) {
+            if (hipMemcpyAsync(st_tmp, st, sizeof(ze_seq_dev), hipMemcpyDeviceToDevice, s) != hipSuccess) r = ze_fail(e, ZE_ERR_HIP, "hipMemcpyAsync failed");
+        } else if (hipMemsetAsync(st_tmp, 0, sizeof(ze_seq_dev), s) != hipSuccess) {
+            r = ze_fail(e, ZE_ERR_HIP, "hipMemsetAsync failed");
+        }
+        ze_launch_set_ints(&st_tmp->token, &token, 1, s);
+        st = st_tmp;
+    }
+    ze_gemv_args a;
+    memset(&a, 0, sizeof(a));
+    a.W = (const bf16_t*)w_bf16;
+    a.ldw = K;
+    a.W8 = (const uint8_t*)w8;
+    a.scale8 = (const float*)scale8;
+    a.ldw8 = K;
+    a.N = N;
+    a.K = K;
+    a.x = (const bf16_t*)x_bf16;
+    a.norm_w = (const bf16_t*)norm_w;
+    a.eps = eps;
+    a.bias = (const bf16_t*)bias_bf16;
+    a.out_bf16 = (bf16_t*)out_bf16;
+    a.out_f32 = out_f32;
+    a.D = 128;
+    a.act8 = act8 ? 1 : 0;
+    a.st = st;
+    if (epi == ZE_GV_QKV_ROPE) {
+        a.cosT = e->cosT;
+        a.sinT = e->sinT;
+        a.kcache = e->kc(layer, seq);
+        a.vcache = e->vc(layer, seq);
+        a.heads = c.heads;
+        a.kv_heads = c.kv_heads;
+        a.max_ctx = c.max_ctx;
+    }
+    a.embed = (const bf16_t*)embed;
+    a.embed_out = (bf16_t*)embed_out;
+    if (out_token) {  // the engine's own partial slots (created once with the engine: ze_launch_amax_init), as the decode step uses them
+        a.seen = seen;
+        a.penalty = penalty;
+        a.amax_ws = e->damax;
+    }
+    if (r == ZE_OK && !ze_launch_gemv(epi, a, s))
+        r = ze_fail(e, (w8 && K % 16) ? ZE_ERR_INVALID : ZE_ERR_NOMEM,
+                    "shape refused by the GEMV launcher (x does not fit the LDS stage, or the FP8 stream with K % 16 != 0)");
+    if (r == ZE_OK && out_token) {
+        seen_tmp = reinterpret_cast<uint8_t*>(tok_tmp + 2);
+        const int fresh[3] = {0, 0, 1};  // finished, n_gen, max_gen: the token lands in tok_tmp[0]
+        ze_launch_set_ints(&st_tmp->finished, fresh, 3, s);
+        ze_launch_sample_folded(e->damax, N, seen_tmp, st_tmp, e->eos_dev, 0, c.pad_token_id, /*ignore_eos=*/1, /*advance_ctx=*/0, tok_tmp, s);
+        if (hipMemcpyAsync(out_token, tok_tmp, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) r = ze_fail(e, ZE_ERR_HIP, "hipMemcpyAsync failed");
+    }
+    if (r == ZE_OK && hipGetLastError() != hipSuccess) r = ze_fail(e, ZE_ERR_HIP, "GEMV launch failed");
+    if (st_tmp) {
+        if (hipStreamSynchronize(s) != hipSuccess && r == ZE_OK) r = ze_fail(e, ZE_ERR_HIP, "hipStreamSynchronize failed");
+        hipFree(st_tmp);
+    }
+    return r;
+}
+
+// fp32 logits of n hidden rows through the lm_head pass of the prefill paths (ze_launch_logits_rows: k_logits_multi, final RMSNorm
+// fused, one pass over W per eight rows).  A K the launcher refuses (eight staged rows do not fit in LDS) is ZE_ERR_NOMEM.
+extern "C" int ze_op_logits_rows(ze_engine* e, const void* w_bf16, const void* norm_w, float eps, const void* x_bf16, float* out_f32,
+                                 int n, int N, int K, void* stream) {
+    if (!e || !w_bf16 || !norm_w || !x_bf16 || !out_f32) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    if (n <= 0 || N <= 0 || K < 8 || K % 8) return ze_fail(e, ZE_ERR_INVALID, "n and N positive, K a multiple of 8");
+    hipSetDevice(e->device);
+    std::vector<const bf16_t*> xr(n);
+    std::vector<float*> lo(n);
+    for (int i = 0; i < n; ++i) {
+        xr[i] = (const bf16_t*)x_bf16 + (size_t)i * K;
+        lo[i] = out_f32 + (size_t)i * N;
+    }
+    if (!ze_launch_logits_rows((const bf16_t*)w_bf16, K, N, K, (const bf16_t*)norm_w, eps, xr.data(), lo.data(), n, (hipStream_t)stream))
+        return ze_fail(e, ZE_ERR_NOMEM, "shape refused by the logits-rows launcher (eight staged rows do not fit the LDS stage)");
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
 // ================================================================== fp8 decode weights
 static int quantize_linear(ze_engine* e, ze_linear& l, int rows, int cols, uint8_t*& cur8, float*& curs, hipStream_t s) {
     l.ld8 = (cols + 15) / 16 * 16;

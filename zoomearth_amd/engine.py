@@ -739,6 +739,40 @@ class Engine:
         self._check(self.lib.ze_op_kv_read(self.h, seq, layer, start, n, _ptr(k), _ptr(v), self._stream()))
         return k, v
 
+    GV_QKV_ROPE, GV_RESIDUAL, GV_SWIGLU, GV_LOGITS, GV_PLAIN = 0, 1, 2, 3, 4   # epilogues of op_gemv
+
+    def op_gemv(self, epi: int, x, w=None, w8=None, scale8=None, norm_w=None, eps: float = 1e-6, bias=None, act8: bool = False, out=None,
+                argmax: bool = False, seen=None, penalty: float = 1.0, seq: int = 0, layer: int = 0, embed=None, token: int = -1,
+                embed_out=None):
+        """One launch of the single-chain decode GEMV family (ze_op_gemv): w bf16 [N, K] or (w8 u8 [N, K], scale8 f32 [N]); x bf16
+        [K] (or row `token` of embed [V, K], copied to embed_out [K]).  `out` (allocated when None; RESIDUAL: the hidden row, updated
+        in place): bf16 [N] (PLAIN, RESIDUAL), bf16 [N / 2] (SWIGLU), f32 [N] (LOGITS), bf16 [heads x 128] (QKV_ROPE: k / v go to row
+        ctx of `layer`'s cache of chain `seq`).  Returns out, or (out, token) with argmax (LOGITS: the folded greedy arg-max, `seen`
+        u8 [N] and `penalty` as the sampler's)."""
+        mat = w8 if w8 is not None else w
+        n, k = mat.shape
+        if out is None:
+            t = self.config.text
+            shape, dt = {self.GV_SWIGLU: (n // 2, torch.bfloat16), self.GV_LOGITS: (n, torch.float32),
+                         self.GV_QKV_ROPE: (t.hidden_size, torch.bfloat16)}.get(epi, (n, torch.bfloat16))
+            out = torch.empty(shape, dtype=dt, device=self.device)
+        tok = C.c_int32(-1)
+        f32 = epi == self.GV_LOGITS
+        self._check(self.lib.ze_op_gemv(self.h, epi, _ptr(w), _ptr(w8), _ptr(scale8), _ptr(x), _ptr(norm_w), eps, _ptr(bias), int(act8),
+                                        n, k, None if f32 else _ptr(out), _ptr(out) if f32 else None, _ptr(seen), penalty,
+                                        C.byref(tok) if argmax else None, seq, layer, _ptr(embed), int(token), _ptr(embed_out),
+                                        self._stream()))
+        return (out, int(tok.value)) if argmax else out
+
+    def op_logits_rows(self, x: torch.Tensor, w: torch.Tensor, norm_w: torch.Tensor, eps: float = 1e-6, out=None) -> torch.Tensor:
+        """fp32 logits [n, N] of n hidden rows x bf16 [n, K] through the prefill paths' lm_head pass (ze_op_logits_rows)."""
+        rows, k = x.shape
+        n = w.shape[0]
+        if out is None:
+            out = torch.empty((rows, n), dtype=torch.float32, device=self.device)
+        self._check(self.lib.ze_op_logits_rows(self.h, _ptr(w), _ptr(norm_w), eps, _ptr(x), _ptr(out), rows, n, k, self._stream()))
+        return out
+
     def op_numeric_helpers(self, x: torch.Tensor, y: torch.Tensor):
         """(bf16(x) | bf16(bf16(silu(x)) * y) << 16, pack_bf16x2(x, y)) as two int32 tensors (u32 bit patterns): x, y f32 on the device."""
         n = x.numel()
