@@ -313,7 +313,7 @@ int ze_op_sample_temperature(ze_engine* e, int seq, const float* logits, float r
  * ZE_ERR_INVALID for top_k < 0, top_p outside (0, 1], min_p outside [0, 1].  The values travel as kernel arguments on `stream`
  * into a per-slot device table: chains with different filters share one burst and one captured graph.  Honoured by
  * ze_op_sample_temperature, ze_generate, ze_generate_batch, ze_chain_begin and ze_decode_burst* when p->do_sample is set
- * (greedy ignores it); cleared wherever the chain's repetition-penalty set is (ze_seq_reset, ze_seq_truncate,
+ * or the chain's own request (ze_seq_set_sampling) is sampled (greedy ignores it); cleared wherever the chain's repetition-penalty set is (ze_seq_reset, ze_seq_truncate,
  * ze_seq_copy_prefix into the slot).  While no chain of the engine has a filter, every sampling step launches exactly what
  * it launches without this entry. */
 int ze_seq_set_sampling_filter(ze_engine* e, int seq, int top_k, float top_p, float min_p, void* stream);
@@ -323,6 +323,38 @@ int ze_seq_set_sampling_filter(ze_engine* e, int seq, int top_k, float top_p, fl
 int ze_op_sample_filter(ze_engine* e, const float* logits, int rows, int vocab, int ld, const float* temperature,
                         const int32_t* top_k, const float* top_p, const float* min_p, float* out_cut, int32_t* out_kept,
                         void* stream);
+
+/* Sampling request of one chain (replaces: the do_sample / temperature / seed / repetition_penalty of ze_gen_params, which a call
+ * takes once for all its chains -- as the OpenAI-compatible back-end of src/eval/infer_vllm.py:244-271 takes `temperature`,
+ * `seed` and `repetition_penalty` per request).  mode: -1 clear (the chain follows the call's ze_gen_params again; the other
+ * arguments are not looked at), 0 greedy, 1 temperature sampling.  A chain with a request uses its own
+ *   (greedy | temperature, seed, repetition_penalty)
+ * in ze_generate, ze_generate_batch, ze_chain_begin, ze_decode_burst and ze_decode_burst_begin/_end; the four fields of the
+ * ze_gen_params handed to the call apply only to chains without one (ignore_eos and use_graph stay per call).  The draw is the
+ * one of ze_op_sample_temperature, u = f(seed, sample stream of the chain, index of the generated token), with the chain's own
+ * seed and the stream ze_chain_begin / the row of ze_generate_batch gives it; the sampling filter of the chain
+ * (ze_seq_set_sampling_filter) is honoured when its EFFECTIVE mode is sampled, with its own temperature; a chain whose effective
+ * mode is greedy picks the penalised arg-max with its own penalty.  A chain's tokens are bit for bit those of a call whose
+ * ze_gen_params carry the same values.  Set it after the chain's prefill and before its first draw.  The values travel as
+ * kernel arguments on `stream` into a per-slot device table (no stream synchronisation), so chains with different requests share
+ * one burst and one captured graph: the batched step reads the table through per-chain forms of the sampling kernels
+ * (ze_sample.hip), captured once per batch size for every mix of requests; the single-chain calls resolve the request on the
+ * host (a captured single-chain graph is re-captured when the effective values change).  Cleared wherever the sampling filter
+ * is (ze_seq_reset, ze_seq_truncate, ze_seq_copy_prefix into the slot).  While no chain of the engine has a request, every step
+ * launches exactly what it launches without this entry.  ZE_ERR_INVALID -- the chain's request is then unchanged -- for a mode
+ * outside {-1, 0, 1}, for mode 1 with a temperature that is not finite and > 0, and for mode 0 / 1 with a repetition_penalty
+ * that is not finite and > 0 (1 = off).  The table (max_seqs x 16 B) is allocated by the first request, which waits once for
+ * it to be cleared; ZE_ERR_NOMEM if that fails, and the engine stays usable. */
+int ze_seq_set_sampling(ze_engine* e, int seq, int mode, float temperature, uint64_t seed, float repetition_penalty, void* stream);
+/* One draw per row on caller-supplied rows, each with values of its own (the kernels of the batched step with row = chain):
+ * logits f32 [rows, ld] device (ld >= vocab); seen uint8 [rows, vocab] device (nonzero = penalised) or NULL (no penalty); host
+ * arrays of length `rows`: temperature (0 = greedy arg-max, lowest index on ties, 0 for a row of NaN), repetition_penalty, seed,
+ * sample_stream and index (the draw is u = f(seed[r], sample_stream[r], index[r]) as in ze_op_sample_temperature); top_k / top_p /
+ * min_p as ze_op_sample_filter takes them, or all three NULL; out_tokens int32 [rows] device.  Marks nothing as seen and touches
+ * no chain.  Waits for `stream`. */
+int ze_op_sample_rows(ze_engine* e, const float* logits, int rows, int vocab, int ld, const uint8_t* seen, const float* temperature,
+                      const float* repetition_penalty, const uint64_t* seed, const int32_t* sample_stream, const int32_t* index,
+                      const int32_t* top_k, const float* top_p, const float* min_p, int32_t* out_tokens, void* stream);
 
 /* Log-probabilities of the generated tokens (replaces: the `logprobs` / `top_logprobs` the OpenAI-compatible back-end of
  * src/eval/infer_vllm.py:244-271 can return with a sampled token, and the completion positions of `old_per_token_logps`,

@@ -135,6 +135,10 @@ _SIGS = {
     "ze_seq_set_sampling_filter": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, _P]),
     "ze_op_sample_filter": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P]),
+    "ze_seq_set_sampling": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_float, _P]),
+    "ze_op_sample_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
     "ze_seq_set_logprobs": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ze_chain_logprobs": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int,
                                     C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),

@@ -127,6 +127,13 @@ struct ze_engine {
     int n_filters = 0;
     float *filt_dev = nullptr, *cut_dev = nullptr;
     std::vector<int> graph_filters;  // whether the chain's graph was captured with the selection kernel in it
+    // Sampling requests (ze_seq_set_sampling): samp_host is the truth (penalty = 0: the slot has none), samp_dev the per-slot
+    // table the per-chain sampling kernels read, allocated by the first request and written in stream order by the setter;
+    // n_sampling = slots with a request, n_sampled = those of them that draw (temperature > 0).  While n_sampling is 0 every
+    // step launches the scalar kernels, under the graph keys it always had.
+    std::vector<ze_chain_sampling> samp_host;
+    int n_sampling = 0, n_sampled = 0;
+    ze_chain_sampling* samp_dev = nullptr;
     // Log-probabilities of generated tokens (ze_seq_set_logprobs): lp_host is the truth (-1 off, 0 chosen token only, 1..20
     // alternatives), lp_dev the per-slot table the kernel reads, written in stream order by the setter; n_logprobs = slots with
     // a request.  While it is 0 no step launches the kernel.  History, allocated by the first request that needs it: lp_tok f32

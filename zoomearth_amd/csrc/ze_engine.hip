@@ -305,6 +305,7 @@ extern "C" int ze_engine_create(const ze_config* cfg, int device_id, ze_engine**
     e->filt_host.assign(c.max_seqs, ze_engine::filter_host{});
     chk(dev_alloc(e, &e->filt_dev, (size_t)c.max_seqs * 4));
     chk(dev_alloc(e, &e->cut_dev, (size_t)c.max_seqs * 2));
+    e->samp_host.assign(c.max_seqs, ze_chain_sampling{0.f, 0.f, 0ull});
     e->graph_logprobs.assign(c.max_seqs, 0);
     e->lp_host.assign(c.max_seqs, -1);
     chk(dev_alloc(e, &e->lp_dev, (size_t)c.max_seqs, false));
@@ -475,7 +476,7 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
                    e->vo, e->va, e->vz, e->vz2, e->vcos, e->vsin, e->vperm, e->vinv, e->vtiles_win, e->vtiles_full,
                    e->th, e->ty, e->tqkv, e->to, e->ta, e->tsrc, e->tpos, e->ttiles, e->ttile_aux, e->trow_aux, e->dh, e->dq, e->dattn, e->dact,
                    e->dlogits, e->dpartial, e->dsample, e->atickets, e->gslab, e->gtickets, e->pslab, e->ptickets, e->bh, e->by, e->bqkv, e->bo, e->ba, e->bseq, e->bmate, e->blogits, e->bpartial, e->bsample, e->arena8, e->arena_f, e->arena_f8,
-                   e->ty8, e->ty8_scale, e->damax, e->ty8p, e->ty8p_scale, e->filt_dev, e->cut_dev,
+                   e->ty8, e->ty8_scale, e->damax, e->ty8p, e->ty8p_scale, e->filt_dev, e->cut_dev, e->samp_dev,
                    e->lp_dev, e->lp_tok, e->lp_top_ids, e->lp_top_lps, e->xl_dev,
                    e->la_dev, e->la_bias_ids, e->la_bias_vals, e->la_rows, e->la_counts,
                    e->tr_dev, e->tr_stop, e->tr_ban, e->tr_ctx};

@@ -422,6 +422,55 @@ extern "C" int ze_seq_set_sampling_filter(ze_engine* e, int seq, int top_k, floa
     return ZE_OK;
 }
 
+// ---- sampling requests (greedy | temperature, seed, repetition penalty per chain; ze_engine::samp_host is the truth, the per-chain
+// kernels of ze_sample.hip read samp_dev)
+static void write_sampling(ze_engine* e, int seq, const ze_chain_sampling& v, hipStream_t s) {
+    ze_chain_sampling& h = e->samp_host[seq];
+    const bool was = h.penalty > 0.f, on = v.penalty > 0.f;
+    e->n_sampling += (int)on - (int)was;
+    e->n_sampled += (int)(on && v.temperature > 0.f) - (int)(was && h.temperature > 0.f);
+    h = v;
+    if (was || on) ze_launch_set_sampling(e->samp_dev, seq, v, s);
+}
+// the slot goes to another chain (wherever its filter is cleared): it never inherits a request.  Nothing is launched for a slot
+// that has none.
+static void clear_sampling(ze_engine* e, int seq, hipStream_t s) {
+    if (e->samp_host[seq].penalty > 0.f) write_sampling(e, seq, ze_chain_sampling{0.f, 0.f, 0ull}, s);
+}
+
+extern "C" int ze_seq_set_sampling(ze_engine* e, int seq, int mode, float temperature, uint64_t seed, float repetition_penalty,
+                                   void* stream) {
+    ZE_TRY(check_seq(e, seq));
+    if (mode < -1 || mode > 1) return ze_fail(e, ZE_ERR_INVALID, "mode must be -1 (clear), 0 (greedy) or 1 (temperature sampling)");
+    if (mode == 1 && !(std::isfinite(temperature) && temperature > 0.f))
+        return ze_fail(e, ZE_ERR_INVALID, "temperature must be finite and > 0");
+    if (mode >= 0 && !(std::isfinite(repetition_penalty) && repetition_penalty > 0.f))
+        return ze_fail(e, ZE_ERR_INVALID, "repetition_penalty must be finite and > 0 (1 = off)");
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    // the table, on first use: a failed allocation leaves the engine as it was
+    if (mode >= 0 && !e->samp_dev) {
+        ze_chain_sampling* t = nullptr;
+        if (hipMalloc((void**)&t, (size_t)e->cfg.max_seqs * sizeof(ze_chain_sampling)) != hipSuccess) {
+            (void)hipGetLastError();
+            return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the sampling-request table failed");
+        }
+        // all zero = no request.  Once per engine, and waited for: setters on other streams may write their entries at once
+        if (hipMemset(t, 0, (size_t)e->cfg.max_seqs * sizeof(ze_chain_sampling)) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+            (void)hipGetLastError();
+            hipFree(t);
+            return ze_fail(e, ZE_ERR_HIP, "hipMemset of the sampling-request table failed");
+        }
+        e->samp_dev = t;
+    }
+    if (mode < 0)
+        clear_sampling(e, seq, s);
+    else
+        write_sampling(e, seq, ze_chain_sampling{mode == 1 ? temperature : 0.f, repetition_penalty, mode == 1 ? (unsigned long long)seed : 0ull}, s);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
 // ---- log-probabilities of generated tokens (ze_engine::lp_host is the truth, ze_logprobs.hip the kernel)
 static void write_logprobs(ze_engine* e, int seq, int top_n, hipStream_t s) {
     const int was = e->lp_host[seq];
@@ -673,6 +722,7 @@ extern "C" int ze_seq_reset(ze_engine* e, int seq, void* stream) {
     e->pfx_host[seq] = 0;
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)seq * e->cfg.vocab, 0, e->cfg.vocab, s));
     clear_filter(e, seq, s);
+    clear_sampling(e, seq, s);
     clear_logprobs(e, seq, s);
     clear_adjust(e, seq, s);
     clear_rules(e, seq, s);
@@ -736,6 +786,7 @@ extern "C" int ze_seq_truncate(ze_engine* e, int seq, int keep_len, void* stream
     // the seen-set belongs to the dropped continuation: the caller re-marks the (new) prompt
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)seq * e->cfg.vocab, 0, e->cfg.vocab, (hipStream_t)stream));
     clear_filter(e, seq, (hipStream_t)stream);
+    clear_sampling(e, seq, (hipStream_t)stream);
     clear_logprobs(e, seq, (hipStream_t)stream);
     clear_adjust(e, seq, (hipStream_t)stream);
     clear_rules(e, seq, (hipStream_t)stream);
@@ -772,6 +823,7 @@ extern "C" int ze_seq_copy_prefix(ze_engine* e, int dst_seq, int src_seq, int n_
     }
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)dst_seq * c.vocab, 0, c.vocab, s));
     clear_filter(e, dst_seq, s);
+    clear_sampling(e, dst_seq, s);
     clear_logprobs(e, dst_seq, s);
     clear_adjust(e, dst_seq, s);
     clear_rules(e, dst_seq, s);
@@ -1322,7 +1374,7 @@ extern "C" int ze_decode_step(ze_engine* e, int seq, int token, float* out_logit
 // A sampled launch learns about filters only while some chain of the engine has one: with none set it is today's launch
 // sequence.  `batch`: the cuts of a batched step (one per row) -- otherwise the slot's own word.
 static void attach_filters(ze_engine* e, ze_sample_opts& so, bool batch) {
-    if (so.temperature > 0.f && e->n_filters > 0) {
+    if (so.draws() && e->n_filters > 0) {
         so.filt = e->filt_dev;
         so.cuts = batch ? e->cut_dev : e->cut_dev + e->cfg.max_seqs + so.slot;
     }
@@ -1352,8 +1404,67 @@ extern "C" int ze_op_sample_filter(ze_engine* e, const float* logits, int rows, 
     int r = ZE_OK;
     if (hipMemcpyAsync(dev, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)
         r = ze_fail(e, ZE_ERR_HIP, "hipMemcpyAsync failed");
-    if (r == ZE_OK) ze_launch_sample_filter(logits, vocab, ld, nullptr, nullptr, 0, rows, 1.0f, 1.0f, dev, out_cut, out_kept, s);
+    if (r == ZE_OK) ze_launch_sample_filter(logits, vocab, ld, nullptr, nullptr, 0, rows, 1.0f, 1.0f, dev, out_cut, out_kept, nullptr, s);
     if (r == ZE_OK && hipGetLastError() != hipSuccess) r = ze_fail(e, ZE_ERR_HIP, "selection kernel launch failed");
+    if (hipStreamSynchronize(s) != hipSuccess && r == ZE_OK) r = ze_fail(e, ZE_ERR_HIP, "hipStreamSynchronize failed");
+    hipFree(dev);
+    return r;
+}
+
+// One draw per caller row with a (temperature | greedy, penalty, seed, stream, index) of its own: the per-chain kernels of
+// ze_sample.hip with row = slot, on tables built for the call
+extern "C" int ze_op_sample_rows(ze_engine* e, const float* logits, int rows, int vocab, int ld, const uint8_t* seen,
+                                 const float* temperature, const float* repetition_penalty, const uint64_t* seed,
+                                 const int32_t* sample_stream, const int32_t* index, const int32_t* top_k, const float* top_p,
+                                 const float* min_p, int32_t* out_tokens, void* stream) {
+    if (!e || !logits || !temperature || !repetition_penalty || !seed || !sample_stream || !index || !out_tokens)
+        return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    if (rows <= 0 || vocab <= 0 || ld < vocab) return ze_fail(e, ZE_ERR_INVALID, "rows and vocab must be positive, ld >= vocab");
+    const bool filters = top_k || top_p || min_p;
+    if (filters && !(top_k && top_p && min_p)) return ze_fail(e, ZE_ERR_INVALID, "top_k, top_p and min_p come together or not at all");
+    // one block of 4-byte words: requests (4 per row) | chain states (8) | filters (4) | row ids (1) | cuts (1) | arg-max
+    // partials (256) | chunk sums (128); the 16-byte entries come first, so they stay aligned
+    const size_t o_samp = 0, o_st = o_samp + 4 * (size_t)rows, o_filt = o_st + 8 * (size_t)rows, o_ids = o_filt + 4 * (size_t)rows,
+                 o_cut = o_ids + rows, o_part = o_cut + rows, o_sum = o_part + 256 * (size_t)rows, words = o_sum + 128 * (size_t)rows;
+    static_assert(sizeof(ze_chain_sampling) == 16 && sizeof(ze_seq_dev) == 32, "table strides");
+    std::vector<int32_t> host(o_cut, 0);
+    bool draws = false;
+    for (int r = 0; r < rows; ++r) {
+        if (!(std::isfinite(temperature[r]) && temperature[r] >= 0.f)) return ze_fail(e, ZE_ERR_INVALID, "temperature must be finite and >= 0 (0 = greedy)");
+        if (!(std::isfinite(repetition_penalty[r]) && repetition_penalty[r] > 0.f))
+            return ze_fail(e, ZE_ERR_INVALID, "repetition_penalty must be finite and > 0 (1 = off)");
+        if (index[r] < 0) return ze_fail(e, ZE_ERR_INVALID, "index must be >= 0");
+        const ze_chain_sampling req{temperature[r], repetition_penalty[r], temperature[r] > 0.f ? (unsigned long long)seed[r] : 0ull};
+        memcpy(&host[o_samp + 4 * (size_t)r], &req, sizeof(req));
+        draws |= temperature[r] > 0.f;
+        ze_seq_dev st;
+        memset(&st, 0, sizeof(st));
+        st.n_gen = index[r];
+        st.stream = sample_stream[r];
+        memcpy(&host[o_st + 8 * (size_t)r], &st, sizeof(st));
+        host[o_ids + r] = r;
+        if (filters) {
+            if (top_k[r] < 0) return ze_fail(e, ZE_ERR_INVALID, "top_k must be >= 0 (0 = off)");
+            if (!(top_p[r] > 0.f && top_p[r] <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "top_p must be in (0, 1] (1 = off)");
+            if (!(min_p[r] >= 0.f && min_p[r] <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "min_p must be in [0, 1] (0 = off)");
+            host[o_filt + 4 * (size_t)r] = top_k[r];
+            memcpy(&host[o_filt + 4 * (size_t)r + 1], &top_p[r], sizeof(float));
+            memcpy(&host[o_filt + 4 * (size_t)r + 2], &min_p[r], sizeof(float));
+        }
+    }
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    int32_t* dev = nullptr;
+    ZE_HIP(hipMalloc((void**)&dev, words * sizeof(int32_t)));
+    int r = ZE_OK;
+    if (hipMemcpyAsync(dev, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess)
+        r = ze_fail(e, ZE_ERR_HIP, "hipMemcpyAsync failed");
+    if (r == ZE_OK)
+        ze_launch_sample_rows(logits, vocab, ld, seen, reinterpret_cast<const ze_seq_dev*>(dev + o_st), dev + o_ids, rows,
+                              reinterpret_cast<const ze_chain_sampling*>(dev + o_samp), draws,
+                              filters ? reinterpret_cast<const float*>(dev + o_filt) : nullptr, reinterpret_cast<float*>(dev + o_cut),
+                              reinterpret_cast<float*>(dev + o_part), reinterpret_cast<float*>(dev + o_sum), out_tokens, s);
+    if (r == ZE_OK && hipGetLastError() != hipSuccess) r = ze_fail(e, ZE_ERR_HIP, "sampling kernel launch failed");
     if (hipStreamSynchronize(s) != hipSuccess && r == ZE_OK) r = ze_fail(e, ZE_ERR_HIP, "hipStreamSynchronize failed");
     hipFree(dev);
     return r;
@@ -1395,11 +1506,28 @@ extern "C" int ze_op_sample_temperature(ze_engine* e, int seq, const float* logi
     return op_sample(e, seq, logits, repetition_penalty, so, index, out_token, (hipStream_t)stream);
 }
 
+// The repetition penalty a single-chain launch runs with: the chain's own while it has a sampling request, else the call's
+static float penalty_of(const ze_engine* e, const ze_gen_params* p, int seq) {
+    if (e->samp_host[seq].penalty > 0.f) return e->samp_host[seq].penalty;
+    return p->repetition_penalty > 0.f ? p->repetition_penalty : 1.0f;
+}
+
+// A single-chain launch serves one known chain: its request (ze_seq_set_sampling) is resolved here, on the host, and the scalar
+// kernels run with the chain's own values.  `batch`: the call's values stay the launch's defaults, and the per-slot table joins
+// them while some chain of the engine has a request -- with none it is today's launch sequence.
 static ze_sample_opts sample_opts_of(ze_engine* e, const ze_gen_params* p, int slot, bool batch = false) {
     ze_sample_opts so;
-    if (p->do_sample && p->temperature > 0.f) {
+    const ze_chain_sampling& req = e->samp_host[slot];
+    if (!batch && req.penalty > 0.f) {
+        so.temperature = req.temperature;
+        so.seed = req.temperature > 0.f ? req.seed : 0ull;
+    } else if (p->do_sample && p->temperature > 0.f) {
         so.temperature = p->temperature;
         so.seed = p->seed;
+    }
+    if (batch && e->n_sampling > 0) {
+        so.samp = e->samp_dev;
+        so.samp_draws = e->n_sampled > 0;
     }
     so.slot = slot;
     attach_filters(e, so, batch);
@@ -1421,7 +1549,7 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
     // the last generated token is never fed back, so ctx grows by max_new - 1
     if (e->ctx_host[seq] + max_new - 1 > c.max_ctx) max_new = c.max_ctx - e->ctx_host[seq] + 1;
     if (max_new <= 0) return ze_fail(e, ZE_ERR_NOMEM, "sequence exceeds max_ctx");
-    const float pen = p->repetition_penalty > 0.f ? p->repetition_penalty : 1.0f;
+    const float pen = penalty_of(e, p, seq);  // (the graph below is keyed by the effective values: a new request re-captures it)
     const int ign = p->ignore_eos ? 1 : 0;
     int32_t* dev_out = e->out_tokens + (size_t)seq * c.max_ctx;
     ze_seq_dev* st = e->st_dev + seq;
@@ -1843,7 +1971,9 @@ extern "C" int ze_decode_batch(ze_engine* e, const int32_t* seqs, int n, const i
 // The captured batched decode step for `na` chains (chain ids / positions live in device memory, so one graph per
 // batch size and sampling setting serves every composition); nullptr in *out = run eagerly.
 static int batch_step_graph(ze_engine* e, int na, float pen, int ign, const ze_sample_opts& bso, hipGraphExec_t* out) {
-    auto key = std::make_tuple(na, pen, ign, bso.temperature, bso.seed, e->live_parts * 64 + e->live_parts_long, (int)(bso.filt != nullptr),
+    auto key = std::make_tuple(na, pen, ign, bso.temperature, bso.seed, e->live_parts * 64 + e->live_parts_long,
+                               // (per-chain sampling: the mode and whether the draw is launched -- never a request's values)
+                               (int)(bso.filt != nullptr) | (int)(bso.samp != nullptr) << 1 | (int)bso.samp_draws << 2,
                                e->lp_mode(), e->la_mode(), e->tr_mode());
     if (e->bgraph_epoch != ze_tune_epoch) {
         for (auto& kv : e->bgraphs) hipGraphExecDestroy(kv.second);
@@ -1892,8 +2022,9 @@ static int run_burst(ze_engine* e, const std::vector<int>& active, int steps, co
 }
 
 // first token of a chain from the logits its prefill left behind; `sample_stream` = the chain's random stream
-static int begin_chain(ze_engine* e, int q, const ze_gen_params* p, float pen, int ign, int sample_stream, hipStream_t s) {
+static int begin_chain(ze_engine* e, int q, const ze_gen_params* p, int ign, int sample_stream, hipStream_t s) {
     const ze_config& c = e->cfg;
+    const float pen = penalty_of(e, p, q);
     ze_sample_opts so = sample_opts_of(e, p, q);
     if (so.temperature > 0.f) ze_launch_set_ints(&(e->st_dev + q)->stream, &sample_stream, 1, s);
     ze_launch_sample(adjusted_rows(e, e->dlogits + (size_t)q * c.vocab, nullptr, q, 1, s), c.vocab, e->seen + (size_t)q * c.vocab, pen,
@@ -1929,7 +2060,7 @@ extern "C" int ze_generate_batch(ze_engine* e, const int32_t* seqs, int n, const
     const int ign = p->ignore_eos ? 1 : 0;
     const ze_sample_opts bso = sample_opts_of(e, p, 0, true);
     // sampling stream of a chain = its row in this call (reproducible per request)
-    for (int i = 0; i < n; ++i) ZE_TRY(begin_chain(e, seqs[i], p, pen, ign, i, s));
+    for (int i = 0; i < n; ++i) ZE_TRY(begin_chain(e, seqs[i], p, ign, i, s));
     std::vector<int> active;
     std::vector<int> produced(c.max_seqs, 0);
     for (int i = 0; i < n; ++i) {
@@ -1987,9 +2118,8 @@ extern "C" int ze_chain_begin(ze_engine* e, int seq, const ze_gen_params* p, int
     hipSetDevice(e->device);
     hipStream_t s = (hipStream_t)stream;
     ZE_TRY(ensure_fragments(e, s));
-    const float pen = p->repetition_penalty > 0.f ? p->repetition_penalty : 1.0f;
     const int t_s = ze_timer_begin(e, 4, s);
-    const int r = begin_chain(e, seq, p, pen, p->ignore_eos ? 1 : 0, sample_stream, s);
+    const int r = begin_chain(e, seq, p, p->ignore_eos ? 1 : 0, sample_stream, s);
     ze_timer_end(e, t_s, s);
     return r;
 }

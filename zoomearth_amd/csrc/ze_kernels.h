@@ -289,6 +289,13 @@ void ze_launch_kv_copy_prefix(bf16_t* kcache, bf16_t* vcache, size_t layer_strid
                               int layers, int kv_heads, int D, int src, int dst, int n_tokens, hipStream_t s);
 
 // ---- sampling
+// Request of one chain slot (ze_seq_set_sampling): 16 bytes, one load per workgroup.  penalty = 0: the slot has no request (a
+// request's penalty is > 0) and the row follows the launch's scalars; temperature = 0: greedy.
+struct __attribute__((aligned(16))) ze_chain_sampling {
+    float temperature;
+    float penalty;
+    unsigned long long seed;
+};
 struct ze_sample_opts {
     float temperature = 0.f;      // 0: greedy arg-max; > 0: multinomial draw from softmax(score / temperature)
     unsigned long long seed = 0;  // draw = f(seed, ze_seq_dev::stream of the chain, index of the generated token)
@@ -297,13 +304,27 @@ struct ze_sample_opts {
     // launch); both null unless some chain of the engine has a filter -- then the draw launches exactly what it always did
     const float* filt = nullptr;
     float* cuts = nullptr;
+    // per-chain sampling requests (batched launches only; a single-chain launch resolves its chain's request on the host):
+    // the per-slot table, null unless some chain of the engine has a request -- then the step launches exactly what it always
+    // did; samp_draws: some chain of the engine has a SAMPLED request, so the draw is launched whatever `temperature` says
+    const ze_chain_sampling* samp = nullptr;
+    bool samp_draws = false;
+    bool draws() const { return temperature > 0.f || samp_draws; }
 };
 // The cut of each of n rows (ze_sample_filter.hip): row b reads filt[seq_ids ? seq_ids[b] : slot0 + b]; seen_base is per slot
-// when seq_ids is given, the chain's own set (or null) otherwise; out_kept may be null.
+// when seq_ids is given, the chain's own set (or null) otherwise; out_kept may be null.  samp (or null): the per-slot sampling
+// requests -- a row whose slot has one takes its temperature and penalty from it, and a greedy row gets cut = -inf at once.
 void ze_launch_sample_filter(const float* logits, int vocab, int ld, const uint8_t* seen_base, const int* seq_ids, int slot0,
                              int n, float penalty, float temperature, const float* filt, float* out_cut, int* out_kept,
-                             hipStream_t s);
+                             const ze_chain_sampling* samp, hipStream_t s);
 void ze_launch_set_filter(float* filt, int slot, int top_k, float top_p, float min_p, float temperature, hipStream_t s);
+void ze_launch_set_sampling(ze_chain_sampling* table, int slot, ze_chain_sampling v, hipStream_t s);
+// One draw per row on caller rows (ze_op_sample_rows): logits [n, ld]; seen [n, vocab] or null; samp / st / filt (or null) have
+// one entry per ROW (ids = 0 .. n-1 on the device); ws_part 2 * 128 * n, ws_sum 128 * n, cuts n floats.  Touches neither seen
+// nor st: out_tokens[row] = the token.
+void ze_launch_sample_rows(const float* logits, int vocab, int ld, const uint8_t* seen, const ze_seq_dev* st, const int* ids, int n,
+                           const ze_chain_sampling* samp, bool draws, const float* filt, float* cuts, float* ws_part, float* ws_sum,
+                           int32_t* out_tokens, hipStream_t s);
 // ws: 2 * 128 arg-max partials + 64 spare + 128 chunk sums (floats)
 void ze_launch_sample(const float* logits, int vocab, uint8_t* seen, float penalty, ze_seq_dev* st,
                       const int* eos_ids, int n_eos, int pad_id, int ignore_eos, int advance_ctx,

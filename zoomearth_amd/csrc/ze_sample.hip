@@ -118,18 +118,18 @@ __device__ __forceinline__ void accept_token(int bi, uint8_t* __restrict__ seen,
     }
 }
 
-void ze_launch_multinomial(const float* logits, int vocab, const uint8_t* seen_base, const ze_seq_dev* st,
+void ze_launch_multinomial(const float* logits, int vocab, int ld, const uint8_t* seen_base, const ze_seq_dev* st,
                            const int* seq_ids, int slot0, int n, float penalty, float temperature,
                            unsigned long long seed, float* ws_part, float* ws_sum, const float* filt, float* cuts,
-                           hipStream_t s);
+                           const ze_chain_sampling* samp, hipStream_t s);
 
 void ze_launch_sample(const float* logits, int vocab, uint8_t* seen, float penalty, ze_seq_dev* st,
                       const int* eos_ids, int n_eos, int pad_id, int ignore_eos, int advance_ctx,
                       int32_t* out_tokens, float* ws, const ze_sample_opts& so, hipStream_t s) {
     k_argmax_partial<<<SAMPLE_BLOCKS, 256, 0, s>>>(logits, vocab, seen, penalty, ws);
     if (so.temperature > 0.f)
-        ze_launch_multinomial(logits, vocab, seen, st, nullptr, so.slot, 1, penalty, so.temperature, so.seed, ws,
-                              ws + 2 * SAMPLE_BLOCKS + 64, so.filt, so.cuts, s);
+        ze_launch_multinomial(logits, vocab, vocab, seen, st, nullptr, so.slot, 1, penalty, so.temperature, so.seed, ws,
+                              ws + 2 * SAMPLE_BLOCKS + 64, so.filt, so.cuts, nullptr, s);
     k_argmax_final<<<1, 64, 0, s>>>(ws, seen, st, eos_ids, n_eos, pad_id, ignore_eos, advance_ctx, out_tokens, vocab);
 }
 
@@ -187,13 +187,9 @@ void ze_launch_gather_chain_tokens(const ze_seq_dev* st, const int* out_tokens, 
 }
 
 // ------------------------------------------------------------------ batched sampling: grid.y = chain
-__global__ void __launch_bounds__(256) k_argmax_partial_batch(const float* __restrict__ logits, int vocab,
-                                                              const uint8_t* __restrict__ seen_base,
-                                                              const int* __restrict__ seq_ids, float penalty,
-                                                              float* __restrict__ ws) {
-    const int b = blockIdx.y;
-    const float* lg = logits + (size_t)b * vocab;
-    const uint8_t* seen = seen_base + (size_t)seq_ids[b] * vocab;
+// this workgroup's (value, index) partial of one row -> o[2 * blockIdx.x ..]
+__device__ __forceinline__ void argmax_partial_row(const float* __restrict__ lg, int vocab, const uint8_t* __restrict__ seen,
+                                                   float penalty, float* __restrict__ o) {
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += SAMPLE_BLOCKS * 256) {
@@ -216,10 +212,44 @@ __global__ void __launch_bounds__(256) k_argmax_partial_batch(const float* __res
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
-        float* o = ws + (size_t)b * 2 * SAMPLE_BLOCKS;
         o[2 * blockIdx.x] = bv;
         reinterpret_cast<int*>(o)[2 * blockIdx.x + 1] = bi;
     }
+}
+
+__global__ void __launch_bounds__(256) k_argmax_partial_batch(const float* __restrict__ logits, int vocab,
+                                                              const uint8_t* __restrict__ seen_base,
+                                                              const int* __restrict__ seq_ids, float penalty,
+                                                              float* __restrict__ ws) {
+    const int b = blockIdx.y;
+    argmax_partial_row(logits + (size_t)b * vocab, vocab, seen_base + (size_t)seq_ids[b] * vocab, penalty,
+                       ws + (size_t)b * 2 * SAMPLE_BLOCKS);
+}
+
+// ---- per-chain forms (ze_seq_set_sampling), launched only while some chain of the engine has a request.  A row reads the
+// entry of its slot -- one 16-byte load, the same address for the whole workgroup, so every branch on it is uniform -- and
+// follows the launch's scalars when the slot has none: such a chain computes what the scalar kernels compute, bit for bit.
+__device__ __forceinline__ ze_chain_sampling chain_sampling_of(const ze_chain_sampling* __restrict__ samp, int slot, float penalty,
+                                                               float temperature, unsigned long long seed) {
+    ze_chain_sampling r = samp[slot];
+    if (!(r.penalty > 0.f)) {
+        r.temperature = temperature;
+        r.penalty = penalty;
+        r.seed = seed;
+    }
+    return r;
+}
+
+// rows [n, ld]; seen_base null (unit op without a seen-set): no penalty
+__global__ void __launch_bounds__(256) k_argmax_partial_chain(const float* __restrict__ logits, int vocab, int ld,
+                                                              const uint8_t* __restrict__ seen_base,
+                                                              const int* __restrict__ seq_ids, float penalty,
+                                                              const ze_chain_sampling* __restrict__ samp,
+                                                              float* __restrict__ ws) {
+    const int b = blockIdx.y, slot = seq_ids[b];
+    const ze_chain_sampling r = chain_sampling_of(samp, slot, penalty, 0.f, 0ull);
+    argmax_partial_row(logits + (size_t)b * ld, vocab, seen_base ? seen_base + (size_t)slot * vocab : nullptr,
+                       seen_base ? r.penalty : 1.0f, ws + (size_t)b * 2 * SAMPLE_BLOCKS);
 }
 
 __global__ void __launch_bounds__(64) k_argmax_final_batch(const float* __restrict__ ws, uint8_t* __restrict__ seen_base,
@@ -266,10 +296,13 @@ void ze_launch_sample_batch(const float* logits, int vocab, uint8_t* seen_base, 
                             float* ws_sum, const ze_sample_opts& so, hipStream_t s) {
     if (n <= 0) return;
     if (sample) {
-        k_argmax_partial_batch<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, seen_base, seq_ids, penalty, ws);
-        if (so.temperature > 0.f)
-            ze_launch_multinomial(logits, vocab, seen_base, st, seq_ids, 0, n, penalty, so.temperature, so.seed, ws,
-                                  ws_sum, so.filt, so.cuts, s);
+        if (so.samp)
+            k_argmax_partial_chain<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, vocab, seen_base, seq_ids, penalty, so.samp, ws);
+        else
+            k_argmax_partial_batch<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, seen_base, seq_ids, penalty, ws);
+        if (so.draws())
+            ze_launch_multinomial(logits, vocab, vocab, seen_base, st, seq_ids, 0, n, penalty, so.temperature, so.seed, ws,
+                                  ws_sum, so.filt, so.cuts, so.samp, s);
     }
     k_argmax_final_batch<<<n, 64, 0, s>>>(ws, seen_base, st, seq_ids, vocab, eos_ids, n_eos, pad_id, ignore_eos,
                                           advance_ctx, sample, out_tokens_base, max_gen);
@@ -332,45 +365,56 @@ __device__ __forceinline__ void sample_chunk_sums(const float* lg, const uint8_t
     __syncthreads();
 }
 
+// chunk sum blockIdx.x of one row -> sums[blockIdx.x]
+__device__ __forceinline__ void softmax_partial_row(const float* __restrict__ lg, int vocab, const uint8_t* __restrict__ seen,
+                                                    float penalty, float temperature, const float* __restrict__ part,
+                                                    float* __restrict__ sums, float cut) {
+    const float zmax = sample_zmax(part, temperature);
+    const int chunk = (vocab + SAMPLE_BLOCKS - 1) / SAMPLE_BLOCKS, run = (chunk + 255) / 256;
+    const int start = blockIdx.x * chunk, end = min(vocab, start + chunk);
+    __shared__ float sRun[256];
+    __shared__ float sTot;
+    sample_chunk_sums(lg, seen, penalty, temperature, zmax, cut, start, end, run, sRun, &sTot);
+    if (threadIdx.x == 0) sums[blockIdx.x] = sTot;
+}
+
 __global__ void __launch_bounds__(256) k_softmax_partial(const float* __restrict__ logits, int vocab,
                                                          const uint8_t* __restrict__ seen_base,
                                                          const int* __restrict__ seq_ids, float penalty,
                                                          float temperature, const float* __restrict__ ws_part,
                                                          float* __restrict__ ws_sum, const float* __restrict__ cuts) {
     const int b = blockIdx.y;
-    const float* lg = logits + (size_t)b * vocab;
-    const uint8_t* seen = seen_base + (seq_ids ? (size_t)seq_ids[b] * vocab : 0);
-    const float zmax = sample_zmax(ws_part + (size_t)b * 2 * SAMPLE_BLOCKS, temperature);
-    const int chunk = (vocab + SAMPLE_BLOCKS - 1) / SAMPLE_BLOCKS, run = (chunk + 255) / 256;
-    const int start = blockIdx.x * chunk, end = min(vocab, start + chunk);
-    __shared__ float sRun[256];
-    __shared__ float sTot;
-    sample_chunk_sums(lg, seen, penalty, temperature, zmax, cuts ? cuts[b] : -INFINITY, start, end, run, sRun, &sTot);
-    if (threadIdx.x == 0) ws_sum[(size_t)b * SAMPLE_BLOCKS + blockIdx.x] = sTot;
+    softmax_partial_row(logits + (size_t)b * vocab, vocab, seen_base + (seq_ids ? (size_t)seq_ids[b] * vocab : 0), penalty, temperature,
+                        ws_part + (size_t)b * 2 * SAMPLE_BLOCKS, ws_sum + (size_t)b * SAMPLE_BLOCKS, cuts ? cuts[b] : -INFINITY);
 }
 
-__global__ void __launch_bounds__(256) k_multinomial_pick(const float* __restrict__ logits, int vocab,
-                                                          const uint8_t* __restrict__ seen_base,
-                                                          const ze_seq_dev* __restrict__ st_base,
-                                                          const int* __restrict__ seq_ids, int slot0, float penalty,
-                                                          float temperature, unsigned long long seed,
-                                                          float* __restrict__ ws_part,
-                                                          const float* __restrict__ ws_sum,
-                                                          const float* __restrict__ cuts) {
-    const int b = blockIdx.x, slot = seq_ids ? seq_ids[b] : slot0;
-    const ze_seq_dev* st = seq_ids ? st_base + slot : st_base;
-    const float* lg = logits + (size_t)b * vocab;
-    const uint8_t* seen = seen_base + (seq_ids ? (size_t)slot * vocab : 0);
-    float* part = ws_part + (size_t)b * 2 * SAMPLE_BLOCKS;
+// a greedy row leaves at once: its arg-max partials stay as they are and k_argmax_final_batch picks greedily
+__global__ void __launch_bounds__(256) k_softmax_partial_chain(const float* __restrict__ logits, int vocab, int ld,
+                                                               const uint8_t* __restrict__ seen_base,
+                                                               const int* __restrict__ seq_ids, float penalty,
+                                                               float temperature, const ze_chain_sampling* __restrict__ samp,
+                                                               const float* __restrict__ ws_part, float* __restrict__ ws_sum,
+                                                               const float* __restrict__ cuts) {
+    const int b = blockIdx.y, slot = seq_ids[b];
+    const ze_chain_sampling r = chain_sampling_of(samp, slot, penalty, temperature, 0ull);
+    if (!(r.temperature > 0.f)) return;
+    softmax_partial_row(logits + (size_t)b * ld, vocab, seen_base ? seen_base + (size_t)slot * vocab : nullptr,
+                        seen_base ? r.penalty : 1.0f, r.temperature, ws_part + (size_t)b * 2 * SAMPLE_BLOCKS,
+                        ws_sum + (size_t)b * SAMPLE_BLOCKS, cuts ? cuts[b] : -INFINITY);
+}
+
+// the draw of one row (one workgroup): the pick replaces part[0..1]
+__device__ __forceinline__ void multinomial_pick_row(const float* __restrict__ lg, int vocab, const uint8_t* __restrict__ seen,
+                                                     const ze_seq_dev* __restrict__ st, float penalty, float temperature,
+                                                     unsigned long long seed, float* __restrict__ part,
+                                                     const float* __restrict__ sums, float cut) {
     const float zmax = sample_zmax(part, temperature);
-    const float cut = cuts ? cuts[b] : -INFINITY;
     const int chunk = (vocab + SAMPLE_BLOCKS - 1) / SAMPLE_BLOCKS, run = (chunk + 255) / 256;
     __shared__ float sRun[256];
     __shared__ float sTot;
     __shared__ int sBlk;
     __shared__ float sTarget;
     if (threadIdx.x == 0) {
-        const float* sums = ws_sum + (size_t)b * SAMPLE_BLOCKS;
         float total = 0.f;
         for (int k = 0; k < SAMPLE_BLOCKS; ++k) total += sums[k];
         const unsigned long long key = ze_mix64(seed ^ ze_mix64((unsigned long long)st->stream + 1ull));
@@ -430,19 +474,88 @@ __global__ void __launch_bounds__(256) k_multinomial_pick(const float* __restric
     }
 }
 
-void ze_launch_multinomial(const float* logits, int vocab, const uint8_t* seen_base, const ze_seq_dev* st,
+__global__ void __launch_bounds__(256) k_multinomial_pick(const float* __restrict__ logits, int vocab,
+                                                          const uint8_t* __restrict__ seen_base,
+                                                          const ze_seq_dev* __restrict__ st_base,
+                                                          const int* __restrict__ seq_ids, int slot0, float penalty,
+                                                          float temperature, unsigned long long seed,
+                                                          float* __restrict__ ws_part,
+                                                          const float* __restrict__ ws_sum,
+                                                          const float* __restrict__ cuts) {
+    const int b = blockIdx.x, slot = seq_ids ? seq_ids[b] : slot0;
+    multinomial_pick_row(logits + (size_t)b * vocab, vocab, seen_base + (seq_ids ? (size_t)slot * vocab : 0),
+                         seq_ids ? st_base + slot : st_base, penalty, temperature, seed, ws_part + (size_t)b * 2 * SAMPLE_BLOCKS,
+                         ws_sum + (size_t)b * SAMPLE_BLOCKS, cuts ? cuts[b] : -INFINITY);
+}
+
+__global__ void __launch_bounds__(256) k_multinomial_pick_chain(const float* __restrict__ logits, int vocab, int ld,
+                                                                const uint8_t* __restrict__ seen_base,
+                                                                const ze_seq_dev* __restrict__ st_base,
+                                                                const int* __restrict__ seq_ids, float penalty,
+                                                                float temperature, unsigned long long seed,
+                                                                const ze_chain_sampling* __restrict__ samp,
+                                                                float* __restrict__ ws_part, const float* __restrict__ ws_sum,
+                                                                const float* __restrict__ cuts) {
+    const int b = blockIdx.x, slot = seq_ids[b];
+    const ze_chain_sampling r = chain_sampling_of(samp, slot, penalty, temperature, seed);
+    if (!(r.temperature > 0.f)) return;
+    multinomial_pick_row(logits + (size_t)b * ld, vocab, seen_base ? seen_base + (size_t)slot * vocab : nullptr, st_base + slot,
+                         seen_base ? r.penalty : 1.0f, r.temperature, r.seed, ws_part + (size_t)b * 2 * SAMPLE_BLOCKS,
+                         ws_sum + (size_t)b * SAMPLE_BLOCKS, cuts ? cuts[b] : -INFINITY);
+}
+
+// samp (batched launches only, seq_ids given): the per-chain forms -- the same passes over the rows, the values per row
+void ze_launch_multinomial(const float* logits, int vocab, int ld, const uint8_t* seen_base, const ze_seq_dev* st,
                            const int* seq_ids, int slot0, int n, float penalty, float temperature,
                            unsigned long long seed, float* ws_part, float* ws_sum, const float* filt, float* cuts,
-                           hipStream_t s) {
+                           const ze_chain_sampling* samp, hipStream_t s) {
     if (n <= 0) return;
     // filt = null (no chain of the engine has a filter): the two launches of the plain draw, nothing else
     if (!filt) cuts = nullptr;
     if (cuts)
-        ze_launch_sample_filter(logits, vocab, vocab, seen_base, seq_ids, slot0, n, penalty, temperature, filt, cuts, nullptr, s);
+        ze_launch_sample_filter(logits, vocab, ld, seen_base, seq_ids, slot0, n, penalty, temperature, filt, cuts, nullptr, samp, s);
+    if (samp) {
+        k_softmax_partial_chain<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, ld, seen_base, seq_ids, penalty, temperature,
+                                                                       samp, ws_part, ws_sum, cuts);
+        k_multinomial_pick_chain<<<n, 256, 0, s>>>(logits, vocab, ld, seen_base, st, seq_ids, penalty, temperature, seed, samp,
+                                                   ws_part, ws_sum, cuts);
+        return;
+    }
     k_softmax_partial<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, seen_base, seq_ids, penalty, temperature,
                                                              ws_part, ws_sum, cuts);
     k_multinomial_pick<<<n, 256, 0, s>>>(logits, vocab, seen_base, st, seq_ids, slot0, penalty, temperature, seed,
                                          ws_part, ws_sum, cuts);
+}
+
+// samp[slot] = v: the values travel as kernel arguments
+__global__ void k_set_sampling(ze_chain_sampling* table, int slot, ze_chain_sampling v) { table[slot] = v; }
+void ze_launch_set_sampling(ze_chain_sampling* table, int slot, ze_chain_sampling v, hipStream_t s) {
+    k_set_sampling<<<1, 1, 0, s>>>(table, slot, v);
+}
+
+// ---- one draw per caller row (ze_op_sample_rows): the per-chain kernels with row = slot, and a final reduction that touches
+// no chain state
+__global__ void __launch_bounds__(64) k_argmax_final_rows(const float* __restrict__ ws, int vocab, int32_t* __restrict__ out_tokens) {
+    const float* w = ws + (size_t)blockIdx.x * 2 * SAMPLE_BLOCKS;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < SAMPLE_BLOCKS; i += 64) better(bv, bi, w[2 * i], reinterpret_cast<const int*>(w)[2 * i + 1]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(bv, off, 64);
+        const int oi = __shfl_xor(bi, off, 64);
+        better(bv, bi, ov, oi);
+    }
+    if (threadIdx.x == 0) out_tokens[blockIdx.x] = (unsigned)bi >= (unsigned)vocab ? 0 : bi;  // every logit NaN: torch.argmax gives 0
+}
+
+void ze_launch_sample_rows(const float* logits, int vocab, int ld, const uint8_t* seen, const ze_seq_dev* st, const int* ids, int n,
+                           const ze_chain_sampling* samp, bool draws, const float* filt, float* cuts, float* ws_part, float* ws_sum,
+                           int32_t* out_tokens, hipStream_t s) {
+    if (n <= 0) return;
+    k_argmax_partial_chain<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, ld, seen, ids, 1.0f, samp, ws_part);
+    if (draws) ze_launch_multinomial(logits, vocab, ld, seen, st, ids, 0, n, 1.0f, 0.f, 0ull, ws_part, ws_sum, filt, cuts, samp, s);
+    k_argmax_final_rows<<<n, 64, 0, s>>>(ws_part, vocab, out_tokens);
 }
 
 // ----------------------------------------------------------------------------------------------------------------

@@ -143,16 +143,22 @@ __global__ void __launch_bounds__(FILT_THREADS) k_sample_filter(const float* __r
                                                                 const uint8_t* __restrict__ seen_base,
                                                                 const int* __restrict__ seq_ids, int slot0, float penalty,
                                                                 float temperature, const float4* __restrict__ filt,
-                                                                float* __restrict__ out_cut, int* __restrict__ out_kept) {
+                                                                float* __restrict__ out_cut, int* __restrict__ out_kept,
+                                                                const ze_chain_sampling* __restrict__ samp) {
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63;
     const int slot = seq_ids ? seq_ids[b] : slot0 + b;
     const float4 fp = filt[slot];
     int top_k = __float_as_int(fp.x);
     const float top_p = fp.y, min_p = fp.z;
     if (fp.w > 0.f) temperature = fp.w;  // the unit op: a temperature per row
+    if (samp) {  // per-chain sampling requests (ze_seq_set_sampling): the slot's own temperature and penalty; uniform per workgroup
+        const ze_chain_sampling r = samp[slot];
+        if (r.penalty > 0.f) temperature = r.temperature, penalty = r.penalty;
+    }
+    const bool greedy = !(temperature > 0.f);  // (only a per-chain row: the scalar launch exists for sampled steps alone)
     if (top_k >= vocab) top_k = 0;
     const bool has_k = top_k > 0, has_p = top_p < 1.0f, has_m = min_p > 0.f;
-    if (!has_k && !has_p && !has_m) {
+    if (greedy || (!has_k && !has_p && !has_m)) {
         if (t == 0) {
             out_cut[b] = -INFINITY;
             if (out_kept) out_kept[b] = vocab;
@@ -294,10 +300,10 @@ __global__ void __launch_bounds__(FILT_THREADS) k_sample_filter(const float* __r
 
 void ze_launch_sample_filter(const float* logits, int vocab, int ld, const uint8_t* seen_base, const int* seq_ids, int slot0,
                              int n, float penalty, float temperature, const float* filt, float* out_cut, int* out_kept,
-                             hipStream_t s) {
+                             const ze_chain_sampling* samp, hipStream_t s) {
     if (n <= 0) return;
     k_sample_filter<<<n, FILT_THREADS, 0, s>>>(logits, vocab, ld, seen_base, seq_ids, slot0, penalty, temperature,
-                                               reinterpret_cast<const float4*>(filt), out_cut, out_kept);
+                                               reinterpret_cast<const float4*>(filt), out_cut, out_kept, samp);
 }
 
 // filt[slot] = (top_k bits, top_p, min_p, temperature of the row or 0): the values travel as kernel arguments

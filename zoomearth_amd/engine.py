@@ -292,6 +292,49 @@ class Engine:
                                                  m.ctypes.data_as(fp), _ptr(cut), _ptr(kept), self._stream()))
         return cut, kept
 
+    def set_sampling(self, seq: int, do_sample: Optional[bool] = None, temperature: float = 1.0, seed: int = 0,
+                     repetition_penalty: float = 1.0):
+        """Sampling request of chain `seq` (ze_seq_set_sampling): do_sample False = greedy, True = temperature sampling with the
+        chain's own temperature and seed, None = clear (the chain follows the call's gen_params again); repetition_penalty is
+        the chain's own in both modes.  Replaces the do_sample / temperature / seed / repetition_penalty of the gen_params of
+        every generate / chain_begin / decode_burst call the chain takes part in, until the slot is reset, truncated or copied
+        into.  Chains with different requests share bursts and graphs; a chain's tokens are those of a call whose gen_params
+        carry its values."""
+        mode = -1 if do_sample is None else int(bool(do_sample))
+        self._check(self.lib.ze_seq_set_sampling(self.h, int(seq), mode, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                 float(repetition_penalty), self._stream()))
+
+    def sample_rows(self, logits: torch.Tensor, temperature, repetition_penalty=1.0, seed=0, sample_stream=0, index=0,
+                    seen: Optional[torch.Tensor] = None, top_k=None, top_p=None, min_p=None) -> torch.Tensor:
+        """One draw per row with values of its own (ze_op_sample_rows, the per-chain sampling kernels of the batched step): logits
+        f32 [rows, vocab] (row stride >= vocab); temperature (0 = greedy), repetition_penalty, seed, sample_stream and index per
+        row (scalars broadcast); seen uint8 [rows, vocab] (nonzero = penalised) or None; top_k / top_p / min_p per row, or all
+        None.  Returns the tokens, int32 [rows]; marks nothing as seen."""
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+        rows, vocab = int(logits.shape[0]), int(logits.shape[1])
+        if seen is not None:
+            assert seen.dtype == torch.uint8 and seen.is_contiguous() and tuple(seen.shape) == (rows, vocab)
+            self._use(seen)
+
+        def per_row(v, dtype):
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (rows,)))
+        t, pen = per_row(temperature, np.float32), per_row(repetition_penalty, np.float32)
+        sd, strm, idx = per_row(seed, np.uint64), per_row(sample_stream, np.int32), per_row(index, np.int32)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        filt = (None, None, None)
+        if top_k is not None or top_p is not None or min_p is not None:
+            filt = (per_row(0 if top_k is None else top_k, np.int32), per_row(1.0 if top_p is None else top_p, np.float32),
+                    per_row(0.0 if min_p is None else min_p, np.float32))
+        out = torch.empty(rows, dtype=torch.int32, device=self.device)
+        ld = int(logits.stride(0)) if rows > 1 else vocab   # (the stride of a one-row tensor means nothing)
+        self._use(logits)
+        self._check(self.lib.ze_op_sample_rows(
+            self.h, _ptr(logits), rows, vocab, ld, _ptr(seen) if seen is not None else None, t.ctypes.data_as(fp),
+            pen.ctypes.data_as(fp), sd.ctypes.data_as(C.POINTER(C.c_uint64)), strm.ctypes.data_as(ip), idx.ctypes.data_as(ip),
+            filt[0].ctypes.data_as(ip) if filt[0] is not None else None, filt[1].ctypes.data_as(fp) if filt[1] is not None else None,
+            filt[2].ctypes.data_as(fp) if filt[2] is not None else None, _ptr(out), self._stream()))
+        return out
+
     def set_logprobs(self, seq: int, top_n: Optional[int] = 0):
         """Log-probabilities of the tokens chain `seq` generates from now on (ze_seq_set_logprobs): None / -1 = off, 0 = the chosen
         token only, 1 .. MAX_TOP_LOGPROBS = that many best alternatives too.  Computed on the device from the step's own fp32

@@ -58,6 +58,13 @@ class Request:
     stop_ids: Optional[list] = None
     bad_words_ids: Optional[list] = None
     no_repeat_ngram_size: Optional[int] = None
+    # sampling of this request (None = the scheduler's own value): greedy or sampled, temperature, seed and repetition penalty.
+    # A request that names one carries its values into the engine's per-slot table, so requests with different values share the
+    # same bursts; its draws are those of a scheduler whose own values are these (same stream_id)
+    do_sample: Optional[bool] = None
+    temperature: Optional[float] = None
+    seed: Optional[int] = None
+    repetition_penalty: Optional[float] = None
     # filled by the scheduler
     slot: int = -1
     n_prompt: int = 0
@@ -98,7 +105,8 @@ class ChainScheduler:
         self.logprobs = logprobs
         # Sampling filters (top-k / top-p / min-p): the defaults of requests that name none; settable between requests.  A request's
         # filter is written into its slot's row of the engine's table right before its first draw, so requests with different
-        # filters share the same bursts.  A greedy scheduler never touches the table.
+        # filters share the same bursts.  Written for a request whose effective mode is sampled (its own `do_sample`, else the
+        # scheduler's): a greedy scheduler without such requests never touches the table.
         self.do_sample = bool(do_sample)
         self.top_k, self.top_p, self.min_p = top_k, top_p, min_p
         gc = model.generation_config
@@ -106,6 +114,7 @@ class ChainScheduler:
         if do_sample and temperature is None:
             temperature = getattr(gc, "temperature", None) or 1.0
         self.penalty = float(pen)
+        self.temperature, self.seed = float(temperature or 1.0), int(seed)
         # Captured hipGraphs for the decode steps: yes in the fragment regime (at most 64 chains: a step of ~3.4 ms is ~330
         # launches), no in the row-streaming regime -- its steps take 6-25 ms, the host runs far ahead of the GPU, and a graph
         # is keyed by (live chains, attention grid), i.e. captured anew at almost every burst (stream: 72.1 / 72.0 questions/s
@@ -532,14 +541,16 @@ class ChainScheduler:
             return
         final = [it for it in ok if it["final"]]                # (pass A: the chain is completed by pass B)
         try:
-            if self.penalty != 1.0 and final:
+            # (a request with a repetition penalty of its own is marked by ITS value: 1.0 reads no set)
+            marked = [it for it in final if self._penalty_of(it["req"]) != 1.0]
+            if marked:
                 # the prompts' ids into the repetition-penalty sets (cleared by the reset / truncate above): one copy and one
                 # launch for the pass, IN FRONT of it -- behind it, the next call would find its staging buffer busy until the
                 # whole pass has run
                 if hasattr(e, "mark_seen_batch") and not _PER_CHAIN:
-                    e.mark_seen_batch([it["req"].slot for it in final], [it["ids"] for it in final])
+                    e.mark_seen_batch([it["req"].slot for it in marked], [it["ids"] for it in marked])
                 else:
-                    for it in final:
+                    for it in marked:
                         e.mark_seen(it["req"].slot, it["ids"])
             e.prefill_batch(slots, ids_l, emb_l, pos_l, dl)
         except Exception as ex:
@@ -554,10 +565,31 @@ class ChainScheduler:
             req.n_prompt = len(ids)
             self._ready.append((req, tuple(ids), tuple(keys)))
 
+    def _samples(self, req) -> bool:
+        mode = getattr(req, "do_sample", None)
+        return self.do_sample if mode is None else bool(mode)
+
+    def _penalty_of(self, req) -> float:
+        pen = getattr(req, "repetition_penalty", None)
+        return self.penalty if pen is None else float(pen)
+
+    def _set_sampling(self, req) -> None:
+        """The request's own (greedy | temperature, seed, repetition penalty) into its slot (cleared, like the filter, by the slot's
+        reset / truncate / prefix copy), before its first draw.  Values it does not name are the scheduler's; a request that
+        names none never reaches the engine, and follows the scheduler's gen_params."""
+        named = [getattr(req, k, None) for k in ("do_sample", "temperature", "seed", "repetition_penalty")]
+        if all(v is None for v in named):
+            return
+        mode, temperature, seed, penalty = named
+        self.engine.set_sampling(req.slot, do_sample=self._samples(req),
+                                 temperature=self.temperature if temperature is None else float(temperature),
+                                 seed=self.seed if seed is None else int(seed),
+                                 repetition_penalty=self._penalty_of(req))
+
     def _set_filter(self, req) -> None:
         """The request's own filter into its slot (the slot's reset / truncate / prefix copy cleared the previous chain's), before
-        its first draw."""
-        if not self.do_sample:
+        its first draw.  Only for a request whose effective mode is sampled."""
+        if not self._samples(req):
             return
         top_k = req.top_k if req.top_k is not None else self.top_k
         top_p = req.top_p if req.top_p is not None else self.top_p
@@ -623,6 +655,7 @@ class ChainScheduler:
                     keep_from = i
                     break
         for req, ids, keys in self._ready[:keep_from]:
+            self._set_sampling(req)
             self._set_filter(req)
             self._set_logprobs(req)
             self._set_logit_adjust(req)

@@ -7,6 +7,7 @@ Request: the subset that client sends -- `messages` with `role` in {system, user
 string or a list of `{"type": "text", "text": ...}` / `{"type": "image_url", "image_url": {"url": "data:image/...;
 base64,..."}}` items, plus `max_tokens`, `temperature`, `seed`, `top_p` and the vLLM extensions `top_k` (-1 / 0 = off) and
 `min_p` (`n` must be 1, `stream` is not offered); the three filters apply to sampled requests, each request its own.
+vLLM's `repetition_penalty` (finite, > 0; absent = the checkpoint's generation_config) is per request too.
 `presence_penalty` / `frequency_penalty` ([-2, 2]), `logit_bias` (at most 300 `"id": bias` entries in [-100, 100]) and vLLM's
 `min_tokens` adjust every step's logits on the device, each request its own values, greedy requests included.
 `stop` (a string or up to 4 strings), vLLM's `stop_token_ids` and `no_repeat_ngram_size` are token rules on the device: the chain
@@ -20,15 +21,18 @@ generation prompt `<|im_start|>assistant\\n`).  temperature 0 / absent -> greedy
 Concurrent requests (infer_vllm.py keeps up to 100 in flight, :244-271) share the GPU through continuous batching
 (`zoomearth_amd/scheduler.py`): a dispatcher thread admits greedy requests into the RUNNING batch between bursts of
 decode steps -- newcomers are prefilled together and join the next burst, a finished request frees its KV slot and its
-response returns at once -- with each request's tokens independent of which other requests share its steps; sampled
-requests run alone (temperature and seed are part of the captured decode step).  Images are decoded on the host and
-uploaded.
+response returns at once -- with each request's tokens independent of which other requests share its steps.  Sampled
+requests join the same running batch: temperature, seed and repetition penalty are per chain on the device
+(`Engine.set_sampling`), so a request draws what it would draw running alone whatever its company.  (An engine without that
+entry keeps the old path: sampled requests wait for the batch to drain and run grouped by temperature and seed.)  Images
+are decoded on the host and uploaded.
 
     python -m zoomearth_amd.serve --model_name /ckpt/ZoomEarth-3B --port 8000
 """
 
 import base64
 import io
+import math
 import threading
 import time
 import uuid
@@ -91,7 +95,7 @@ def build_prompt(messages):
 class _Parsed:
     __slots__ = ("req", "prompt", "pil_images", "max_tokens", "sample", "temperature", "seed", "future", "top_k", "top_p",
                  "min_p", "logprobs", "presence_penalty", "frequency_penalty", "logit_bias", "min_tokens", "stop", "stop_token_ids",
-                 "no_repeat_ngram_size")
+                 "no_repeat_ngram_size", "repetition_penalty")
 
     def rules(self) -> bool:
         return bool(self.stop or self.stop_token_ids or self.no_repeat_ngram_size)
@@ -145,6 +149,15 @@ class ChatServer:
         p.sample = t is not None and float(t) > 0.0
         p.temperature = float(t) if p.sample else None
         p.seed = int(req.get("seed") or 0)
+        # vLLM's `repetition_penalty`: None = the model's own (generation_config)
+        rp = req.get("repetition_penalty")
+        if rp is not None:
+            if isinstance(rp, bool) or not isinstance(rp, (int, float)):
+                raise BadRequest(f"repetition_penalty must be a number, got {rp!r}")
+            rp = float(rp)
+            if not (math.isfinite(rp) and rp > 0.0):
+                raise BadRequest(f"repetition_penalty must be finite and > 0, got {rp}")
+        p.repetition_penalty = rp
         # sampling filters (OpenAI `top_p`; vLLM's `top_k`, -1 = off, and `min_p`): 0 / 1.0 / 0.0 = off
         try:
             p.top_p = 1.0 if req.get("top_p") is None else float(req["top_p"])
@@ -308,6 +321,8 @@ class ChatServer:
             kw = dict(max_new_tokens=max(p.max_tokens for p in batch), num_beams=1, do_sample=p0.sample)
             if p0.sample:
                 kw.update(temperature=p0.temperature, top_k=p0.top_k, top_p=p0.top_p, min_p=p0.min_p, seed=p0.seed)
+            if p0.repetition_penalty is not None:
+                kw.update(repetition_penalty=p0.repetition_penalty)
             kw.update(p0.adjust_kw(self.processor.tokenizer))
             want = [p.logprobs for p in batch if p.logprobs is not None]
             if not want:
@@ -325,8 +340,10 @@ class ChatServer:
         return self._run([self._parse(req)])[0]
 
     def complete_many(self, reqs) -> list:
-        """The requests as ONE batch (all must be greedy; at most max_seqs of them)."""
+        """The requests as ONE batch (all must be greedy with the model's own repetition penalty; at most max_seqs of them)."""
         batch = [self._parse(r) for r in reqs]
+        if any(p.repetition_penalty is not None for p in batch) and len(batch) > 1:
+            raise BadRequest("requests with a repetition_penalty of their own are not batched")
         if any(p.sample for p in batch) and len(batch) > 1:
             raise BadRequest("sampled requests are not batched")
         if any(p.adjusts() for p in batch) and len(batch) > 1:
@@ -360,14 +377,18 @@ class ChatServer:
         """Running-batch admission (the concurrency model of /root/reference/src/eval/infer_vllm.py:244-271, where the
         client keeps up to 100 requests in flight): greedy requests go to a `ChainScheduler` -- a request that arrives
         while others are decoding is prefilled and joins their next burst, one that finishes frees its KV slot at once --
-        and each future resolves as soon as ITS chain ends.  Sampled requests (temperature / seed are baked into the captured
-        decode step) wait for the running chains to drain; those that share a temperature and a seed then run together
-        as a batch of their own."""
+        and each future resolves as soon as ITS chain ends.  With an engine that offers `set_sampling` there is this ONE
+        scheduler: a sampled request is submitted to it like a greedy one, with its own temperature and seed (and random
+        stream 0: what it would draw running alone) in the engine's per-slot table, and joins the running batch.  The fallback
+        for an engine without the entry: sampled requests (temperature / seed are then baked into the captured decode step)
+        wait for the running chains to drain; those that share a temperature and a seed then run together as a batch of
+        their own."""
         from .image import DeviceImage
         from .scheduler import ChainScheduler, Request
 
         sched = None
         sampled, held = [], []
+        per_chain = hasattr(self.model.engine, "set_sampling")
         while True:
             with self._cv:
                 while not self._queue and not self._stop and not sampled and not held and not (sched is not None and sched.busy()):
@@ -389,9 +410,18 @@ class ChatServer:
                 held.extend(new)
                 new, held = (held, []) if not sampled else ([p for p in held if p.sample], [p for p in held if not p.sample])
                 for p in new:  # (greedy arrivals wait behind a pending sampled request: it needs the engine alone)
-                    if p.sample:
+                    if p.sample and not per_chain:
                         sampled.append(p)
                         continue
+                    own = {}
+                    if p.sample:
+                        own = dict(do_sample=True, temperature=p.temperature, seed=p.seed, stream_id=0, top_k=p.top_k, top_p=p.top_p,
+                                   min_p=p.min_p)
+                    if p.repetition_penalty is not None:
+                        if not per_chain:
+                            p.future.set_exception(BadRequest("repetition_penalty per request needs an engine with set_sampling"))
+                            continue
+                        own["repetition_penalty"] = p.repetition_penalty
 
                     def done(req, tokens, text, p=p):
                         p.future.set_result(self._response(p, tokens, req.n_prompt, (req.token_logprobs, req.top_logprobs)))
@@ -408,7 +438,7 @@ class ChatServer:
                                              on_error=failed, logprobs=p.logprobs, presence_penalty=p.presence_penalty,
                                              frequency_penalty=p.frequency_penalty, logit_bias=p.logit_bias,
                                              min_new_tokens=p.min_tokens, stop_ids=p.stop_records(self.processor.tokenizer),
-                                             no_repeat_ngram_size=p.no_repeat_ngram_size))
+                                             no_repeat_ngram_size=p.no_repeat_ngram_size, **own))
                     except Exception as ex:
                         failed(None, ex)
                 if sched.busy():
