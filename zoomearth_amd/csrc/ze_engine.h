@@ -12,6 +12,7 @@
 //   chain state   ze_seq_dev[max_seqs], seen-set u8 [max_seqs][vocab], out tokens int32 [max_seqs][max_ctx]
 //   workspaces    ViT activations for max_patches rows; prefill activations for max_ctx rows; decode vectors
 #pragma once
+#include <algorithm>
 #include <map>
 #include <tuple>
 #include <set>
@@ -50,6 +51,104 @@ struct ze_dest {
     bf16_t* dst = nullptr;
     int rows = 0, cols = 0, ld = 0, mode = 0, offset = 0;
     int kind = 0;  // 0 matrix, 1 norm weight, 2 bias, 3 embedding / lm_head
+};
+
+// What a captured decode step was captured under: every value its launch sequence or a kernel argument depends on.  Built in one
+// place, ze_step_key_of (ze_requests.hip); a request kind that changes what a step launches adds its mode here and there.
+struct ze_step_key {
+    int n = 0;  // chains of a batched step; 0 = the single-chain step
+    float penalty = 0.f;
+    int ignore_eos = 0;
+    float temperature = 0.f;
+    unsigned long long seed = 0;
+    unsigned tune_epoch = 0;                   // single-chain step only (the batched graphs are flushed when the epoch changes)
+    int live_parts = 0, live_parts_long = 0;   // batched step only: the attention grids' extents
+    int sampling_bits = 0;                     // bit 0 = sampling filters, bit 1 = per-chain sampling table, bit 2 = ... with a draw
+    int lp_mode = 0, la_mode = 0, tr_mode = 0;
+    auto tied() const {
+        return std::tie(n, penalty, ignore_eos, temperature, seed, tune_epoch, live_parts, live_parts_long, sampling_bits, lp_mode, la_mode,
+                        tr_mode);
+    }
+    bool operator==(const ze_step_key& o) const { return tied() == o.tied(); }
+    bool operator<(const ze_step_key& o) const { return tied() < o.tied(); }
+};
+
+// Per-chain requests (ze_requests.hip: the setters, what a step launches for them, and the keys of the captured steps).  Each kind
+// keeps its truth on the host, a per-slot device table written in stream order by its setter, a count of the slots that have
+// one, and buffers allocated by the first request that needs them.  A step launches nothing for a kind no chain has asked for.
+struct ze_requests {
+    // Sampling filters (ze_seq_set_sampling_filter): filt_host is the truth, filt_dev the per-slot table the selection kernel reads
+    // ((top_k bits, top_p, min_p, 0) per slot; all zero = off), written in stream order by the setter; n_filters = slots with a
+    // filter.  While it is 0 no sampling launch knows about filters at all.  cut_dev: [max_seqs] cuts of a batched step (one per
+    // row of the launch), then [max_seqs] for the single-chain launches (one per slot).
+    struct filter_host { int top_k = 0; float top_p = 1.f, min_p = 0.f; bool on() const { return top_k > 0 || top_p < 1.f || min_p > 0.f; } };
+    std::vector<filter_host> filt_host;
+    int n_filters = 0;
+    float *filt_dev = nullptr, *cut_dev = nullptr;
+    // Sampling requests (ze_seq_set_sampling): samp_host is the truth (penalty = 0: the slot has none), samp_dev the per-slot
+    // table the per-chain sampling kernels read, allocated by the first request and written in stream order by the setter;
+    // n_sampling = slots with a request, n_sampled = those of them that draw (temperature > 0).  While n_sampling is 0 every
+    // step launches the scalar kernels, under the graph keys it always had.
+    std::vector<ze_chain_sampling> samp_host;
+    int n_sampling = 0, n_sampled = 0;
+    ze_chain_sampling* samp_dev = nullptr;
+    // Log-probabilities of generated tokens (ze_seq_set_logprobs): lp_host is the truth (-1 off, 0 chosen token only, 1..20
+    // alternatives), lp_dev the per-slot table the kernel reads, written in stream order by the setter; n_logprobs = slots with
+    // a request.  While it is 0 no step launches the kernel.  History, allocated by the first request that needs it: lp_tok f32
+    // [max_seqs, max_ctx]; lp_top_ids int32 / lp_top_lps f32 [max_seqs, max_ctx, 20].
+    std::vector<int> lp_host;
+    int n_logprobs = 0;
+    int* lp_dev = nullptr;
+    float* lp_tok = nullptr;
+    int* lp_top_ids = nullptr;
+    float* lp_top_lps = nullptr;
+    // what a captured step must have been captured with: 0 = no kernel, 1 = chosen-token history only, 2 = alternatives too
+    int lp_mode() const { return n_logprobs > 0 ? (lp_top_ids ? 2 : 1) : 0; }
+    ze_logprob_bufs lp_bufs() const { return ze_logprob_bufs{lp_dev, lp_tok, lp_top_ids, lp_top_lps}; }
+    // Logit adjustments (ze_seq_set_logit_adjust): la_host is the truth, la_dev the per-slot table the kernels read (ZE_LA_WORDS
+    // ints per slot, all zero = off), written in stream order by the setter; n_adjust = slots with a request.  While it is 0 no
+    // step launches anything for them.  Allocated by the first request: la_bias_ids / la_bias_vals [max_seqs, ZE_MAX_LOGIT_BIAS]
+    // and la_rows f32 [max_seqs + 1, vocab], the adjusted rows the sampler reads (row b of a batched step; the last row serves
+    // the single-chain launches, which share one workspace as it is); by the first request with a penalty: la_counts u16
+    // [max_seqs, vocab].
+    struct adjust_host {
+        float presence = 0.f, frequency = 0.f;
+        int min_new = 0, n_bias = 0;
+        bool penalties() const { return presence != 0.f || frequency != 0.f; }
+        bool on() const { return penalties() || min_new > 0 || n_bias > 0; }
+    };
+    std::vector<adjust_host> la_host;
+    int n_adjust = 0;
+    int* la_dev = nullptr;
+    int* la_bias_ids = nullptr;
+    float* la_bias_vals = nullptr;
+    float* la_rows = nullptr;
+    uint16_t* la_counts = nullptr;
+    // what a captured step must have been captured with: 0 = nothing, 1 = the adjust kernel, 2 = the count kernel too
+    int la_mode() const { return n_adjust > 0 ? (la_counts ? 2 : 1) : 0; }
+    // (of a single-chain step, which serves one chain: nothing while THAT chain has no request -- it then reads its raw row)
+    int la_mode(int seq) const { return la_host[seq].on() ? la_mode() : 0; }
+    ze_logit_adjust_bufs la_bufs() const { return ze_logit_adjust_bufs{la_dev, la_bias_ids, la_bias_vals, la_counts}; }
+    // Token rules (ze_seq_set_token_rules): tr_host is the truth, tr_dev the per-slot table the kernels read (ZE_TR_WORDS ints per
+    // slot, all zero = off), written in stream order by the setter; n_bans / n_stops = slots with n-gram or ban records / with
+    // stop records.  While both are 0 no step launches anything for them.  Allocated by the first request: tr_stop / tr_ban
+    // [max_seqs, ZE_MAX_RULE_INTS] (and, with bans, the adjusted rows la_rows); by the first request with a context: tr_ctx
+    // [max_seqs, max_ctx].
+    struct rules_host {
+        int ngram = 0, n_stop_ints = 0, n_stop_words = 0, n_ban_ints = 0, n_ban_words = 0, n_context = 0;
+        bool bans() const { return ngram > 0 || n_ban_words > 0; }
+        bool stops() const { return n_stop_words > 0; }
+        bool on() const { return bans() || stops(); }
+    };
+    std::vector<rules_host> tr_host;
+    int n_bans = 0, n_stops = 0;
+    int *tr_dev = nullptr, *tr_stop = nullptr, *tr_ban = nullptr, *tr_ctx = nullptr;
+    // what a captured step must have been captured with: bit 0 = adjusted copy + ban pass, bit 1 = stop pass, bit 2 = the
+    // context history exists (a kernel argument)
+    int tr_mode() const { return n_bans + n_stops > 0 ? (n_bans > 0) | (n_stops > 0) << 1 | (tr_ctx != nullptr) << 2 : 0; }
+    // (of a single-chain step: by THAT chain's request)
+    int tr_mode(int seq) const { return tr_host[seq].on() ? (int)tr_host[seq].bans() | (int)tr_host[seq].stops() << 1 | (tr_ctx != nullptr) << 2 : 0; }
+    ze_token_rule_bufs tr_bufs() const { return ze_token_rule_bufs{tr_dev, tr_stop, tr_ban, tr_ctx}; }
 };
 
 struct ze_engine {
@@ -118,87 +217,10 @@ struct ze_engine {
     int* pfx_dev = nullptr;
     std::vector<hipEvent_t> pfx_copy_ev;
     bool prefix_hints = true;      // the hint fits its 16 + 16 bits (ze_tune knob 17 = 1: every chain reads its own rows)
-    // Sampling filters (ze_seq_set_sampling_filter): filt_host is the truth, filt_dev the per-slot table the selection kernel reads
-    // ((top_k bits, top_p, min_p, 0) per slot; all zero = off), written in stream order by the setter; n_filters = slots with a
-    // filter.  While it is 0 no sampling launch knows about filters at all.  cut_dev: [max_seqs] cuts of a batched step (one per
-    // row of the launch), then [max_seqs] for the single-chain launches (one per slot).
-    struct filter_host { int top_k = 0; float top_p = 1.f, min_p = 0.f; bool on() const { return top_k > 0 || top_p < 1.f || min_p > 0.f; } };
-    std::vector<filter_host> filt_host;
-    int n_filters = 0;
-    float *filt_dev = nullptr, *cut_dev = nullptr;
-    std::vector<int> graph_filters;  // whether the chain's graph was captured with the selection kernel in it
-    // Sampling requests (ze_seq_set_sampling): samp_host is the truth (penalty = 0: the slot has none), samp_dev the per-slot
-    // table the per-chain sampling kernels read, allocated by the first request and written in stream order by the setter;
-    // n_sampling = slots with a request, n_sampled = those of them that draw (temperature > 0).  While n_sampling is 0 every
-    // step launches the scalar kernels, under the graph keys it always had.
-    std::vector<ze_chain_sampling> samp_host;
-    int n_sampling = 0, n_sampled = 0;
-    ze_chain_sampling* samp_dev = nullptr;
-    // Log-probabilities of generated tokens (ze_seq_set_logprobs): lp_host is the truth (-1 off, 0 chosen token only, 1..20
-    // alternatives), lp_dev the per-slot table the kernel reads, written in stream order by the setter; n_logprobs = slots with
-    // a request.  While it is 0 no step launches the kernel.  History, allocated by the first request that needs it: lp_tok f32
-    // [max_seqs, max_ctx]; lp_top_ids int32 / lp_top_lps f32 [max_seqs, max_ctx, 20].
-    std::vector<int> lp_host;
-    int n_logprobs = 0;
-    int* lp_dev = nullptr;
-    float* lp_tok = nullptr;
-    int* lp_top_ids = nullptr;
-    float* lp_top_lps = nullptr;
-    // what a captured step must have been captured with: 0 = no kernel, 1 = chosen-token history only, 2 = alternatives too
-    int lp_mode() const { return n_logprobs > 0 ? (lp_top_ids ? 2 : 1) : 0; }
-    ze_logprob_bufs lp_bufs() const { return ze_logprob_bufs{lp_dev, lp_tok, lp_top_ids, lp_top_lps}; }
-    std::vector<int> graph_logprobs;  // lp_mode() the chain's graph was captured under
-    int *xl_host = nullptr, *xl_dev = nullptr;  // gather scratch of ze_chain_logprobs* (pinned + device, grown on demand)
-    size_t xl_cap = 0;
-    // Logit adjustments (ze_seq_set_logit_adjust): la_host is the truth, la_dev the per-slot table the kernels read (ZE_LA_WORDS
-    // ints per slot, all zero = off), written in stream order by the setter; n_adjust = slots with a request.  While it is 0 no
-    // step launches anything for them.  Allocated by the first request: la_bias_ids / la_bias_vals [max_seqs, ZE_MAX_LOGIT_BIAS]
-    // and la_rows f32 [max_seqs + 1, vocab], the adjusted rows the sampler reads (row b of a batched step; the last row serves
-    // the single-chain launches, which share one workspace as it is); by the first request with a penalty: la_counts u16
-    // [max_seqs, vocab].
-    struct adjust_host {
-        float presence = 0.f, frequency = 0.f;
-        int min_new = 0, n_bias = 0;
-        bool penalties() const { return presence != 0.f || frequency != 0.f; }
-        bool on() const { return penalties() || min_new > 0 || n_bias > 0; }
-    };
-    std::vector<adjust_host> la_host;
-    int n_adjust = 0;
-    int* la_dev = nullptr;
-    int* la_bias_ids = nullptr;
-    float* la_bias_vals = nullptr;
-    float* la_rows = nullptr;
-    uint16_t* la_counts = nullptr;
-    // what a captured step must have been captured with: 0 = nothing, 1 = the adjust kernel, 2 = the count kernel too
-    int la_mode() const { return n_adjust > 0 ? (la_counts ? 2 : 1) : 0; }
-    // (of a single-chain step, which serves one chain: nothing while THAT chain has no request -- it then reads its raw row)
-    int la_mode(int seq) const { return la_host[seq].on() ? la_mode() : 0; }
-    ze_logit_adjust_bufs la_bufs() const { return ze_logit_adjust_bufs{la_dev, la_bias_ids, la_bias_vals, la_counts}; }
-    std::vector<int> graph_adjust;  // la_mode(seq) the chain's graph was captured under
-    // Token rules (ze_seq_set_token_rules): tr_host is the truth, tr_dev the per-slot table the kernels read (ZE_TR_WORDS ints per
-    // slot, all zero = off), written in stream order by the setter; n_bans / n_stops = slots with n-gram or ban records / with
-    // stop records.  While both are 0 no step launches anything for them.  Allocated by the first request: tr_stop / tr_ban
-    // [max_seqs, ZE_MAX_RULE_INTS] (and, with bans, the adjusted rows la_rows); by the first request with a context: tr_ctx
-    // [max_seqs, max_ctx].
-    struct rules_host {
-        int ngram = 0, n_stop_ints = 0, n_stop_words = 0, n_ban_ints = 0, n_ban_words = 0, n_context = 0;
-        bool bans() const { return ngram > 0 || n_ban_words > 0; }
-        bool stops() const { return n_stop_words > 0; }
-        bool on() const { return bans() || stops(); }
-    };
-    std::vector<rules_host> tr_host;
-    int n_bans = 0, n_stops = 0;
-    int *tr_dev = nullptr, *tr_stop = nullptr, *tr_ban = nullptr, *tr_ctx = nullptr;
-    // what a captured step must have been captured with: bit 0 = adjusted copy + ban pass, bit 1 = stop pass, bit 2 = the
-    // context history exists (a kernel argument)
-    int tr_mode() const { return n_bans + n_stops > 0 ? (n_bans > 0) | (n_stops > 0) << 1 | (tr_ctx != nullptr) << 2 : 0; }
-    // (of a single-chain step: by THAT chain's request)
-    int tr_mode(int seq) const { return tr_host[seq].on() ? (int)tr_host[seq].bans() | (int)tr_host[seq].stops() << 1 | (tr_ctx != nullptr) << 2 : 0; }
-    ze_token_rule_bufs tr_bufs() const { return ze_token_rule_bufs{tr_dev, tr_stop, tr_ban, tr_ctx}; }
-    std::vector<int> graph_rules;  // tr_mode(seq) the chain's graph was captured under
+    ze_requests req;  // per-chain requests (above)
+    // captured single-chain decode step per slot, and the key it was captured under (ze_step_key_of)
     std::vector<hipGraphExec_t> graphs;
-    std::vector<float> graph_penalty;
-    std::vector<int> graph_ignore_eos;
+    std::vector<ze_step_key> graph_key;
 
     // front-end workspace
     uint8_t *fe_tmp = nullptr, *fe_img = nullptr;
@@ -234,6 +256,8 @@ struct ze_engine {
     // max_ctx ints, allocated at first use
     int *xs_host = nullptr, *xs_dev = nullptr, *xt_host = nullptr, *xt_dev = nullptr;
     size_t xs_cap = 0, xt_cap = 0;
+    int *xl_host = nullptr, *xl_dev = nullptr;  // gather scratch of ze_chain_logprobs* (pinned + device, grown on demand)
+    size_t xl_cap = 0;
     hipEvent_t xs_staged = nullptr;
 
     // decode workspace
@@ -242,10 +266,7 @@ struct ze_engine {
     int max_splits = 64;
     int* d_host_ints = nullptr;  // pinned, small
     unsigned* atickets = nullptr;  // decode attention: one arrival ticket per (chain, kv head)
-    std::vector<int> graph_variant;  // ze_tune epoch the chain's graph was captured under
-    unsigned bgraph_epoch = 0;
-    std::vector<float> graph_temperature;
-    std::vector<unsigned long long> graph_seed;
+    unsigned bgraph_epoch = 0;  // ze_tune epoch the batched graphs were captured under (a change flushes them)
     // split-K GEMM workspace
     float* gslab = nullptr;       // split-K slabs of the weight-streaming GEMMs (ze_gemm_ws)
     size_t gslab_floats = 0;
@@ -267,7 +288,7 @@ struct ze_engine {
     int* bseq = nullptr;
     float *blogits = nullptr, *bpartial = nullptr, *bsample = nullptr;
     ze_seq_dev* bstate_host = nullptr;  // pinned
-    std::map<std::tuple<int, float, int, float, unsigned long long, int, int, int, int, int>, hipGraphExec_t> bgraphs;  // captured batched decode step per batch size (and attention grid)
+    std::map<ze_step_key, hipGraphExec_t> bgraphs;  // captured batched decode steps
     int live_parts = 0;  // 192-key parts the longest chain of the current batch needs (the attention grid's extent); 0 = all
 
     // timers
@@ -286,10 +307,50 @@ struct ze_engine {
     }
 };
 
+#define ZE_TRY(x)               \
+    do {                        \
+        int _r = (x);           \
+        if (_r != 0) return _r; \
+    } while (0)
+#define ZE_KCHECK() ZE_HIP(hipGetLastError())
+
 // engine internals used across translation units
 extern unsigned ze_tune_epoch;
 void ze_weights_changed(ze_engine* e);
 int ze_engine_build_layout(ze_engine* e);
 int ze_timer_begin(ze_engine* e, int phase, hipStream_t s);
 void ze_timer_end(ze_engine* e, int handle, hipStream_t s);
-int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int ignore_eos, bool sample, hipStream_t s);
+
+template <typename T>
+static int dev_alloc(ze_engine* e, T** p, size_t count, bool zero = true) {
+    ZE_HIP(hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T)));
+    if (zero) ZE_HIP(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(T)));
+    return 0;
+}
+static inline int check_seq(ze_engine* e, int seq) {
+    if (!e) return ze_fail(e, ZE_ERR_INVALID, "null engine");
+    if (seq < 0 || seq >= e->cfg.max_seqs) return ze_fail(e, ZE_ERR_NOTFOUND, "sequence id out of range");
+    return ZE_OK;
+}
+
+// ---- per-chain requests (ze_requests.hip), kept out of the library's dynamic symbols
+#pragma GCC visibility push(hidden)
+int ze_requests_create(ze_engine* e);  // host tables and the per-slot device tables (ze_engine_create); first error, 0 = none
+void ze_requests_free(ze_engine* e);
+// the slot goes to another chain (reset, truncate, copy_prefix): it never inherits a request.  Nothing is launched for a slot without one.
+void ze_requests_clear(ze_engine* e, int seq, hipStream_t s);
+// The rows the sampler of a step reads: the step's own while no chain of it has a request (the step then launches what it always
+// did), else their adjusted copy.  seq_ids = null: the one chain `slot0`, whose row `logits` is.
+const float* ze_requests_rows(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s);
+// after the token of a step was accepted: log-probability entries, then token counts, then stop records -- each only for chains
+// that asked (ze_requests_logprobs: the first of the three alone)
+void ze_requests_logprobs(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s);
+void ze_requests_after_token(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s);
+int ze_check_filter(ze_engine* e, int top_k, float top_p, float min_p);
+// the sampling options of a launch: see ze_requests.hip
+void ze_attach_filters(ze_engine* e, ze_sample_opts& so, bool batch);
+float ze_penalty_of(const ze_engine* e, const ze_gen_params* p, int seq);
+ze_sample_opts ze_sample_opts_of(ze_engine* e, const ze_gen_params* p, int slot, bool batch = false);
+// n = 0: the single-chain step of chain `seq`; else the batched step of n chains
+ze_step_key ze_step_key_of(const ze_engine* e, int n, int seq, float penalty, int ignore_eos, const ze_sample_opts& so);
+#pragma GCC visibility pop

@@ -161,18 +161,6 @@ int ze_engine_build_layout(ze_engine* e) {
     return 0;
 }
 
-template <typename T>
-static int dev_alloc(ze_engine* e, T** p, size_t count, bool zero = true) {
-    ZE_HIP(hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T)));
-    if (zero) ZE_HIP(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(T)));
-    return 0;
-}
-#define ZE_TRY(x)              \
-    do {                       \
-        int _r = (x);          \
-        if (_r != 0) return _r; \
-    } while (0)
-
 static int init_tables(ze_engine* e) {
     const ze_config& c = e->cfg;
     const int half = e->head_dim / 2;
@@ -296,27 +284,8 @@ extern "C" int ze_engine_create(const ze_config* cfg, int device_id, ze_engine**
     e->delta_host.assign(c.max_seqs, 0);
     e->split_host.assign(c.max_seqs, 0);
     e->graphs.assign(c.max_seqs, nullptr);
-    e->graph_penalty.assign(c.max_seqs, 0.f);
-    e->graph_ignore_eos.assign(c.max_seqs, 0);
-    e->graph_variant.assign(c.max_seqs, 0);
-    e->graph_temperature.assign(c.max_seqs, 0.f);
-    e->graph_seed.assign(c.max_seqs, 0ull);
-    e->graph_filters.assign(c.max_seqs, 0);
-    e->filt_host.assign(c.max_seqs, ze_engine::filter_host{});
-    chk(dev_alloc(e, &e->filt_dev, (size_t)c.max_seqs * 4));
-    chk(dev_alloc(e, &e->cut_dev, (size_t)c.max_seqs * 2));
-    e->samp_host.assign(c.max_seqs, ze_chain_sampling{0.f, 0.f, 0ull});
-    e->graph_logprobs.assign(c.max_seqs, 0);
-    e->lp_host.assign(c.max_seqs, -1);
-    chk(dev_alloc(e, &e->lp_dev, (size_t)c.max_seqs, false));
-    if (e->lp_dev && hipMemset(e->lp_dev, 0xff, (size_t)c.max_seqs * sizeof(int)) != hipSuccess) chk(ZE_ERR_HIP);  // every slot -1 = off
-
-    e->graph_adjust.assign(c.max_seqs, 0);
-    e->la_host.assign(c.max_seqs, ze_engine::adjust_host{});
-    chk(dev_alloc(e, &e->la_dev, (size_t)c.max_seqs * ZE_LA_WORDS));  // all zero = off
-    e->graph_rules.assign(c.max_seqs, 0);
-    e->tr_host.assign(c.max_seqs, ze_engine::rules_host{});
-    chk(dev_alloc(e, &e->tr_dev, (size_t)c.max_seqs * ZE_TR_WORDS));  // all zero = off
+    e->graph_key.assign(c.max_seqs, ze_step_key{});
+    chk(ze_requests_create(e));
 
     // front-end workspace: horizontal-pass image (box_h x out_w) and resized image
     const size_t side = (size_t)std::max(c.max_tile_side, 1024);
@@ -476,12 +445,10 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
                    e->vo, e->va, e->vz, e->vz2, e->vcos, e->vsin, e->vperm, e->vinv, e->vtiles_win, e->vtiles_full,
                    e->th, e->ty, e->tqkv, e->to, e->ta, e->tsrc, e->tpos, e->ttiles, e->ttile_aux, e->trow_aux, e->dh, e->dq, e->dattn, e->dact,
                    e->dlogits, e->dpartial, e->dsample, e->atickets, e->gslab, e->gtickets, e->pslab, e->ptickets, e->bh, e->by, e->bqkv, e->bo, e->ba, e->bseq, e->bmate, e->blogits, e->bpartial, e->bsample, e->arena8, e->arena_f, e->arena_f8,
-                   e->ty8, e->ty8_scale, e->damax, e->ty8p, e->ty8p_scale, e->filt_dev, e->cut_dev, e->samp_dev,
-                   e->lp_dev, e->lp_tok, e->lp_top_ids, e->lp_top_lps, e->xl_dev,
-                   e->la_dev, e->la_bias_ids, e->la_bias_vals, e->la_rows, e->la_counts,
-                   e->tr_dev, e->tr_stop, e->tr_ban, e->tr_ctx};
+                   e->ty8, e->ty8_scale, e->damax, e->ty8p, e->ty8p_scale, e->xl_dev};
     for (void* p : dev)
         if (p) hipFree(p);
+    ze_requests_free(e);
     if (e->pfx_dev) hipFree(e->pfx_dev);
     if (e->arena_p) hipFree(e->arena_p);
     if (e->qkv_epi_dev) hipFree(e->qkv_epi_dev);

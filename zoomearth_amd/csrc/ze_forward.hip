@@ -8,12 +8,6 @@
 
 #include "ze_engine.h"
 
-#define ZE_TRY(x)               \
-    do {                        \
-        int _r = (x);           \
-        if (_r != 0) return _r; \
-    } while (0)
-#define ZE_KCHECK() ZE_HIP(hipGetLastError())
 extern int ze_gemv_knobs[24];
 
 // ================================================================== front-end
@@ -334,12 +328,6 @@ extern "C" int ze_vit_forward(ze_engine* e, const float* pixel_values, const int
 }
 
 // ================================================================== chains
-static int check_seq(ze_engine* e, int seq) {
-    if (!e) return ze_fail(e, ZE_ERR_INVALID, "null engine");
-    if (seq < 0 || seq >= e->cfg.max_seqs) return ze_fail(e, ZE_ERR_NOTFOUND, "sequence id out of range");
-    return ZE_OK;
-}
-
 // ---- shared-prefix hints (ze_engine::pfx_host / pfx_dev; the ownership rule is stated in ze_engine.h)
 static void set_prefix_hint(ze_engine* e, int seq, int value) { e->pfx_host[seq] = value; }
 // the K/V rows chain `d` copied (ze_seq_copy_prefix) have landed: nothing recorded, or the event behind the copy is over
@@ -396,321 +384,6 @@ static int push_state(ze_engine* e, int seq, hipStream_t s, int token, int n_gen
     return ZE_OK;
 }
 
-// ---- sampling filters (top-k / top-p / min-p per chain; ze_engine::filt_host is the truth, ze_sample_filter.hip the kernel)
-static void write_filter(ze_engine* e, int seq, int top_k, float top_p, float min_p, hipStream_t s) {
-    ze_engine::filter_host& f = e->filt_host[seq];
-    const bool was = f.on();
-    f.top_k = top_k, f.top_p = top_p, f.min_p = min_p;
-    e->n_filters += (int)f.on() - (int)was;
-    // the table keeps all zeros for "off" (a zero top_p is no legal value)
-    if (was || f.on()) ze_launch_set_filter(e->filt_dev, seq, top_k, f.on() ? top_p : 0.f, min_p, 0.f, s);
-}
-// the slot goes to another chain (wherever its seen-set is cleared): it never inherits a filter.  Nothing is launched for a
-// slot that has none.
-static void clear_filter(ze_engine* e, int seq, hipStream_t s) {
-    if (e->filt_host[seq].on()) write_filter(e, seq, 0, 1.f, 0.f, s);
-}
-
-extern "C" int ze_seq_set_sampling_filter(ze_engine* e, int seq, int top_k, float top_p, float min_p, void* stream) {
-    ZE_TRY(check_seq(e, seq));
-    if (top_k < 0) return ze_fail(e, ZE_ERR_INVALID, "top_k must be >= 0 (0 = off)");
-    if (!(top_p > 0.f && top_p <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "top_p must be in (0, 1] (1 = off)");
-    if (!(min_p >= 0.f && min_p <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "min_p must be in [0, 1] (0 = off)");
-    hipSetDevice(e->device);
-    write_filter(e, seq, top_k, top_p, min_p, (hipStream_t)stream);
-    ZE_KCHECK();
-    return ZE_OK;
-}
-
-// ---- sampling requests (greedy | temperature, seed, repetition penalty per chain; ze_engine::samp_host is the truth, the per-chain
-// kernels of ze_sample.hip read samp_dev)
-static void write_sampling(ze_engine* e, int seq, const ze_chain_sampling& v, hipStream_t s) {
-    ze_chain_sampling& h = e->samp_host[seq];
-    const bool was = h.penalty > 0.f, on = v.penalty > 0.f;
-    e->n_sampling += (int)on - (int)was;
-    e->n_sampled += (int)(on && v.temperature > 0.f) - (int)(was && h.temperature > 0.f);
-    h = v;
-    if (was || on) ze_launch_set_sampling(e->samp_dev, seq, v, s);
-}
-// the slot goes to another chain (wherever its filter is cleared): it never inherits a request.  Nothing is launched for a slot
-// that has none.
-static void clear_sampling(ze_engine* e, int seq, hipStream_t s) {
-    if (e->samp_host[seq].penalty > 0.f) write_sampling(e, seq, ze_chain_sampling{0.f, 0.f, 0ull}, s);
-}
-
-extern "C" int ze_seq_set_sampling(ze_engine* e, int seq, int mode, float temperature, uint64_t seed, float repetition_penalty,
-                                   void* stream) {
-    ZE_TRY(check_seq(e, seq));
-    if (mode < -1 || mode > 1) return ze_fail(e, ZE_ERR_INVALID, "mode must be -1 (clear), 0 (greedy) or 1 (temperature sampling)");
-    if (mode == 1 && !(std::isfinite(temperature) && temperature > 0.f))
-        return ze_fail(e, ZE_ERR_INVALID, "temperature must be finite and > 0");
-    if (mode >= 0 && !(std::isfinite(repetition_penalty) && repetition_penalty > 0.f))
-        return ze_fail(e, ZE_ERR_INVALID, "repetition_penalty must be finite and > 0 (1 = off)");
-    hipSetDevice(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    // the table, on first use: a failed allocation leaves the engine as it was
-    if (mode >= 0 && !e->samp_dev) {
-        ze_chain_sampling* t = nullptr;
-        if (hipMalloc((void**)&t, (size_t)e->cfg.max_seqs * sizeof(ze_chain_sampling)) != hipSuccess) {
-            (void)hipGetLastError();
-            return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the sampling-request table failed");
-        }
-        // all zero = no request.  Once per engine, and waited for: setters on other streams may write their entries at once
-        if (hipMemset(t, 0, (size_t)e->cfg.max_seqs * sizeof(ze_chain_sampling)) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
-            (void)hipGetLastError();
-            hipFree(t);
-            return ze_fail(e, ZE_ERR_HIP, "hipMemset of the sampling-request table failed");
-        }
-        e->samp_dev = t;
-    }
-    if (mode < 0)
-        clear_sampling(e, seq, s);
-    else
-        write_sampling(e, seq, ze_chain_sampling{mode == 1 ? temperature : 0.f, repetition_penalty, mode == 1 ? (unsigned long long)seed : 0ull}, s);
-    ZE_KCHECK();
-    return ZE_OK;
-}
-
-// ---- log-probabilities of generated tokens (ze_engine::lp_host is the truth, ze_logprobs.hip the kernel)
-static void write_logprobs(ze_engine* e, int seq, int top_n, hipStream_t s) {
-    const int was = e->lp_host[seq];
-    if (was == top_n) return;
-    e->lp_host[seq] = top_n;
-    e->n_logprobs += (int)(top_n >= 0) - (int)(was >= 0);
-    ze_launch_set_logprobs(e->lp_dev, seq, top_n, s);
-}
-// the slot goes to another chain (wherever its filter is cleared): it never inherits a request.  Nothing is launched for a slot
-// that has none.
-static void clear_logprobs(ze_engine* e, int seq, hipStream_t s) { write_logprobs(e, seq, -1, s); }
-
-extern "C" int ze_seq_set_logprobs(ze_engine* e, int seq, int top_n, void* stream) {
-    ZE_TRY(check_seq(e, seq));
-    if (top_n < -1 || top_n > ZE_MAX_TOP_LOGPROBS) return ze_fail(e, ZE_ERR_INVALID, "top_n must be in [-1, 20] (-1 = off)");
-    hipSetDevice(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t entries = (size_t)e->cfg.max_seqs * e->cfg.max_ctx;
-    // history, on first use: a failed allocation leaves the engine as it was
-    if (top_n >= 0 && !e->lp_tok) {
-        float* t = nullptr;
-        if (hipMalloc((void**)&t, entries * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the log-probability history failed");
-        }
-        e->lp_tok = t;
-    }
-    if (top_n >= 1 && !e->lp_top_ids) {
-        int* ids = nullptr;
-        float* lps = nullptr;
-        if (hipMalloc((void**)&ids, entries * ZE_MAX_TOP_LOGPROBS * sizeof(int)) != hipSuccess ||
-            hipMalloc((void**)&lps, entries * ZE_MAX_TOP_LOGPROBS * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (ids) hipFree(ids);
-            return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the top-logprobs history failed");
-        }
-        e->lp_top_ids = ids;
-        e->lp_top_lps = lps;
-    }
-    write_logprobs(e, seq, top_n, s);
-    ZE_KCHECK();
-    return ZE_OK;
-}
-
-// after the token of a step was accepted: the chains' entries (only while some chain of the engine has a request -- without one
-// the step launches what it always did).  seq_ids = null: the one chain `slot0`, whose row `logits` is.
-static void launch_logprobs(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s) {
-    if (e->n_logprobs > 0)
-        ze_launch_chain_logprobs(logits, e->cfg.vocab, e->cfg.vocab, e->st_dev, seq_ids, slot0, n, e->lp_bufs(), e->cfg.max_ctx, s);
-}
-
-// ---- logit adjustments (ze_engine::la_host is the truth, ze_logit_adjust.hip the kernels)
-static void write_adjust(ze_engine* e, int seq, const ze_engine::adjust_host& h, const int32_t* ids, const float* vals, hipStream_t s) {
-    const bool was = e->la_host[seq].on();
-    e->la_host[seq] = h;
-    e->n_adjust += (int)h.on() - (int)was;
-    if (!was && !h.on()) return;
-    if (h.n_bias > 0) {  // the list travels as kernel arguments, 128 words a launch
-        ze_launch_set_ints(e->la_bias_ids + (size_t)seq * ZE_MAX_LOGIT_BIAS, ids, h.n_bias, s);
-        ze_launch_set_ints(reinterpret_cast<int*>(e->la_bias_vals + (size_t)seq * ZE_MAX_LOGIT_BIAS), reinterpret_cast<const int*>(vals),
-                           h.n_bias, s);
-    }
-    // (also the word that remembers a finished chain: every request starts from a live chain with zero counts)
-    ze_launch_set_logit_adjust(e->la_dev, seq, h.presence, h.frequency, h.min_new, h.n_bias, s);
-}
-// the slot goes to another chain (wherever its filter is cleared): it never inherits a request.  Nothing is launched for a slot
-// that has none.
-static void clear_adjust(ze_engine* e, int seq, hipStream_t s) {
-    if (e->la_host[seq].on()) write_adjust(e, seq, ze_engine::adjust_host{}, nullptr, nullptr, s);
-}
-
-template <typename T>
-static bool la_alloc(T** p, size_t count) {
-    if (hipMalloc((void**)p, count * sizeof(T)) == hipSuccess) return true;
-    (void)hipGetLastError();
-    *p = nullptr;
-    return false;
-}
-
-// the adjusted rows and the bias lists, on first use (a logit-adjust request, or token rules with bans)
-static int ensure_adjusted_rows(ze_engine* e) {
-    if (e->la_rows) return ZE_OK;
-    const ze_config& c = e->cfg;
-    int* ids = nullptr;
-    float *vals = nullptr, *rows = nullptr;
-    if (!la_alloc(&ids, (size_t)c.max_seqs * ZE_MAX_LOGIT_BIAS) || !la_alloc(&vals, (size_t)c.max_seqs * ZE_MAX_LOGIT_BIAS) ||
-        !la_alloc(&rows, ((size_t)c.max_seqs + 1) * c.vocab)) {
-        if (ids) hipFree(ids);
-        if (vals) hipFree(vals);
-        return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the adjusted-row buffer failed");
-    }
-    e->la_bias_ids = ids, e->la_bias_vals = vals, e->la_rows = rows;
-    return ZE_OK;
-}
-
-extern "C" int ze_seq_set_logit_adjust(ze_engine* e, int seq, float presence_penalty, float frequency_penalty, int min_new_tokens,
-                                       const int32_t* bias_ids, const float* bias_vals, int n_bias, void* stream) {
-    ZE_TRY(check_seq(e, seq));
-    const ze_config& c = e->cfg;
-    if (!std::isfinite(presence_penalty) || !std::isfinite(frequency_penalty))
-        return ze_fail(e, ZE_ERR_INVALID, "presence_penalty and frequency_penalty must be finite (0 = off)");
-    if (min_new_tokens < 0) return ze_fail(e, ZE_ERR_INVALID, "min_new_tokens must be >= 0 (0 = off)");
-    if (n_bias < 0 || n_bias > ZE_MAX_LOGIT_BIAS) return ze_fail(e, ZE_ERR_INVALID, "n_bias must be in [0, 512]");
-    if (n_bias > 0 && (!bias_ids || !bias_vals)) return ze_fail(e, ZE_ERR_INVALID, "null bias arrays");
-    for (int i = 0; i < n_bias; ++i) {
-        if (bias_ids[i] < 0 || bias_ids[i] >= c.vocab) return ze_fail(e, ZE_ERR_INVALID, "bias token id out of range");
-        if (std::isnan(bias_vals[i]) || bias_vals[i] == INFINITY)
-            return ze_fail(e, ZE_ERR_INVALID, "a bias must be finite or -inf (-inf = the token is banned)");
-    }
-    if (n_bias > 1) {
-        std::vector<int32_t> sorted(bias_ids, bias_ids + n_bias);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-            return ze_fail(e, ZE_ERR_INVALID, "duplicate bias token id");
-    }
-    ze_engine::adjust_host h;
-    h.presence = presence_penalty + 0.f;  // (-0 -> +0: "no penalty" has one spelling)
-    h.frequency = frequency_penalty + 0.f;
-    h.min_new = min_new_tokens;
-    h.n_bias = n_bias;
-    hipSetDevice(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    // buffers, on first use: a failed allocation leaves the engine as it was
-    if (h.on()) ZE_TRY(ensure_adjusted_rows(e));
-    if (h.penalties() && !e->la_counts) {
-        uint16_t* counts = nullptr;
-        if (!la_alloc(&counts, (size_t)c.max_seqs * c.vocab)) return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the token counts failed");
-        e->la_counts = counts;
-    }
-    if (h.penalties()) ZE_HIP(hipMemsetAsync(e->la_counts + (size_t)seq * c.vocab, 0, (size_t)c.vocab * sizeof(uint16_t), s));
-    write_adjust(e, seq, h, bias_ids, bias_vals, s);
-    ZE_KCHECK();
-    return ZE_OK;
-}
-
-// The rows the sampler of a step reads: the step's own while no chain of it has a request (the step then launches what it always
-// did), else their adjusted copy.  seq_ids = null: the one chain `slot0`, whose row `logits` is.
-// A chain with bans (token rules) counts as adjusted: the ban pass writes -inf into its copy behind the adjust kernel, which
-// leaves the row of an all-zero request untouched.
-static const float* adjusted_rows(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s) {
-    const bool bans = seq_ids ? e->n_bans > 0 : e->tr_host[slot0].bans();
-    if (!bans && (seq_ids ? e->n_adjust == 0 : !e->la_host[slot0].on())) return logits;
-    float* out = seq_ids ? e->la_rows : e->la_rows + (size_t)e->cfg.max_seqs * e->cfg.vocab;
-    ze_launch_chain_logit_adjust(logits, e->cfg.vocab, e->st_dev, seq_ids, slot0, n, e->la_bufs(), e->eos_dev, e->cfg.n_eos, out, s);
-    if (bans) ze_launch_chain_token_ban(out, e->cfg.vocab, e->st_dev, seq_ids, slot0, n, e->tr_bufs(), e->out_tokens, e->cfg.max_ctx, s);
-    return out;
-}
-// after the token of a step was accepted, next to launch_logprobs: the chains' counts
-static void launch_counts(ze_engine* e, const int* seq_ids, int slot0, int n, hipStream_t s) {
-    if (seq_ids ? e->n_adjust == 0 : !e->la_host[slot0].on()) return;
-    ze_launch_count_tokens(e->st_dev, seq_ids, slot0, n, e->la_bufs(), e->cfg.vocab, s);
-}
-
-// ---- token rules (ze_engine::tr_host is the truth, ze_token_rules.hip the kernels)
-static void write_rules(ze_engine* e, int seq, const ze_engine::rules_host& h, const int32_t* stop, const int32_t* ban, hipStream_t s) {
-    const ze_engine::rules_host was = e->tr_host[seq];
-    e->tr_host[seq] = h;
-    e->n_bans += (int)h.bans() - (int)was.bans();
-    e->n_stops += (int)h.stops() - (int)was.stops();
-    if (!was.on() && !h.on()) return;
-    // the lists travel as kernel arguments, 128 words a launch
-    if (h.n_stop_ints > 0) ze_launch_set_ints(e->tr_stop + (size_t)seq * ZE_MAX_RULE_INTS, stop, h.n_stop_ints, s);
-    if (h.n_ban_ints > 0) ze_launch_set_ints(e->tr_ban + (size_t)seq * ZE_MAX_RULE_INTS, ban, h.n_ban_ints, s);
-    ze_launch_set_token_rules(e->tr_dev, seq, h.ngram, h.n_stop_ints, h.n_stop_words, h.n_ban_ints, h.n_ban_words, h.n_context, s);
-}
-// the slot goes to another chain (wherever its filter is cleared): it never inherits a request.  Nothing is launched for a slot
-// that has none.
-static void clear_rules(ze_engine* e, int seq, hipStream_t s) {
-    if (e->tr_host[seq].on()) write_rules(e, seq, ze_engine::rules_host{}, nullptr, nullptr, s);
-}
-
-// ints of a packed list of n_words records (len, id0 .. id(len-1), ...), or -1 with the message set
-static int check_records(ze_engine* e, const int32_t* seqs, int n_words, const char* what) {
-    const auto bad = [&](const char* why) {
-        ze_fail(e, ZE_ERR_INVALID, (std::string(what) + ": " + why).c_str());
-        return -1;
-    };
-    if (n_words < 0 || n_words > ZE_MAX_RULE_WORDS) return bad("at most 64 records");
-    if (n_words > 0 && !seqs) return bad("null list");
-    int off = 0;
-    for (int w = 0; w < n_words; ++w) {
-        if (off >= ZE_MAX_RULE_INTS) return bad("a packed list holds at most 1024 ints");
-        const int len = seqs[off];
-        if (len < 1 || len > ZE_MAX_RULE_LEN) return bad("a record holds 1 to 16 token ids");
-        if (off + 1 + len > ZE_MAX_RULE_INTS) return bad("a packed list holds at most 1024 ints");
-        for (int i = 0; i < len; ++i)
-            if (seqs[off + 1 + i] < 0 || seqs[off + 1 + i] >= e->cfg.vocab) return bad("token id out of range");
-        off += 1 + len;
-    }
-    return off;
-}
-
-extern "C" int ze_seq_set_token_rules(ze_engine* e, int seq, int no_repeat_ngram, const int32_t* stop_seqs, int n_stop_words,
-                                      const int32_t* ban_seqs, int n_ban_words, const int32_t* context_ids, int n_context, void* stream) {
-    ZE_TRY(check_seq(e, seq));
-    const ze_config& c = e->cfg;
-    if (no_repeat_ngram < 0 || no_repeat_ngram > ZE_MAX_RULE_LEN) return ze_fail(e, ZE_ERR_INVALID, "no_repeat_ngram must be in [0, 16] (0 = off)");
-    const int stop_ints = check_records(e, stop_seqs, n_stop_words, "stop_seqs");
-    if (stop_ints < 0) return ZE_ERR_INVALID;
-    const int ban_ints = check_records(e, ban_seqs, n_ban_words, "ban_seqs");
-    if (ban_ints < 0) return ZE_ERR_INVALID;
-    if (n_context < 0 || n_context > c.max_ctx) return ze_fail(e, ZE_ERR_INVALID, "n_context must be in [0, max_ctx]");
-    if (n_context > 0 && !context_ids) return ze_fail(e, ZE_ERR_INVALID, "null context_ids");
-    for (int i = 0; i < n_context; ++i)
-        if (context_ids[i] < 0 || context_ids[i] >= c.vocab) return ze_fail(e, ZE_ERR_INVALID, "context token id out of range");
-    ze_engine::rules_host h;
-    h.ngram = no_repeat_ngram, h.n_stop_ints = stop_ints, h.n_stop_words = n_stop_words, h.n_ban_ints = ban_ints, h.n_ban_words = n_ban_words;
-    h.n_context = h.bans() ? n_context : 0;  // (stop records never look at the context)
-    hipSetDevice(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    // buffers, on first use: a failed allocation leaves the engine as it was
-    if (h.bans()) ZE_TRY(ensure_adjusted_rows(e));
-    if (h.on() && !e->tr_stop) {
-        int *st = nullptr, *bn = nullptr;
-        if (!la_alloc(&st, (size_t)c.max_seqs * ZE_MAX_RULE_INTS) || !la_alloc(&bn, (size_t)c.max_seqs * ZE_MAX_RULE_INTS)) {
-            if (st) hipFree(st);
-            return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the token-rule lists failed");
-        }
-        e->tr_stop = st, e->tr_ban = bn;
-    }
-    if (h.n_context > 0 && !e->tr_ctx) {
-        int* ctx = nullptr;
-        if (!la_alloc(&ctx, (size_t)c.max_seqs * c.max_ctx)) return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the context history failed");
-        e->tr_ctx = ctx;
-    }
-    // (a copy from pageable memory has left the caller's array when the call returns, and is ordered on the stream)
-    if (h.n_context > 0)
-        ZE_HIP(hipMemcpyAsync(e->tr_ctx + (size_t)seq * c.max_ctx, context_ids, (size_t)h.n_context * sizeof(int), hipMemcpyHostToDevice, s));
-    write_rules(e, seq, h, stop_seqs, ban_seqs, s);
-    ZE_KCHECK();
-    return ZE_OK;
-}
-
-// after the token of a step was accepted, next to launch_logprobs / launch_counts: a stop record at the tail of the generated ids
-// finishes its chain
-static void launch_stops(ze_engine* e, const int* seq_ids, int slot0, int n, hipStream_t s) {
-    if (seq_ids ? e->n_stops == 0 : !e->tr_host[slot0].stops()) return;
-    ze_launch_chain_token_stop(e->st_dev, seq_ids, slot0, n, e->tr_bufs(), e->la_dev, e->out_tokens, e->cfg.max_ctx, s);
-}
-
 extern "C" int ze_seq_reset(ze_engine* e, int seq, void* stream) {
     ZE_TRY(check_seq(e, seq));
     hipSetDevice(e->device);
@@ -721,11 +394,7 @@ extern "C" int ze_seq_reset(ze_engine* e, int seq, void* stream) {
     prefix_source_gone(e, seq, 0);
     e->pfx_host[seq] = 0;
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)seq * e->cfg.vocab, 0, e->cfg.vocab, s));
-    clear_filter(e, seq, s);
-    clear_sampling(e, seq, s);
-    clear_logprobs(e, seq, s);
-    clear_adjust(e, seq, s);
-    clear_rules(e, seq, s);
+    ze_requests_clear(e, seq, s);
     return push_state(e, seq, s, 0, 0, 0);
 }
 
@@ -785,11 +454,7 @@ extern "C" int ze_seq_truncate(ze_engine* e, int seq, int keep_len, void* stream
     if ((e->pfx_host[seq] & 0xffff) > keep_len) e->pfx_host[seq] = 0;
     // the seen-set belongs to the dropped continuation: the caller re-marks the (new) prompt
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)seq * e->cfg.vocab, 0, e->cfg.vocab, (hipStream_t)stream));
-    clear_filter(e, seq, (hipStream_t)stream);
-    clear_sampling(e, seq, (hipStream_t)stream);
-    clear_logprobs(e, seq, (hipStream_t)stream);
-    clear_adjust(e, seq, (hipStream_t)stream);
-    clear_rules(e, seq, (hipStream_t)stream);
+    ze_requests_clear(e, seq, (hipStream_t)stream);
     return push_state(e, seq, (hipStream_t)stream, 0, 0, 0);
 }
 
@@ -822,11 +487,7 @@ extern "C" int ze_seq_copy_prefix(ze_engine* e, int dst_seq, int src_seq, int n_
         e->pfx_host[dst_seq] = (e->prefix_hints && n_tokens < 65536 && src != dst_seq) ? ((src << 16) | n_tokens) : 0;
     }
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)dst_seq * c.vocab, 0, c.vocab, s));
-    clear_filter(e, dst_seq, s);
-    clear_sampling(e, dst_seq, s);
-    clear_logprobs(e, dst_seq, s);
-    clear_adjust(e, dst_seq, s);
-    clear_rules(e, dst_seq, s);
+    ze_requests_clear(e, dst_seq, s);
     return push_state(e, dst_seq, s, 0, 0, 0);
 }
 
@@ -1218,8 +879,8 @@ extern "C" int ze_prefill_batch(ze_engine* e, const int32_t* seqs, int n, const 
 // ================================================================== decode
 // One token for chain `seq`: everything is read from the device-side chain state, so the same launch
 // sequence can be captured once into a hipGraph and replayed.
-int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int ignore_eos, bool sample, const ze_sample_opts& so,
-                           hipStream_t s) {
+static int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int ignore_eos, bool sample, const ze_sample_opts& so,
+                                  hipStream_t s) {
     const ze_config& c = e->cfg;
     const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nqkv = nq + 2 * c.kv_heads * hd;
     const ze_seq_dev* st = e->st_dev + seq;
@@ -1328,7 +989,7 @@ int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int ignore_eos,
     a.D = hd;
     // greedy: the arg-max partials come out of the lm_head launch itself (knob 14 = 1: the separate partial kernel)
     // (a chain with a logit-adjust request keeps off it: the folded arg-max never sees the row)
-    const bool folded = sample && so.temperature <= 0.f && ze_gemv_knobs[14] != 1 && !e->la_host[seq].on() && !e->tr_host[seq].bans();
+    const bool folded = sample && so.temperature <= 0.f && ze_gemv_knobs[14] != 1 && !e->req.la_host[seq].on() && !e->req.tr_host[seq].bans();
     if (folded) {
         a.seen = e->seen + (size_t)seq * c.vocab;
         a.penalty = penalty;
@@ -1339,16 +1000,12 @@ int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int ignore_eos,
         ze_launch_sample_folded(e->damax, c.vocab, e->seen + (size_t)seq * c.vocab, e->st_dev + seq, e->eos_dev, c.n_eos,
                                 c.pad_token_id, ignore_eos, /*advance_ctx=*/1, e->out_tokens + (size_t)seq * c.max_ctx, s);
     else if (sample)
-        ze_launch_sample(adjusted_rows(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s), c.vocab, e->seen + (size_t)seq * c.vocab,
+        ze_launch_sample(ze_requests_rows(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s), c.vocab, e->seen + (size_t)seq * c.vocab,
                          penalty, e->st_dev + seq, e->eos_dev, c.n_eos, c.pad_token_id, ignore_eos, /*advance_ctx=*/1,
                          e->out_tokens + (size_t)seq * c.max_ctx, e->dsample, so, s);
     else
         ze_launch_advance_ctx(e->st_dev + seq, s);  // teacher forcing: the caller chooses the next token
-    if (sample) {
-        launch_logprobs(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s);
-        launch_counts(e, nullptr, seq, 1, s);
-        launch_stops(e, nullptr, seq, 1, s);
-    }
+    if (sample) ze_requests_after_token(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s);
     ZE_KCHECK();
     return ZE_OK;
 }
@@ -1371,15 +1028,6 @@ extern "C" int ze_decode_step(ze_engine* e, int seq, int token, float* out_logit
     return ZE_OK;
 }
 
-// A sampled launch learns about filters only while some chain of the engine has one: with none set it is today's launch
-// sequence.  `batch`: the cuts of a batched step (one per row) -- otherwise the slot's own word.
-static void attach_filters(ze_engine* e, ze_sample_opts& so, bool batch) {
-    if (so.draws() && e->n_filters > 0) {
-        so.filt = e->filt_dev;
-        so.cuts = batch ? e->cut_dev : e->cut_dev + e->cfg.max_seqs + so.slot;
-    }
-}
-
 // The selection alone, on caller-supplied rows (unit op: any vocab / ld, a filter and a temperature per row, no repetition penalty)
 extern "C" int ze_op_sample_filter(ze_engine* e, const float* logits, int rows, int vocab, int ld, const float* temperature,
                                    const int32_t* top_k, const float* top_p, const float* min_p, float* out_cut,
@@ -1389,9 +1037,7 @@ extern "C" int ze_op_sample_filter(ze_engine* e, const float* logits, int rows, 
     std::vector<float> table((size_t)rows * 4);
     for (int r = 0; r < rows; ++r) {
         if (!(temperature[r] > 0.f)) return ze_fail(e, ZE_ERR_INVALID, "temperature must be positive");
-        if (top_k[r] < 0) return ze_fail(e, ZE_ERR_INVALID, "top_k must be >= 0 (0 = off)");
-        if (!(top_p[r] > 0.f && top_p[r] <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "top_p must be in (0, 1] (1 = off)");
-        if (!(min_p[r] >= 0.f && min_p[r] <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "min_p must be in [0, 1] (0 = off)");
+        ZE_TRY(ze_check_filter(e, top_k[r], top_p[r], min_p[r]));
         memcpy(&table[4 * r], &top_k[r], sizeof(int));
         table[4 * r + 1] = top_p[r];
         table[4 * r + 2] = min_p[r];
@@ -1444,9 +1090,7 @@ extern "C" int ze_op_sample_rows(ze_engine* e, const float* logits, int rows, in
         memcpy(&host[o_st + 8 * (size_t)r], &st, sizeof(st));
         host[o_ids + r] = r;
         if (filters) {
-            if (top_k[r] < 0) return ze_fail(e, ZE_ERR_INVALID, "top_k must be >= 0 (0 = off)");
-            if (!(top_p[r] > 0.f && top_p[r] <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "top_p must be in (0, 1] (1 = off)");
-            if (!(min_p[r] >= 0.f && min_p[r] <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "min_p must be in [0, 1] (0 = off)");
+            ZE_TRY(ze_check_filter(e, top_k[r], top_p[r], min_p[r]));
             host[o_filt + 4 * (size_t)r] = top_k[r];
             memcpy(&host[o_filt + 4 * (size_t)r + 1], &top_p[r], sizeof(float));
             memcpy(&host[o_filt + 4 * (size_t)r + 2], &min_p[r], sizeof(float));
@@ -1483,7 +1127,7 @@ static int op_sample(ze_engine* e, int seq, const float* logits, float repetitio
     if (index) ze_launch_set_ints(&(e->st_dev + seq)->n_gen, &index, 1, s);
     ze_launch_sample(logits, c.vocab, e->seen + (size_t)seq * c.vocab, repetition_penalty, e->st_dev + seq, e->eos_dev,
                      c.n_eos, c.pad_token_id, 1, 0, e->out_tokens + (size_t)seq * c.max_ctx, e->dsample, so, s);
-    launch_logprobs(e, logits, nullptr, seq, 1, s);
+    ze_requests_logprobs(e, logits, nullptr, seq, 1, s);
     ZE_KCHECK();
     ZE_HIP(hipMemcpyAsync(out_token, e->out_tokens + (size_t)seq * c.max_ctx + index, sizeof(int), hipMemcpyDeviceToHost, s));
     ZE_HIP(hipStreamSynchronize(s));
@@ -1502,36 +1146,46 @@ extern "C" int ze_op_sample_temperature(ze_engine* e, int seq, const float* logi
     so.temperature = temperature;
     so.seed = seed;
     so.slot = seq;
-    if (check_seq(e, seq) == 0) attach_filters(e, so, false);
+    if (check_seq(e, seq) == 0) ze_attach_filters(e, so, false);
     return op_sample(e, seq, logits, repetition_penalty, so, index, out_token, (hipStream_t)stream);
 }
 
-// The repetition penalty a single-chain launch runs with: the chain's own while it has a sampling request, else the call's
-static float penalty_of(const ze_engine* e, const ze_gen_params* p, int seq) {
-    if (e->samp_host[seq].penalty > 0.f) return e->samp_host[seq].penalty;
-    return p->repetition_penalty > 0.f ? p->repetition_penalty : 1.0f;
+// One decode step, as `enqueue` puts it on the stream it is given, captured into an executable graph
+template <typename F>
+static int capture_step(ze_engine* e, F enqueue, hipGraphExec_t* exec) {
+    hipStream_t cs;
+    ZE_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    hipGraph_t graph = nullptr;
+    int r = ZE_OK;
+    if (hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess)
+        r = ze_fail(e, ZE_ERR_HIP, "hipStreamBeginCapture failed");
+    if (r == ZE_OK) r = enqueue(cs);
+    if (hipStreamEndCapture(cs, &graph) != hipSuccess && r == ZE_OK)
+        r = ze_fail(e, ZE_ERR_HIP, "hipStreamEndCapture failed");
+    if (r == ZE_OK && hipGraphInstantiate(exec, graph, nullptr, nullptr, 0) != hipSuccess)
+        r = ze_fail(e, ZE_ERR_HIP, "hipGraphInstantiate failed");
+    if (graph) hipGraphDestroy(graph);
+    hipStreamDestroy(cs);
+    return r;
 }
 
-// A single-chain launch serves one known chain: its request (ze_seq_set_sampling) is resolved here, on the host, and the scalar
-// kernels run with the chain's own values.  `batch`: the call's values stay the launch's defaults, and the per-slot table joins
-// them while some chain of the engine has a request -- with none it is today's launch sequence.
-static ze_sample_opts sample_opts_of(ze_engine* e, const ze_gen_params* p, int slot, bool batch = false) {
-    ze_sample_opts so;
-    const ze_chain_sampling& req = e->samp_host[slot];
-    if (!batch && req.penalty > 0.f) {
-        so.temperature = req.temperature;
-        so.seed = req.temperature > 0.f ? req.seed : 0ull;
-    } else if (p->do_sample && p->temperature > 0.f) {
-        so.temperature = p->temperature;
-        so.seed = p->seed;
-    }
-    if (batch && e->n_sampling > 0) {
-        so.samp = e->samp_dev;
-        so.samp_draws = e->n_sampled > 0;
-    }
-    so.slot = slot;
-    attach_filters(e, so, batch);
-    return so;
+// first token of chain `q` from the logits its prefill left behind (no cache growth)
+static int first_token(ze_engine* e, int q, float pen, int ign, const ze_sample_opts& so, hipStream_t s) {
+    const ze_config& c = e->cfg;
+    const float* row = e->dlogits + (size_t)q * c.vocab;
+    ze_launch_sample(ze_requests_rows(e, row, nullptr, q, 1, s), c.vocab, e->seen + (size_t)q * c.vocab, pen, e->st_dev + q, e->eos_dev,
+                     c.n_eos, c.pad_token_id, ign, 0, e->out_tokens + (size_t)q * c.max_ctx, e->dsample, so, s);
+    ze_requests_after_token(e, row, nullptr, q, 1, s);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
+// tokens up to and including the first EOS (those after it are pad, as HF emits for finished rows)
+static int trim_at_eos(const ze_config& c, const int32_t* tokens, int n) {
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < c.n_eos; ++k)
+            if (tokens[i] == c.eos_token_ids[k]) return i + 1;
+    return n;
 }
 
 extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_t* out_tokens, int* n_out,
@@ -1549,57 +1203,28 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
     // the last generated token is never fed back, so ctx grows by max_new - 1
     if (e->ctx_host[seq] + max_new - 1 > c.max_ctx) max_new = c.max_ctx - e->ctx_host[seq] + 1;
     if (max_new <= 0) return ze_fail(e, ZE_ERR_NOMEM, "sequence exceeds max_ctx");
-    const float pen = penalty_of(e, p, seq);  // (the graph below is keyed by the effective values: a new request re-captures it)
+    const float pen = ze_penalty_of(e, p, seq);  // (the graph below is keyed by the effective values: a new request re-captures it)
     const int ign = p->ignore_eos ? 1 : 0;
+    const ze_sample_opts so = ze_sample_opts_of(e, p, seq);
     int32_t* dev_out = e->out_tokens + (size_t)seq * c.max_ctx;
     ze_seq_dev* st = e->st_dev + seq;
 
     const int t_s = ze_timer_begin(e, 4, s);
-    // first token from the prefill logits (no cache growth)
-    const ze_sample_opts so = sample_opts_of(e, p, seq);
-    ze_launch_sample(adjusted_rows(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s), c.vocab, e->seen + (size_t)seq * c.vocab,
-                     pen, st, e->eos_dev, c.n_eos, c.pad_token_id, ign, 0, dev_out, e->dsample, so, s);
-    launch_logprobs(e, e->dlogits + (size_t)seq * c.vocab, nullptr, seq, 1, s);
-    launch_counts(e, nullptr, seq, 1, s);
-    launch_stops(e, nullptr, seq, 1, s);
+    const int r0 = first_token(e, seq, pen, ign, so, s);
     ze_timer_end(e, t_s, s);
-    ZE_KCHECK();
+    ZE_TRY(r0);
 
     // decode-step graph for this chain (re-captured when the sampling options change)
     hipGraphExec_t gexec = nullptr;
     if (p->use_graph && max_new > 1) {
-        if (!e->graphs[seq] || e->graph_penalty[seq] != pen || e->graph_ignore_eos[seq] != ign ||
-            e->graph_variant[seq] != (int)ze_tune_epoch || e->graph_temperature[seq] != so.temperature ||
-            e->graph_seed[seq] != so.seed || e->graph_filters[seq] != (int)(so.filt != nullptr) ||
-            e->graph_logprobs[seq] != e->lp_mode() || e->graph_adjust[seq] != e->la_mode(seq) ||
-            e->graph_rules[seq] != e->tr_mode(seq)) {
+        const ze_step_key key = ze_step_key_of(e, 0, seq, pen, ign, so);
+        if (!e->graphs[seq] || !(e->graph_key[seq] == key)) {
             if (e->graphs[seq]) {
                 hipGraphExecDestroy(e->graphs[seq]);
                 e->graphs[seq] = nullptr;
             }
-            hipStream_t cs;
-            ZE_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-            hipGraph_t graph = nullptr;
-            int r = ZE_OK;
-            if (hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess)
-                r = ze_fail(e, ZE_ERR_HIP, "hipStreamBeginCapture failed");
-            if (r == ZE_OK) r = ze_enqueue_decode_step(e, seq, pen, ign, true, so, cs);
-            if (hipStreamEndCapture(cs, &graph) != hipSuccess && r == ZE_OK)
-                r = ze_fail(e, ZE_ERR_HIP, "hipStreamEndCapture failed");
-            if (r == ZE_OK && hipGraphInstantiate(&e->graphs[seq], graph, nullptr, nullptr, 0) != hipSuccess)
-                r = ze_fail(e, ZE_ERR_HIP, "hipGraphInstantiate failed");
-            if (graph) hipGraphDestroy(graph);
-            hipStreamDestroy(cs);
-            ZE_TRY(r);
-            e->graph_penalty[seq] = pen;
-            e->graph_ignore_eos[seq] = ign;
-            e->graph_variant[seq] = (int)ze_tune_epoch;
-            e->graph_temperature[seq] = so.temperature;
-            e->graph_seed[seq] = so.seed;
-            e->graph_filters[seq] = so.filt != nullptr;
-            e->graph_logprobs[seq] = e->lp_mode();
-            e->graph_adjust[seq] = e->la_mode(seq);
-            e->graph_rules[seq] = e->tr_mode(seq);
+            ZE_TRY(capture_step(e, [&](hipStream_t cs) { return ze_enqueue_decode_step(e, seq, pen, ign, true, so, cs); }, &e->graphs[seq]));
+            e->graph_key[seq] = key;
         }
         gexec = e->graphs[seq];
     }
@@ -1627,19 +1252,7 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
     ze_timer_end(e, t_d, s);
     ZE_HIP(hipMemcpyAsync(out_tokens, dev_out, (size_t)produced * sizeof(int), hipMemcpyDeviceToHost, s));
     ZE_HIP(hipStreamSynchronize(s));
-    // trim at the first EOS (tokens after it are pad, as HF emits for finished rows)
-    int n = produced;
-    if (!ign) {
-        for (int i = 0; i < produced; ++i) {
-            bool is_eos = false;
-            for (int k = 0; k < c.n_eos; ++k) is_eos |= out_tokens[i] == c.eos_token_ids[k];
-            if (is_eos) {
-                n = i + 1;
-                break;
-            }
-        }
-    }
-    *n_out = n;
+    *n_out = ign ? produced : trim_at_eos(c, out_tokens, produced);
     return ZE_OK;
 }
 
@@ -1932,14 +1545,10 @@ static int enqueue_decode_batch(ze_engine* e, int n, float penalty, int ignore_e
     else
         ze_launch_gemm_stream(ZE_EPI_F32, e->by, H, e->lm_head, H, nullptr, nullptr, 0, (bf16_t*)e->blogits, c.vocab, n,
                               c.vocab, H, e->gemm_ws(), s);
-    ze_launch_sample_batch(sample ? adjusted_rows(e, e->blogits, e->bseq, 0, n, s) : e->blogits, c.vocab, e->seen, penalty, e->st_dev,
+    ze_launch_sample_batch(sample ? ze_requests_rows(e, e->blogits, e->bseq, 0, n, s) : e->blogits, c.vocab, e->seen, penalty, e->st_dev,
                            e->bseq, n, e->eos_dev, c.n_eos, c.pad_token_id, ignore_eos, 1, sample, e->out_tokens, c.max_ctx, e->bsample,
                            e->bsample + (size_t)c.max_seqs * 2 * 128, so, s);
-    if (sample) {
-        launch_logprobs(e, e->blogits, e->bseq, 0, n, s);
-        launch_counts(e, e->bseq, 0, n, s);
-        launch_stops(e, e->bseq, 0, n, s);
-    }
+    if (sample) ze_requests_after_token(e, e->blogits, e->bseq, 0, n, s);
     ZE_KCHECK();
     return ZE_OK;
 }
@@ -1971,10 +1580,7 @@ extern "C" int ze_decode_batch(ze_engine* e, const int32_t* seqs, int n, const i
 // The captured batched decode step for `na` chains (chain ids / positions live in device memory, so one graph per
 // batch size and sampling setting serves every composition); nullptr in *out = run eagerly.
 static int batch_step_graph(ze_engine* e, int na, float pen, int ign, const ze_sample_opts& bso, hipGraphExec_t* out) {
-    auto key = std::make_tuple(na, pen, ign, bso.temperature, bso.seed, e->live_parts * 64 + e->live_parts_long,
-                               // (per-chain sampling: the mode and whether the draw is launched -- never a request's values)
-                               (int)(bso.filt != nullptr) | (int)(bso.samp != nullptr) << 1 | (int)bso.samp_draws << 2,
-                               e->lp_mode(), e->la_mode(), e->tr_mode());
+    const ze_step_key key = ze_step_key_of(e, na, 0, pen, ign, bso);
     if (e->bgraph_epoch != ze_tune_epoch) {
         for (auto& kv : e->bgraphs) hipGraphExecDestroy(kv.second);
         e->bgraphs.clear();
@@ -1982,21 +1588,8 @@ static int batch_step_graph(ze_engine* e, int na, float pen, int ign, const ze_s
     }
     auto it = e->bgraphs.find(key);
     if (it == e->bgraphs.end()) {
-        hipStream_t cs;
-        ZE_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-        hipGraph_t graph = nullptr;
-        int r = ZE_OK;
-        if (hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess)
-            r = ze_fail(e, ZE_ERR_HIP, "hipStreamBeginCapture failed");
-        if (r == ZE_OK) r = enqueue_decode_batch(e, na, pen, ign, 1, bso, cs);
-        if (hipStreamEndCapture(cs, &graph) != hipSuccess && r == ZE_OK)
-            r = ze_fail(e, ZE_ERR_HIP, "hipStreamEndCapture failed");
         hipGraphExec_t ex = nullptr;
-        if (r == ZE_OK && hipGraphInstantiate(&ex, graph, nullptr, nullptr, 0) != hipSuccess)
-            r = ze_fail(e, ZE_ERR_HIP, "hipGraphInstantiate failed");
-        if (graph) hipGraphDestroy(graph);
-        hipStreamDestroy(cs);
-        ZE_TRY(r);
+        ZE_TRY(capture_step(e, [&](hipStream_t cs) { return enqueue_decode_batch(e, na, pen, ign, 1, bso, cs); }, &ex));
         it = e->bgraphs.emplace(key, ex).first;
     }
     *out = it->second;
@@ -2021,19 +1614,11 @@ static int run_burst(ze_engine* e, const std::vector<int>& active, int steps, co
     return ZE_OK;
 }
 
-// first token of a chain from the logits its prefill left behind; `sample_stream` = the chain's random stream
+// first_token for a chain of a batch; `sample_stream` = the chain's random stream
 static int begin_chain(ze_engine* e, int q, const ze_gen_params* p, int ign, int sample_stream, hipStream_t s) {
-    const ze_config& c = e->cfg;
-    const float pen = penalty_of(e, p, q);
-    ze_sample_opts so = sample_opts_of(e, p, q);
+    const ze_sample_opts so = ze_sample_opts_of(e, p, q);
     if (so.temperature > 0.f) ze_launch_set_ints(&(e->st_dev + q)->stream, &sample_stream, 1, s);
-    ze_launch_sample(adjusted_rows(e, e->dlogits + (size_t)q * c.vocab, nullptr, q, 1, s), c.vocab, e->seen + (size_t)q * c.vocab, pen,
-                     e->st_dev + q, e->eos_dev, c.n_eos, c.pad_token_id, ign, 0, e->out_tokens + (size_t)q * c.max_ctx, e->dsample, so, s);
-    launch_logprobs(e, e->dlogits + (size_t)q * c.vocab, nullptr, q, 1, s);
-    launch_counts(e, nullptr, q, 1, s);
-    launch_stops(e, nullptr, q, 1, s);
-    ZE_KCHECK();
-    return ZE_OK;
+    return first_token(e, q, ze_penalty_of(e, p, q), ign, so, s);
 }
 
 extern "C" int ze_generate_batch(ze_engine* e, const int32_t* seqs, int n, const ze_gen_params* p, int32_t* out_tokens,
@@ -2058,7 +1643,7 @@ extern "C" int ze_generate_batch(ze_engine* e, const int32_t* seqs, int n, const
     }
     const float pen = p->repetition_penalty > 0.f ? p->repetition_penalty : 1.0f;
     const int ign = p->ignore_eos ? 1 : 0;
-    const ze_sample_opts bso = sample_opts_of(e, p, 0, true);
+    const ze_sample_opts bso = ze_sample_opts_of(e, p, 0, true);
     // sampling stream of a chain = its row in this call (reproducible per request)
     for (int i = 0; i < n; ++i) ZE_TRY(begin_chain(e, seqs[i], p, ign, i, s));
     std::vector<int> active;
@@ -2095,18 +1680,7 @@ extern "C" int ze_generate_batch(ze_engine* e, const int32_t* seqs, int n, const
         // (on the caller's stream: a legacy-stream copy would synchronise with every other engine's stream of the process)
         ZE_HIP(hipMemcpyAsync(dst, e->out_tokens + (size_t)q * c.max_ctx, (size_t)produced[q] * sizeof(int), hipMemcpyDeviceToHost, s));
         ZE_HIP(hipStreamSynchronize(s));
-        int cnt = produced[q];
-        if (!ign) {
-            for (int t = 0; t < produced[q]; ++t) {
-                bool is_eos = false;
-                for (int k = 0; k < c.n_eos; ++k) is_eos |= dst[t] == c.eos_token_ids[k];
-                if (is_eos) {
-                    cnt = t + 1;
-                    break;
-                }
-            }
-        }
-        n_out[i] = cnt;
+        n_out[i] = ign ? produced[q] : trim_at_eos(c, dst, produced[q]);
     }
     return ZE_OK;
 }
@@ -2143,7 +1717,7 @@ extern "C" int ze_decode_burst_begin(ze_engine* e, const int32_t* seqs, int n, i
     const float pen = p->repetition_penalty > 0.f ? p->repetition_penalty : 1.0f;
     const int ign = p->ignore_eos ? 1 : 0;
     const int td = ze_timer_begin(e, 3, s);
-    if (steps > 0) ZE_TRY(run_burst(e, active, steps, p, pen, ign, sample_opts_of(e, p, 0, true), s));
+    if (steps > 0) ZE_TRY(run_burst(e, active, steps, p, pen, ign, ze_sample_opts_of(e, p, 0, true), s));
     ze_timer_end(e, td, s);
     return steps;
 }
@@ -2185,16 +1759,7 @@ extern "C" int ze_chain_tokens(ze_engine* e, int seq, int32_t* out, int cap, int
         ZE_HIP(hipMemcpyAsync(out, e->out_tokens + (size_t)seq * c.max_ctx, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
         ZE_HIP(hipStreamSynchronize(s));
     }
-    // trim at the first EOS (tokens after it are pad, as HF emits for finished rows)
-    for (int i = 0; i < n; ++i) {
-        bool is_eos = false;
-        for (int k = 0; k < c.n_eos; ++k) is_eos |= out[i] == c.eos_token_ids[k];
-        if (is_eos && st.finished) {
-            n = i + 1;
-            break;
-        }
-    }
-    *n_out = n;
+    *n_out = st.finished ? trim_at_eos(c, out, n) : n;
     return ZE_OK;
 }
 
@@ -2221,18 +1786,10 @@ extern "C" int ze_chain_tokens_batch(ze_engine* e, const int32_t* seqs, int n, i
     ZE_HIP(hipMemcpyAsync(e->xt_host, e->xt_dev, words * sizeof(int), hipMemcpyDeviceToHost, s));
     ZE_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < n; ++i) {
-        int m = e->xt_host[2 * i];
-        const bool finished = e->xt_host[2 * i + 1] != 0;
         const int* row = e->xt_host + 2 * (size_t)n + (size_t)i * cap;
-        for (int t = 0; t < m; ++t) {  // trim at the first EOS, as ze_chain_tokens
-            out[(size_t)i * cap + t] = row[t];
-            bool is_eos = false;
-            for (int k = 0; k < c.n_eos; ++k) is_eos |= row[t] == c.eos_token_ids[k];
-            if (is_eos && finished) {
-                m = t + 1;
-                break;
-            }
-        }
+        const bool finished = e->xt_host[2 * i + 1] != 0;
+        const int m = finished ? trim_at_eos(c, row, e->xt_host[2 * i]) : e->xt_host[2 * i];  // (as ze_chain_tokens)
+        memcpy(out + (size_t)i * cap, row, (size_t)m * sizeof(int));
         n_out[i] = m;
     }
     return ZE_OK;
@@ -2249,7 +1806,7 @@ extern "C" int ze_chain_logprobs_batch(ze_engine* e, const int32_t* seqs, int n,
     const ze_config& c = e->cfg;
     for (int i = 0; i < n; ++i) {
         ZE_TRY(check_seq(e, seqs[i]));
-        if (e->lp_host[seqs[i]] < 0) return ze_fail(e, ZE_ERR_INVALID, "the chain has no log-probability request (ze_seq_set_logprobs)");
+        if (e->req.lp_host[seqs[i]] < 0) return ze_fail(e, ZE_ERR_INVALID, "the chain has no log-probability request (ze_seq_set_logprobs)");
     }
     cap = std::min(cap, c.max_ctx);
     const int stride = (out_top_ids && out_top_logprobs) ? top_n_stride : 0;
@@ -2261,7 +1818,7 @@ extern "C" int ze_chain_logprobs_batch(ze_engine* e, const int32_t* seqs, int n,
     int* slots_dev = e->xl_dev + words;
     memcpy(e->xl_host + words, seqs, (size_t)n * sizeof(int));
     ZE_HIP(hipMemcpyAsync(slots_dev, e->xl_host + words, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    ze_launch_gather_chain_logprobs(e->st_dev, e->out_tokens, e->lp_bufs(), c.max_ctx, slots_dev, n, cap, stride, e->xl_dev, s);
+    ze_launch_gather_chain_logprobs(e->st_dev, e->out_tokens, e->req.lp_bufs(), c.max_ctx, slots_dev, n, cap, stride, e->xl_dev, s);
     ZE_KCHECK();
     ZE_HIP(hipMemcpyAsync(e->xl_host, e->xl_dev, words * sizeof(int), hipMemcpyDeviceToHost, s));
     ZE_HIP(hipStreamSynchronize(s));
@@ -2270,16 +1827,8 @@ extern "C" int ze_chain_logprobs_batch(ze_engine* e, const int32_t* seqs, int n,
     const int* h_ids = e->xl_host + 3 * (size_t)n + 2 * rows;
     const float* h_tlp = reinterpret_cast<const float*>(e->xl_host + 3 * (size_t)n + 2 * rows + rows * stride);
     for (int i = 0; i < n; ++i) {
-        int m = e->xl_host[3 * i];
         const bool finished = e->xl_host[3 * i + 1] != 0;
-        for (int t = 0; t < m; ++t) {  // trim at the first EOS, as ze_chain_tokens
-            bool is_eos = false;
-            for (int k = 0; k < c.n_eos; ++k) is_eos |= h_tok[(size_t)i * cap + t] == c.eos_token_ids[k];
-            if (is_eos && finished) {
-                m = t + 1;
-                break;
-            }
-        }
+        const int m = finished ? trim_at_eos(c, h_tok + (size_t)i * cap, e->xl_host[3 * i]) : e->xl_host[3 * i];  // (as ze_chain_tokens)
         memcpy(out_logprobs + (size_t)i * cap, h_lp + (size_t)i * cap, (size_t)m * sizeof(float));
         if (stride) {
             memcpy(out_top_ids + (size_t)i * cap * stride, h_ids + (size_t)i * cap * stride, (size_t)m * stride * sizeof(int));
@@ -2294,7 +1843,7 @@ extern "C" int ze_chain_logprobs(ze_engine* e, int seq, float* out_logprobs, int
                                  int cap, int* n_out, int* top_n, void* stream) {
     ZE_TRY(check_seq(e, seq));
     if (!out_logprobs || !n_out || cap < 0) return ze_fail(e, ZE_ERR_INVALID, "null argument");
-    const int tn = e->lp_host[seq];
+    const int tn = e->req.lp_host[seq];
     if (tn < 0) return ze_fail(e, ZE_ERR_INVALID, "the chain has no log-probability request (ze_seq_set_logprobs)");
     if (top_n) *top_n = tn;
     const int32_t sq = seq;
