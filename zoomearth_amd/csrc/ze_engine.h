@@ -353,4 +353,27 @@ float ze_penalty_of(const ze_engine* e, const ze_gen_params* p, int seq);
 ze_sample_opts ze_sample_opts_of(ze_engine* e, const ze_gen_params* p, int slot, bool batch = false);
 // n = 0: the single-chain step of chain `seq`; else the batched step of n chains
 ze_step_key ze_step_key_of(const ze_engine* e, int n, int seq, float penalty, int ignore_eos, const ze_sample_opts& so);
+
+// ---- the launch sites of the forward passes (ze_forward.hip) that the profilers (ze_profile.hip) time: a projection's launcher is
+// chosen in these functions only, so a profiler cannot launch anything but what the pass launches
+enum { ZE_PROJ_QKV = 0, ZE_PROJ_O = 1, ZE_PROJ_GATE_UP = 2, ZE_PROJ_DOWN = 3 };
+enum { ZE_NORM_IN = 0, ZE_NORM_POST = 1, ZE_NORM_FINAL = 2 };
+// prefill: projection `which` of layer L on `rows` rows into out; norm = false: on the normalised rows the last pass left
+void prefill_projection(ze_engine* e, const ze_text_layer& L, int which, int rows, bool norm, bf16_t* out, int ldo, hipStream_t s);
+// single-chain decode: the cleared GEMV arguments with the weight (the FP8 copy too on a quantised engine), N, K, x and D set
+ze_gemv_args gemv_args_of(const ze_engine* e, const ze_linear& lin, int N, int K, const bf16_t* x);
+ze_linear lm_head_linear(const ze_engine* e, bool decode);
+// batched decode: one launch kind each for the n chains of e->bseq; a projection returns whether it streamed FP8 weights
+void batch_norm(ze_engine* e, int li, int n, int which, hipStream_t s);
+bool batch_qkv(ze_engine* e, int li, int n, hipStream_t s);  // with the rope / KV-append launch where that is not fused
+void batch_attention(ze_engine* e, int li, int n, hipStream_t s);
+bool batch_o(ze_engine* e, int li, int n, hipStream_t s);
+bool batch_gate_up(ze_engine* e, int li, int n, hipStream_t s);
+bool batch_down(ze_engine* e, int li, int n, hipStream_t s);
+bool batch_lm_head(ze_engine* e, int li, int n, hipStream_t s);
+// what a batched step sets up before its launches
+int ensure_fragments(ze_engine* e, hipStream_t s);
+void sync_prefix(ze_engine* e, const int32_t* seqs, int n, hipStream_t s);
+void upload_mates(ze_engine* e, const int32_t* seqs, int n, hipStream_t s);
+void set_live_parts(ze_engine* e, const int32_t* seqs, int n, int steps);
 #pragma GCC visibility pop

@@ -356,7 +356,7 @@ static void prefix_source_gone(ze_engine* e, int seq, int keep) {
 }
 // Before a batched decode step is enqueued on `s`: the device words of ITS chains follow the host's (the one place pfx_dev is
 // written, on the one stream that reads it)
-static void sync_prefix(ze_engine* e, const int32_t* seqs, int n, hipStream_t s) {
+void sync_prefix(ze_engine* e, const int32_t* seqs, int n, hipStream_t s) {
     int idx[64], val[64], m = 0;
     for (int i = 0; i < n; ++i) {
         const int q = seqs[i];
@@ -593,19 +593,167 @@ static void note_split(ze_engine* e, int seq, const int32_t* ids, int len, int p
         }
 }
 
-// RMSNorm + the projection behind it, on `rows` prefill rows of e->th.  With FP8 activations on a quantised engine the row
-// goes out as E4M3 bytes + one scale and the product runs on the block-scaled FP8 MFMA against the FP8 weight rows
+// RMSNorm (norm_w non-null) + the projection behind it, on `rows` prefill rows of e->th.  With FP8 activations on a quantised
+// engine the row goes out as E4M3 bytes + one scale and the product runs on the block-scaled FP8 MFMA against the FP8 weight rows
 // (k_gemm_ring_mx: the values of the fake-quantised bf16 path, another summation order; ze_tune knob 12 = 1 keeps that path).
+// norm_w null (the profilers): the same GEMM on the rows the last pass left in e->ty / e->ty8p.
 static void prefill_norm_gemm(ze_engine* e, const bf16_t* norm_w, const ze_linear& lin, const bf16_t* bias, int epi, bf16_t* out,
                               int ldo, int rows, int N, hipStream_t s) {
     const ze_config& c = e->cfg;
     const int H = c.hidden;
     if (e->fp8_act && lin.w8 && ze_gemv_knobs[12] != 1 && H % 128 == 0 && H >= 256 && lin.ld8 % 16 == 0) {
-        ze_launch_rmsnorm(e->th, H, norm_w, e->ty, H, rows, H, c.rms_eps, s, 0, 3, e->ty8p, e->ty8p_scale);
+        if (norm_w) ze_launch_rmsnorm(e->th, H, norm_w, e->ty, H, rows, H, c.rms_eps, s, 0, 3, e->ty8p, e->ty8p_scale);
         if (ze_launch_gemm_mx(epi, e->ty8p, H, e->ty8p_scale, lin.w8, lin.ld8, lin.scale8, bias, out, ldo, rows, N, H, s)) return;
     }
-    ze_launch_rmsnorm(e->th, H, norm_w, e->ty, H, rows, H, c.rms_eps, s, 0, e->fp8_act ? 1 : 0);
+    if (norm_w) ze_launch_rmsnorm(e->th, H, norm_w, e->ty, H, rows, H, c.rms_eps, s, 0, e->fp8_act ? 1 : 0);
     ze_launch_gemm(epi, e->ty, H, lin.w, lin.ld, bias, nullptr, 0, out, ldo, nullptr, rows, N, H, s, e->prefill_ws());
+}
+
+// Projection `which` (ZE_PROJ_*) of layer L on `rows` prefill rows, into out (leading dimension ldo): the ONE place a prefill
+// projection is launched.  The pass gives norm = true and, for o and down, the residual stream itself (e->th, in place); a profiler
+// gives norm = false and scratch rows, so that the residual stream is read, never written.
+void prefill_projection(ze_engine* e, const ze_text_layer& L, int which, int rows, bool norm, bf16_t* out, int ldo, hipStream_t s) {
+    const int H = e->cfg.hidden, nq = e->cfg.heads * e->head_dim, nqkv = nq + 2 * e->cfg.kv_heads * e->head_dim, ip = e->text_ipad;
+    switch (which) {
+        case ZE_PROJ_QKV:
+            prefill_norm_gemm(e, norm ? L.in_norm : nullptr, L.qkv, L.qkv.bias, ZE_EPI_NONE, out, ldo, rows, nqkv, s);
+            break;
+        case ZE_PROJ_O:
+            ze_launch_gemm(ZE_EPI_RESIDUAL, e->to, nq, L.o.w, L.o.ld, nullptr, e->th, H, out, ldo, nullptr, rows, H, nq, s, e->prefill_ws());
+            break;
+        case ZE_PROJ_GATE_UP:
+            prefill_norm_gemm(e, norm ? L.post_norm : nullptr, L.gate_up, nullptr, ZE_EPI_SWIGLU, out, ldo, rows, 2 * ip, s);
+            break;
+        default:
+            ze_launch_gemm(ZE_EPI_RESIDUAL, e->ta, ip, L.down.w, L.down.ld, nullptr, e->th, H, out, ldo, nullptr, rows, H, ip, s, e->prefill_ws());
+            break;
+    }
+}
+
+// query rows per attention tile: 128 -- two query tiles per wave, half the LDS fragment reads per MFMA -- on the LDS-DMA
+// staging form of the kernel (no staging registers: 248 VGPRs, two workgroups per CU; with register staging the same tile
+// needs 280 and lost: 120.5 against 116.9 ms per pass pair).  16-chain pass pair: register-staged 64-row tiles 107.0 ms,
+// DMA 64-row 105.3, DMA 128-row 104.3.  ze_tune knob 1 = 9: 64-row tiles, 7: the register-staged form.  Same bits either way.
+static int prefill_bq() { return (ze_gemv_knobs[1] == 9 || ze_gemv_knobs[1] == 7) ? 64 : ZE_FA_BQ_LONG; }
+
+// How a prefill pass addresses the KV cache: one chain appends behind its own `past` rows (no aux tables), a batch of chains
+// goes through (chain slot, cache position) per row and (chain slot, position offset) per attention tile.
+struct prefill_kv {
+    int slot;             // K/V base of layer li: e->kc(li, slot) / e->vc(li, slot)
+    int past;
+    const int* row_aux;   // null: the single-chain form of the M-RoPE / KV-append kernel
+    const int* tile_aux;  // null: the single-chain form of the flash kernel
+    size_t seq_stride;
+    int n_tiles;
+    int rope_rows;        // rows of the pass's position table (ze_fa_rope::T)
+};
+
+// The decoder layers of a prefill pass over `rows` rows of e->th (tokens embedded, e->tpos / e->ttiles and the aux tables staged):
+// norm + qkv, M-RoPE + KV append, flash attention, o, norm + gate/up, down.
+static void prefill_layers(ze_engine* e, int rows, const prefill_kv& kv, hipStream_t s) {
+    const ze_config& c = e->cfg;
+    const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nqkv = nq + 2 * c.kv_heads * hd;
+    const float scale = 1.0f / sqrtf((float)hd);
+    const int bq = prefill_bq();
+    // the queries' M-RoPE inside the flash kernel (k_mrope_kv_vec then moves K and V only: a fifth of its rows); ze_tune knob 22 = 1:
+    // the two-launch form of rounds 1-5 (the same bits: tests/test_gpu_model.py)
+    const bool q_in_flash = hd == 128 && ze_mrope_vec_ok != 0 && ze_gemv_knobs[22] != 1;
+    const ze_fa_rope rope = q_in_flash ? ze_fa_rope{e->cosT, e->sinT, e->tpos, c.mrope_section[0], c.mrope_section[0] + c.mrope_section[1], kv.rope_rows}
+                                       : ze_fa_rope{nullptr, nullptr, nullptr, 0, 0, 0};
+    for (int li = 0; li < c.layers; ++li) {
+        const ze_text_layer& L = e->tl[li];
+        bf16_t *k = e->kc(li, kv.slot), *v = e->vc(li, kv.slot);
+        prefill_projection(e, L, ZE_PROJ_QKV, rows, true, e->tqkv, nqkv, s);
+        ze_launch_mrope_kv(e->tqkv, rows, c.heads, c.kv_heads, hd, e->cosT, e->sinT, e->tpos, e->axis_of, k, v, c.max_ctx, kv.past,
+                           kv.row_aux, kv.seq_stride, s, q_in_flash ? 1 : 0);
+        ze_launch_flash_attn(hd, 1, e->tqkv, nqkv, hd, k, hd, c.max_ctx * hd, v, hd, c.max_ctx * hd, e->to, nq, hd, e->ttiles, kv.n_tiles,
+                             c.heads, c.heads / c.kv_heads, scale, kv.past, s, kv.tile_aux, kv.seq_stride, bq, 0, rope);
+        prefill_projection(e, L, ZE_PROJ_O, rows, true, e->th, H, s);
+        prefill_projection(e, L, ZE_PROJ_GATE_UP, rows, true, e->ta, e->text_ipad, s);
+        prefill_projection(e, L, ZE_PROJ_DOWN, rows, true, e->th, H, s);
+    }
+}
+
+// the lm_head as a ze_linear: the bf16 rows (the embedding table when tied) and, for the decode step of a quantised engine with an
+// untied head, its FP8 copy.  The prefill paths read the bf16 rows whatever the engine.
+ze_linear lm_head_linear(const ze_engine* e, bool decode) {
+    ze_linear l;
+    l.w = e->lm_head;
+    l.ld = e->cfg.hidden;
+    if (decode) {
+        l.w8 = e->lm_head8.w8;
+        l.scale8 = e->lm_head8.scale8;
+        l.ld8 = e->lm_head8.ld8;
+    }
+    return l;
+}
+
+// the fields every launch of the single-chain GEMV family shares; the caller adds its norm, bias, epilogue targets and extras
+ze_gemv_args gemv_args_of(const ze_engine* e, const ze_linear& lin, int N, int K, const bf16_t* x) {
+    ze_gemv_args a;
+    memset(&a, 0, sizeof(a));
+    a.W = lin.w;
+    a.ldw = lin.ld;
+    if (e->fp8_ready && lin.w8) {
+        a.W8 = lin.w8;
+        a.scale8 = lin.scale8;
+        a.ldw8 = lin.ld8;
+    }
+    a.N = N;
+    a.K = K;
+    a.x = x;
+    a.D = e->head_dim;
+    return a;
+}
+
+// Final norm + lm_head on the rows x[0..n) into out[0..n) (logits_to_keep = 1, HF:...:1386-1387): the weight matrix streamed once
+// per EIGHT rows (ze_gemv_logits.hip), one kernel whatever n -- the first token does not depend on how the chain was prefilled;
+// a shape that kernel does not cover takes the single-chain GEMV per row.
+static void prefill_logits(ze_engine* e, const bf16_t* const* x, float* const* out, int n, hipStream_t s) {
+    const ze_config& c = e->cfg;
+    if (ze_launch_logits_rows(e->lm_head, c.hidden, c.vocab, c.hidden, e->final_norm, c.rms_eps, x, out, n, s)) return;
+    for (int i = 0; i < n; ++i) {
+        ze_gemv_args a = gemv_args_of(e, lm_head_linear(e, false), c.vocab, c.hidden, x[i]);
+        a.norm_w = e->final_norm;
+        a.eps = c.rms_eps;
+        a.out_f32 = out[i];
+        ze_launch_gemv(ZE_GV_LOGITS, a, s);
+    }
+}
+
+// One chain's `len` rows of a prefill pass of `total` rows, from row `row0`, into the pinned staging: ids (an image token becomes
+// -1 - its feature row, counted on in `img`) and the three position rows.
+static int stage_chain(ze_engine* e, const int32_t* ids, const int32_t* position_ids, int len, int row0, int total, int* src, int* pos,
+                       int& img) {
+    const ze_config& c = e->cfg;
+    for (int t = row0; t < row0 + len; ++t) {
+        const int id = ids[t];
+        if (id < 0 || id >= c.vocab) return ze_fail(e, ZE_ERR_INVALID, "token id out of range");
+        src[t] = (id == c.image_token_id) ? -1 - img++ : id;
+        for (int a = 0; a < 3; ++a) {
+            const int p = position_ids[(size_t)a * total + t];
+            if (p < 0 || p >= e->max_pos) return ze_fail(e, ZE_ERR_INVALID, "position id out of range");
+            pos[(size_t)a * total + t] = p;
+        }
+    }
+    return ZE_OK;
+}
+
+// the attention tiles of a chain's rows [row0, row0 + len) behind `past` cached rows; returns the new tile count
+static int stage_tiles(int* tiles, int nt, int row0, int len, int past) {
+    const int bq = prefill_bq();
+    for (int q0 = 0; q0 < len; q0 += bq, ++nt) {
+        tiles[4 * nt + 0] = row0 + q0;
+        tiles[4 * nt + 1] = row0 + std::min(q0 + bq, len);
+        tiles[4 * nt + 2] = 0;
+        tiles[4 * nt + 3] = past + len;
+    }
+    return nt;
+}
+
+static int image_mismatch(ze_engine* e, int tokens, int features) {
+    return ze_fail(e, ZE_ERR_MISMATCH, "Image features and image tokens do not match, tokens: " + std::to_string(tokens) +
+                                           ", features: " + std::to_string(features));
 }
 
 static int prefill_impl(ze_engine* e, int seq, const int32_t* input_ids, int len, const void* image_embeds,
@@ -618,39 +766,17 @@ static int prefill_impl(ze_engine* e, int seq, const int32_t* input_ids, int len
     if (past + len > c.max_ctx) return ze_fail(e, ZE_ERR_NOMEM, "sequence exceeds max_ctx");
     hipStream_t s = (hipStream_t)stream;
     hipSetDevice(e->device);
-    const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nkv = c.kv_heads * hd, nqkv = nq + 2 * nkv;
+    const int H = c.hidden;
 
     ZE_TRY(stage_acquire(e, e->t_staged));  // pinned staging reuse
     int* src = e->t_host_ints;
     int* pos = src + len;
     int* tiles = pos + 3 * len;
     int img = 0;
-    for (int t = 0; t < len; ++t) {
-        const int id = input_ids[t];
-        if (id < 0 || id >= c.vocab) return ze_fail(e, ZE_ERR_INVALID, "token id out of range");
-        src[t] = (id == c.image_token_id) ? -1 - img++ : id;
-        for (int a = 0; a < 3; ++a) {
-            const int p = position_ids[a * len + t];
-            if (p < 0 || p >= e->max_pos) return ze_fail(e, ZE_ERR_INVALID, "position id out of range");
-            pos[a * len + t] = p;
-        }
-    }
-    if (img != n_image_rows || (img > 0 && !image_embeds))
-        return ze_fail(e, ZE_ERR_MISMATCH, "Image features and image tokens do not match, tokens: " +
-                                               std::to_string(img) + ", features: " + std::to_string(n_image_rows));
+    ZE_TRY(stage_chain(e, input_ids, position_ids, len, 0, len, src, pos, img));
+    if (img != n_image_rows || (img > 0 && !image_embeds)) return image_mismatch(e, img, n_image_rows);
     note_split(e, seq, input_ids, len, past);
-    int nt = 0;
-    // query rows per attention tile: 128 -- two query tiles per wave, half the LDS fragment reads per MFMA -- on the LDS-DMA
-    // staging form of the kernel (no staging registers: 248 VGPRs, two workgroups per CU; with register staging the same tile
-    // needs 280 and lost: 120.5 against 116.9 ms per pass pair).  16-chain pass pair: register-staged 64-row tiles 107.0 ms,
-    // DMA 64-row 105.3, DMA 128-row 104.3.  ze_tune knob 1 = 9: 64-row tiles, 7: the register-staged form.  Same bits either way.
-    const int bq = (ze_gemv_knobs[1] == 9 || ze_gemv_knobs[1] == 7) ? 64 : ZE_FA_BQ_LONG;
-    for (int q0 = 0; q0 < len; q0 += bq, ++nt) {
-        tiles[4 * nt + 0] = q0;
-        tiles[4 * nt + 1] = std::min(q0 + bq, len);
-        tiles[4 * nt + 2] = 0;
-        tiles[4 * nt + 3] = past + len;
-    }
+    const int nt = stage_tiles(tiles, 0, 0, len, past);
     ZE_HIP(hipMemcpyAsync(e->tsrc, src, (size_t)len * sizeof(int), hipMemcpyHostToDevice, s));
     ZE_HIP(hipMemcpyAsync(e->tpos, pos, (size_t)3 * len * sizeof(int), hipMemcpyHostToDevice, s));
     ZE_HIP(hipMemcpyAsync(e->ttiles, tiles, (size_t)nt * 16, hipMemcpyHostToDevice, s));
@@ -658,42 +784,11 @@ static int prefill_impl(ze_engine* e, int seq, const int32_t* input_ids, int len
 
     const int th = ze_timer_begin(e, 2, s);
     ze_launch_embed_rows(e->tsrc, e->embed, (const bf16_t*)image_embeds, e->th, len, H, s);
-    const float scale = 1.0f / sqrtf((float)hd);
-    // the queries' M-RoPE inside the flash kernel (k_mrope_kv_vec then moves K and V only: a fifth of its rows); ze_tune knob 22 = 1:
-    // the two-launch form of rounds 1-5 (the same bits: tests/test_gpu_model.py)
-    const bool q_in_flash = hd == 128 && ze_mrope_vec_ok != 0 && ze_gemv_knobs[22] != 1;
-    for (int li = 0; li < c.layers; ++li) {
-        const ze_text_layer& L = e->tl[li];
-        prefill_norm_gemm(e, L.in_norm, L.qkv, L.qkv.bias, ZE_EPI_NONE, e->tqkv, nqkv, len, nqkv, s);
-        ze_launch_mrope_kv(e->tqkv, len, c.heads, c.kv_heads, hd, e->cosT, e->sinT, e->tpos, e->axis_of,
-                           e->kc(li, seq), e->vc(li, seq), c.max_ctx, past, nullptr, 0, s, q_in_flash ? 1 : 0);
-        ze_launch_flash_attn(hd, 1, e->tqkv, nqkv, hd, e->kc(li, seq), hd, c.max_ctx * hd, e->vc(li, seq), hd,
-                             c.max_ctx * hd, e->to, nq, hd, e->ttiles, nt, c.heads, c.heads / c.kv_heads, scale, past,
-                             s, nullptr, 0, bq, 0, q_in_flash ? ze_fa_rope{e->cosT, e->sinT, e->tpos, c.mrope_section[0], c.mrope_section[0] + c.mrope_section[1], len} : ze_fa_rope{nullptr, nullptr, nullptr, 0, 0, 0});
-        ze_launch_gemm(ZE_EPI_RESIDUAL, e->to, nq, L.o.w, L.o.ld, nullptr, e->th, H, e->th, H, nullptr, len, H, nq, s, e->prefill_ws());
-        prefill_norm_gemm(e, L.post_norm, L.gate_up, nullptr, ZE_EPI_SWIGLU, e->ta, e->text_ipad, len, 2 * e->text_ipad, s);
-        ze_launch_gemm(ZE_EPI_RESIDUAL, e->ta, e->text_ipad, L.down.w, L.down.ld, nullptr, e->th, H, e->th, H, nullptr,
-                       len, H, e->text_ipad, s, e->prefill_ws());
-    }
-    // last position: final norm fused into the lm_head stream (logits_to_keep = 1, HF:...:1386-1387) -- the kernel of the
-    // batched pass with one chain, so the first token does not depend on how the chain was prefilled
+    prefill_layers(e, len, prefill_kv{seq, past, nullptr, nullptr, 0, nt, len}, s);
     {
         const bf16_t* xr = e->th + (size_t)(len - 1) * H;
         float* lo = e->dlogits + (size_t)seq * c.vocab;
-        if (!ze_launch_logits_rows(e->lm_head, H, c.vocab, H, e->final_norm, c.rms_eps, &xr, &lo, 1, s)) {
-            ze_gemv_args a;
-            memset(&a, 0, sizeof(a));
-            a.W = e->lm_head;
-            a.ldw = H;
-            a.N = c.vocab;
-            a.K = H;
-            a.x = xr;
-            a.norm_w = e->final_norm;
-            a.eps = c.rms_eps;
-            a.out_f32 = lo;
-            a.D = hd;
-            ze_launch_gemv(ZE_GV_LOGITS, a, s);
-        }
+        prefill_logits(e, &xr, &lo, 1, s);
     }
     if (out_logps && len > 1) {
         // every position: final norm, lm_head GEMM in row chunks (bf16 logits as HF's lm_head gives them), then the
@@ -745,7 +840,7 @@ extern "C" int ze_prefill_batch(ze_engine* e, const int32_t* seqs, int n, const 
     const ze_config& c = e->cfg;
     hipStream_t s = (hipStream_t)stream;
     hipSetDevice(e->device);
-    const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nkv = c.kv_heads * hd, nqkv = nq + 2 * nkv;
+    const int H = c.hidden;
     int total = 0;
     for (int i = 0; i < n; ++i) {
         ZE_TRY(check_seq(e, seqs[i]));
@@ -762,50 +857,26 @@ extern "C" int ze_prefill_batch(ze_engine* e, const int32_t* seqs, int n, const 
     int* pos = src + total;
     int* row_aux = pos + 3 * total;
     int* tiles = row_aux + 2 * total;
-    int img = 0, nt = 0, row0 = 0, img_expected = 0;
-    // query rows per attention tile: 128 -- two query tiles per wave, half the LDS fragment reads per MFMA -- on the LDS-DMA
-    // staging form of the kernel (no staging registers: 248 VGPRs, two workgroups per CU; with register staging the same tile
-    // needs 280 and lost: 120.5 against 116.9 ms per pass pair).  16-chain pass pair: register-staged 64-row tiles 107.0 ms,
-    // DMA 64-row 105.3, DMA 128-row 104.3.  ze_tune knob 1 = 9: 64-row tiles, 7: the register-staged form.  Same bits either way.
-    const int bq = (ze_gemv_knobs[1] == 9 || ze_gemv_knobs[1] == 7) ? 64 : ZE_FA_BQ_LONG;
+    int img = 0, nt = 0, row0 = 0;
     std::vector<int> tile_aux;
     for (int i = 0; i < n; ++i) {
-        const int seq = seqs[i], len = lens[i], past = e->ctx_host[seq];
-        int img_chain = 0;
+        const int seq = seqs[i], len = lens[i], past = e->ctx_host[seq], img0 = img;
+        ZE_TRY(stage_chain(e, input_ids, position_ids, len, row0, total, src, pos, img));
         for (int t = 0; t < len; ++t) {
-            const int id = input_ids[row0 + t];
-            if (id < 0 || id >= c.vocab) return ze_fail(e, ZE_ERR_INVALID, "token id out of range");
-            if (id == c.image_token_id) {
-                src[row0 + t] = -1 - img++;
-                ++img_chain;
-            } else {
-                src[row0 + t] = id;
-            }
-            for (int a = 0; a < 3; ++a) {
-                const int p = position_ids[(size_t)a * total + row0 + t];
-                if (p < 0 || p >= e->max_pos) return ze_fail(e, ZE_ERR_INVALID, "position id out of range");
-                pos[(size_t)a * total + row0 + t] = p;
-            }
             row_aux[2 * (row0 + t)] = seq;
             row_aux[2 * (row0 + t) + 1] = past + t;
         }
         note_split(e, seq, input_ids + row0, len, past);
         const int want = n_image_rows ? n_image_rows[i] : 0;
-        if (img_chain != want || (img_chain > 0 && !image_embeds))
-            return ze_fail(e, ZE_ERR_MISMATCH, "Image features and image tokens do not match, tokens: " +
-                                                   std::to_string(img_chain) + ", features: " + std::to_string(want));
-        img_expected += want;
-        for (int q0 = 0; q0 < len; q0 += bq, ++nt) {
-            tiles[4 * nt + 0] = row0 + q0;
-            tiles[4 * nt + 1] = row0 + std::min(q0 + bq, len);
-            tiles[4 * nt + 2] = 0;
-            tiles[4 * nt + 3] = past + len;
+        if (img - img0 != want || (img > img0 && !image_embeds)) return image_mismatch(e, img - img0, want);
+        const int nt0 = nt;
+        nt = stage_tiles(tiles, nt, row0, len, past);
+        for (int t = nt0; t < nt; ++t) {
             tile_aux.push_back(seq);
             tile_aux.push_back(past - row0);  // key index visible to row r: <= r + (past - row0)
         }
         row0 += len;
     }
-    (void)img_expected;
     int* taux = tiles + 4 * nt;
     memcpy(taux, tile_aux.data(), tile_aux.size() * sizeof(int));
     ZE_HIP(hipMemcpyAsync(e->tsrc, src, (size_t)total * sizeof(int), hipMemcpyHostToDevice, s));
@@ -817,28 +888,8 @@ extern "C" int ze_prefill_batch(ze_engine* e, const int32_t* seqs, int n, const 
 
     const int th = ze_timer_begin(e, 2, s);
     ze_launch_embed_rows(e->tsrc, e->embed, (const bf16_t*)image_embeds, e->th, total, H, s);
-    const float scale = 1.0f / sqrtf((float)hd);
-    const size_t seq_stride = (size_t)c.kv_heads * c.max_ctx * hd;
-    // the queries' M-RoPE inside the flash kernel (k_mrope_kv_vec then moves K and V only: a fifth of its rows); ze_tune knob 22 = 1:
-    // the two-launch form of rounds 1-5 (the same bits: tests/test_gpu_model.py)
-    const bool q_in_flash = hd == 128 && ze_mrope_vec_ok != 0 && ze_gemv_knobs[22] != 1;
-    for (int li = 0; li < c.layers; ++li) {
-        const ze_text_layer& L = e->tl[li];
-        prefill_norm_gemm(e, L.in_norm, L.qkv, L.qkv.bias, ZE_EPI_NONE, e->tqkv, nqkv, total, nqkv, s);
-        ze_launch_mrope_kv(e->tqkv, total, c.heads, c.kv_heads, hd, e->cosT, e->sinT, e->tpos, e->axis_of, e->kc(li, 0),
-                           e->vc(li, 0), c.max_ctx, 0, e->trow_aux, seq_stride, s, q_in_flash ? 1 : 0);
-        ze_launch_flash_attn(hd, 1, e->tqkv, nqkv, hd, e->kc(li, 0), hd, c.max_ctx * hd, e->vc(li, 0), hd,
-                             c.max_ctx * hd, e->to, nq, hd, e->ttiles, nt, c.heads, c.heads / c.kv_heads, scale, 0, s,
-                             e->ttile_aux, seq_stride, bq, 0,
-                             q_in_flash ? ze_fa_rope{e->cosT, e->sinT, e->tpos, c.mrope_section[0], c.mrope_section[0] + c.mrope_section[1], total} : ze_fa_rope{nullptr, nullptr, nullptr, 0, 0, 0});
-        ze_launch_gemm(ZE_EPI_RESIDUAL, e->to, nq, L.o.w, L.o.ld, nullptr, e->th, H, e->th, H, nullptr, total, H, nq, s, e->prefill_ws());
-        prefill_norm_gemm(e, L.post_norm, L.gate_up, nullptr, ZE_EPI_SWIGLU, e->ta, e->text_ipad, total, 2 * e->text_ipad, s);
-        ze_launch_gemm(ZE_EPI_RESIDUAL, e->ta, e->text_ipad, L.down.w, L.down.ld, nullptr, e->th, H, e->th, H, nullptr,
-                       total, H, e->text_ipad, s, e->prefill_ws());
-    }
-    // last position of every chain: final norm + lm_head, the weight matrix streamed once per EIGHT chains (ze_gemv_logits.hip;
-    // per chain the arithmetic -- and the kernel -- of ze_prefill)
-    {
+    prefill_layers(e, total, prefill_kv{0, 0, e->trow_aux, e->ttile_aux, (size_t)c.kv_heads * c.max_ctx * e->head_dim, nt, total}, s);
+    {  // last position of every chain
         std::vector<const bf16_t*> xr(n);
         std::vector<float*> lo(n);
         row0 = 0;
@@ -847,22 +898,7 @@ extern "C" int ze_prefill_batch(ze_engine* e, const int32_t* seqs, int n, const 
             lo[i] = e->dlogits + (size_t)seqs[i] * c.vocab;
             row0 += lens[i];
         }
-        if (!ze_launch_logits_rows(e->lm_head, H, c.vocab, H, e->final_norm, c.rms_eps, xr.data(), lo.data(), n, s)) {
-            for (int i = 0; i < n; ++i) {
-                ze_gemv_args a;
-                memset(&a, 0, sizeof(a));
-                a.W = e->lm_head;
-                a.ldw = H;
-                a.N = c.vocab;
-                a.K = H;
-                a.x = xr[i];
-                a.norm_w = e->final_norm;
-                a.eps = c.rms_eps;
-                a.out_f32 = lo[i];
-                a.D = hd;
-                ze_launch_gemv(ZE_GV_LOGITS, a, s);
-            }
-        }
+        prefill_logits(e, xr.data(), lo.data(), n, s);
     }
     ze_timer_end(e, th, s);
     ZE_KCHECK();
@@ -887,19 +923,7 @@ static int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int igno
     const float scale = 1.0f / sqrtf((float)hd);
     for (int li = 0; li < c.layers; ++li) {
         const ze_text_layer& L = e->tl[li];
-        {
-        ze_gemv_args a;
-        memset(&a, 0, sizeof(a));
-        a.W = L.qkv.w;
-        a.ldw = L.qkv.ld;
-        if (e->fp8_ready) {
-            a.W8 = L.qkv.w8;
-            a.scale8 = L.qkv.scale8;
-            a.ldw8 = L.qkv.ld8;
-        }
-        a.N = nqkv;
-        a.K = H;
-        a.x = e->dh;
+        ze_gemv_args a = gemv_args_of(e, L.qkv, nqkv, H, e->dh);
         a.norm_w = L.in_norm;
         a.eps = c.rms_eps;
         a.bias = L.qkv.bias;
@@ -911,7 +935,6 @@ static int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int igno
         a.vcache = e->vc(li, seq);
         a.heads = c.heads;
         a.kv_heads = c.kv_heads;
-        a.D = hd;
         a.max_ctx = c.max_ctx;
         a.act8 = e->fp8_act ? 1 : 0;
         if (li == 0) {
@@ -921,72 +944,23 @@ static int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int igno
         ze_launch_gemv(ZE_GV_QKV_ROPE, a, s);
         ze_launch_attn_decode(e->dq, 0, e->kc(li, seq), e->vc(li, seq), 0, e->dattn, 0, st, nullptr, 1, c.heads,
                               c.kv_heads, hd, c.max_ctx, scale, e->dpartial, e->max_splits, e->atickets, s);
-        ze_gemv_args o;
-        memset(&o, 0, sizeof(o));
-        o.W = L.o.w;
-        o.ldw = L.o.ld;
-        if (e->fp8_ready) {
-            o.W8 = L.o.w8;
-            o.scale8 = L.o.scale8;
-            o.ldw8 = L.o.ld8;
-        }
-        o.N = H;
-        o.K = nq;
-        o.x = e->dattn;
+        ze_gemv_args o = gemv_args_of(e, L.o, H, nq, e->dattn);
         o.out_bf16 = e->dh;
-        o.D = hd;
         ze_launch_gemv(ZE_GV_RESIDUAL, o, s);
-        }
-        ze_gemv_args g;
-        memset(&g, 0, sizeof(g));
-        g.W = L.gate_up.w;
-        g.ldw = L.gate_up.ld;
-        if (e->fp8_ready) {
-            g.W8 = L.gate_up.w8;
-            g.scale8 = L.gate_up.scale8;
-            g.ldw8 = L.gate_up.ld8;
-        }
-        g.N = 2 * e->text_ipad;
-        g.K = H;
-        g.x = e->dh;
+        ze_gemv_args g = gemv_args_of(e, L.gate_up, 2 * e->text_ipad, H, e->dh);
         g.norm_w = L.post_norm;
         g.eps = c.rms_eps;
         g.out_bf16 = e->dact;
-        g.D = hd;
         g.act8 = e->fp8_act ? 1 : 0;
         ze_launch_gemv(ZE_GV_SWIGLU, g, s);
-        ze_gemv_args d;
-        memset(&d, 0, sizeof(d));
-        d.W = L.down.w;
-        d.ldw = L.down.ld;
-        if (e->fp8_ready) {
-            d.W8 = L.down.w8;
-            d.scale8 = L.down.scale8;
-            d.ldw8 = L.down.ld8;
-        }
-        d.N = H;
-        d.K = e->text_ipad;
-        d.x = e->dact;
+        ze_gemv_args d = gemv_args_of(e, L.down, H, e->text_ipad, e->dact);
         d.out_bf16 = e->dh;
-        d.D = hd;
         ze_launch_gemv(ZE_GV_RESIDUAL, d, s);
     }
-    ze_gemv_args a;
-    memset(&a, 0, sizeof(a));
-    a.W = e->lm_head;
-    a.ldw = H;
-    if (e->fp8_ready && e->lm_head8.w8) {
-        a.W8 = e->lm_head8.w8;
-        a.scale8 = e->lm_head8.scale8;
-        a.ldw8 = e->lm_head8.ld8;
-    }
-    a.N = c.vocab;
-    a.K = H;
-    a.x = e->dh;
+    ze_gemv_args a = gemv_args_of(e, lm_head_linear(e, true), c.vocab, H, e->dh);
     a.norm_w = e->final_norm;
     a.eps = c.rms_eps;
     a.out_f32 = e->dlogits + (size_t)seq * c.vocab;
-    a.D = hd;
     // greedy: the arg-max partials come out of the lm_head launch itself (knob 14 = 1: the separate partial kernel)
     // (a chain with a logit-adjust request keeps off it: the folded arg-max never sees the row)
     const bool folded = sample && so.temperature <= 0.f && ze_gemv_knobs[14] != 1 && !e->req.la_host[seq].on() && !e->req.tr_host[seq].bans();
@@ -1263,7 +1237,7 @@ extern "C" int ze_generate(ze_engine* e, int seq, const ze_gen_params* p, int32_
 // depend on which other chains share its steps.
 // Fragment-major copies of the wide, short-K decode projections for the batched step (see ze_engine.h).  Shapes the
 // fragment kernel does not cover (rows % 16, K % 32, K > 4096) keep wf = null and stay on the row-major launchers.
-static int ensure_fragments(ze_engine* e, hipStream_t s) {
+int ensure_fragments(ze_engine* e, hipStream_t s) {
     if (e->frag_ready) return ZE_OK;
     const ze_config& c = e->cfg;
     const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nqkv = nq + 2 * c.kv_heads * hd, ip = e->text_ipad;
@@ -1374,7 +1348,7 @@ static int ensure_fragments(ze_engine* e, hipStream_t s) {
 }
 
 // the attention grid's extent for the next `steps` decode steps of these chains: the parts of the longest context
-static void set_live_parts(ze_engine* e, const int32_t* seqs, int n, int steps) {
+void set_live_parts(ze_engine* e, const int32_t* seqs, int n, int steps) {
     int mx = 0, ml = 0;
     for (int i = 0; i < n; ++i) {
         const int c = e->ctx_host[seqs[i]] + std::max(1, steps) + 1, sp = e->split_host[seqs[i]];
@@ -1389,7 +1363,7 @@ static void set_live_parts(ze_engine* e, const int32_t* seqs, int n, int steps) 
 // read the rows below it from the same holder -- the holder itself included -- under the hints this very step uses (sync_prefix ran on
 // this stream just before): first come, first paired, in batch order (the questions of a tile sit next to each other).  Symmetric;
 // -1 = alone.  A pairing changes who computes a partial, never its bits.
-static void upload_mates(ze_engine* e, const int32_t* seqs, int n, hipStream_t s) {
+void upload_mates(ze_engine* e, const int32_t* seqs, int n, hipStream_t s) {
     std::vector<int> mate(n, -1);
     if (e->prefix_hints && ze_gemv_knobs[17] != 1) {
         std::map<long long, int> open;   // (holder, split) -> the row waiting for a partner
@@ -1459,92 +1433,150 @@ static void launch_batch_attention(ze_engine* e, int li, int n, bool frag_out, h
     }
 }
 
+// Which kernel family the projections of a batched step run on, decided here and nowhere else.
+//   fr / fl: every layer projection / the lm_head on fragment-major operands when the copy exists (ensure_fragments) and n <= 64:
+//     the norms, the attention merge and the SwiGLU epilogue then write their outputs in that layout too
+//   tiled: beyond 64 chains (no fragment kernels) the prefill tile policy for qkv / o / gate-up / lm_head (one pass over K
+//     per output tile, no split: at 256 chains qkv 12.0 against 24.7 us on the split-K streaming launcher, o 11.9 /
+//     17.7, gate/up 43.6 / 56.9, lm_head 250 / 336; tools/bench_midm.py), the streaming launcher for down (32.4 / 44.3).
+//     Every one of them sums an output's K range in an order fixed by (N, K): batch invariance within this path.
+//   a8q / a8g: FP8 activations -- the fragment path with FP8 weight fragments takes the row as FP8 fragments + a scale (fp8 x
+//     fp8 MFMA); any other path takes the same values as bf16
+struct batch_regime {
+    bool fr, tiled, a8q, a8g, fl;
+};
+// the FP8 fragment stream of a projection (quantised engine; ze_tune knob 10 = 1: the bf16 fragments)
+static bool frag8(const ze_linear& l) { return l.wf8 && ze_gemv_knobs[10] != 1; }
+static batch_regime regime_of(const ze_engine* e, int li) {
+    const ze_text_layer& L = e->tl[li];
+    batch_regime r;
+    r.fr = L.qkv.wf && !e->wide_regime() && ze_gemv_knobs[5] != 1;
+    r.tiled = e->wide_regime() && ze_gemv_knobs[13] != 1;
+    r.a8q = e->fp8_act && r.fr && frag8(L.qkv);
+    r.a8g = e->fp8_act && r.fr && frag8(L.gate_up);
+    r.fl = e->lm_head_f && !e->wide_regime() && ze_gemv_knobs[5] != 1;
+    return r;
+}
+
+// The launches of a batched decode step over n chains, one function per kind: the step is their sequence, and
+// ze_profile_batch_kernel times these very functions.  A projection returns whether it streamed FP8 weights.
+void batch_norm(ze_engine* e, int li, int n, int which, hipStream_t s) {
+    const ze_config& c = e->cfg;
+    const int H = c.hidden;
+    const batch_regime r = regime_of(e, li);
+    if (which == ZE_NORM_FINAL) {
+        ze_launch_rmsnorm(e->bh, H, e->final_norm, e->by, H, n, H, c.rms_eps, s, r.fl ? 1 : 2);
+        return;
+    }
+    const bool a8 = which == ZE_NORM_IN ? r.a8q : r.a8g;
+    ze_launch_rmsnorm(e->bh, H, which == ZE_NORM_IN ? e->tl[li].in_norm : e->tl[li].post_norm, e->by, H, n, H, c.rms_eps, s, r.fr ? 1 : 2,
+                      a8 ? 2 : (e->fp8_act ? 1 : 0), e->ty8, e->ty8_scale);
+}
+
+bool batch_qkv(ze_engine* e, int li, int n, hipStream_t s) {
+    const ze_config& c = e->cfg;
+    const int H = c.hidden, hd = e->head_dim, nqkv = (c.heads + 2 * c.kv_heads) * hd;
+    const size_t seq_stride = (size_t)c.kv_heads * c.max_ctx * hd;
+    const ze_text_layer& L = e->tl[li];
+    const batch_regime r = regime_of(e, li);
+    const ze_gemm_ws ws = e->gemm_ws();
+    if (r.fr) {  // projection + M-RoPE + KV append in one launch (the fragment copy of qkv is packed for it)
+        const bool w8 = frag8(L.qkv);
+        ze_launch_qkv_rope_oneshot(r.a8q ? (const bf16_t*)e->ty8 : e->by, w8 ? (const bf16_t*)L.qkv.wf8 : L.qkv.wf, L.qkv.bias,
+                                   e->bqkv, nqkv, n, H, c.heads, c.kv_heads, e->cosT, e->sinT, e->st_dev, e->bseq,
+                                   e->kc(li, 0), e->vc(li, 0), seq_stride, c.max_ctx, s, w8 ? L.qkv.scale8 : nullptr,
+                                   r.a8q ? e->ty8_scale : nullptr);
+        return w8;
+    }
+    // row streaming: projection + M-RoPE + KV append in ONE launch on the permuted rows (same bits as the pair of
+    // launches below; knob 13 = 2 keeps the pair, for A/B runs and the bit-equality test)
+    if (r.tiled && L.qkv.wp && ze_gemv_knobs[13] != 2) {
+        ze_launch_gemm_qkv_rope(e->by, H, L.qkv.wp, H, L.qkv.bias_p, e->qkv_epi_dev + li, e->bqkv, nqkv, n, nqkv, H, s);
+        return false;
+    }
+    if (r.tiled) ze_launch_gemm_wide(ZE_EPI_NONE, e->by, H, L.qkv.w, L.qkv.ld, L.qkv.bias, nullptr, 0, e->bqkv, nqkv, n, nqkv, H, ws, s);
+    else ze_launch_gemm_stream(ZE_EPI_NONE, e->by, H, L.qkv.w, L.qkv.ld, L.qkv.bias, nullptr, 0, e->bqkv, nqkv, n, nqkv, H, ws, s);
+    ze_launch_rope_kv_batch(e->bqkv, n, c.heads, c.kv_heads, hd, e->cosT, e->sinT, e->st_dev, e->bseq, e->kc(li, 0), e->vc(li, 0),
+                            seq_stride, c.max_ctx, s);
+    return false;
+}
+
+void batch_attention(ze_engine* e, int li, int n, hipStream_t s) { launch_batch_attention(e, li, n, regime_of(e, li).fr, s); }
+
+bool batch_o(ze_engine* e, int li, int n, hipStream_t s) {
+    const int H = e->cfg.hidden, nq = e->cfg.heads * e->head_dim;
+    const ze_text_layer& L = e->tl[li];
+    const batch_regime r = regime_of(e, li);
+    if (r.fr && ze_gemv_knobs[9] != 1) {
+        const bool w8 = frag8(L.o);
+        ze_launch_gemm_oneshot(ZE_EPI_RESIDUAL, e->bo, w8 ? (const bf16_t*)L.o.wf8 : L.o.wf, nullptr, e->bh, H, e->bh, H, n, H, nq, s,
+                               w8 ? L.o.scale8 : nullptr);
+        return w8;
+    }
+    if (r.fr) ze_launch_gemm_frag(ZE_EPI_RESIDUAL, e->bo, L.o.wf, nullptr, e->bh, H, e->bh, H, n, H, nq, s);
+    else if (r.tiled) ze_launch_gemm_wide(ZE_EPI_RESIDUAL, e->bo, nq, L.o.w, L.o.ld, nullptr, e->bh, H, e->bh, H, n, H, nq, e->gemm_ws(), s);
+    else ze_launch_gemm_stream(ZE_EPI_RESIDUAL, e->bo, nq, L.o.w, L.o.ld, nullptr, e->bh, H, e->bh, H, n, H, nq, e->gemm_ws(), s);
+    return false;
+}
+
+bool batch_gate_up(ze_engine* e, int li, int n, hipStream_t s) {
+    const int H = e->cfg.hidden, ip = e->text_ipad;
+    const ze_text_layer& L = e->tl[li];
+    const batch_regime r = regime_of(e, li);
+    if (r.fr) {
+        const bool w8 = frag8(L.gate_up);
+        ze_launch_gemm_frag(ZE_EPI_SWIGLU, r.a8g ? (const bf16_t*)e->ty8 : e->by, w8 ? (const bf16_t*)L.gate_up.wf8 : L.gate_up.wf, nullptr,
+                            nullptr, 0, e->ba, ip, n, 2 * ip, H, s, w8 ? L.gate_up.scale8 : nullptr, r.a8g ? e->ty8_scale : nullptr);
+        return w8;
+    }
+    if (r.tiled) ze_launch_gemm_wide(ZE_EPI_SWIGLU, e->by, H, L.gate_up.w, L.gate_up.ld, nullptr, nullptr, 0, e->ba, ip, n, 2 * ip, H, e->gemm_ws(), s);
+    else ze_launch_gemm_stream(ZE_EPI_SWIGLU, e->by, H, L.gate_up.w, L.gate_up.ld, nullptr, nullptr, 0, e->ba, ip, n, 2 * ip, H, e->gemm_ws(), s);
+    return false;
+}
+
+// the down projection (K = 11008) stays on the split-K ring: the fragment kernel with K split over 8 x 32
+// workgroups measured 22.6-25.3 us against 17.9 (slab reduction included in both)
+bool batch_down(ze_engine* e, int li, int n, hipStream_t s) {
+    const int H = e->cfg.hidden, ip = e->text_ipad;
+    const ze_text_layer& L = e->tl[li];
+    if (regime_of(e, li).tiled) ze_launch_gemm_wide(ZE_EPI_RESIDUAL, e->ba, ip, L.down.w, L.down.ld, nullptr, e->bh, H, e->bh, H, n, H, ip, e->gemm_ws(), s);
+    else ze_launch_gemm_stream(ZE_EPI_RESIDUAL, e->ba, ip, L.down.w, L.down.ld, nullptr, e->bh, H, e->bh, H, n, H, ip, e->gemm_ws(), s);
+    return false;
+}
+
+// (li: unused -- the regime's fl does not depend on the layer)
+bool batch_lm_head(ze_engine* e, int li, int n, hipStream_t s) {
+    const ze_config& c = e->cfg;
+    const int H = c.hidden;
+    const batch_regime r = regime_of(e, li);
+    if (r.fl) {
+        const bool w8 = frag8(e->lm_head8);
+        ze_launch_gemm_frag(ZE_EPI_F32, e->by, w8 ? (const bf16_t*)e->lm_head8.wf8 : e->lm_head_f, nullptr, nullptr, 0,
+                            (bf16_t*)e->blogits, c.vocab, n, c.vocab, H, s, w8 ? e->lm_head8.scale8 : nullptr);
+        return w8;
+    }
+    if (r.tiled)  // (one pass over K whatever the row count: batch invariance)
+        ze_launch_gemm_wide(ZE_EPI_F32, e->by, H, e->lm_head, H, nullptr, nullptr, 0, (bf16_t*)e->blogits, c.vocab, n, c.vocab, H, e->gemm_ws(), s);
+    else
+        ze_launch_gemm_stream(ZE_EPI_F32, e->by, H, e->lm_head, H, nullptr, nullptr, 0, (bf16_t*)e->blogits, c.vocab, n, c.vocab, H, e->gemm_ws(), s);
+    return false;
+}
+
 static int enqueue_decode_batch(ze_engine* e, int n, float penalty, int ignore_eos, int sample, const ze_sample_opts& so,
                                 hipStream_t s) {
     const ze_config& c = e->cfg;
-    const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nkv = c.kv_heads * hd, nqkv = nq + 2 * nkv;
-    const size_t seq_stride = (size_t)c.kv_heads * c.max_ctx * hd;
-    ze_launch_embed_tokens_batch(e->st_dev, e->bseq, n, e->embed, e->bh, H, s);
+    ze_launch_embed_tokens_batch(e->st_dev, e->bseq, n, e->embed, e->bh, c.hidden, s);
     for (int li = 0; li < c.layers; ++li) {
-        const ze_text_layer& L = e->tl[li];
-        // every projection on fragment-major operands when the copy exists (ensure_fragments) and n <= 64: the norms, the
-        // attention merge and the SwiGLU epilogue then write their outputs in that layout too
-        const bool fr = L.qkv.wf && !e->wide_regime() && ze_gemv_knobs[5] != 1;
-        const ze_gemm_ws ws = e->gemm_ws();
-        // Beyond 64 chains (no fragment kernels): the prefill tile policy for qkv / o / gate-up / lm_head (one pass over K
-        // per output tile, no split: at 256 chains qkv 12.0 against 24.7 us on the split-K streaming launcher, o 11.9 /
-        // 17.7, gate/up 43.6 / 56.9, lm_head 250 / 336; tools/bench_midm.py), the streaming launcher for down (32.4 / 44.3).
-        // Every one of them sums an output's K range in an order fixed by (N, K): batch invariance within this path.
-        const bool tiled = e->wide_regime() && ze_gemv_knobs[13] != 1;
-        // FP8 activations: the fragment path with FP8 weight fragments takes the row as FP8 fragments + a scale (fp8 x
-        // fp8 MFMA); any other path takes the same values as bf16
-        const bool a8q = e->fp8_act && fr && L.qkv.wf8 && ze_gemv_knobs[10] != 1;
-        const bool a8g = e->fp8_act && fr && L.gate_up.wf8 && ze_gemv_knobs[10] != 1;
-        ze_launch_rmsnorm(e->bh, H, L.in_norm, e->by, H, n, H, c.rms_eps, s, fr ? 1 : 2, a8q ? 2 : (e->fp8_act ? 1 : 0), e->ty8,
-                          e->ty8_scale);
-        if (fr) {  // projection + M-RoPE + KV append in one launch (the fragment copy of qkv is packed for it)
-            const bool w8 = L.qkv.wf8 && ze_gemv_knobs[10] != 1;  // FP8 fragment stream (quantised engine)
-            ze_launch_qkv_rope_oneshot(a8q ? (const bf16_t*)e->ty8 : e->by, w8 ? (const bf16_t*)L.qkv.wf8 : L.qkv.wf, L.qkv.bias,
-                                       e->bqkv, nqkv, n, H, c.heads, c.kv_heads, e->cosT, e->sinT, e->st_dev, e->bseq,
-                                       e->kc(li, 0), e->vc(li, 0), seq_stride, c.max_ctx, s, w8 ? L.qkv.scale8 : nullptr,
-                                       a8q ? e->ty8_scale : nullptr);
-        } else {
-            // row streaming: projection + M-RoPE + KV append in ONE launch on the permuted rows (same bits as the pair of
-            // launches below; knob 13 = 2 keeps the pair, for A/B runs and the bit-equality test)
-            if (tiled && L.qkv.wp && ze_gemv_knobs[13] != 2) {
-                ze_launch_gemm_qkv_rope(e->by, H, L.qkv.wp, H, L.qkv.bias_p, e->qkv_epi_dev + li, e->bqkv, nqkv, n, nqkv, H, s);
-            } else {
-                if (tiled) ze_launch_gemm_wide(ZE_EPI_NONE, e->by, H, L.qkv.w, L.qkv.ld, L.qkv.bias, nullptr, 0, e->bqkv, nqkv, n, nqkv, H, ws, s);
-                else ze_launch_gemm_stream(ZE_EPI_NONE, e->by, H, L.qkv.w, L.qkv.ld, L.qkv.bias, nullptr, 0, e->bqkv, nqkv, n, nqkv, H, ws, s);
-                ze_launch_rope_kv_batch(e->bqkv, n, c.heads, c.kv_heads, hd, e->cosT, e->sinT, e->st_dev, e->bseq, e->kc(li, 0),
-                                        e->vc(li, 0), seq_stride, c.max_ctx, s);
-            }
-        }
-        launch_batch_attention(e, li, n, fr, s);
-        if (fr && ze_gemv_knobs[9] != 1) {
-            const bool w8 = L.o.wf8 && ze_gemv_knobs[10] != 1;
-            ze_launch_gemm_oneshot(ZE_EPI_RESIDUAL, e->bo, w8 ? (const bf16_t*)L.o.wf8 : L.o.wf, nullptr, e->bh, H, e->bh, H, n, H,
-                                   nq, s, w8 ? L.o.scale8 : nullptr);
-        } else if (fr)
-            ze_launch_gemm_frag(ZE_EPI_RESIDUAL, e->bo, L.o.wf, nullptr, e->bh, H, e->bh, H, n, H, nq, s);
-        else if (tiled)
-            ze_launch_gemm_wide(ZE_EPI_RESIDUAL, e->bo, nq, L.o.w, L.o.ld, nullptr, e->bh, H, e->bh, H, n, H, nq, ws, s);
-        else
-            ze_launch_gemm_stream(ZE_EPI_RESIDUAL, e->bo, nq, L.o.w, L.o.ld, nullptr, e->bh, H, e->bh, H, n, H, nq, ws, s);
-        ze_launch_rmsnorm(e->bh, H, L.post_norm, e->by, H, n, H, c.rms_eps, s, fr ? 1 : 2, a8g ? 2 : (e->fp8_act ? 1 : 0), e->ty8,
-                          e->ty8_scale);
-        if (fr) {
-            const bool w8 = L.gate_up.wf8 && ze_gemv_knobs[10] != 1;
-            ze_launch_gemm_frag(ZE_EPI_SWIGLU, a8g ? (const bf16_t*)e->ty8 : e->by, w8 ? (const bf16_t*)L.gate_up.wf8 : L.gate_up.wf,
-                                nullptr, nullptr, 0, e->ba, e->text_ipad, n, 2 * e->text_ipad, H, s,
-                                w8 ? L.gate_up.scale8 : nullptr, a8g ? e->ty8_scale : nullptr);
-        } else if (tiled)
-            ze_launch_gemm_wide(ZE_EPI_SWIGLU, e->by, H, L.gate_up.w, L.gate_up.ld, nullptr, nullptr, 0, e->ba, e->text_ipad, n,
-                                2 * e->text_ipad, H, ws, s);
-        else
-            ze_launch_gemm_stream(ZE_EPI_SWIGLU, e->by, H, L.gate_up.w, L.gate_up.ld, nullptr, nullptr, 0, e->ba, e->text_ipad, n,
-                                  2 * e->text_ipad, H, ws, s);
-        // the down projection (K = 11008) stays on the split-K ring: the fragment kernel with K split over 8 x 32
-        // workgroups measured 22.6-25.3 us against 17.9 (slab reduction included in both)
-        if (tiled)
-            ze_launch_gemm_wide(ZE_EPI_RESIDUAL, e->ba, e->text_ipad, L.down.w, L.down.ld, nullptr, e->bh, H, e->bh, H, n, H,
-                                e->text_ipad, ws, s);
-        else
-            ze_launch_gemm_stream(ZE_EPI_RESIDUAL, e->ba, e->text_ipad, L.down.w, L.down.ld, nullptr, e->bh, H, e->bh, H, n, H,
-                                  e->text_ipad, ws, s);
+        batch_norm(e, li, n, ZE_NORM_IN, s);
+        batch_qkv(e, li, n, s);
+        batch_attention(e, li, n, s);
+        batch_o(e, li, n, s);
+        batch_norm(e, li, n, ZE_NORM_POST, s);
+        batch_gate_up(e, li, n, s);
+        batch_down(e, li, n, s);
     }
-    const bool fl = e->lm_head_f && !e->wide_regime() && ze_gemv_knobs[5] != 1;
-    ze_launch_rmsnorm(e->bh, H, e->final_norm, e->by, H, n, H, c.rms_eps, s, fl ? 1 : 2);
-    if (fl) {
-        const bool w8 = e->lm_head8.wf8 && ze_gemv_knobs[10] != 1;
-        ze_launch_gemm_frag(ZE_EPI_F32, e->by, w8 ? (const bf16_t*)e->lm_head8.wf8 : e->lm_head_f, nullptr, nullptr, 0,
-                            (bf16_t*)e->blogits, c.vocab, n, c.vocab, H, s, w8 ? e->lm_head8.scale8 : nullptr);
-    } else if (e->wide_regime() && ze_gemv_knobs[13] != 1)  // (one pass over K whatever the row count: batch invariance)
-        ze_launch_gemm_wide(ZE_EPI_F32, e->by, H, e->lm_head, H, nullptr, nullptr, 0, (bf16_t*)e->blogits, c.vocab, n, c.vocab, H,
-                            e->gemm_ws(), s);
-    else
-        ze_launch_gemm_stream(ZE_EPI_F32, e->by, H, e->lm_head, H, nullptr, nullptr, 0, (bf16_t*)e->blogits, c.vocab, n,
-                              c.vocab, H, e->gemm_ws(), s);
+    batch_norm(e, 0, n, ZE_NORM_FINAL, s);
+    batch_lm_head(e, 0, n, s);
     ze_launch_sample_batch(sample ? ze_requests_rows(e, e->blogits, e->bseq, 0, n, s) : e->blogits, c.vocab, e->seen, penalty, e->st_dev,
                            e->bseq, n, e->eos_dev, c.n_eos, c.pad_token_id, ignore_eos, 1, sample, e->out_tokens, c.max_ctx, e->bsample,
                            e->bsample + (size_t)c.max_seqs * 2 * 128, so, s);
@@ -2399,286 +2431,6 @@ extern "C" int ze_tune(int knob, int value) {
     ++ze_tune_epoch;  // captured decode steps bake the launch policy in: engines drop their graphs on the next use
     return ZE_OK;
 }
-extern "C" int ze_profile_decode_kernel(ze_engine* e, int which, int iters, float* avg_us, double* bytes_per_launch,
-                                        void* stream) {
-    if (!e || !avg_us || !bytes_per_launch || iters <= 0) return ze_fail(e, ZE_ERR_INVALID, "bad argument");
-    const ze_config& c = e->cfg;
-    hipStream_t s = (hipStream_t)stream;
-    hipSetDevice(e->device);
-    const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nqkv = nq + 2 * c.kv_heads * hd;
-    hipEvent_t a, b;
-    ZE_HIP(hipEventCreate(&a));
-    ZE_HIP(hipEventCreate(&b));
-    ZE_HIP(hipMemsetAsync(e->dh, 0, (size_t)H * 2, s));
-    ZE_HIP(hipMemsetAsync(e->dattn, 0, (size_t)nq * 2, s));
-    ZE_HIP(hipMemsetAsync(e->dact, 0, (size_t)e->text_ipad * 2, s));
-    double bytes = 0;
-    auto launch = [&](int it) {
-        const ze_text_layer& L = e->tl[it % c.layers];
-        ze_gemv_args g;
-        memset(&g, 0, sizeof(g));
-        g.D = hd;
-        // a quantised engine streams the FP8 copy (1 byte per weight + one fp32 scale per row), as its decode step does
-        auto fp8 = [&](const ze_linear& l, double rows, double cols) {
-            if (e->fp8_ready && l.w8) {
-                g.W8 = l.w8;
-                g.scale8 = l.scale8;
-                g.ldw8 = l.ld8;
-                return rows * cols + rows * 4.0;
-            }
-            return rows * cols * 2.0;
-        };
-        switch (which) {
-            case 0:
-                g.W = L.qkv.w; g.ldw = L.qkv.ld; g.N = nqkv; g.K = H; g.x = e->dh; g.norm_w = L.in_norm;
-                g.eps = c.rms_eps; g.bias = L.qkv.bias; g.out_bf16 = e->dq; g.st = e->st_dev; g.cosT = e->cosT;
-                g.sinT = e->sinT; g.kcache = e->kc(it % c.layers, 0); g.vcache = e->vc(it % c.layers, 0);
-                g.heads = c.heads; g.kv_heads = c.kv_heads; g.max_ctx = c.max_ctx;
-                bytes = fp8(L.qkv, nqkv, H);
-                ze_launch_gemv(ZE_GV_QKV_ROPE, g, s);
-                break;
-            case 1:
-                g.W = L.o.w; g.ldw = L.o.ld; g.N = H; g.K = nq; g.x = e->dattn; g.out_bf16 = e->dh;
-                bytes = fp8(L.o, H, nq);
-                ze_launch_gemv(ZE_GV_RESIDUAL, g, s);
-                break;
-            case 2:
-                g.W = L.gate_up.w; g.ldw = L.gate_up.ld; g.N = 2 * e->text_ipad; g.K = H; g.x = e->dh;
-                g.norm_w = L.post_norm; g.eps = c.rms_eps; g.out_bf16 = e->dact;
-                bytes = fp8(L.gate_up, 2.0 * c.intermediate, H);
-                ze_launch_gemv(ZE_GV_SWIGLU, g, s);
-                break;
-            case 3:
-                g.W = L.down.w; g.ldw = L.down.ld; g.N = H; g.K = e->text_ipad; g.x = e->dact; g.out_bf16 = e->dh;
-                bytes = fp8(L.down, H, c.intermediate);
-                ze_launch_gemv(ZE_GV_RESIDUAL, g, s);
-                break;
-            default:
-                g.W = e->lm_head; g.ldw = H; g.N = c.vocab; g.K = H; g.x = e->dh; g.norm_w = e->final_norm;
-                g.eps = c.rms_eps; g.out_f32 = e->dlogits;
-                bytes = fp8(e->lm_head8, c.vocab, H);
-                ze_launch_gemv(ZE_GV_LOGITS, g, s);
-                break;
-        }
-    };
-    for (int i = 0; i < std::min(iters, 4); ++i) launch(i);  // warm-up
-    ZE_HIP(hipEventRecord(a, s));
-    for (int i = 0; i < iters; ++i) launch(i);
-    ZE_HIP(hipEventRecord(b, s));
-    ZE_HIP(hipEventSynchronize(b));
-    float ms = 0.f;
-    ZE_HIP(hipEventElapsedTime(&ms, a, b));
-    hipEventDestroy(a);
-    hipEventDestroy(b);
-    ZE_KCHECK();
-    *avg_us = ms * 1000.0f / (float)iters;
-    *bytes_per_launch = bytes;
-    return ZE_OK;
-}
-
-// The kernels of the BATCHED decode step (ze_decode_batch / ze_decode_burst) at n chains (slots 0..n-1, with whatever
-// context they hold), one kind per call, cycling through the layers' real weights and KV caches, bracketed by HIP events
-// on `stream`.  which: 0 qkv, 1 o_proj, 2 gate_up (SwiGLU), 3 down, 4 lm_head, 5 decode attention, 6 RMSNorm,
-// 7 rope + KV append.  bytes_per_launch = algorithmic bytes: the weight matrix (0-4), the K/V rows of the n chains (5),
-// the activation rows read + written (6, 7).
-extern "C" int ze_profile_batch_kernel(ze_engine* e, int which, int n, int iters, float* avg_us, double* bytes_per_launch,
-                                       void* stream) {
-    if (!e || !avg_us || !bytes_per_launch || iters <= 0 || n <= 0 || n > e->cfg.max_seqs || (n > 64 && !e->wide_regime()))
-        return ze_fail(e, ZE_ERR_INVALID, "bad argument");
-    const ze_config& c = e->cfg;
-    hipStream_t s = (hipStream_t)stream;
-    hipSetDevice(e->device);
-    ZE_TRY(ensure_fragments(e, s));
-    const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nkv = c.kv_heads * hd, nqkv = nq + 2 * nkv;
-    const size_t seq_stride = (size_t)c.kv_heads * c.max_ctx * hd;
-    std::vector<int> seqs(n);
-    double kv_bytes = 0;
-    for (int i = 0; i < n; ++i) {
-        seqs[i] = i;
-        kv_bytes += (double)(std::min(e->ctx_host[i] + 1, c.max_ctx)) * nkv * 2 * 2;
-    }
-    ze_launch_set_ints(e->bseq, seqs.data(), n, s);
-    sync_prefix(e, seqs.data(), n, s);
-    upload_mates(e, seqs.data(), n, s);
-    set_live_parts(e, seqs.data(), n, 1);  // (the grid a decode step of these chains would launch)
-    double bytes = 0;
-    auto launch = [&](int it) {
-        const int li = it % c.layers;
-        const ze_text_layer& L = e->tl[li];
-        const bool fr = L.qkv.wf && !e->wide_regime() && ze_gemv_knobs[5] != 1;  // (as enqueue_decode_batch)
-        const bool tiled = e->wide_regime() && ze_gemv_knobs[13] != 1;
-        const ze_gemm_ws ws = e->gemm_ws();
-        switch (which) {
-            case 0:
-                if (fr) ze_launch_qkv_rope_oneshot(e->by, L.qkv.wf, L.qkv.bias, e->bqkv, nqkv, n, H, c.heads, c.kv_heads, e->cosT, e->sinT,
-                                                   e->st_dev, e->bseq, e->kc(li, 0), e->vc(li, 0), seq_stride, c.max_ctx, s);
-                else if (tiled && L.qkv.wp && ze_gemv_knobs[13] != 2)
-                    ze_launch_gemm_qkv_rope(e->by, H, L.qkv.wp, H, L.qkv.bias_p, e->qkv_epi_dev + li, e->bqkv, nqkv, n, nqkv, H, s);
-                else if (tiled) ze_launch_gemm_wide(ZE_EPI_NONE, e->by, H, L.qkv.w, L.qkv.ld, L.qkv.bias, nullptr, 0, e->bqkv, nqkv, n, nqkv, H, ws, s);
-                else ze_launch_gemm_stream(ZE_EPI_NONE, e->by, H, L.qkv.w, L.qkv.ld, L.qkv.bias, nullptr, 0, e->bqkv, nqkv, n, nqkv, H, ws, s);
-                bytes = (double)nqkv * H * 2;
-                break;
-            case 1:
-                if (fr && ze_gemv_knobs[9] != 1) ze_launch_gemm_oneshot(ZE_EPI_RESIDUAL, e->bo, L.o.wf, nullptr, e->bh, H, e->bh, H, n, H, nq, s);
-                else if (fr) ze_launch_gemm_frag(ZE_EPI_RESIDUAL, e->bo, L.o.wf, nullptr, e->bh, H, e->bh, H, n, H, nq, s);
-                else if (tiled) ze_launch_gemm_wide(ZE_EPI_RESIDUAL, e->bo, nq, L.o.w, L.o.ld, nullptr, e->bh, H, e->bh, H, n, H, nq, ws, s);
-                else ze_launch_gemm_stream(ZE_EPI_RESIDUAL, e->bo, nq, L.o.w, L.o.ld, nullptr, e->bh, H, e->bh, H, n, H, nq, ws, s);
-                bytes = (double)H * nq * 2;
-                break;
-            case 2:
-                if (fr) ze_launch_gemm_frag(ZE_EPI_SWIGLU, e->by, L.gate_up.wf, nullptr, nullptr, 0, e->ba, e->text_ipad, n, 2 * e->text_ipad, H, s);
-                else if (tiled) ze_launch_gemm_wide(ZE_EPI_SWIGLU, e->by, H, L.gate_up.w, L.gate_up.ld, nullptr, nullptr, 0, e->ba, e->text_ipad, n, 2 * e->text_ipad, H, ws, s);
-                else ze_launch_gemm_stream(ZE_EPI_SWIGLU, e->by, H, L.gate_up.w, L.gate_up.ld, nullptr, nullptr, 0, e->ba, e->text_ipad, n, 2 * e->text_ipad, H, ws, s);
-                bytes = 2.0 * c.intermediate * H * 2;
-                break;
-            case 3:
-                if (tiled) ze_launch_gemm_wide(ZE_EPI_RESIDUAL, e->ba, e->text_ipad, L.down.w, L.down.ld, nullptr, e->bh, H, e->bh, H, n, H, e->text_ipad, ws, s);
-                else ze_launch_gemm_stream(ZE_EPI_RESIDUAL, e->ba, e->text_ipad, L.down.w, L.down.ld, nullptr, e->bh, H, e->bh, H, n, H, e->text_ipad, ws, s);
-                bytes = (double)H * c.intermediate * 2;
-                break;
-            case 4:
-                if (e->lm_head_f && fr) ze_launch_gemm_frag(ZE_EPI_F32, e->by, e->lm_head_f, nullptr, nullptr, 0, (bf16_t*)e->blogits, c.vocab, n, c.vocab, H, s);
-                else if (tiled) ze_launch_gemm_wide(ZE_EPI_F32, e->by, H, e->lm_head, H, nullptr, nullptr, 0, (bf16_t*)e->blogits, c.vocab, n, c.vocab, H, ws, s);
-                else ze_launch_gemm_stream(ZE_EPI_F32, e->by, H, e->lm_head, H, nullptr, nullptr, 0, (bf16_t*)e->blogits, c.vocab, n, c.vocab, H, ws, s);
-                bytes = (double)c.vocab * H * 2;
-                break;
-            case 5:
-                launch_batch_attention(e, li, n, fr, s);
-                bytes = kv_bytes;
-                break;
-            case 6:
-                ze_launch_rmsnorm(e->bh, H, L.in_norm, e->by, H, n, H, c.rms_eps, s, fr ? 1 : 2);
-                bytes = (double)n * H * 2 * 2;
-                break;
-            default:
-                ze_launch_rope_kv_batch(e->bqkv, n, c.heads, c.kv_heads, hd, e->cosT, e->sinT, e->st_dev, e->bseq, e->kc(li, 0),
-                                        e->vc(li, 0), seq_stride, c.max_ctx, s);
-                bytes = (double)n * nqkv * 2 * 2;
-                break;
-        }
-    };
-    hipEvent_t a, b;
-    ZE_HIP(hipEventCreate(&a));
-    ZE_HIP(hipEventCreate(&b));
-    for (int i = 0; i < std::min(iters, 4); ++i) launch(i);  // warm-up
-    ZE_HIP(hipEventRecord(a, s));
-    for (int i = 0; i < iters; ++i) launch(i);
-    ZE_HIP(hipEventRecord(b, s));
-    ZE_HIP(hipEventSynchronize(b));
-    float ms = 0.f;
-    ZE_HIP(hipEventElapsedTime(&ms, a, b));
-    hipEventDestroy(a);
-    hipEventDestroy(b);
-    ZE_KCHECK();
-    *avg_us = ms * 1000.0f / (float)iters;
-    *bytes_per_launch = bytes;
-    return ZE_OK;
-}
-
-// The projections of a PREFILL pass, one kind per call, on the pass's own operands: the engine's layer weights in rotation and the
-// activation rows the last ze_prefill_batch / ze_prefill left in the workspace (normalised hidden rows, attention output, SwiGLU
-// output of its last layer -- rows beyond that pass hold older passes' rows or zeros), through the launcher the pass uses
-// (ze_launch_gemm: k_gemm_p8 from ~1.5 K rows on).  which: 0 qkv, 1 o_proj (+ residual), 2 gate_up (SwiGLU), 3 down (+ residual).
-// Outputs go to scratch rows (the residual stream is read, never written).  flops_per_launch = 2 x rows x N x K of the real shape.
-extern "C" int ze_profile_prefill_kernel(ze_engine* e, int which, int rows, int iters, float* avg_us, double* flops_per_launch,
-                                         void* stream) {
-    if (!e || !avg_us || !flops_per_launch || iters <= 0 || rows <= 0 || rows > e->prefill_rows || which < 0 || which > 3)
-        return ze_fail(e, ZE_ERR_INVALID, "bad argument");
-    const ze_config& c = e->cfg;
-    hipStream_t s = (hipStream_t)stream;
-    hipSetDevice(e->device);
-    const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nqkv = nq + 2 * c.kv_heads * hd, ip = e->text_ipad;
-    if (nqkv < H) return ze_fail(e, ZE_ERR_INVALID, "scratch rows too short for this shape");
-    double flops = 0;
-    auto launch = [&](int it) {
-        const ze_text_layer& L = e->tl[it % c.layers];
-        switch (which) {
-            case 0:
-                ze_launch_gemm(ZE_EPI_NONE, e->ty, H, L.qkv.w, L.qkv.ld, L.qkv.bias, nullptr, 0, e->tqkv, nqkv, nullptr, rows, nqkv, H, s, e->prefill_ws());
-                flops = 2.0 * rows * nqkv * H;
-                break;
-            case 1:
-                ze_launch_gemm(ZE_EPI_RESIDUAL, e->to, nq, L.o.w, L.o.ld, nullptr, e->th, H, e->tqkv, nqkv, nullptr, rows, H, nq, s, e->prefill_ws());
-                flops = 2.0 * rows * H * nq;
-                break;
-            case 2:
-                ze_launch_gemm(ZE_EPI_SWIGLU, e->ty, H, L.gate_up.w, L.gate_up.ld, nullptr, nullptr, 0, e->ta, ip, nullptr, rows, 2 * ip, H, s, e->prefill_ws());
-                flops = 2.0 * rows * 2.0 * c.intermediate * H;
-                break;
-            default:
-                ze_launch_gemm(ZE_EPI_RESIDUAL, e->ta, ip, L.down.w, L.down.ld, nullptr, e->th, H, e->tqkv, nqkv, nullptr, rows, H, ip, s, e->prefill_ws());
-                flops = 2.0 * rows * H * c.intermediate;
-                break;
-        }
-    };
-    hipEvent_t a, b;
-    ZE_HIP(hipEventCreate(&a));
-    ZE_HIP(hipEventCreate(&b));
-    for (int i = 0; i < std::min(iters, 3); ++i) launch(i);  // warm-up
-    ZE_HIP(hipEventRecord(a, s));
-    for (int i = 0; i < iters; ++i) launch(i);
-    ZE_HIP(hipEventRecord(b, s));
-    ZE_HIP(hipEventSynchronize(b));
-    float ms = 0.f;
-    ZE_HIP(hipEventElapsedTime(&ms, a, b));
-    hipEventDestroy(a);
-    hipEventDestroy(b);
-    ZE_KCHECK();
-    *avg_us = ms * 1000.0f / (float)iters;
-    *flops_per_launch = flops;
-    return ZE_OK;
-}
-
-// The four projections of a prefill layer in PASS ORDER (qkv, o, gate/up, down; layer after layer, as ze_prefill_batch issues them --
-// minus the norm / rope / attention launches between them), every launch bracketed by its own pair of HIP events: per-projection
-// averages under the clocks and cache state a pass gives them (twelve back-to-back launches of ONE projection run 5-9 % slower than
-// the same kernel inside a pass: rocprofv3 of the replayed pass, profiles/r06_prefill_by_shape.csv).  Operands as
-// ze_profile_prefill_kernel.  avg_us / flops: [0] qkv, [1] o, [2] gate/up, [3] down.
-extern "C" int ze_profile_prefill_layer(ze_engine* e, int rows, int layers_run, float avg_us[4], double flops[4], void* stream) {
-    if (!e || !avg_us || !flops || layers_run <= 0 || layers_run > 256 || rows <= 0 || rows > e->prefill_rows)
-        return ze_fail(e, ZE_ERR_INVALID, "bad argument");
-    const ze_config& c = e->cfg;
-    hipStream_t s = (hipStream_t)stream;
-    hipSetDevice(e->device);
-    const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nqkv = nq + 2 * c.kv_heads * hd, ip = e->text_ipad;
-    if (nqkv < H) return ze_fail(e, ZE_ERR_INVALID, "scratch rows too short for this shape");
-    auto launch = [&](int li, int which) {
-        const ze_text_layer& L = e->tl[li % c.layers];
-        switch (which) {
-            case 0: ze_launch_gemm(ZE_EPI_NONE, e->ty, H, L.qkv.w, L.qkv.ld, L.qkv.bias, nullptr, 0, e->tqkv, nqkv, nullptr, rows, nqkv, H, s, e->prefill_ws()); break;
-            case 1: ze_launch_gemm(ZE_EPI_RESIDUAL, e->to, nq, L.o.w, L.o.ld, nullptr, e->th, H, e->tqkv, nqkv, nullptr, rows, H, nq, s, e->prefill_ws()); break;
-            case 2: ze_launch_gemm(ZE_EPI_SWIGLU, e->ty, H, L.gate_up.w, L.gate_up.ld, nullptr, nullptr, 0, e->ta, ip, nullptr, rows, 2 * ip, H, s, e->prefill_ws()); break;
-            default: ze_launch_gemm(ZE_EPI_RESIDUAL, e->ta, ip, L.down.w, L.down.ld, nullptr, e->th, H, e->tqkv, nqkv, nullptr, rows, H, ip, s, e->prefill_ws()); break;
-        }
-    };
-    flops[0] = 2.0 * rows * nqkv * H;
-    flops[1] = 2.0 * rows * H * nq;
-    flops[2] = 2.0 * rows * 2.0 * c.intermediate * H;
-    flops[3] = 2.0 * rows * H * c.intermediate;
-    std::vector<hipEvent_t> ev((size_t)layers_run * 8);
-    for (auto& x : ev) ZE_HIP(hipEventCreate(&x));
-    for (int li = 0; li < 2; ++li)   // warm-up
-        for (int w = 0; w < 4; ++w) launch(li, w);
-    for (int li = 0; li < layers_run; ++li)
-        for (int w = 0; w < 4; ++w) {
-            ZE_HIP(hipEventRecord(ev[(size_t)(li * 4 + w) * 2], s));
-            launch(li, w);
-            ZE_HIP(hipEventRecord(ev[(size_t)(li * 4 + w) * 2 + 1], s));
-        }
-    ZE_HIP(hipStreamSynchronize(s));
-    double sum[4] = {0, 0, 0, 0};
-    for (int li = 0; li < layers_run; ++li)
-        for (int w = 0; w < 4; ++w) {
-            float ms = 0.f;
-            ZE_HIP(hipEventElapsedTime(&ms, ev[(size_t)(li * 4 + w) * 2], ev[(size_t)(li * 4 + w) * 2 + 1]));
-            sum[w] += ms;
-        }
-    for (auto& x : ev) hipEventDestroy(x);
-    ZE_KCHECK();
-    for (int w = 0; w < 4; ++w) avg_us[w] = (float)(sum[w] * 1000.0 / layers_run);
-    return ZE_OK;
-}
-
 // The numeric helpers every epilogue of the library shares (ze_common.h: f32_to_bf16 / pack_bf16x2 = v_cvt_pk_bf16_f32, silu_f =
 // x * v_rcp_f32(1 + v_exp_f32(-x))), alone: out[i] = bf16(x[i]) | bf16(bf16(silu(x[i])) * y[i]) << 16, out2[i] = pack(x[i], y[i]).
 extern "C" int ze_op_numeric_helpers(ze_engine* e, const float* x, const float* y, uint32_t* out, uint32_t* out2, int n, void* stream) {
