@@ -478,6 +478,52 @@ int ze_op_token_rules(ze_engine* e, const float* logits, int rows, int vocab, in
                       const int32_t* ban_offsets, const int32_t* stop_seqs, const int32_t* stop_offsets, const int32_t* min_new,
                       float* out_rows, int32_t* out_stop, void* stream);
 
+/* Guided decoding: a chain held to a format by a deterministic token automaton (replaces: vLLM's `guided_regex` / `guided_choice` of
+ * the OpenAI-compatible back-end src/eval/infer_vllm.py talks to, and HF's `prefix_allowed_tokens_fn`,
+ * HF:generation/logits_process.py PrefixConstrainedLogitsProcessor).  A GRAMMAR is shared by the chains that use it and immutable:
+ *   token_class  uint16 [vocab]               the class of every token id
+ *   trans        int16 [n_states, n_classes]  the next state, or -1 when the class is not allowed in that state
+ *   accepting    uint8 [n_states]             in an accepting state the config's EOS ids are allowed, in every other state they
+ *                                             are -inf; the class of an EOS id is never looked at
+ * (zoomearth_amd/grammar.py compiles a regular expression or a list of choices into these tables.)  ze_grammar_create validates on
+ * the host -- ZE_ERR_INVALID, the engine unchanged, for a size over a limit below, a class >= n_classes, a trans entry outside
+ * [-1, n_states), a state that is not accepting and allows no token at all (a dead end), or a 17th grammar -- copies the tables
+ * to the device and launches a kernel that derives the per-state allow bits (bit t % 32 of word t / 32 of a state covers token t; the
+ * EOS bits from accepting): the host never ships the masks.  It is off the step path and waits for `stream`.  Buffers come with the
+ * first grammar (per-slot table, the adjusted rows of ze_seq_set_logit_adjust) and with each grammar (n_states x ceil(vocab / 32) x
+ * 4 B of bits + the tables); ZE_ERR_NOMEM if that fails, and the engine stays as it was.  ze_grammar_destroy frees a grammar's id
+ * (it waits for the device); ZE_ERR_INVALID while a chain still uses it.
+ * ze_seq_set_grammar puts chain `seq` into `state` (normally 0, the start) of `grammar`; -1 clears.  Before every draw of the chain each
+ * token whose bit is clear in its state's row becomes -inf in the adjusted copy of the step's row, behind the additive terms and the
+ * bans of ze_seq_set_token_rules and before the repetition penalty, temperature, filters and the draw -- -inf commutes with all of
+ * them; greedy decoding honours it (such a chain stays off the folded arg-max).  After the token was accepted the state moves on:
+ * state = trans[state][token_class[token]].  A pad step of a finished chain, an EOS id and a token the automaton does not allow leave
+ * the state alone; the last can happen only when other requests banned every allowed id and the arg-max of an all -inf row fell on id
+ * 0, and sets the chain's `violated` word.  ze_chain_grammar_state reports both (state -1: the chain has no grammar); it waits for
+ * `stream`.  Log-probabilities keep reporting the raw row; min_new_tokens and stop records act independently; ignore_eos does not
+ * switch the mask off.  Set after the chain's prefill and before its first draw.  The values travel as kernel arguments on `stream`
+ * into a per-slot device table, so chains of different grammars, states and none share one burst and one captured graph.  Honoured
+ * by ze_generate, ze_generate_batch, ze_chain_begin and ze_decode_burst*.  Cleared wherever the sampling filter is (ze_seq_reset,
+ * ze_seq_truncate, ze_seq_copy_prefix into the slot).  While no chain of the engine has a grammar every step launches exactly what
+ * it launches without this entry. */
+#define ZE_MAX_GRAMMARS 16           /* grammars of one engine */
+#define ZE_MAX_GRAMMAR_STATES 2048   /* states of one grammar */
+#define ZE_MAX_GRAMMAR_CLASSES 4096  /* token classes of one grammar */
+int ze_grammar_create(ze_engine* e, const uint16_t* token_class, int n_classes, const int16_t* trans, int n_states,
+                      const uint8_t* accepting, int* out_grammar, void* stream);
+int ze_grammar_destroy(ze_engine* e, int grammar);
+int ze_seq_set_grammar(ze_engine* e, int seq, int grammar, int state, void* stream);
+int ze_chain_grammar_state(ze_engine* e, int seq, int* state, int* violated, void* stream);
+/* The two kernels alone on caller rows, every array on the device.  Mask: logits / out f32 [rows, ld] (0 < vocab <= the engine's,
+ * ld >= vocab, out != logits; the columns beyond vocab are left alone), states int32 [rows]; out = logits with -inf where the bit of
+ * the row's state is clear (a row whose state is -1 has no grammar and comes back identical; the row is never read, so NaN and -inf
+ * at allowed ids stay).  Advance: out_states[r] = the state after tokens[r] in states[r], or -1 when the automaton does not allow the
+ * token (an EOS id keeps an accepting state and is not allowed in any other).  Asynchronous on `stream`. */
+int ze_op_grammar_mask(ze_engine* e, int grammar, const float* logits, int rows, int vocab, int ld, const int32_t* states, float* out,
+                       void* stream);
+int ze_op_grammar_advance(ze_engine* e, int grammar, const int32_t* states, const int32_t* tokens, int rows, int32_t* out_states,
+                          void* stream);
+
 /* FP8 decode weights (BASELINE.json configs[4], "fp8 weights"): quantises the decoder's linear layers (and an untied
  * lm_head) to OCP E4M3 with one power-of-two scale per output row, REPLACES the bf16 copies by the dequantised
  * values (exactly representable) so that prefill and decode compute with identical weights, and switches the batch-1

@@ -151,6 +151,13 @@ _SIGS = {
     "ze_seq_set_token_rules": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int,
                                          C.POINTER(C.c_int32), C.c_int, _P]),
     "ze_op_token_rules": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ze_grammar_create": (C.c_int, [_P, C.POINTER(C.c_uint16), C.c_int, C.POINTER(C.c_int16), C.c_int, C.POINTER(C.c_uint8),
+                                    C.POINTER(C.c_int), _P]),
+    "ze_grammar_destroy": (C.c_int, [_P, C.c_int]),
+    "ze_seq_set_grammar": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    "ze_chain_grammar_state": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "ze_op_grammar_mask": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "ze_op_grammar_advance": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P]),
     "ze_weights_quantize_fp8": (C.c_int, [_P, _P]),
     "ze_set_fp8_activations": (C.c_int, [_P, C.c_int]),
     "ze_op_quantize_fp8": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),

@@ -64,10 +64,10 @@ struct ze_step_key {
     unsigned tune_epoch = 0;                   // single-chain step only (the batched graphs are flushed when the epoch changes)
     int live_parts = 0, live_parts_long = 0;   // batched step only: the attention grids' extents
     int sampling_bits = 0;                     // bit 0 = sampling filters, bit 1 = per-chain sampling table, bit 2 = ... with a draw
-    int lp_mode = 0, la_mode = 0, tr_mode = 0;
+    int lp_mode = 0, la_mode = 0, tr_mode = 0, gr_mode = 0;
     auto tied() const {
         return std::tie(n, penalty, ignore_eos, temperature, seed, tune_epoch, live_parts, live_parts_long, sampling_bits, lp_mode, la_mode,
-                        tr_mode);
+                        tr_mode, gr_mode);
     }
     bool operator==(const ze_step_key& o) const { return tied() == o.tied(); }
     bool operator<(const ze_step_key& o) const { return tied() < o.tied(); }
@@ -149,6 +149,26 @@ struct ze_requests {
     // (of a single-chain step: by THAT chain's request)
     int tr_mode(int seq) const { return tr_host[seq].on() ? (int)tr_host[seq].bans() | (int)tr_host[seq].stops() << 1 | (tr_ctx != nullptr) << 2 : 0; }
     ze_token_rule_bufs tr_bufs() const { return ze_token_rule_bufs{tr_dev, tr_stop, tr_ban, tr_ctx}; }
+    // Guided decoding (ze_grammar_create / ze_seq_set_grammar): gr_tab holds the engine's grammars -- `block` one allocation with the
+    // allow bits and the three tables of a grammar, null = a free id, users = slots set to it (ze_grammar_destroy refuses while > 0);
+    // gr_host is the truth per slot (the grammar id, -1 = none), gr_dev the per-slot table the kernels read (ZE_GR_WORDS ints per
+    // slot, all zero = off; the state lives there alone, moved by the advance pass), gr_desc the grammars as the kernels see them;
+    // n_grammar = slots with a grammar.  While it is 0 no step launches anything for them.  gr_dev and gr_desc (and the adjusted
+    // rows la_rows) come with the first grammar.
+    struct grammar_host {
+        void* block = nullptr;
+        int n_states = 0, n_classes = 0, users = 0;
+    };
+    grammar_host gr_tab[ZE_MAX_GRAMMARS];
+    std::vector<int> gr_host;
+    int n_grammar = 0;
+    int* gr_dev = nullptr;
+    ze_grammar_dev* gr_desc = nullptr;
+    // what a captured step must have been captured with: 1 = the mask pass (on the adjusted copy) and the advance pass
+    int gr_mode() const { return n_grammar > 0; }
+    // (of a single-chain step: by THAT chain's request)
+    int gr_mode(int seq) const { return gr_host[seq] >= 0; }
+    ze_grammar_bufs gr_bufs() const { return ze_grammar_bufs{gr_dev, gr_desc}; }
 };
 
 struct ze_engine {
@@ -342,8 +362,8 @@ void ze_requests_clear(ze_engine* e, int seq, hipStream_t s);
 // The rows the sampler of a step reads: the step's own while no chain of it has a request (the step then launches what it always
 // did), else their adjusted copy.  seq_ids = null: the one chain `slot0`, whose row `logits` is.
 const float* ze_requests_rows(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s);
-// after the token of a step was accepted: log-probability entries, then token counts, then stop records -- each only for chains
-// that asked (ze_requests_logprobs: the first of the three alone)
+// after the token of a step was accepted: log-probability entries, then token counts, then stop records, then the grammar's
+// state -- each only for chains that asked (ze_requests_logprobs: the first of the three alone)
 void ze_requests_logprobs(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s);
 void ze_requests_after_token(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s);
 int ze_check_filter(ze_engine* e, int top_k, float top_p, float min_p);

@@ -962,8 +962,9 @@ static int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int igno
     a.eps = c.rms_eps;
     a.out_f32 = e->dlogits + (size_t)seq * c.vocab;
     // greedy: the arg-max partials come out of the lm_head launch itself (knob 14 = 1: the separate partial kernel)
-    // (a chain with a logit-adjust request keeps off it: the folded arg-max never sees the row)
-    const bool folded = sample && so.temperature <= 0.f && ze_gemv_knobs[14] != 1 && !e->req.la_host[seq].on() && !e->req.tr_host[seq].bans();
+    // (a chain with a logit-adjust request, bans or a grammar keeps off it: the folded arg-max never sees the row)
+    const bool folded = sample && so.temperature <= 0.f && ze_gemv_knobs[14] != 1 && !e->req.la_host[seq].on() && !e->req.tr_host[seq].bans() &&
+                        e->req.gr_host[seq] < 0;
     if (folded) {
         a.seen = e->seen + (size_t)seq * c.vocab;
         a.penalty = penalty;

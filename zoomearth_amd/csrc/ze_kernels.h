@@ -423,4 +423,35 @@ void ze_launch_chain_token_stop(ze_seq_dev* st, const int* seq_ids, int slot0, i
                                 const int* out_tokens, int max_ctx, hipStream_t s);
 void ze_launch_set_token_rules(int* table, int slot, int ngram, int n_stop_ints, int n_stop_words, int n_ban_ints, int n_ban_words,
                                int n_context, hipStream_t s);
+// ---- guided decoding (ze_grammar.hip)
+#define ZE_GR_WORDS 4  // ints per slot of the request table: grammar id + 1 (0 = none), state, violated, done
+// one grammar on the device: token_class [vocab], trans [n_states, n_classes] (-1 = not allowed), accepting [n_states], and the
+// allow bits the build kernel derives from them, [n_states, words] with words = ceil(vocab / 32)
+struct ze_grammar_dev {
+    const uint16_t* token_class = nullptr;
+    const int16_t* trans = nullptr;
+    const uint8_t* accepting = nullptr;
+    const uint32_t* allow = nullptr;
+    int n_states = 0, n_classes = 0, words = 0, pad = 0;
+};
+// the engine's per-slot request table and its grammars (null until the first grammar)
+struct ze_grammar_bufs {
+    int* table = nullptr;                       // [slots, ZE_GR_WORDS]
+    const ze_grammar_dev* grammars = nullptr;   // [ZE_MAX_GRAMMARS]
+};
+void ze_launch_grammar_build(const ze_grammar_dev& g, int vocab, const int* eos_ids, int n_eos, uint32_t* allow, hipStream_t s);
+// unit forms, everything on the device: -inf into rows [n, ld] in place where the bit of states[r] is clear (a state outside
+// [0, n_states) leaves its row alone); out_states[r] = the state after tokens[r] in states[r], or -1
+void ze_launch_grammar_mask(float* rows, int n, int vocab, int ld, const ze_grammar_dev& g, const int* states, hipStream_t s);
+void ze_launch_grammar_advance(int n, int vocab, const ze_grammar_dev& g, const int* states, const int* tokens, const int* eos_ids,
+                               int n_eos, int* out_states, hipStream_t s);
+// chain forms: row b is chain slot seq_ids ? seq_ids[b] : slot0.  Mask pass before the sampler of a step, on the rows it reads
+// ([n, vocab]); chains without a grammar and finished chains are left alone.  Advance pass after the token was accepted: the
+// slot's state moves on, or its violated word is set (pad steps of a finished chain move nothing).
+void ze_launch_chain_grammar_mask(float* rows, int vocab, ze_seq_dev* st, const int* seq_ids, int slot0, int n, const ze_grammar_bufs& gr,
+                                  hipStream_t s);
+void ze_launch_chain_grammar_advance(ze_seq_dev* st, const int* seq_ids, int slot0, int n, const ze_grammar_bufs& gr, int vocab,
+                                     const int* eos_ids, int n_eos, const int* out_tokens, int max_ctx, hipStream_t s);
+void ze_launch_set_grammar(int* table, int slot, int grammar, int state, hipStream_t s);
+void ze_launch_set_grammar_desc(ze_grammar_dev* grammars, int id, const ze_grammar_dev& g, hipStream_t s);
 void ze_launch_numeric_helpers(const float* x, const float* y, uint32_t* out, uint32_t* out2, int n, hipStream_t s);

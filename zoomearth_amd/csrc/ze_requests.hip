@@ -1,6 +1,6 @@
 // Per-chain requests of the engine (ze_requests in ze_engine.h): the setters of the C ABI, what a decode step launches for the
 // chains that asked, the sampling options of a launch, and the key of a captured step.  Host code only: the kernels live in
-// ze_sample*.hip, ze_logprobs.hip, ze_logit_adjust.hip and ze_token_rules.hip.
+// ze_sample*.hip, ze_logprobs.hip, ze_logit_adjust.hip, ze_token_rules.hip and ze_grammar.hip.
 #include <cmath>
 
 #include <initializer_list>
@@ -51,15 +51,18 @@ int ze_requests_create(ze_engine* e) {
     chk(dev_alloc(e, &q.la_dev, (size_t)c.max_seqs * ZE_LA_WORDS));  // all zero = off
     q.tr_host.assign(c.max_seqs, ze_requests::rules_host{});
     chk(dev_alloc(e, &q.tr_dev, (size_t)c.max_seqs * ZE_TR_WORDS));  // all zero = off
+    q.gr_host.assign(c.max_seqs, -1);
     return r;
 }
 
 void ze_requests_free(ze_engine* e) {
     const ze_requests& q = e->req;
     void* dev[] = {q.filt_dev, q.cut_dev, q.samp_dev, q.lp_dev, q.lp_tok, q.lp_top_ids, q.lp_top_lps, q.la_dev, q.la_bias_ids,
-                   q.la_bias_vals, q.la_rows, q.la_counts, q.tr_dev, q.tr_stop, q.tr_ban, q.tr_ctx};
+                   q.la_bias_vals, q.la_rows, q.la_counts, q.tr_dev, q.tr_stop, q.tr_ban, q.tr_ctx, q.gr_dev, q.gr_desc};
     for (void* p : dev)
         if (p) hipFree(p);
+    for (const ze_requests::grammar_host& g : q.gr_tab)
+        if (g.block) hipFree(g.block);
 }
 
 // ---- sampling filters (top-k / top-p / min-p per chain; ze_sample_filter.hip the kernel)
@@ -224,15 +227,17 @@ extern "C" int ze_seq_set_logit_adjust(ze_engine* e, int seq, float presence_pen
     return ZE_OK;
 }
 
-// A chain with bans (token rules) counts as adjusted: the ban pass writes -inf into its copy behind the adjust kernel, which
-// leaves the row of an all-zero request untouched.
+// A chain with bans (token rules) or a grammar counts as adjusted: the ban pass and the grammar's mask pass write -inf into its
+// copy behind the adjust kernel, which leaves the row of an all-zero request untouched.
 const float* ze_requests_rows(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s) {
     const ze_requests& q = e->req;
     const bool bans = seq_ids ? q.n_bans > 0 : q.tr_host[slot0].bans();
-    if (!bans && (seq_ids ? q.n_adjust == 0 : !q.la_host[slot0].on())) return logits;
+    const bool guided = seq_ids ? q.n_grammar > 0 : q.gr_host[slot0] >= 0;
+    if (!bans && !guided && (seq_ids ? q.n_adjust == 0 : !q.la_host[slot0].on())) return logits;
     float* out = seq_ids ? q.la_rows : q.la_rows + (size_t)e->cfg.max_seqs * e->cfg.vocab;
     ze_launch_chain_logit_adjust(logits, e->cfg.vocab, e->st_dev, seq_ids, slot0, n, q.la_bufs(), e->eos_dev, e->cfg.n_eos, out, s);
     if (bans) ze_launch_chain_token_ban(out, e->cfg.vocab, e->st_dev, seq_ids, slot0, n, q.tr_bufs(), e->out_tokens, e->cfg.max_ctx, s);
+    if (guided) ze_launch_chain_grammar_mask(out, e->cfg.vocab, e->st_dev, seq_ids, slot0, n, q.gr_bufs(), s);
     return out;
 }
 
@@ -304,6 +309,187 @@ extern "C" int ze_seq_set_token_rules(ze_engine* e, int seq, int no_repeat_ngram
     return ZE_OK;
 }
 
+// ---- guided decoding (ze_grammar.hip the kernels)
+static void write_grammar(ze_engine* e, int seq, int grammar, int state, hipStream_t s) {
+    ze_requests& q = e->req;
+    const int was = q.gr_host[seq];
+    if (was < 0 && grammar < 0) return;
+    if (was >= 0) q.gr_tab[was].users -= 1;
+    if (grammar >= 0) q.gr_tab[grammar].users += 1;
+    q.gr_host[seq] = grammar;
+    q.n_grammar += (int)(grammar >= 0) - (int)(was >= 0);
+    ze_launch_set_grammar(q.gr_dev, seq, grammar, state, s);
+}
+
+static int check_grammar(ze_engine* e, int grammar) {
+    if (!e) return ze_fail(e, ZE_ERR_INVALID, "null engine");
+    if (grammar < 0 || grammar >= ZE_MAX_GRAMMARS || !e->req.gr_tab[grammar].block) return ze_fail(e, ZE_ERR_NOTFOUND, "no such grammar");
+    return ZE_OK;
+}
+
+// the grammar as the kernels see it: four tables in one allocation, the 4-byte words first
+static ze_grammar_dev grammar_layout(void* block, int vocab, int n_states, int n_classes) {
+    ze_grammar_dev g;
+    g.n_states = n_states, g.n_classes = n_classes, g.words = ze_cdiv(vocab, 32);
+    char* p = (char*)block;
+    g.allow = (const uint32_t*)p;
+    p += (size_t)n_states * g.words * sizeof(uint32_t);
+    g.trans = (const int16_t*)p;
+    p += (size_t)n_states * n_classes * sizeof(int16_t);
+    g.token_class = (const uint16_t*)p;
+    p += (size_t)vocab * sizeof(uint16_t);
+    g.accepting = (const uint8_t*)p;
+    return g;
+}
+static size_t grammar_bytes(int vocab, int n_states, int n_classes) {
+    return (size_t)n_states * ze_cdiv(vocab, 32) * sizeof(uint32_t) + (size_t)n_states * n_classes * sizeof(int16_t) +
+           (size_t)vocab * sizeof(uint16_t) + (size_t)n_states;
+}
+
+extern "C" int ze_grammar_create(ze_engine* e, const uint16_t* token_class, int n_classes, const int16_t* trans, int n_states,
+                                 const uint8_t* accepting, int* out_grammar, void* stream) {
+    if (!e) return ze_fail(e, ZE_ERR_INVALID, "null engine");
+    if (!token_class || !trans || !accepting || !out_grammar) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    const ze_config& c = e->cfg;
+    if (n_states < 1 || n_states > ZE_MAX_GRAMMAR_STATES) return ze_fail(e, ZE_ERR_INVALID, "n_states must be in [1, 2048]");
+    if (n_classes < 1 || n_classes > ZE_MAX_GRAMMAR_CLASSES) return ze_fail(e, ZE_ERR_INVALID, "n_classes must be in [1, 4096]");
+    const auto is_eos = [&](int t) {
+        for (int k = 0; k < c.n_eos; ++k)
+            if (c.eos_token_ids[k] == t) return true;
+        return false;
+    };
+    std::vector<uint8_t> used(n_classes, 0);  // classes some token other than an EOS id has
+    for (int t = 0; t < c.vocab; ++t) {
+        if (is_eos(t)) continue;  // (its class is never looked at)
+        if (token_class[t] >= n_classes) return ze_fail(e, ZE_ERR_INVALID, "token class out of range");
+        used[token_class[t]] = 1;
+    }
+    for (int st = 0; st < n_states; ++st) {
+        bool open = accepting[st] != 0;
+        for (int k = 0; k < n_classes; ++k) {
+            const int to = trans[(size_t)st * n_classes + k];
+            if (to < -1 || to >= n_states) return ze_fail(e, ZE_ERR_INVALID, "transition outside [-1, n_states)");
+            open |= to >= 0 && used[k];
+        }
+        if (!open) return ze_fail(e, ZE_ERR_INVALID, "a state that is not accepting allows no token (dead end)");
+    }
+    ze_requests& q = e->req;
+    int id = 0;
+    while (id < ZE_MAX_GRAMMARS && q.gr_tab[id].block) ++id;
+    if (id == ZE_MAX_GRAMMARS) return ze_fail(e, ZE_ERR_INVALID, "an engine holds at most 16 grammars");
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (!q.gr_dev) {
+        ZE_TRY(ensure_adjusted_rows(e));
+        int* table = nullptr;
+        ze_grammar_dev* desc = nullptr;
+        const size_t entries = (size_t)c.max_seqs * ZE_GR_WORDS;
+        ZE_TRY(alloc_first_use(e, {buf_of(table, entries), buf_of(desc, (size_t)ZE_MAX_GRAMMARS)}, "hipMalloc of the grammar tables failed"));
+        // all zero = no grammar.  Once per engine, and waited for: setters on other streams may write their entries at once
+        if (hipMemset(table, 0, entries * sizeof(int)) != hipSuccess || hipMemset(desc, 0, ZE_MAX_GRAMMARS * sizeof(ze_grammar_dev)) != hipSuccess ||
+            hipStreamSynchronize(nullptr) != hipSuccess) {
+            (void)hipGetLastError();
+            hipFree(table);
+            hipFree(desc);
+            return ze_fail(e, ZE_ERR_HIP, "hipMemset of the grammar tables failed");
+        }
+        q.gr_dev = table, q.gr_desc = desc;
+    }
+    void* block = nullptr;
+    if (hipMalloc(&block, grammar_bytes(c.vocab, n_states, n_classes)) != hipSuccess) {
+        (void)hipGetLastError();
+        return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the grammar failed");
+    }
+    const ze_grammar_dev g = grammar_layout(block, c.vocab, n_states, n_classes);
+    // (a copy from pageable memory has left the caller's array when the call returns, and is ordered on the stream)
+    bool ok = hipMemcpyAsync((void*)g.trans, trans, (size_t)n_states * n_classes * sizeof(int16_t), hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync((void*)g.token_class, token_class, (size_t)c.vocab * sizeof(uint16_t), hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync((void*)g.accepting, accepting, (size_t)n_states, hipMemcpyHostToDevice, s) == hipSuccess;
+    if (ok) {
+        ze_launch_grammar_build(g, c.vocab, e->eos_dev, c.n_eos, (uint32_t*)g.allow, s);
+        ze_launch_set_grammar_desc(q.gr_desc, id, g, s);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    // off the step path: the grammar is complete before any stream may use it
+    if (hipStreamSynchronize(s) != hipSuccess) ok = false;
+    if (!ok) {
+        (void)hipGetLastError();
+        hipFree(block);
+        return ze_fail(e, ZE_ERR_HIP, "building the grammar on the device failed");
+    }
+    q.gr_tab[id].block = block, q.gr_tab[id].n_states = n_states, q.gr_tab[id].n_classes = n_classes, q.gr_tab[id].users = 0;
+    *out_grammar = id;
+    return ZE_OK;
+}
+
+extern "C" int ze_grammar_destroy(ze_engine* e, int grammar) {
+    ZE_TRY(check_grammar(e, grammar));
+    ze_requests::grammar_host& g = e->req.gr_tab[grammar];
+    if (g.users > 0) return ze_fail(e, ZE_ERR_INVALID, "the grammar is still set on a chain");
+    hipSetDevice(e->device);
+    ZE_HIP(hipDeviceSynchronize());  // steps of chains that used it may still be in flight
+    ze_launch_set_grammar_desc(e->req.gr_desc, grammar, ze_grammar_dev{}, nullptr);
+    ZE_HIP(hipStreamSynchronize(nullptr));
+    ZE_HIP(hipFree(g.block));
+    g = ze_requests::grammar_host{};
+    return ZE_OK;
+}
+
+extern "C" int ze_seq_set_grammar(ze_engine* e, int seq, int grammar, int state, void* stream) {
+    ZE_TRY(check_seq(e, seq));
+    if (grammar < -1) return ze_fail(e, ZE_ERR_INVALID, "grammar must be an id or -1 (clear)");
+    if (grammar >= 0) {
+        ZE_TRY(check_grammar(e, grammar));
+        if (state < 0 || state >= e->req.gr_tab[grammar].n_states) return ze_fail(e, ZE_ERR_INVALID, "state outside the grammar");
+    }
+    hipSetDevice(e->device);
+    write_grammar(e, seq, grammar, state, (hipStream_t)stream);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
+extern "C" int ze_chain_grammar_state(ze_engine* e, int seq, int* state, int* violated, void* stream) {
+    ZE_TRY(check_seq(e, seq));
+    if (!state || !violated) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    *state = -1, *violated = 0;
+    if (e->req.gr_host[seq] < 0) return ZE_OK;  // no grammar: state -1
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    int w[ZE_GR_WORDS];
+    ZE_HIP(hipMemcpyAsync(w, e->req.gr_dev + (size_t)seq * ZE_GR_WORDS, sizeof(w), hipMemcpyDeviceToHost, s));
+    ZE_HIP(hipStreamSynchronize(s));
+    *state = w[1], *violated = w[2];
+    return ZE_OK;
+}
+
+extern "C" int ze_op_grammar_mask(ze_engine* e, int grammar, const float* logits, int rows, int vocab, int ld, const int32_t* states, float* out,
+                                  void* stream) {
+    ZE_TRY(check_grammar(e, grammar));
+    if (!logits || !states || !out || out == logits) return ze_fail(e, ZE_ERR_INVALID, "bad grammar_mask arguments");
+    if (rows < 0 || vocab <= 0 || vocab > e->cfg.vocab || ld < vocab) return ze_fail(e, ZE_ERR_INVALID, "rows >= 0, 0 < vocab <= the engine's and ld >= vocab");
+    if (rows == 0) return ZE_OK;
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    const ze_requests::grammar_host& h = e->req.gr_tab[grammar];
+    ZE_HIP(hipMemcpy2DAsync(out, (size_t)ld * sizeof(float), logits, (size_t)ld * sizeof(float), (size_t)vocab * sizeof(float), rows,
+                            hipMemcpyDeviceToDevice, s));
+    ze_launch_grammar_mask(out, rows, vocab, ld, grammar_layout(h.block, e->cfg.vocab, h.n_states, h.n_classes), states, s);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
+extern "C" int ze_op_grammar_advance(ze_engine* e, int grammar, const int32_t* states, const int32_t* tokens, int rows, int32_t* out_states,
+                                     void* stream) {
+    ZE_TRY(check_grammar(e, grammar));
+    if (!states || !tokens || !out_states || rows < 0) return ze_fail(e, ZE_ERR_INVALID, "bad grammar_advance arguments");
+    hipSetDevice(e->device);
+    const ze_requests::grammar_host& h = e->req.gr_tab[grammar];
+    ze_launch_grammar_advance(rows, e->cfg.vocab, grammar_layout(h.block, e->cfg.vocab, h.n_states, h.n_classes), states, tokens, e->eos_dev,
+                              e->cfg.n_eos, out_states, (hipStream_t)stream);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
 // ---- all kinds together
 void ze_requests_clear(ze_engine* e, int seq, hipStream_t s) {
     const ze_requests& q = e->req;
@@ -312,6 +498,7 @@ void ze_requests_clear(ze_engine* e, int seq, hipStream_t s) {
     write_logprobs(e, seq, -1, s);
     if (q.la_host[seq].on()) write_adjust(e, seq, ze_requests::adjust_host{}, nullptr, nullptr, s);
     if (q.tr_host[seq].on()) write_rules(e, seq, ze_requests::rules_host{}, nullptr, nullptr, s);
+    if (q.gr_host[seq] >= 0) write_grammar(e, seq, -1, 0, s);
 }
 
 void ze_requests_after_token(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s) {
@@ -321,6 +508,10 @@ void ze_requests_after_token(ze_engine* e, const float* logits, const int* seq_i
     // a stop record at the tail of the generated ids finishes its chain
     if (seq_ids ? q.n_stops > 0 : q.tr_host[slot0].stops())
         ze_launch_chain_token_stop(e->st_dev, seq_ids, slot0, n, q.tr_bufs(), q.la_dev, e->out_tokens, e->cfg.max_ctx, s);
+    // the accepted token moves the chain's automaton on (last: it remembers whether the step finished the chain)
+    if (seq_ids ? q.n_grammar > 0 : q.gr_host[slot0] >= 0)
+        ze_launch_chain_grammar_advance(e->st_dev, seq_ids, slot0, n, q.gr_bufs(), e->cfg.vocab, e->eos_dev, e->cfg.n_eos, e->out_tokens,
+                                        e->cfg.max_ctx, s);
 }
 
 // ---- the sampling options of a launch
@@ -378,5 +569,6 @@ ze_step_key ze_step_key_of(const ze_engine* e, int n, int seq, float penalty, in
     k.lp_mode = q.lp_mode();
     k.la_mode = n ? q.la_mode() : q.la_mode(seq);
     k.tr_mode = n ? q.tr_mode() : q.tr_mode(seq);
+    k.gr_mode = n ? q.gr_mode() : q.gr_mode(seq);
     return k;
 }

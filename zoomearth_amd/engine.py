@@ -18,6 +18,7 @@ from .config import ModelConfig
 MAX_TOP_LOGPROBS = 20  # ZE_MAX_TOP_LOGPROBS (OpenAI's cap on top_logprobs)
 MAX_LOGIT_BIAS = 512   # ZE_MAX_LOGIT_BIAS (pairs of one chain's bias list)
 MAX_RULE_INTS, MAX_RULE_WORDS, MAX_RULE_LEN = 1024, 64, 16   # ZE_MAX_RULE_* (token rules: ints of a packed list, records, ids of a record)
+MAX_GRAMMARS = 16      # ZE_MAX_GRAMMARS (grammars of one engine; zoomearth_amd/grammar.py holds the limits of one grammar)
 
 
 def pack_records(records) -> np.ndarray:
@@ -489,6 +490,63 @@ class Engine:
                                                self._stream()))
         self._keep = d   # (the launch is asynchronous: alive until the next one)
         return out, hit
+
+    def grammar_create(self, automaton) -> int:
+        """A grammar on the device (ze_grammar_create): `automaton` has token_class uint16 [vocab], trans int16 [n_states, n_classes]
+        (-1 = not allowed) and accepting uint8 [n_states] -- what zoomearth_amd.grammar.compile_regex / compile_choice return.
+        Returns its id; at most MAX_GRAMMARS live at once.  Off the step path: it waits for the current stream."""
+        tc = np.ascontiguousarray(automaton.token_class, dtype=np.uint16).reshape(-1)
+        tr = np.ascontiguousarray(automaton.trans, dtype=np.int16)
+        ac = np.ascontiguousarray(automaton.accepting, dtype=np.uint8).reshape(-1)
+        if tr.ndim != 2 or ac.size != tr.shape[0] or tc.size != self.config.text.vocab_size:
+            raise ValueError("automaton: token_class [vocab], trans [n_states, n_classes], accepting [n_states]")
+        out = C.c_int(-1)
+        self._check(self.lib.ze_grammar_create(self.h, tc.ctypes.data_as(C.POINTER(C.c_uint16)), int(tr.shape[1]),
+                                               tr.ctypes.data_as(C.POINTER(C.c_int16)), int(tr.shape[0]),
+                                               ac.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(out), self._stream()))
+        return out.value
+
+    def grammar_destroy(self, grammar: int):
+        """Frees the grammar's id (ze_grammar_destroy); refused while a chain still uses it."""
+        self._check(self.lib.ze_grammar_destroy(self.h, int(grammar)))
+
+    def set_grammar(self, seq: int, grammar: Optional[int], state: int = 0):
+        """Chain `seq` is held to `grammar` from `state` on (ze_seq_set_grammar), on the device inside every step: before each draw
+        every token the automaton does not allow in the chain's state is -inf, after it the state moves on.  None / -1 clears.  Set
+        after the chain's prefill and before its first draw; held until the slot is reset, truncated or copied into.  Chains of
+        different grammars, states and none share bursts and graphs."""
+        self._check(self.lib.ze_seq_set_grammar(self.h, int(seq), -1 if grammar is None else int(grammar), int(state), self._stream()))
+
+    def chain_grammar_state(self, seq: int):
+        """(state, violated) of chain `seq` (ze_chain_grammar_state); state -1: the chain has no grammar.  Waits for the stream."""
+        st, vi = C.c_int(-1), C.c_int(0)
+        self._check(self.lib.ze_chain_grammar_state(self.h, int(seq), C.byref(st), C.byref(vi), self._stream()))
+        return st.value, vi.value
+
+    def op_grammar_mask(self, grammar: int, logits: torch.Tensor, states, out: Optional[torch.Tensor] = None):
+        """The mask kernel alone (ze_op_grammar_mask): logits f32 [rows, vocab] (row stride >= vocab, vocab <= the engine's), states
+        per row (-1: a row without a grammar).  Returns the rows with -inf at every id the row's state does not allow, f32 with the
+        stride of `logits` (columns beyond vocab are not written)."""
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+        rows, vocab = int(logits.shape[0]), int(logits.shape[1])
+        ld = int(logits.stride(0)) if rows > 1 else vocab
+        st = torch.from_numpy(np.broadcast_to(np.asarray(states, dtype=np.int32), (rows,)).copy()).to(self.device)
+        if out is None:
+            out = torch.empty_strided((rows, vocab), (ld, 1), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.stride(1) == 1 and (rows <= 1 or int(out.stride(0)) == ld)
+        self._check(self.lib.ze_op_grammar_mask(self.h, int(grammar), _ptr(logits), rows, vocab, ld, _ptr(st), _ptr(out), self._stream()))
+        self._keep = (st,)   # (the launch is asynchronous: alive until the next one)
+        return out
+
+    def op_grammar_advance(self, grammar: int, states, tokens) -> torch.Tensor:
+        """The advance kernel alone (ze_op_grammar_advance): int32 [rows] next states, -1 where the token is not allowed."""
+        st = torch.from_numpy(np.ascontiguousarray(states, dtype=np.int32).reshape(-1)).to(self.device)
+        tk = torch.from_numpy(np.ascontiguousarray(tokens, dtype=np.int32).reshape(-1)).to(self.device)
+        assert st.numel() == tk.numel()
+        out = torch.empty(max(st.numel(), 1), dtype=torch.int32, device=self.device)
+        self._check(self.lib.ze_op_grammar_advance(self.h, int(grammar), _ptr(st), _ptr(tk), int(st.numel()), _ptr(out), self._stream()))
+        self._keep = (st, tk)
+        return out[:st.numel()]
 
     def seq_truncate(self, seq: int, keep: int):
         self._check(self.lib.ze_seq_truncate(self.h, seq, keep, self._stream()))

@@ -307,6 +307,39 @@ class ZoomEarthForConditionalGeneration:
             return None
         return int(ngram or 0), stop, bad, strings, tokenizer
 
+    def compile_grammar(self, guided_regex=None, guided_choice=None, tokenizer=None):
+        """The token automaton (zoomearth_amd.grammar.TokenAutomaton) of vLLM's `guided_regex` (a pattern) or `guided_choice` (a list
+        of strings) against `tokenizer`'s vocabulary, padded to the model's; compiled once per pattern and tokenizer (a small memo on
+        the host).  ValueError for both at once, a wrong type, a tokenizer that is no byte-level BPE or a pattern that does not
+        compile."""
+        from . import grammar
+        if guided_regex is not None and guided_choice is not None:
+            raise ValueError("`guided_regex` and `guided_choice` exclude each other")
+        if guided_regex is not None and not isinstance(guided_regex, str):
+            raise ValueError(f"`guided_regex` has to be a string, but is {guided_regex!r}")
+        if guided_regex is None and (not isinstance(guided_choice, (list, tuple)) or not guided_choice or
+                                     any(not isinstance(c, str) or not c for c in guided_choice)):
+            raise ValueError(f"`guided_choice` has to be a non-empty list of non-empty strings, but is {guided_choice!r}")
+        tokenizer = tokenizer if tokenizer is not None else getattr(self, "tokenizer", None)
+        if tokenizer is None:
+            raise ValueError("guided decoding compiles the pattern against the vocabulary: pass the model's tokenizer to the "
+                             "`tokenizer` argument of `generate`.")
+        memo = self.__dict__.setdefault("_automata", OrderedDict())
+        key = (id(tokenizer), "regex", guided_regex) if guided_regex is not None else (id(tokenizer), "choice", tuple(guided_choice))
+        if key in memo:
+            memo.move_to_end(key)
+            return memo[key][1]
+        vkey = (id(tokenizer), "vocab")
+        if vkey not in memo:
+            memo[vkey] = (tokenizer, grammar.token_bytes(tokenizer, self.config.text.vocab_size)[:self.config.text.vocab_size])
+        vocab = memo[vkey][1]
+        memo.move_to_end(vkey)
+        auto = grammar.compile_regex(guided_regex, vocab) if guided_regex is not None else grammar.compile_choice(guided_choice, vocab)
+        memo[key] = (tokenizer, auto)   # (the tokenizer is kept alive: its id is the key)
+        while len(memo) > 33:
+            memo.popitem(last=False)
+        return auto
+
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, pixel_values=None, image_grid_thw=None,
                  mm_token_type_ids=None, image_keys=None, max_new_tokens: int = 20, do_sample: bool = False,
@@ -314,7 +347,9 @@ class ZoomEarthForConditionalGeneration:
                  ignore_eos: bool = False, logprobs: Optional[int] = None, **kw):
         """`logprobs`: None returns the id tensor; an int in 0 .. 20 returns a GenerateOutput with the log-probability of every
         generated token under the model's own distribution (the step's fp32 logits, before repetition penalty, temperature
-        and filters) and that many best alternatives per step, computed on the device inside the decode step."""
+        and filters) and that many best alternatives per step, computed on the device inside the decode step.
+        `guided_regex` / `guided_choice` (vLLM's; with `tokenizer=`): every row is held to the pattern by a token automaton on the
+        device (zoomearth_amd/grammar.py), set after each chain's prefill where the token rules are set."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not part of the ZoomEarth path (num_beams=1 everywhere)")
         if logprobs is not None:
@@ -349,10 +384,27 @@ class ZoomEarthForConditionalGeneration:
                            min_p=float(min_p or 0.0))
         adjust = self._logit_adjust_request(kw)
         rules = self._token_rules_request(kw)
+        guided = None
+        if kw.get("guided_regex") is not None or kw.get("guided_choice") is not None:
+            guided = self.compile_grammar(kw.get("guided_regex"), kw.get("guided_choice"), kw.get("tokenizer"))
         if do_sample and temperature is None:
             temperature = 1.0
         sample_kw = dict(do_sample=bool(do_sample), temperature=float(temperature or 1.0),
                          seed=int(kw.get("seed", getattr(gc, "seed", 0) or 0)), **filt_kw)
+        gid = self.engine.grammar_create(guided) if guided is not None else None
+        try:
+            return self._generate_rows(ids_cpu, mask, grids, keys, offs, pixel_values, input_ids, pen, max_new_tokens, ignore_eos, logprobs,
+                                       adjust, rules, gid, sample_kw)
+        finally:
+            if gid is not None:   # the grammar lives for the call: off the chains, then off the engine
+                for slot in range(self.engine.max_seqs):
+                    if self.engine.chain_grammar_state(slot)[0] >= 0:
+                        self.engine.set_grammar(slot, None)
+                self.engine.grammar_destroy(gid)
+
+    def _generate_rows(self, ids_cpu, mask, grids, keys, offs, pixel_values, input_ids, pen, max_new_tokens, ignore_eos, logprobs, adjust,
+                       rules, gid, sample_kw):
+        e, cfg = self.engine, self.config
         gi = 0
         outs = []
         nrows = ids_cpu.shape[0]
@@ -404,6 +456,8 @@ class ZoomEarthForConditionalGeneration:
                     e.seq_set_logit_adjust(slot, *adjust)
                 if rules is not None and (rules[0] or rules[1] or rules[2]):
                     e.set_token_rules(slot, rules[0], rules[1], rules[2], context=ids if (rules[0] or rules[2]) else None)
+                if gid is not None:
+                    e.set_grammar(slot, gid)
                 outs.append(e.generate(slot, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw))
                 if logprobs is not None:
                     lps.append(e.chain_logprobs(slot, max_new_tokens))
@@ -430,6 +484,9 @@ class ZoomEarthForConditionalGeneration:
             if rules is not None and (rules[0] or rules[1] or rules[2]):
                 for slot, _, _, _, _, ids in pending:
                     e.set_token_rules(slot, rules[0], rules[1], rules[2], context=ids if (rules[0] or rules[2]) else None)
+            if gid is not None:
+                for slot in slots:
+                    e.set_grammar(slot, gid)
             outs = e.generate_batch(slots, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw)
             if logprobs is not None:
                 lps = e.chain_logprobs_batch(slots, logprobs, max_new_tokens)

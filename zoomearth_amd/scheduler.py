@@ -58,6 +58,10 @@ class Request:
     stop_ids: Optional[list] = None
     bad_words_ids: Optional[list] = None
     no_repeat_ngram_size: Optional[int] = None
+    # guided decoding of this request (vLLM's `guided_regex`, a pattern, or `guided_choice`, a list of strings; not both): the chain
+    # is held to it by a token automaton on the device (zoomearth_amd/grammar.py); requests of different grammars and none share bursts
+    guided_regex: Optional[str] = None
+    guided_choice: Optional[list] = None
     # sampling of this request (None = the scheduler's own value): greedy or sampled, temperature, seed and repetition penalty.
     # A request that names one carries its values into the engine's per-slot table, so requests with different values share the
     # same bursts; its draws are those of a scheduler whose own values are these (same stream_id)
@@ -74,6 +78,36 @@ class Request:
     # model's own distribution at its step, and the step's best alternatives as (id, logprob), best first
     token_logprobs: List[float] = field(default_factory=list)
     top_logprobs: List[list] = field(default_factory=list)
+
+
+class GrammarCache:
+    """The compiled grammars of one engine, least recently used first: at most `capacity` (ZE_MAX_GRAMMARS) live on the device,
+    keyed by their pattern.  `acquire` returns the device id of the key's grammar -- compiling and creating it on first use, and
+    evicting the least recently used grammar no live chain uses when the engine is full -- and counts the chain as a user;
+    `release` gives the use back.  With every grammar in use, `acquire` raises: that request fails, nothing waits."""
+
+    def __init__(self, engine, compile_fn, capacity: int = 16):
+        self.engine, self.compile, self.capacity = engine, compile_fn, int(capacity)
+        self.ids = OrderedDict()   # key -> device id, least recently used first
+        self.users = {}            # key -> live chains
+
+    def acquire(self, key) -> int:
+        if key not in self.ids:
+            automaton = self.compile(key)   # (first: a pattern that does not compile evicts nothing)
+            if len(self.ids) >= self.capacity:
+                idle = next((k for k in self.ids if self.users.get(k, 0) == 0), None)
+                if idle is None:
+                    raise RuntimeError(f"all {self.capacity} grammars of the engine are in use by live chains")
+                self.engine.grammar_destroy(self.ids.pop(idle))
+                self.users.pop(idle, None)
+            self.ids[key] = self.engine.grammar_create(automaton)
+        self.ids.move_to_end(key)
+        self.users[key] = self.users.get(key, 0) + 1
+        return self.ids[key]
+
+    def release(self, key) -> None:
+        if self.users.get(key, 0) > 0:
+            self.users[key] -= 1
 
 
 class _Live:
@@ -630,6 +664,42 @@ class ChainScheduler:
             self.engine.set_token_rules(req.slot, ngram, stop, bad, context=list(prompt_ids) if (bad or ngram > 0) else None)
 
     @staticmethod
+    def _grammar_key(req):
+        regex, choice = getattr(req, "guided_regex", None), getattr(req, "guided_choice", None)
+        if regex is None and choice is None:
+            return None
+        if regex is not None and choice is not None:
+            raise ValueError("`guided_regex` and `guided_choice` exclude each other")
+        return ("regex", regex) if regex is not None else ("choice", tuple(choice) if isinstance(choice, (list, tuple)) else choice)
+
+    def _set_grammar(self, req) -> None:
+        """The request's grammar into its slot (cleared, like the filter, by the slot's reset / truncate / prefix copy), before its
+        first draw; without one nothing is launched.  Raises when the pattern does not compile or every grammar is in use."""
+        key = self._grammar_key(req)
+        if key is None:
+            return
+        if getattr(self, "grammars", None) is None:
+            def compile_key(k):
+                kw = {"guided_regex": k[1]} if k[0] == "regex" else {"guided_choice": list(k[1]) if isinstance(k[1], tuple) else k[1]}
+                return self.model.compile_grammar(tokenizer=self.processor.tokenizer, **kw)
+            from .engine import MAX_GRAMMARS
+            self.grammars = GrammarCache(self.engine, compile_key, MAX_GRAMMARS)
+        gid = self.grammars.acquire(key)
+        req._grammar_key = key
+        self.engine.set_grammar(req.slot, gid)
+
+    def _drop_grammar(self, req) -> None:
+        """The chain is over: its slot lets go of the grammar, which may be evicted from now on."""
+        key = getattr(req, "_grammar_key", None)
+        if key is not None:
+            req._grammar_key = None
+            self.grammars.release(key)
+            try:
+                self.engine.set_grammar(req.slot, None)
+            except Exception:
+                pass
+
+    @staticmethod
     def _attach_logprobs(req, lp, n: int) -> None:
         logps, ids, tlps = lp
         m = len(req.tokens)
@@ -660,6 +730,11 @@ class ChainScheduler:
             self._set_logprobs(req)
             self._set_logit_adjust(req)
             self._set_token_rules(req, ids)
+            try:
+                self._set_grammar(req)
+            except Exception as ex:   # no grammar to be had (a bad pattern, or all in use): this request fails, the round goes on
+                self._fail(req, ex)
+                continue
             self.engine.chain_begin(req.slot, self.params, req.stream_id)
             self.live[req.slot] = _Live(req, ids, keys)
             self.stats["admitted"] += 1
@@ -766,6 +841,7 @@ class ChainScheduler:
             if n is not None:
                 req.tokens = list(req.tokens[:n])
         req.text = self.processor.tokenizer.decode(req.tokens, skip_special_tokens=True).strip()
+        self._drop_grammar(req)
         n_lp = self._want_logprobs(req)
         if n_lp is not None:
             if logprobs is None:
@@ -800,6 +876,7 @@ class ChainScheduler:
 
     def _release(self, req: Request) -> None:
         if req.slot >= 0:
+            self._drop_grammar(req)
             self.parked.pop(req.slot, None)
             try:
                 self._retire_slot(req.slot)

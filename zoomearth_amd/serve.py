@@ -13,6 +13,8 @@ vLLM's `repetition_penalty` (finite, > 0; absent = the checkpoint's generation_c
 `stop` (a string or up to 4 strings), vLLM's `stop_token_ids` and `no_repeat_ngram_size` are token rules on the device: the chain
 ends in the step that completes a stop sequence (`finish_reason: "stop"`); the text is cut before a stop string, a stop token id
 is kept as an EOS is.
+vLLM's top-level `guided_regex` (a pattern) and `guided_choice` (a list of strings; not both) hold the reply to a format: a token
+automaton on the device masks every step (`zoomearth_amd/grammar.py`); a pattern that does not compile is a 400.
 `logprobs: true` (with `top_logprobs: 0..20`) adds `choices[0].logprobs.content`, one entry per completion token, from the
 decode step's own logits (the model's distribution, before repetition penalty, temperature and filters).
 Prompt: the Qwen2.5-VL chat template (`<|im_start|>role\\n ... <|im_end|>\\n`, an image item becomes
@@ -95,19 +97,24 @@ def build_prompt(messages):
 class _Parsed:
     __slots__ = ("req", "prompt", "pil_images", "max_tokens", "sample", "temperature", "seed", "future", "top_k", "top_p",
                  "min_p", "logprobs", "presence_penalty", "frequency_penalty", "logit_bias", "min_tokens", "stop", "stop_token_ids",
-                 "no_repeat_ngram_size", "repetition_penalty")
+                 "no_repeat_ngram_size", "repetition_penalty", "guided_regex", "guided_choice")
+
+    def guided(self) -> bool:
+        return self.guided_regex is not None or self.guided_choice is not None
 
     def rules(self) -> bool:
         return bool(self.stop or self.stop_token_ids or self.no_repeat_ngram_size)
 
     def adjusts(self) -> bool:
         """The request carries values generate() gives every row of a call alike: it runs alone, or through the dispatcher."""
-        return bool(self.presence_penalty or self.frequency_penalty or self.logit_bias or self.min_tokens) or self.rules()
+        return bool(self.presence_penalty or self.frequency_penalty or self.logit_bias or self.min_tokens) or self.rules() or self.guided()
 
     def adjust_kw(self, tokenizer=None) -> dict:
         """generate()'s keyword arguments of the request's logit adjustments and token rules (none when they are all off)."""
         kw = dict(presence_penalty=self.presence_penalty, frequency_penalty=self.frequency_penalty, logit_bias=self.logit_bias,
                   min_new_tokens=self.min_tokens) if self.adjusts() else {}
+        if self.guided():
+            kw.update(guided_regex=self.guided_regex, guided_choice=self.guided_choice, tokenizer=tokenizer)
         if self.rules():
             kw.update(stop_strings=list(self.stop) or None, tokenizer=tokenizer, stop_token_ids=list(self.stop_token_ids) or None,
                       no_repeat_ngram_size=self.no_repeat_ngram_size or None)
@@ -253,6 +260,21 @@ class ChatServer:
         if ng is not None and not (0 <= ng <= 16):
             raise BadRequest(f"no_repeat_ngram_size must be in [0, 16], got {ng}")
         p.no_repeat_ngram_size = int(ng or 0)
+        # vLLM's `guided_regex` (a pattern) / `guided_choice` (a list of strings): a token automaton on the device holds the chain to
+        # it (zoomearth_amd/grammar.py).  Compiled here, so that a pattern that does not compile is a 400 before anything is queued.
+        gr, gc = req.get("guided_regex"), req.get("guided_choice")
+        if gr is not None and gc is not None:
+            raise BadRequest("guided_regex and guided_choice exclude each other")
+        if gr is not None and not isinstance(gr, str):
+            raise BadRequest(f"guided_regex must be a string, got {gr!r}")
+        if gc is not None and (not isinstance(gc, list) or not gc or any(not isinstance(x, str) or not x for x in gc)):
+            raise BadRequest(f"guided_choice must be a non-empty list of non-empty strings, got {gc!r}")
+        if gr is not None or gc is not None:
+            try:
+                self.model.compile_grammar(guided_regex=gr, guided_choice=gc, tokenizer=self.processor.tokenizer)
+            except ValueError as ex:
+                raise BadRequest(f"guided decoding: {ex}") from ex
+        p.guided_regex, p.guided_choice = gr, gc
         p.future = None
         return p
 
@@ -348,7 +370,7 @@ class ChatServer:
             raise BadRequest("sampled requests are not batched")
         if any(p.adjusts() for p in batch) and len(batch) > 1:
             raise BadRequest("requests with presence_penalty / frequency_penalty / logit_bias / min_tokens / stop / stop_token_ids / "
-                             "no_repeat_ngram_size are not batched")
+                             "no_repeat_ngram_size / guided_regex / guided_choice are not batched")
         if len(batch) > self.max_batch:
             raise BadRequest(f"batch of {len(batch)} exceeds max_seqs = {self.max_batch}")
         return self._run(batch)
@@ -438,7 +460,8 @@ class ChatServer:
                                              on_error=failed, logprobs=p.logprobs, presence_penalty=p.presence_penalty,
                                              frequency_penalty=p.frequency_penalty, logit_bias=p.logit_bias,
                                              min_new_tokens=p.min_tokens, stop_ids=p.stop_records(self.processor.tokenizer),
-                                             no_repeat_ngram_size=p.no_repeat_ngram_size, **own))
+                                             no_repeat_ngram_size=p.no_repeat_ngram_size, guided_regex=p.guided_regex,
+                                             guided_choice=p.guided_choice, **own))
                     except Exception as ex:
                         failed(None, ex)
                 if sched.busy():
@@ -478,7 +501,8 @@ class ChatServer:
                                               min_p=p.min_p, logprobs=p.logprobs, presence_penalty=p.presence_penalty,
                                               frequency_penalty=p.frequency_penalty, logit_bias=p.logit_bias,
                                               min_new_tokens=p.min_tokens, stop_ids=p.stop_records(self.processor.tokenizer),
-                                              no_repeat_ngram_size=p.no_repeat_ngram_size))
+                                              no_repeat_ngram_size=p.no_repeat_ngram_size, guided_regex=p.guided_regex,
+                                              guided_choice=p.guided_choice))
                         except Exception as ex:
                             failed(None, ex)
                     try:
