@@ -440,14 +440,28 @@ def test_submit_zoom_chain_on_the_scheduler():
     assert res[2] == dict(prompt=H.stage1_prompt("Q13 ?"), output1="nothing here", output2="", error=True, bbox=None)
 
 
-def test_serve_dispatcher_admits_into_the_running_batch():
+def test_serve_dispatcher_admits_into_the_running_batch(monkeypatch):
     """The OpenAI shim's dispatcher (src/eval/infer_vllm.py:244-271 keeps up to 100 requests in flight): greedy
     requests join the running batch, each future resolves when its own chain ends, per-request max_tokens / EOS
-    trimming, sampled requests batched per sampling configuration, malformed requests rejected at submit, an engine failure
-    reaches every request of the running batch and the server recovers."""
-    from zoomearth_amd import serve
+    trimming, sampled requests on the same scheduler with their own values, malformed requests rejected at submit, an engine
+    failure reaches every request of the running batch and the server recovers."""
+    from zoomearth_amd import scheduler, serve
 
+    built = []
+
+    class Counted(ChainScheduler):
+        def __init__(self, *a, **kw):
+            built.append(self)
+            super().__init__(*a, **kw)
+
+    class SamplingStub(StubEngine):
+        def set_sampling(self, slot, do_sample=None, temperature=1.0, seed=0, repetition_penalty=1.0):
+            self.requests.append((self.chains[slot]["ids"][0], do_sample, temperature, seed, repetition_penalty))
+
+    monkeypatch.setattr(scheduler, "ChainScheduler", Counted)
     model = make_model(max_seqs=3)
+    model.engine = SamplingStub(max_seqs=3)
+    model.engine.requests = []
     model.calls = []
 
     def generate(input_ids=None, attention_mask=None, max_new_tokens=8, do_sample=False, **kw):
@@ -477,7 +491,9 @@ def test_serve_dispatcher_admits_into_the_running_batch():
             srv.submit(req("cccc", max_tokens=6, temperature=0.7, seed=9)), srv.submit(req("dd", max_tokens=4)),
             srv.submit(req("eeee")), srv.submit(req("ffff", max_tokens=2))]
     res = [f.result(timeout=10) for f in futs]
-    assert model.calls == []                                 # the sampled request ran on a scheduler too (a batch of its own kind)
+    assert model.calls == []                                 # the sampled request ran on the scheduler too: the one there is
+    assert len(built) == 1 and built[0] is srv.scheduler
+    assert model.engine.requests == [(ord("c") % 50 + 10, True, 0.7, 9, 1.0)]
     firsts = [ord(c) % 50 + 10 for c in "abcdef"]
     budgets = [5, 3, 6, 4, 1024, 2]
     for i, r in enumerate(res):

@@ -20,12 +20,13 @@ import os
 from collections import OrderedDict
 from dataclasses import dataclass
 from types import SimpleNamespace
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import processor as _processor
+from .chain_request import ChainRequest
 from .checkpoint import iter_checkpoint
 from .config import ModelConfig
 from .engine import MAX_LOGIT_BIAS, MAX_RULE_INTS, MAX_RULE_LEN, MAX_RULE_WORDS, MAX_TOP_LOGPROBS, Engine
@@ -40,6 +41,18 @@ class GenerateOutput:
     logprobs: torch.Tensor
     top_ids: torch.Tensor
     top_logprobs: torch.Tensor
+
+
+class _Rows(NamedTuple):
+    """The rows of one generate() call as the row loop reads them: ids and mask on the host, the images' grids, keys and patch-row
+    offsets in prompt order, and the caller's tensors."""
+    ids_cpu: np.ndarray
+    mask: np.ndarray
+    grids: list
+    keys: list
+    offs: np.ndarray
+    pixel_values: Optional[torch.Tensor]
+    input_ids: torch.Tensor
 
 
 class ZoomEarthForConditionalGeneration:
@@ -207,8 +220,8 @@ class ZoomEarthForConditionalGeneration:
     # ------------------------------------------------------------------ generate
     @staticmethod
     def _logit_adjust_request(kw):
-        """(presence_penalty, frequency_penalty, min_new_tokens, {id: bias}) from generate's keyword arguments, or None when all
-        are off (nothing is launched then).  HF's `min_new_tokens`, `sequence_bias` (single-token keys) and `suppress_tokens`
+        """(presence_penalty, frequency_penalty, min_new_tokens, {id: bias}) from generate's keyword arguments, all-off values when
+        nothing is asked for.  HF's `min_new_tokens`, `sequence_bias` (single-token keys) and `suppress_tokens`
         with HF's ValueErrors (MinNewTokensLengthLogitsProcessor, SequenceBiasLogitsProcessor, SuppressTokensLogitsProcessor);
         `presence_penalty`, `frequency_penalty` and `logit_bias` {id: bias} as the OpenAI API names them."""
         min_new = kw.get("min_new_tokens")
@@ -256,14 +269,12 @@ class ZoomEarthForConditionalGeneration:
         bias = {k: v for k, v in bias.items() if v != 0.0}
         if len(bias) > MAX_LOGIT_BIAS:
             raise ValueError(f"at most {MAX_LOGIT_BIAS} tokens can carry a bias, but {len(bias)} do")
-        if pens[0] == 0.0 and pens[1] == 0.0 and not min_new and not bias:
-            return None
         return pens[0], pens[1], int(min_new or 0), bias
 
     @staticmethod
     def _token_rules_request(kw):
-        """(no_repeat_ngram_size, stop records, bad-word records, stop strings, tokenizer) from generate's keyword arguments, or
-        None when all are off (nothing is launched then).  HF's `no_repeat_ngram_size`, `bad_words_ids` and `stop_strings` (with
+        """(no_repeat_ngram_size, stop records, bad-word records, stop strings) from generate's keyword arguments, all-off values
+        when nothing is asked for.  HF's `no_repeat_ngram_size`, `bad_words_ids` and `stop_strings` (with
         `tokenizer=`) with HF's ValueErrors (NoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor, GenerationMixin); vLLM's
         `stop_token_ids`."""
         def is_int(t):
@@ -303,9 +314,7 @@ class ZoomEarthForConditionalGeneration:
         for name, recs in (("stop sequences", stop), ("bad_words_ids", bad)):
             if len(recs) > MAX_RULE_WORDS or sum(1 + len(r) for r in recs) > MAX_RULE_INTS or any(len(r) > MAX_RULE_LEN for r in recs):
                 raise ValueError(f"{name}: at most {MAX_RULE_WORDS} sequences of at most {MAX_RULE_LEN} tokens, {MAX_RULE_INTS} ints packed")
-        if not ngram and not bad and not stop and not strings:
-            return None
-        return int(ngram or 0), stop, bad, strings, tokenizer
+        return int(ngram or 0), stop, bad, strings
 
     def compile_grammar(self, guided_regex=None, guided_choice=None, tokenizer=None):
         """The token automaton (zoomearth_amd.grammar.TokenAutomaton) of vLLM's `guided_regex` (a pattern) or `guided_choice` (a list
@@ -382,8 +391,11 @@ class ZoomEarthForConditionalGeneration:
             # (top_p = 0 keeps HF's min_tokens_to_keep = 1, the arg-max: the smallest positive value does the same)
             filt_kw = dict(top_k=int(top_k or 0), top_p=1.0 if top_p is None else max(float(top_p), 1e-37),
                            min_p=float(min_p or 0.0))
-        adjust = self._logit_adjust_request(kw)
-        rules = self._token_rules_request(kw)
+        presence, frequency, min_new, bias = self._logit_adjust_request(kw)
+        ngram, stop, bad, stop_strings = self._token_rules_request(kw)
+        # generate's sampling goes through gen_params and Engine.generate(**sample_kw): the chain carries none of its own, no filter
+        chain = ChainRequest(effective_penalty=float(pen), logprobs=logprobs, presence_penalty=presence, frequency_penalty=frequency,
+                             min_new_tokens=min_new, logit_bias=bias, no_repeat_ngram_size=ngram, stop_ids=stop, bad_words_ids=bad)
         guided = None
         if kw.get("guided_regex") is not None or kw.get("guided_choice") is not None:
             guided = self.compile_grammar(kw.get("guided_regex"), kw.get("guided_choice"), kw.get("tokenizer"))
@@ -393,8 +405,8 @@ class ZoomEarthForConditionalGeneration:
                          seed=int(kw.get("seed", getattr(gc, "seed", 0) or 0)), **filt_kw)
         gid = self.engine.grammar_create(guided) if guided is not None else None
         try:
-            return self._generate_rows(ids_cpu, mask, grids, keys, offs, pixel_values, input_ids, pen, max_new_tokens, ignore_eos, logprobs,
-                                       adjust, rules, gid, sample_kw)
+            return self._generate_rows(_Rows(ids_cpu, mask, grids, keys, offs, pixel_values, input_ids), chain, gid, max_new_tokens,
+                                       ignore_eos, sample_kw, stop_strings, kw.get("tokenizer"))
         finally:
             if gid is not None:   # the grammar lives for the call: off the chains, then off the engine
                 for slot in range(self.engine.max_seqs):
@@ -402,9 +414,10 @@ class ZoomEarthForConditionalGeneration:
                         self.engine.set_grammar(slot, None)
                 self.engine.grammar_destroy(gid)
 
-    def _generate_rows(self, ids_cpu, mask, grids, keys, offs, pixel_values, input_ids, pen, max_new_tokens, ignore_eos, logprobs, adjust,
-                       rules, gid, sample_kw):
+    def _generate_rows(self, rows: _Rows, chain: ChainRequest, gid, max_new_tokens, ignore_eos, sample_kw, stop_strings, tokenizer):
         e, cfg = self.engine, self.config
+        ids_cpu, mask, grids, keys, offs, pixel_values, input_ids = rows
+        pen, logprobs = chain.effective_penalty, chain.logprobs
         gi = 0
         outs = []
         nrows = ids_cpu.shape[0]
@@ -450,14 +463,7 @@ class ZoomEarthForConditionalGeneration:
             if not batched:
                 self._chains[slot] = (tuple(ids), tuple(my_keys))
                 self._chains.move_to_end(slot)
-                if logprobs is not None:
-                    e.set_logprobs(slot, logprobs)  # (the reset / truncate above cleared the slot's previous request)
-                if adjust is not None:
-                    e.seq_set_logit_adjust(slot, *adjust)
-                if rules is not None and (rules[0] or rules[1] or rules[2]):
-                    e.set_token_rules(slot, rules[0], rules[1], rules[2], context=ids if (rules[0] or rules[2]) else None)
-                if gid is not None:
-                    e.set_grammar(slot, gid)
+                chain.install(e, slot, ids, gid)  # (the reset / truncate above cleared the slot's previous request)
                 outs.append(e.generate(slot, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw))
                 if logprobs is not None:
                     lps.append(e.chain_logprobs(slot, max_new_tokens))
@@ -475,29 +481,19 @@ class ZoomEarthForConditionalGeneration:
             if pen != 1.0:
                 for slot, _, _, _, _, ids in pending:
                     e.mark_seen(slot, ids)
-            if logprobs is not None:
-                for slot in slots:
-                    e.set_logprobs(slot, logprobs)
-            if adjust is not None:
-                for slot in slots:
-                    e.seq_set_logit_adjust(slot, *adjust)
-            if rules is not None and (rules[0] or rules[1] or rules[2]):
-                for slot, _, _, _, _, ids in pending:
-                    e.set_token_rules(slot, rules[0], rules[1], rules[2], context=ids if (rules[0] or rules[2]) else None)
-            if gid is not None:
-                for slot in slots:
-                    e.set_grammar(slot, gid)
+            for slot, _, _, _, _, ids in pending:
+                chain.install(e, slot, ids, gid)
             outs = e.generate_batch(slots, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw)
             if logprobs is not None:
                 lps = e.chain_logprobs_batch(slots, logprobs, max_new_tokens)
-        if rules is not None and (rules[1] or rules[3]):
+        if chain.stop_ids or stop_strings:
             # what follows a stop is pad (HF's finished rows): the ids behind a matched stop sequence are the device's own pads;
             # a stop string is exact at text level, whatever tokenization carried it (hostloop.first_stop_cut)
             from .hostloop import first_stop_cut, first_stop_hit
-            min_new = adjust[2] if adjust is not None else 0
+            min_new = chain.min_new_tokens
             for b, t in enumerate(outs):
-                cuts = [first_stop_hit(t, rules[1], min_new)]
-                hit = first_stop_cut(rules[4], t, rules[3], min_new) if rules[3] else None
+                cuts = [first_stop_hit(t, chain.stop_ids, min_new)]
+                hit = first_stop_cut(tokenizer, t, stop_strings, min_new) if stop_strings else None
                 cuts.append(hit[0] if hit else None)
                 cuts = [n for n in cuts if n is not None]
                 if cuts:

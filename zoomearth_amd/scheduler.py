@@ -28,6 +28,8 @@ from typing import Any, Callable, List, Optional
 import numpy as np
 import torch
 
+from .chain_request import ChainRequest
+
 
 @dataclass
 class Request:
@@ -331,6 +333,7 @@ class ChainScheduler:
             self.waiting.popleft()
             last_img = self._first_image_key(req)
             try:
+                req._chain = self._resolve(req)   # once per request: every later stage of the chain's life reads it
                 inp = self.processor(text=[req.prompt], images=list(req.images) or None, return_tensors="pt")
                 ids = inp["input_ids"][0].tolist()
                 grids = inp["image_grid_thw"].tolist() if req.images else []
@@ -576,7 +579,7 @@ class ChainScheduler:
         final = [it for it in ok if it["final"]]                # (pass A: the chain is completed by pass B)
         try:
             # (a request with a repetition penalty of its own is marked by ITS value: 1.0 reads no set)
-            marked = [it for it in final if self._penalty_of(it["req"]) != 1.0]
+            marked = [it for it in final if it["req"]._chain.effective_penalty != 1.0]
             if marked:
                 # the prompts' ids into the repetition-penalty sets (cleared by the reset / truncate above): one copy and one
                 # launch for the pass, IN FRONT of it -- behind it, the next call would find its staging buffer busy until the
@@ -599,69 +602,25 @@ class ChainScheduler:
             req.n_prompt = len(ids)
             self._ready.append((req, tuple(ids), tuple(keys)))
 
-    def _samples(self, req) -> bool:
-        mode = getattr(req, "do_sample", None)
-        return self.do_sample if mode is None else bool(mode)
-
-    def _penalty_of(self, req) -> float:
-        pen = getattr(req, "repetition_penalty", None)
-        return self.penalty if pen is None else float(pen)
-
-    def _set_sampling(self, req) -> None:
-        """The request's own (greedy | temperature, seed, repetition penalty) into its slot (cleared, like the filter, by the slot's
-        reset / truncate / prefix copy), before its first draw.  Values it does not name are the scheduler's; a request that
-        names none never reaches the engine, and follows the scheduler's gen_params."""
-        named = [getattr(req, k, None) for k in ("do_sample", "temperature", "seed", "repetition_penalty")]
-        if all(v is None for v in named):
-            return
-        mode, temperature, seed, penalty = named
-        self.engine.set_sampling(req.slot, do_sample=self._samples(req),
-                                 temperature=self.temperature if temperature is None else float(temperature),
-                                 seed=self.seed if seed is None else int(seed),
-                                 repetition_penalty=self._penalty_of(req))
-
-    def _set_filter(self, req) -> None:
-        """The request's own filter into its slot (the slot's reset / truncate / prefix copy cleared the previous chain's), before
-        its first draw.  Only for a request whose effective mode is sampled."""
-        if not self._samples(req):
-            return
-        top_k = req.top_k if req.top_k is not None else self.top_k
-        top_p = req.top_p if req.top_p is not None else self.top_p
-        min_p = req.min_p if req.min_p is not None else self.min_p
-        top_k, top_p, min_p = int(top_k or 0), float(1.0 if top_p is None else top_p), float(min_p or 0.0)
-        if top_k > 0 or top_p < 1.0 or min_p > 0.0:
-            self.engine.set_sampling_filter(req.slot, top_k, top_p, min_p)
-
-    def _want_logprobs(self, req) -> Optional[int]:
-        n = getattr(req, "logprobs", None)
-        n = self.logprobs if n is None else n
-        return None if n is None else int(n)
-
-    def _set_logprobs(self, req) -> None:
-        """The request's log-probability request into its slot (cleared, like the filter, by the slot's reset / truncate / prefix
-        copy), before its first draw."""
-        n = self._want_logprobs(req)
-        if n is not None:
-            self.engine.set_logprobs(req.slot, n)
-
-    def _set_logit_adjust(self, req) -> None:
-        """The request's logit adjustments into its slot (cleared, like the filter, by the slot's reset / truncate / prefix copy),
-        before its first draw; off values launch nothing."""
-        def pick(name):
+    def _resolve(self, req) -> ChainRequest:
+        """The request's optional fields merged with the scheduler's defaults: its own value, else the scheduler's, else off.  A
+        request that names none of the four sampling values carries none (it never reaches `set_sampling` and follows the
+        scheduler's gen_params); the filter counts only for an effective sampled mode; the token rules have no defaults."""
+        def pick(name, mine=None):   # (`mine`: the scheduler's attribute where its name differs)
             v = getattr(req, name, None)
-            return getattr(self, name) if v is None else v
-        presence, frequency = float(pick("presence_penalty") or 0.0), float(pick("frequency_penalty") or 0.0)
-        bias, min_new = pick("logit_bias") or {}, int(pick("min_new_tokens") or 0)
-        if presence != 0.0 or frequency != 0.0 or bias or min_new > 0:
-            self.engine.seq_set_logit_adjust(req.slot, presence, frequency, min_new, bias)
-
-    def _set_token_rules(self, req, prompt_ids) -> None:
-        """The request's token rules into its slot (cleared, like the filter, by the slot's reset / truncate / prefix copy), before
-        its first draw, with the prompt ids as the context of the bans; without rules nothing is launched."""
-        stop, bad = list(getattr(req, "stop_ids", None) or ()), list(getattr(req, "bad_words_ids", None) or ())
-        ngram = int(getattr(req, "no_repeat_ngram_size", None) or 0)
-        if stop or bad or ngram > 0:
-            self.engine.set_token_rules(req.slot, ngram, stop, bad, context=list(prompt_ids) if (bad or ngram > 0) else None)
+            return getattr(self, mine or name) if v is None else v
+        own = any(getattr(req, k, None) is not None for k in ("do_sample", "temperature", "seed", "repetition_penalty"))
+        sampled, penalty = bool(pick("do_sample")), float(pick("repetition_penalty", "penalty"))
+        top_p, logprobs = pick("top_p"), pick("logprobs")
+        return ChainRequest(
+            sampling=(sampled, float(pick("temperature")), int(pick("seed")), penalty) if own else None,
+            sampled=sampled, effective_penalty=penalty,
+            top_k=int(pick("top_k") or 0), top_p=float(1.0 if top_p is None else top_p), min_p=float(pick("min_p") or 0.0),
+            logprobs=None if logprobs is None else int(logprobs),
+            presence_penalty=float(pick("presence_penalty") or 0.0), frequency_penalty=float(pick("frequency_penalty") or 0.0),
+            min_new_tokens=int(pick("min_new_tokens") or 0), logit_bias=pick("logit_bias") or {},
+            no_repeat_ngram_size=int(getattr(req, "no_repeat_ngram_size", None) or 0),
+            stop_ids=list(getattr(req, "stop_ids", None) or ()), bad_words_ids=list(getattr(req, "bad_words_ids", None) or ()))
 
     @staticmethod
     def _grammar_key(req):
@@ -725,11 +684,7 @@ class ChainScheduler:
                     keep_from = i
                     break
         for req, ids, keys in self._ready[:keep_from]:
-            self._set_sampling(req)
-            self._set_filter(req)
-            self._set_logprobs(req)
-            self._set_logit_adjust(req)
-            self._set_token_rules(req, ids)
+            req._chain.install(self.engine, req.slot, ids)
             try:
                 self._set_grammar(req)
             except Exception as ex:   # no grammar to be had (a bad pattern, or all in use): this request fails, the round goes on
@@ -785,11 +740,11 @@ class ChainScheduler:
             cap = max(self.live[s].req.max_new_tokens for s in out)
             toks = e.chain_tokens_batch(out, cap, stream=ds) if ds is not None else e.chain_tokens_batch(out, cap)
         lps = {}
-        want = [s for s in out if self._want_logprobs(self.live[s].req) is not None]
+        want = [s for s in out if self.live[s].req._chain.wants_logprobs]
         if len(want) > 1 and hasattr(e, "chain_logprobs_batch") and not _PER_CHAIN:   # the same for their log-probabilities
             ds = getattr(self, "_decode_stream", None)
             cap = max(self.live[s].req.max_new_tokens for s in want)
-            top = max(self._want_logprobs(self.live[s].req) for s in want)
+            top = max(self.live[s].req._chain.logprobs for s in want)
             lps = dict(zip(want, e.chain_logprobs_batch(want, top, cap, stream=ds) if ds is not None
                            else e.chain_logprobs_batch(want, top, cap)))
         for i, slot in enumerate(out):
@@ -834,20 +789,19 @@ class ChainScheduler:
         else:
             req.tokens = (self.engine.chain_tokens(slot, req.max_new_tokens, stream=ds) if ds is not None
                           else self.engine.chain_tokens(slot, req.max_new_tokens))
-        if getattr(req, "stop_ids", None):   # the ids behind a stop sequence are the pads of a finished chain
+        chain = req._chain
+        if chain.stop_ids:   # the ids behind a stop sequence are the pads of a finished chain
             from .hostloop import first_stop_hit
-            mn = getattr(req, "min_new_tokens", None)
-            n = first_stop_hit(req.tokens, req.stop_ids, int((self.min_new_tokens if mn is None else mn) or 0))
+            n = first_stop_hit(req.tokens, chain.stop_ids, chain.min_new_tokens)
             if n is not None:
                 req.tokens = list(req.tokens[:n])
         req.text = self.processor.tokenizer.decode(req.tokens, skip_special_tokens=True).strip()
         self._drop_grammar(req)
-        n_lp = self._want_logprobs(req)
-        if n_lp is not None:
+        if chain.wants_logprobs:
             if logprobs is None:
                 logprobs = (self.engine.chain_logprobs(slot, req.max_new_tokens, stream=ds) if ds is not None
                             else self.engine.chain_logprobs(slot, req.max_new_tokens))
-            self._attach_logprobs(req, logprobs, n_lp)
+            self._attach_logprobs(req, logprobs, chain.logprobs)
         follow = None
         try:
             follow = req.on_done(req, req.tokens, req.text) if req.on_done else None

@@ -21,13 +21,10 @@ Prompt: the Qwen2.5-VL chat template (`<|im_start|>role\\n ... <|im_end|>\\n`, a
 `<|vision_start|><|image_pad|><|vision_end|>`, a default system turn when the conversation has none, then the
 generation prompt `<|im_start|>assistant\\n`).  temperature 0 / absent -> greedy, else temperature sampling.
 Concurrent requests (infer_vllm.py keeps up to 100 in flight, :244-271) share the GPU through continuous batching
-(`zoomearth_amd/scheduler.py`): a dispatcher thread admits greedy requests into the RUNNING batch between bursts of
-decode steps -- newcomers are prefilled together and join the next burst, a finished request frees its KV slot and its
-response returns at once -- with each request's tokens independent of which other requests share its steps.  Sampled
-requests join the same running batch: temperature, seed and repetition penalty are per chain on the device
-(`Engine.set_sampling`), so a request draws what it would draw running alone whatever its company.  (An engine without that
-entry keeps the old path: sampled requests wait for the batch to drain and run grouped by temperature and seed.)  Images
-are decoded on the host and uploaded.
+(`zoomearth_amd/scheduler.py`): a dispatcher thread admits every request, greedy or sampled, into the RUNNING batch between
+bursts of decode steps -- newcomers are prefilled together and join the next burst, a finished request frees its KV slot and
+its response returns at once.  Temperature, seed and repetition penalty are per chain on the device (`Engine.set_sampling`), so
+a request's tokens do not depend on which other requests share its steps.  Images are decoded on the host and uploaded.
 
     python -m zoomearth_amd.serve --model_name /ckpt/ZoomEarth-3B --port 8000
 """
@@ -38,6 +35,8 @@ import math
 import threading
 import time
 import uuid
+from dataclasses import dataclass, field
+from typing import Any, Optional
 
 DEFAULT_SYSTEM = "You are a helpful assistant."
 IMAGE_PLACEHOLDER = "<|vision_start|><|image_pad|><|vision_end|>"
@@ -94,10 +93,31 @@ def build_prompt(messages):
     return "".join(parts), images
 
 
+@dataclass
 class _Parsed:
-    __slots__ = ("req", "prompt", "pil_images", "max_tokens", "sample", "temperature", "seed", "future", "top_k", "top_p",
-                 "min_p", "logprobs", "presence_penalty", "frequency_penalty", "logit_bias", "min_tokens", "stop", "stop_token_ids",
-                 "no_repeat_ngram_size", "repetition_penalty", "guided_regex", "guided_choice")
+    """One validated request: OpenAI's / vLLM's fields under their own names, off values where the request names none."""
+    req: dict
+    prompt: str = ""
+    pil_images: list = field(default_factory=list)
+    max_tokens: int = 1024
+    sample: bool = False
+    temperature: Optional[float] = None
+    seed: int = 0
+    repetition_penalty: Optional[float] = None
+    top_k: int = 0
+    top_p: float = 1.0
+    min_p: float = 0.0
+    logprobs: Optional[int] = None
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: dict = field(default_factory=dict)
+    min_tokens: int = 0
+    stop: list = field(default_factory=list)
+    stop_token_ids: list = field(default_factory=list)
+    no_repeat_ngram_size: int = 0
+    guided_regex: Optional[str] = None
+    guided_choice: Optional[list] = None
+    future: Any = None
 
     def guided(self) -> bool:
         return self.guided_regex is not None or self.guided_choice is not None
@@ -148,8 +168,7 @@ class ChatServer:
             raise BadRequest("stream=true is not offered")
         if int(req.get("n", 1) or 1) != 1:
             raise BadRequest("n must be 1")
-        p = _Parsed()
-        p.req = req
+        p = _Parsed(req)
         p.prompt, p.pil_images = build_prompt(req.get("messages"))
         p.max_tokens = int(req.get("max_tokens") or req.get("max_completion_tokens") or 1024)
         t = req.get("temperature")
@@ -275,7 +294,6 @@ class ChatServer:
             except ValueError as ex:
                 raise BadRequest(f"guided decoding: {ex}") from ex
         p.guided_regex, p.guided_choice = gr, gc
-        p.future = None
         return p
 
     def _logprobs_block(self, p: _Parsed, ids, lp) -> dict:
@@ -395,27 +413,44 @@ class ChatServer:
             self._stop = True
             self._cv.notify()
 
-    def _dispatch(self):
-        """Running-batch admission (the concurrency model of /root/reference/src/eval/infer_vllm.py:244-271, where the
-        client keeps up to 100 requests in flight): greedy requests go to a `ChainScheduler` -- a request that arrives
-        while others are decoding is prefilled and joins their next burst, one that finishes frees its KV slot at once --
-        and each future resolves as soon as ITS chain ends.  With an engine that offers `set_sampling` there is this ONE
-        scheduler: a sampled request is submitted to it like a greedy one, with its own temperature and seed (and random
-        stream 0: what it would draw running alone) in the engine's per-slot table, and joins the running batch.  The fallback
-        for an engine without the entry: sampled requests (temperature / seed are then baked into the captured decode step)
-        wait for the running chains to drain; those that share a temperature and a seed then run together as a batch of
-        their own."""
+    def _request(self, p: _Parsed):
+        """The scheduler's Request of a parsed one: its fields under the scheduler's names, the budget clamped to the KV capacity
+        (per request: never fails its batch), its future resolved by the callbacks.  A sampled request carries its own temperature
+        and seed, and random stream 0: what it would draw running alone."""
         from .image import DeviceImage
-        from .scheduler import ChainScheduler, Request
+        from .scheduler import Request
+
+        def done(req, tokens, text):
+            p.future.set_result(self._response(p, tokens, req.n_prompt, (req.token_logprobs, req.top_logprobs)))
+            return None
+
+        def failed(req, ex):
+            if not p.future.done():
+                p.future.set_exception(ex)
+
+        own = dict(do_sample=True, temperature=p.temperature, seed=p.seed, stream_id=0, top_k=p.top_k, top_p=p.top_p,
+                   min_p=p.min_p) if p.sample else {}
+        if p.repetition_penalty is not None:
+            own["repetition_penalty"] = p.repetition_penalty
+        return Request(prompt=p.prompt, images=[DeviceImage.from_pil(im, self.model.engine) for im in p.pil_images],
+                       max_new_tokens=max(1, min(p.max_tokens, self.model.engine.max_ctx)), on_done=done, on_error=failed,
+                       logprobs=p.logprobs, presence_penalty=p.presence_penalty, frequency_penalty=p.frequency_penalty,
+                       logit_bias=p.logit_bias, min_new_tokens=p.min_tokens, stop_ids=p.stop_records(self.processor.tokenizer),
+                       no_repeat_ngram_size=p.no_repeat_ngram_size, guided_regex=p.guided_regex, guided_choice=p.guided_choice, **own)
+
+    def _dispatch(self):
+        """Running-batch admission (the concurrency model of the reference's src/eval/infer_vllm.py:244-271, where the
+        client keeps up to 100 requests in flight): every request goes to ONE `ChainScheduler` -- a request that arrives
+        while others are decoding is prefilled and joins their next burst, one that finishes frees its KV slot at once --
+        and each future resolves as soon as ITS chain ends.  Wait, collect, submit, step."""
+        from .scheduler import ChainScheduler
 
         sched = None
-        sampled, held = [], []
-        per_chain = hasattr(self.model.engine, "set_sampling")
         while True:
             with self._cv:
-                while not self._queue and not self._stop and not sampled and not held and not (sched is not None and sched.busy()):
+                while not self._queue and not self._stop and not (sched is not None and sched.busy()):
                     self._cv.wait()
-                if self._stop and not self._queue and not sampled and not held and not (sched is not None and sched.busy()):
+                if self._stop and not self._queue and not (sched is not None and sched.busy()):
                     return
                 if sched is None or not sched.busy():  # idle: give concurrent arrivals a moment to share the first prefill
                     deadline = time.monotonic() + self.batch_window_s
@@ -429,41 +464,12 @@ class ChatServer:
                 if sched is None:
                     sched = ChainScheduler(self.model, self.processor, do_sample=False, max_batch=self.max_batch, burst=8)
                     self.scheduler = sched
-                held.extend(new)
-                new, held = (held, []) if not sampled else ([p for p in held if p.sample], [p for p in held if not p.sample])
-                for p in new:  # (greedy arrivals wait behind a pending sampled request: it needs the engine alone)
-                    if p.sample and not per_chain:
-                        sampled.append(p)
-                        continue
-                    own = {}
-                    if p.sample:
-                        own = dict(do_sample=True, temperature=p.temperature, seed=p.seed, stream_id=0, top_k=p.top_k, top_p=p.top_p,
-                                   min_p=p.min_p)
-                    if p.repetition_penalty is not None:
-                        if not per_chain:
-                            p.future.set_exception(BadRequest("repetition_penalty per request needs an engine with set_sampling"))
-                            continue
-                        own["repetition_penalty"] = p.repetition_penalty
-
-                    def done(req, tokens, text, p=p):
-                        p.future.set_result(self._response(p, tokens, req.n_prompt, (req.token_logprobs, req.top_logprobs)))
-                        return None
-
-                    def failed(req, ex, p=p):
+                for p in new:
+                    try:
+                        sched.submit(self._request(p))
+                    except Exception as ex:
                         if not p.future.done():
                             p.future.set_exception(ex)
-
-                    try:
-                        imgs = [DeviceImage.from_pil(im, self.model.engine) for im in p.pil_images]
-                        budget = max(1, min(p.max_tokens, self.model.engine.max_ctx))  # per request: never fails its batch
-                        sched.submit(Request(prompt=p.prompt, images=imgs, max_new_tokens=budget, on_done=done,
-                                             on_error=failed, logprobs=p.logprobs, presence_penalty=p.presence_penalty,
-                                             frequency_penalty=p.frequency_penalty, logit_bias=p.logit_bias,
-                                             min_new_tokens=p.min_tokens, stop_ids=p.stop_records(self.processor.tokenizer),
-                                             no_repeat_ngram_size=p.no_repeat_ngram_size, guided_regex=p.guided_regex,
-                                             guided_choice=p.guided_choice, **own))
-                    except Exception as ex:
-                        failed(None, ex)
                 if sched.busy():
                     try:
                         sched.step()
@@ -472,49 +478,6 @@ class ChatServer:
                             if r.on_error:
                                 r.on_error(r, ex)
                         sched = None
-                    continue
-            if sampled:
-                # The running (greedy) batch has drained.  Temperature and seed are baked into the captured decode step, so
-                # the sampled requests that share both run TOGETHER on a scheduler of their own (continuous batching, a
-                # request's random stream = stream 0 of its seed: what it would draw running alone, so a request's tokens
-                # do not depend on its company); other sampling configurations follow in turn.  top_p / top_k / min_p are
-                # per chain on the device, so requests with different filters still share the group.
-                key = (sampled[0].temperature, sampled[0].seed)
-                group = [p for p in sampled if (p.temperature, p.seed) == key]
-                sampled = [p for p in sampled if (p.temperature, p.seed) != key]
-                with self._lock:
-                    ss = ChainScheduler(self.model, self.processor, do_sample=True, temperature=key[0], seed=key[1],
-                                        max_batch=self.max_batch, burst=8)
-                    for p in group:
-                        def done(req, tokens, text, p=p):
-                            p.future.set_result(self._response(p, tokens, req.n_prompt, (req.token_logprobs, req.top_logprobs)))
-                            return None
-
-                        def failed(req, ex, p=p):
-                            if not p.future.done():
-                                p.future.set_exception(ex)
-
-                        try:
-                            imgs = [DeviceImage.from_pil(im, self.model.engine) for im in p.pil_images]
-                            ss.submit(Request(prompt=p.prompt, images=imgs, max_new_tokens=max(1, min(p.max_tokens, self.model.engine.max_ctx)),
-                                              stream_id=0, on_done=done, on_error=failed, top_k=p.top_k, top_p=p.top_p,
-                                              min_p=p.min_p, logprobs=p.logprobs, presence_penalty=p.presence_penalty,
-                                              frequency_penalty=p.frequency_penalty, logit_bias=p.logit_bias,
-                                              min_new_tokens=p.min_tokens, stop_ids=p.stop_records(self.processor.tokenizer),
-                                              no_repeat_ngram_size=p.no_repeat_ngram_size, guided_regex=p.guided_regex,
-                                              guided_choice=p.guided_choice))
-                        except Exception as ex:
-                            failed(None, ex)
-                    try:
-                        ss.run()
-                    except Exception as ex:
-                        for r in ss.pending_requests():
-                            if r.on_error:
-                                r.on_error(r, ex)
-                    for p in group:  # (belt and braces: nobody is left waiting)
-                        if not p.future.done():
-                            p.future.set_exception(RuntimeError("request was dropped by the sampled batch"))
-                    sched = None  # the sampled scheduler used the chain slots: the greedy one starts afresh
 
 
 def create_app(server: ChatServer):
