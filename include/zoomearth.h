@@ -283,6 +283,23 @@ int ze_chain_tokens_batch(ze_engine* e, const int32_t* seqs, int n, int32_t* out
  * ready), so a generation can continue from it.  Arguments as ze_prefill. */
 int ze_score(ze_engine* e, int seq, const int32_t* input_ids, int len, const void* image_embeds, int n_image_rows,
              const int32_t* position_ids, int rope_delta, float* out_logps, void* stream);
+/* Rollout scoring of several chains in ONE pass, from a first scored position per chain on: ze_prefill_batch of the n chains
+ * (every argument up to rope_deltas as there, the same validation and error codes: sum lens <= max_prefill_rows, no chain
+ * twice) plus the log-probabilities of the next ids of the positions asked for.  score_from[i] in [0, lens[i] - 1] indexes
+ * chain i's NEW ids (NULL: 0 for every chain; a value outside the range is ZE_ERR_INVALID); chain i contributes
+ * lens[i] - 1 - score_from[i] values, packed in chain order into out_logps (device f32, sum of those counts):
+ *   out_logps[off_i + j] = log_softmax(logits[score_from[i] + j])[ids_i[score_from[i] + j + 1]]
+ * with the logits in bf16 and the log-softmax in fp32, as in ze_score.  score_from[i] == lens[i] - 1 (lens[i] == 1 is legal)
+ * contributes nothing: the chain is only prefilled.  Only the scored rows go through the final norm and the lm_head (the
+ * trainer's `[:, prompt_length - 1:]`).  A chain may hold cached rows (ze_seq_copy_prefix, ze_seq_truncate): positions count
+ * the new ids only, and the prediction of new id 0 belongs to the last CACHED row, which this pass does not compute -- it is
+ * not available.  Afterwards every chain is exactly as after ze_prefill_batch: KV cache filled, last-position logits in the
+ * engine, a generation can continue.
+ * Contract: a chain's values are bit-identical to the corresponding entries of ze_score of that chain alone; they do not
+ * depend on what shares the pass or on the other chains' score_from. */
+int ze_score_batch(ze_engine* e, const int32_t* seqs, int n, const int32_t* lens, const int32_t* input_ids,
+                   const void* image_embeds, const int32_t* n_image_rows, const int32_t* position_ids,
+                   const int32_t* rope_deltas, const int32_t* score_from, float* out_logps, void* stream);
 /* Marks every id in `ids` (host int32) as seen for the repetition penalty of `seq` (the prompt). */
 int ze_seq_mark_seen(ze_engine* e, int seq, const int32_t* ids, int n, void* stream);
 /* ze_seq_mark_seen for the n chains of a prefill pass at once: ids = the chains' prompts back to back, counts[i] ids for seqs[i]. */

@@ -5,6 +5,7 @@
 
 #include "ze_kernels.h"
 #include "ze_prng.h"
+#include "ze_rmsnorm.h"
 
 // ------------------------------------------------------------------ weight packing
 __device__ __forceinline__ int map_row(int r, int mode, int offset) {
@@ -89,32 +90,11 @@ __global__ void __launch_bounds__(256) k_rmsnorm(const bf16_t* __restrict__ x, i
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
     const bf16_t* xr = x + (size_t)row * ldx;
-    float ss = 0.f;
     const int nv = cols >> 3;  // cols % 8 == 0
-    for (int v = lane; v < nv; v += 64) {
-        const uint4 q = *reinterpret_cast<const uint4*>(xr + v * 8);
-        const uint32_t u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float a = bf16lo(u[j]), b = bf16hi(u[j]);
-            ss += a * a + b * b;
-        }
-    }
-    ss = wave_sum(ss);
-    const float inv = rsqrtf(ss / (float)cols + eps);
+    // (the sum of squares and the normalised vector: ze_rmsnorm.h, shared with the scoring pass's gathering norm)
+    const float inv = rms_wave_inv(xr, cols, eps, lane);
     bf16_t* yr = y + (size_t)row * ldy;
-    auto norm_vec = [&](int v, uint32_t (&o)[4]) {
-        const uint4 q = *reinterpret_cast<const uint4*>(xr + v * 8);
-        const uint4 g = *reinterpret_cast<const uint4*>(w + v * 8);
-        const uint32_t u[4] = {q.x, q.y, q.z, q.w};
-        const uint32_t gw[4] = {g.x, g.y, g.z, g.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float a = bf16_round(bf16lo(u[j]) * inv) * bf16lo(gw[j]);
-            const float b = bf16_round(bf16hi(u[j]) * inv) * bf16hi(gw[j]);
-            o[j] = pack_bf16x2(a, b);
-        }
-    };
+    auto norm_vec = [&](int v, uint32_t (&o)[4]) { rms_norm_vec(xr, w, v, inv, o); };
     float s8 = 1.f, inv8 = 1.f;
     if (act8) {  // a pass for the row's largest magnitude (of the bf16 outputs), then the quantising pass below
         float amax = 0.f;

@@ -268,6 +268,7 @@ struct ze_engine {
     int4* ttiles = nullptr;
     int* ttile_aux = nullptr;  // batched prefill: (chain slot, position offset) per attention tile
     int* trow_aux = nullptr;   // batched prefill: (chain slot, cache position) per row
+    int* tscore = nullptr;     // scoring pass (ze_score_batch): [n] scored rows of the pass's hidden state, then their [n] target ids
     int prefill_rows = 0;
     int* t_host_ints = nullptr;  // pinned
     size_t t_host_ints_cap = 0;
@@ -391,6 +392,12 @@ bool batch_o(ze_engine* e, int li, int n, hipStream_t s);
 bool batch_gate_up(ze_engine* e, int li, int n, hipStream_t s);
 bool batch_down(ze_engine* e, int li, int n, hipStream_t s);
 bool batch_lm_head(ze_engine* e, int li, int n, hipStream_t s);
+// the scored-row path of a scoring pass (ze_score.hip): final norm of the n hidden rows e->tscore lists, lm_head in chunks of the
+// MLP workspace, log-softmax pick of their targets into out (device f32 [n]); n = 0 launches nothing
+void ze_launch_rmsnorm_gather(const bf16_t* x, int ldx, const int* src_rows, const bf16_t* w, bf16_t* y, int ldy, int rows, int cols,
+                              float eps, hipStream_t s);
+int ze_score_chunk_rows(const ze_engine* e, int rows);
+int ze_score_rows(ze_engine* e, int n, float* out, hipStream_t s);
 // what a batched step sets up before its launches
 int ensure_fragments(ze_engine* e, hipStream_t s);
 void sync_prefix(ze_engine* e, const int32_t* seqs, int n, hipStream_t s);

@@ -343,7 +343,8 @@ extern "C" int ze_engine_create(const ze_config* cfg, int device_id, ze_engine**
     chk(dev_alloc(e, &e->ttiles, ntile_cap));
     chk(dev_alloc(e, &e->ttile_aux, ntile_cap * 2));
     chk(dev_alloc(e, &e->trow_aux, tm * 2));
-    e->t_host_ints_cap = tm * 6 + ntile_cap * 6 + 64;
+    chk(dev_alloc(e, &e->tscore, tm * 2));
+    e->t_host_ints_cap = tm * 8 + ntile_cap * 6 + 64;  // (ids, 3 positions, 2 row aux, 2 score table per row; 4 + 2 per tile)
     if (r == 0 && hipHostMalloc((void**)&e->t_host_ints, e->t_host_ints_cap * sizeof(int)) != hipSuccess)
         r = ze_fail(e, ZE_ERR_HIP, "hipHostMalloc failed");
 
@@ -443,7 +444,7 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
     void* dev[] = {e->arena, e->staging, e->cosT, e->sinT, e->axis_of, e->lut, e->eos_dev, e->kcache, e->vcache,
                    e->st_dev, e->seen, e->out_tokens, e->fe_tmp, e->fe_img, e->fe_coef, e->vx, e->vh, e->vy, e->vqkv,
                    e->vo, e->va, e->vz, e->vz2, e->vcos, e->vsin, e->vperm, e->vinv, e->vtiles_win, e->vtiles_full,
-                   e->th, e->ty, e->tqkv, e->to, e->ta, e->tsrc, e->tpos, e->ttiles, e->ttile_aux, e->trow_aux, e->dh, e->dq, e->dattn, e->dact,
+                   e->th, e->ty, e->tqkv, e->to, e->ta, e->tsrc, e->tpos, e->ttiles, e->ttile_aux, e->trow_aux, e->tscore, e->dh, e->dq, e->dattn, e->dact,
                    e->dlogits, e->dpartial, e->dsample, e->atickets, e->gslab, e->gtickets, e->pslab, e->ptickets, e->bh, e->by, e->bqkv, e->bo, e->ba, e->bseq, e->bmate, e->blogits, e->bpartial, e->bsample, e->arena8, e->arena_f, e->arena_f8,
                    e->ty8, e->ty8_scale, e->damax, e->ty8p, e->ty8p_scale, e->xl_dev};
     for (void* p : dev)

@@ -831,10 +831,13 @@ extern "C" int ze_score(ze_engine* e, int seq, const int32_t* input_ids, int len
                         out_logps, stream);
 }
 
-// Prefill of n chains in one pass: all rows share every GEMM, attention and the KV append go per chain.
-extern "C" int ze_prefill_batch(ze_engine* e, const int32_t* seqs, int n, const int32_t* lens, const int32_t* input_ids,
-                                const void* image_embeds, const int32_t* n_image_rows, const int32_t* position_ids,
-                                const int32_t* rope_deltas, void* stream) {
+// Prefill of n chains in one pass: all rows share every GEMM, attention and the KV append go per chain.  The staging and the pass
+// of ze_prefill_batch and ze_score_batch: with out_logps (the scoring pass) chain i's new rows [score_from[i], lens[i] - 1) are
+// listed with their next ids in e->tscore and, behind the layers and the chains' last-position logits, go through the scored-row
+// path (ze_score.hip) into out_logps, packed in chain order.  Without it nothing more is staged or launched than the prefill's own.
+static int prefill_batch_impl(ze_engine* e, const int32_t* seqs, int n, const int32_t* lens, const int32_t* input_ids,
+                              const void* image_embeds, const int32_t* n_image_rows, const int32_t* position_ids,
+                              const int32_t* rope_deltas, const int32_t* score_from, float* out_logps, void* stream) {
     if (!e || !seqs || !lens || !input_ids || !position_ids || !rope_deltas || n <= 0)
         return ze_fail(e, ZE_ERR_INVALID, "bad prefill arguments");
     const ze_config& c = e->cfg;
@@ -851,12 +854,27 @@ extern "C" int ze_prefill_batch(ze_engine* e, const int32_t* seqs, int n, const 
         total += lens[i];
     }
     if (total > e->prefill_rows) return ze_fail(e, ZE_ERR_NOMEM, "batched prefill exceeds max_prefill_rows");
+    int n_scored = 0;
+    if (out_logps)
+        for (int i = 0; i < n; ++i) {
+            const int from = score_from ? score_from[i] : 0;
+            if (from < 0 || from > lens[i] - 1) return ze_fail(e, ZE_ERR_INVALID, "score_from out of range");
+            n_scored += lens[i] - 1 - from;
+        }
+    if (n_scored > 0 && ze_score_chunk_rows(e, n_scored) < 1)
+        return ze_fail(e, ZE_ERR_NOMEM, "prefill workspace too small for one row of logits");
 
     ZE_TRY(stage_acquire(e, e->t_staged));  // pinned staging reuse
     int* src = e->t_host_ints;
     int* pos = src + total;
     int* row_aux = pos + 3 * total;
-    int* tiles = row_aux + 2 * total;
+    int* score_tab = row_aux + 2 * total;  // [n_scored] rows of the pass, then [n_scored] target ids
+    int* tiles = score_tab + 2 * n_scored;
+    for (int i = 0, r0 = 0, k = 0; i < n && out_logps; r0 += lens[i], ++i)
+        for (int t = score_from ? score_from[i] : 0; t < lens[i] - 1; ++t, ++k) {
+            score_tab[k] = r0 + t;
+            score_tab[n_scored + k] = input_ids[r0 + t + 1];
+        }
     int img = 0, nt = 0, row0 = 0;
     std::vector<int> tile_aux;
     for (int i = 0; i < n; ++i) {
@@ -884,6 +902,7 @@ extern "C" int ze_prefill_batch(ze_engine* e, const int32_t* seqs, int n, const 
     ZE_HIP(hipMemcpyAsync(e->trow_aux, row_aux, (size_t)2 * total * sizeof(int), hipMemcpyHostToDevice, s));
     ZE_HIP(hipMemcpyAsync(e->ttiles, tiles, (size_t)nt * 16, hipMemcpyHostToDevice, s));
     ZE_HIP(hipMemcpyAsync(e->ttile_aux, taux, (size_t)nt * 2 * sizeof(int), hipMemcpyHostToDevice, s));
+    if (n_scored > 0) ZE_HIP(hipMemcpyAsync(e->tscore, score_tab, (size_t)2 * n_scored * sizeof(int), hipMemcpyHostToDevice, s));
     ZE_TRY(stage_release(e, e->t_staged, s));
 
     const int th = ze_timer_begin(e, 2, s);
@@ -900,6 +919,7 @@ extern "C" int ze_prefill_batch(ze_engine* e, const int32_t* seqs, int n, const 
         }
         prefill_logits(e, xr.data(), lo.data(), n, s);
     }
+    if (n_scored > 0) ZE_TRY(ze_score_rows(e, n_scored, out_logps, s));
     ze_timer_end(e, th, s);
     ZE_KCHECK();
     row0 = 0;
@@ -910,6 +930,20 @@ extern "C" int ze_prefill_batch(ze_engine* e, const int32_t* seqs, int n, const 
         row0 += lens[i];
     }
     return ZE_OK;
+}
+
+extern "C" int ze_prefill_batch(ze_engine* e, const int32_t* seqs, int n, const int32_t* lens, const int32_t* input_ids,
+                                const void* image_embeds, const int32_t* n_image_rows, const int32_t* position_ids,
+                                const int32_t* rope_deltas, void* stream) {
+    return prefill_batch_impl(e, seqs, n, lens, input_ids, image_embeds, n_image_rows, position_ids, rope_deltas, nullptr, nullptr, stream);
+}
+
+extern "C" int ze_score_batch(ze_engine* e, const int32_t* seqs, int n, const int32_t* lens, const int32_t* input_ids,
+                              const void* image_embeds, const int32_t* n_image_rows, const int32_t* position_ids,
+                              const int32_t* rope_deltas, const int32_t* score_from, float* out_logps, void* stream) {
+    if (!out_logps) return ze_fail(e, ZE_ERR_INVALID, "ze_score_batch needs an output buffer");
+    return prefill_batch_impl(e, seqs, n, lens, input_ids, image_embeds, n_image_rows, position_ids, rope_deltas, score_from, out_logps,
+                              stream);
 }
 
 // ================================================================== decode

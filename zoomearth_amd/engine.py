@@ -610,10 +610,9 @@ class Engine:
                                                  logits.stride(0), _ptr(targets), _ptr(out), self._stream()))
         return out
 
-    def prefill_batch(self, seqs, ids_list, embeds_list, pos_list, deltas):
-        """One prefill pass for several chains (rows of all chains share every GEMM).  Per chain i: ids_list[i] (new
-        token ids), embeds_list[i] (bf16 [rows, hidden] or None), pos_list[i] (int32 [3, len]), deltas[i].  Each
-        chain's result is bit-identical to prefill() of that chain alone."""
+    def _batch_args(self, seqs, ids_list, embeds_list, pos_list, deltas):
+        """The arguments ze_prefill_batch and ze_score_batch share, from per-chain lists: (n, seqs, lens, ids, embeds, image rows,
+        positions, deltas) as the C ABI takes them, and the arrays the pointers point into (alive while the caller holds them)."""
         sq, sp = _i32(seqs)
         lens, lp = _i32([len(x) for x in ids_list])
         ids, ip = _i32(np.concatenate([np.asarray(x, dtype=np.int32) for x in ids_list]))
@@ -626,7 +625,32 @@ class Engine:
             assert emb.dtype == torch.bfloat16
         dl, dp = _i32(deltas)
         self._use(emb, *embs)
-        self._check(self.lib.ze_prefill_batch(self.h, sp, len(sq), lp, ip, _ptr(emb), nrp, pp, dp, self._stream()))
+        return (len(sq), sp, lp, ip, emb, nrp, pp, dp), (sq, lens, ids, pos, nrows, dl)
+
+    def prefill_batch(self, seqs, ids_list, embeds_list, pos_list, deltas):
+        """One prefill pass for several chains (rows of all chains share every GEMM).  Per chain i: ids_list[i] (new
+        token ids), embeds_list[i] (bf16 [rows, hidden] or None), pos_list[i] (int32 [3, len]), deltas[i].  Each
+        chain's result is bit-identical to prefill() of that chain alone."""
+        (n, sp, lp, ip, emb, nrp, pp, dp), _alive = self._batch_args(seqs, ids_list, embeds_list, pos_list, deltas)
+        self._check(self.lib.ze_prefill_batch(self.h, sp, n, lp, ip, _ptr(emb), nrp, pp, dp, self._stream()))
+
+    def score_batch(self, seqs, ids_list, embeds_list, pos_list, deltas, score_from=None):
+        """prefill_batch() plus, for chain i, the log-probability of the next id at its new positions score_from[i] ..
+        len(ids_list[i]) - 2 (ze_score_batch; score_from None: every position, as score()).  Returns (f32 [sum of the chains'
+        counts] on the device, packed in chain order; offsets: n + 1 ints, chain i's values are out[offsets[i]:offsets[i + 1]]).
+        A chain's values are the bits score() of that chain alone gives at those positions."""
+        (n, sp, lp, ip, emb, nrp, pp, dp), alive = self._batch_args(seqs, ids_list, embeds_list, pos_list, deltas)
+        lens = alive[1]
+        sf = np.zeros(n, dtype=np.int32) if score_from is None else np.asarray(score_from, dtype=np.int32).reshape(-1)
+        if len(sf) != n:
+            raise ValueError(f"score_from has {len(sf)} entries for {n} chains")
+        sf, sfp = _i32(sf)
+        # (an out-of-range value is the library's error; the buffer is sized without trusting it)
+        counts = np.clip(lens.astype(np.int64) - 1 - np.clip(sf, 0, None), 0, None)
+        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        out = torch.empty(max(int(offsets[-1]), 1), dtype=torch.float32, device=self.device)
+        self._check(self.lib.ze_score_batch(self.h, sp, n, lp, ip, _ptr(emb), nrp, pp, dp, sfp, _ptr(out), self._stream()))
+        return out[:int(offsets[-1])], offsets.tolist()
 
     def decode_step(self, seq: int, token: int = -1, want_logits: bool = True):
         logits = torch.empty(self.config.text.vocab_size, dtype=torch.float32, device=self.device) if want_logits else None

@@ -29,6 +29,7 @@ from . import processor as _processor
 from .chain_request import ChainRequest
 from .checkpoint import iter_checkpoint
 from .config import ModelConfig
+from .score_plan import PlanItem, plan_score_passes, score_columns
 from .engine import MAX_LOGIT_BIAS, MAX_RULE_INTS, MAX_RULE_LEN, MAX_RULE_WORDS, MAX_TOP_LOGPROBS, Engine
 
 
@@ -41,6 +42,16 @@ class GenerateOutput:
     logprobs: torch.Tensor
     top_ids: torch.Tensor
     top_logprobs: torch.Tensor
+
+
+class ScoreItem(NamedTuple):
+    """One sequence of `score_sequences`: its ids; its images in order -- grids (t, h, w), ViT features bf16 [merged rows,
+    hidden] and identity keys (None: never shared); and the first position whose next-token log-probability is wanted."""
+    ids: list
+    grids: list
+    feats: list
+    keys: Optional[list] = None
+    score_from: int = 0
 
 
 class _Rows(NamedTuple):
@@ -182,12 +193,15 @@ class ZoomEarthForConditionalGeneration:
     # ------------------------------------------------------------------ rollout scoring
     @torch.no_grad()
     def per_token_logps(self, input_ids, attention_mask=None, pixel_values=None, image_grid_thw=None,
-                        image_keys=None, **kw):
+                        image_keys=None, score_from: Optional[int] = None, share_prefix: bool = True, min_shared: int = 64, **kw):
         """Log-probability of every token given its prefix: f32 [B, L - 1], column t = log p(input_ids[:, t + 1]).
         Same result layout as `_get_per_token_logps(model, input_ids, attention_mask, pixel_values=...,
         image_grid_thw=...)` of the reference's GRPO trainer (src/train/RL/src/open-r1-multimodal/src/open_r1/
         trainer/grpo_trainer.py:494-504), which it calls without gradients for the old policy and the reference
-        model (:660-683).  Padded positions (attention_mask 0) are skipped, their columns are 0."""
+        model (:660-683).  Padded positions (attention_mask 0) are skipped, their columns are 0.
+        score_from = k: columns t < k are not computed and stay 0 (the trainer keeps `[:, prompt_length - 1:]` only, so
+        k = prompt_length - 1 skips the final norm, the lm_head and the log-softmax of every prompt position); shape, layout
+        and padding rules are unchanged.  The rows run together through `score_sequences`."""
         e, cfg = self.engine, self.config
         ids_cpu = input_ids.cpu().numpy()
         mask = attention_mask.cpu().numpy().astype(bool) if attention_mask is not None else np.ones_like(ids_cpu, bool)
@@ -196,8 +210,8 @@ class ZoomEarthForConditionalGeneration:
         rows_per = [g[0] * g[1] * g[2] for g in grids]
         offs = np.concatenate([[0], np.cumsum(rows_per)]).astype(int)
         out = torch.zeros((ids_cpu.shape[0], max(ids_cpu.shape[1] - 1, 0)), dtype=torch.float32, device=e.device)
-        self._chains.clear()  # scoring uses slot 0 as scratch
         gi = 0
+        items, where = [], []
         for b in range(ids_cpu.shape[0]):
             valid = np.nonzero(mask[b])[0]
             ids = ids_cpu[b][valid].astype(np.int64).tolist()
@@ -209,13 +223,55 @@ class ZoomEarthForConditionalGeneration:
                 raise ValueError("Image features and image tokens do not match")
             if len(ids) < 2:
                 continue
+            first, cols = score_columns(valid, score_from)
+            if not cols:
+                continue
             feats = [self._features(pixel_values[offs[i]:offs[i + 1]], grids[i], keys[i]) for i in my]
-            emb = (torch.cat(feats) if len(feats) > 1 else feats[0]) if feats else None
-            pos, delta = e.rope_index(ids, [grids[i] for i in my])
-            e.seq_reset(0)
-            lp = e.score(0, ids, emb, pos, delta)
-            out[b, torch.as_tensor(valid[1:] - 1, device=e.device)] = lp
+            items.append(ScoreItem(ids, [grids[i] for i in my], feats, [keys[i] for i in my], first))
+            where.append((b, cols))
+        for (b, cols), lp in zip(where, self.score_sequences(items, share_prefix=share_prefix, min_shared=min_shared)):
+            out[b, torch.as_tensor(cols, device=e.device)] = lp
         return out.to(input_ids.device) if input_ids.device.type != "cpu" else out.cpu()
+
+    @torch.no_grad()
+    def score_sequences(self, items, share_prefix: bool = True, min_shared: int = 64):
+        """Scores many sequences in as few passes as the engine's limits allow: one f32 tensor per ScoreItem, on the device,
+        with the log-probability of the next id at positions item.score_from .. len(ids) - 2 -- the bits `Engine.score` of
+        the sequence alone gives there.  The plan (score_plan.plan_score_passes) packs the sequences into `score_batch`
+        passes of at most max_prefill_rows rows and max_seqs chains; with share_prefix, sequences with a common prompt (the G
+        generations of a sample) prefill it once: one of them whole, in an earlier pass, the others copy its K/V rows
+        (`seq_copy_prefix`, bit-identical) and prefill their tails.  The chain slots are scratch: cached chains of generate()
+        are forgotten.  `last_score_stats` tells what the call did."""
+        e, cfg = self.engine, self.config
+        plan = plan_score_passes([PlanItem(it.ids, list(it.keys) if it.keys is not None else [None] * len(it.grids), it.score_from)
+                                  for it in items], e.max_prefill_rows, e.max_seqs, cfg.image_token_id, share_prefix, min_shared)
+        self._chains.clear()
+        self._next_slot = 0
+        out = [torch.zeros(0, dtype=torch.float32, device=e.device) for _ in items]
+        stats = dict(passes=len(plan), rows_per_pass=[], shared_rows=0, scored_rows=0)
+        for entries in plan:
+            slots, ids_l, emb_l, pos_l, dl, sf = [], [], [], [], [], []
+            for en in entries:
+                it = items[en.item]
+                pos, delta = e.rope_index(it.ids, it.grids)
+                e.seq_reset(en.slot)
+                if en.copy_from is not None:
+                    e.seq_copy_prefix(en.slot, en.copy_from, en.start)
+                    stats["shared_rows"] += en.start
+                feats = list(it.feats[en.n_images:])
+                slots.append(en.slot)
+                ids_l.append(it.ids[en.start:])
+                emb_l.append((torch.cat(feats) if len(feats) > 1 else feats[0]) if feats else None)
+                pos_l.append(pos[:, en.start:])
+                dl.append(delta)
+                sf.append(it.score_from - en.start)
+            flat, off = e.score_batch(slots, ids_l, emb_l, pos_l, dl, sf)
+            stats["rows_per_pass"].append(sum(len(x) for x in ids_l))
+            stats["scored_rows"] += off[-1]
+            for k, en in enumerate(entries):
+                out[en.item] = flat[off[k]:off[k + 1]]
+        self.last_score_stats = stats
+        return out
 
     # ------------------------------------------------------------------ generate
     @staticmethod

@@ -12,7 +12,8 @@ the final prompt + completion ids from the stage-1 prompt length on (`_get_per_t
 
 Here all G x len(samples) chains advance together (sampled decoding at a temperature, one random stream per chain:
 `seed`, stream = sample * G + g for stage 1 and the same + G * len(samples) for stage 2), stage 2 continues on the chain
-slot of stage 1 with the cached stage-1 prompt reused, and scoring runs through `ze_score` (`model.per_token_logps`).
+slot of stage 1 with the cached stage-1 prompt reused, and scoring runs through `ze_score_batch` (`model.score_sequences`: all
+rollouts in one planned call, scored from the stage-1 prompt's end, the generations of a sample sharing its rows).
 The gradient side of the step is out of scope.
 """
 from __future__ import annotations
@@ -56,7 +57,7 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
     open_r1/trainer/grpo_config.py:62-70), applied to every chain of both stages; None = off.
     sampled_logps: fill completion1_logps / completion2_logps with the log-probabilities the decode steps computed for their own
     samples (the model's distribution, before temperature and filters); independent of with_logps, which scores the final
-    sequence with one more pass per chain.
+    sequences with batched passes of their own.
     Returns len(samples) * num_generations rollouts, sample-major."""
     sched = ChainScheduler(model, processor, do_sample=True, temperature=temperature, seed=seed, burst=burst,
                            top_k=top_k, top_p=top_p, min_p=min_p, logprobs=0 if sampled_logps else None)
@@ -105,7 +106,8 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
     sched.run()
 
     if with_logps:
-        import torch
+        from .modeling import ScoreItem
+        scored, items = [], []
         for ro in out:
             if ro.error:
                 continue
@@ -114,8 +116,17 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
             prompt = ro.prompt2 if ro.prompt2 is not None else ro.prompt1
             tail = ro.completion2_ids if ro.prompt2 is not None else ro.completion1_ids
             inp = processor(text=[prompt], images=list(ro.images), return_tensors="pt")
-            ids = torch.cat([inp["input_ids"], torch.tensor([tail], dtype=torch.long)], dim=1)
-            lp = model.per_token_logps(ids, torch.ones_like(ids), inp["pixel_values"], inp["image_grid_thw"],
-                                       image_keys=inp.get("image_keys"))
-            ro.logps = lp[0, max(ro.n_prompt1 - 1, 0):]
+            ids = inp["input_ids"][0].tolist() + [int(t) for t in tail]
+            grids = inp["image_grid_thw"].tolist()
+            keys = list(inp.get("image_keys") or [None] * len(grids))
+            offs = [0]
+            for g in grids:
+                offs.append(offs[-1] + g[0] * g[1] * g[2])
+            feats = [model._features(inp["pixel_values"][offs[i]:offs[i + 1]], grids[i], keys[i]) for i in range(len(grids))]
+            scored.append(ro)
+            items.append(ScoreItem(ids, grids, feats, keys, min(max(ro.n_prompt1 - 1, 0), max(len(ids) - 1, 0))))
+        # ONE planned call for all rollouts: many sequences per pass, the G generations of a sample share their stage-1 prompt's
+        # rows, and only the positions from the stage-1 prompt's end on go through the lm_head (model.score_sequences)
+        for ro, lp in zip(scored, model.score_sequences(items)):
+            ro.logps = lp.cpu()
     return out

@@ -112,6 +112,29 @@ class GrammarCache:
             self.users[key] -= 1
 
 
+def shared_prefix_len(a, b, image_token_id) -> int:
+    """Longest common prefix of two id lists that leaves both a non-empty tail and does not end inside a run of image
+    tokens (a run is fed by one image's feature rows: it is shared whole or not at all).  The rule of every planner that
+    shares K/V rows between chains (ChainScheduler._plan_sharing, score_plan.plan_score_passes)."""
+    n = min(len(a), len(b)) - 1
+    i = 0
+    while i < n and a[i] == b[i]:
+        i += 1
+    return cut_at_image_run(a, i, image_token_id)
+
+
+def cut_at_image_run(ids, i, image_token_id) -> int:
+    """The largest cut <= i of `ids` that does not fall inside a run of image tokens."""
+    while 0 < i < len(ids) and ids[i - 1] == image_token_id and ids[i] == image_token_id:
+        i -= 1
+    return i
+
+
+def images_in(ids, n, image_token_id) -> int:
+    """Image runs that begin in the first n ids."""
+    return sum(1 for t in range(n) if ids[t] == image_token_id and (t == 0 or ids[t - 1] != image_token_id))
+
+
 class _Live:
     __slots__ = ("req", "ids", "keys", "produced")
 
@@ -427,20 +450,10 @@ class ChainScheduler:
 
     # -- shared prompt prefixes
     def _prefix_len(self, a, b) -> int:
-        """Longest common prefix of two id lists that leaves both a non-empty tail and does not end inside a run of image
-        tokens (a run is fed by one image's feature rows: it is shared whole or not at all)."""
-        n = min(len(a), len(b)) - 1
-        i = 0
-        while i < n and a[i] == b[i]:
-            i += 1
-        img = self.model.config.image_token_id
-        while i > 0 and a[i - 1] == img and a[i] == img:
-            i -= 1
-        return i
+        return shared_prefix_len(a, b, self.model.config.image_token_id)
 
     def _images_in(self, ids, n) -> int:
-        img = self.model.config.image_token_id
-        return sum(1 for t in range(n) if ids[t] == img and (t == 0 or ids[t - 1] != img))
+        return images_in(ids, n, self.model.config.image_token_id)
 
     def _plan_sharing(self, prepared):
         """Decides, for every fresh chain of the round, where its leading K/V rows come from; returns the pass-A items."""
