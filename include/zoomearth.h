@@ -300,6 +300,26 @@ int ze_score(ze_engine* e, int seq, const int32_t* input_ids, int len, const voi
 int ze_score_batch(ze_engine* e, const int32_t* seqs, int n, const int32_t* lens, const int32_t* input_ids,
                    const void* image_embeds, const int32_t* n_image_rows, const int32_t* position_ids,
                    const int32_t* rope_deltas, const int32_t* score_from, float* out_logps, void* stream);
+/* ze_score_batch with more than one number per scored position (vLLM's `prompt_logprobs=N`, the per-token entropy of a GRPO
+ * trainer, rank / top-1 agreement of likelihood evaluation).  Every argument up to score_from as ze_score_batch; the same
+ * validation, error codes, staging, pass and chain state afterwards.  Outputs are device arrays packed exactly as out_logps
+ * (total = the sum of the chains' counts); with l the bf16 logits row of a scored position, t its next id and the total order
+ * "a before b" = (value descending, id ascending):
+ *   out_logps        f32 [total]          log_softmax(l)[t]
+ *   out_entropy      f32 [total]          -sum_i p_i log p_i of softmax(l), in fp32; entries of -inf contribute 0
+ *   out_rank         int32 [total]        the number of ids before t in the total order (0: t is the arg-max)
+ *   out_top_ids      int32 [total, top_n] the first top_n ids of the total order ...
+ *   out_top_logprobs f32 [total, top_n]   ... and their log-probabilities; places a row cannot fill with finite entries carry
+ *                                         (-1, -inf)
+ * out_entropy, out_rank and the two top arrays may each be NULL; the top arrays are both NULL or both set with top_n >= 1.
+ * top_n outside [0, ZE_MAX_TOP_LOGPROBS] is ZE_ERR_INVALID.  A row without a finite maximum gives entropy NaN, rank -1 and
+ * empty places.  With every detail pointer NULL the call launches exactly what ze_score_batch launches.
+ * Contract: out_logps is bit-identical to ze_score_batch with the same arguments.  Every output of a chain is bit-identical
+ * whatever shares the pass, whichever chunk of the lm_head its rows fall into, and whatever the other chains' score_from. */
+int ze_score_batch_detail(ze_engine* e, const int32_t* seqs, int n, const int32_t* lens, const int32_t* input_ids,
+                          const void* image_embeds, const int32_t* n_image_rows, const int32_t* position_ids,
+                          const int32_t* rope_deltas, const int32_t* score_from, int top_n, float* out_logps, float* out_entropy,
+                          int32_t* out_rank, int32_t* out_top_ids, float* out_top_logprobs, void* stream);
 /* Marks every id in `ids` (host int32) as seen for the repetition penalty of `seq` (the prompt). */
 int ze_seq_mark_seen(ze_engine* e, int seq, const int32_t* ids, int n, void* stream);
 /* ze_seq_mark_seen for the n chains of a prefill pass at once: ids = the chains' prompts back to back, counts[i] ids for seqs[i]. */
@@ -585,6 +605,13 @@ int ze_op_rmsnorm(ze_engine* e, const void* x_bf16, const void* weight_bf16, voi
  * (ld >= vocab, ld % 8 == 0), targets int32 [rows] device, out f32 [rows] device. */
 int ze_op_token_logprob(ze_engine* e, const void* logits_bf16, int rows, int vocab, int ld, const int32_t* targets,
                         float* out, void* stream);
+/* The per-row kernel of ze_score_batch_detail alone (k_score_detail): logits and targets as ze_op_token_logprob; out_logprob
+ * f32 [rows] (the bits of ze_op_token_logprob), out_entropy f32 [rows], out_rank int32 [rows], out_top_ids / out_top_logprobs
+ * [rows, top_n], all device.  out_entropy, out_rank and the top arrays may be NULL as in ze_score_batch_detail; ZE_ERR_INVALID
+ * for top_n outside [0, ZE_MAX_TOP_LOGPROBS] or ld % 8 != 0. */
+int ze_op_score_detail(ze_engine* e, const void* logits_bf16, int rows, int vocab, int ld, const int32_t* targets, int top_n,
+                       float* out_logprob, float* out_entropy, int32_t* out_rank, int32_t* out_top_ids, float* out_top_logprobs,
+                       void* stream);
 /* Varlen attention over segments: q,k,v,o bf16 [T, heads, D] (D = 80 or 128); cu_seqlens host int32 [n_seg+1];
  * causal applies inside each segment; kv_heads divides heads (GQA). */
 int ze_op_attention(ze_engine* e, const void* q, const void* k, const void* v, void* o, int T, int heads,

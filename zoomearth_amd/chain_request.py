@@ -23,6 +23,8 @@ class ChainRequest:
     top_p: float = 1.0
     min_p: float = 0.0
     logprobs: Optional[int] = None
+    # vLLM's prompt_logprobs: the chain's prefill pass scores its prompt positions (None: a plain prefill); nothing to install
+    prompt_logprobs: Optional[int] = None
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     min_new_tokens: int = 0
@@ -34,6 +36,10 @@ class ChainRequest:
     @property
     def wants_logprobs(self) -> bool:
         return self.logprobs is not None
+
+    @property
+    def wants_prompt_logprobs(self) -> bool:
+        return self.prompt_logprobs is not None
 
     def install(self, engine, slot: int, prompt_ids, grammar: Optional[int] = None) -> None:
         """The request into `slot`, whose reset / truncate / prefix copy cleared the previous chain's, before the first draw.  The

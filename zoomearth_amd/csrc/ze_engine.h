@@ -397,7 +397,17 @@ bool batch_lm_head(ze_engine* e, int li, int n, hipStream_t s);
 void ze_launch_rmsnorm_gather(const bf16_t* x, int ldx, const int* src_rows, const bf16_t* w, bf16_t* y, int ldy, int rows, int cols,
                               float eps, hipStream_t s);
 int ze_score_chunk_rows(const ze_engine* e, int rows);
-int ze_score_rows(ze_engine* e, int n, float* out, hipStream_t s);
+// what a scoring pass writes per scored row beside the log-probability (ze_score_batch_detail); null members are not asked for,
+// a null struct or all members null: k_token_logprob runs, as in ze_score_batch
+struct ze_score_detail_out {
+    int top_n = 0;
+    float* entropy = nullptr;
+    int* rank = nullptr;
+    int* top_ids = nullptr;  // [n, top_n]
+    float* top_lps = nullptr;
+    bool any() const { return entropy || rank || top_ids; }
+};
+int ze_score_rows(ze_engine* e, int n, float* out, const ze_score_detail_out* detail, hipStream_t s);
 // what a batched step sets up before its launches
 int ensure_fragments(ze_engine* e, hipStream_t s);
 void sync_prefix(ze_engine* e, const int32_t* seqs, int n, hipStream_t s);

@@ -837,7 +837,8 @@ extern "C" int ze_score(ze_engine* e, int seq, const int32_t* input_ids, int len
 // path (ze_score.hip) into out_logps, packed in chain order.  Without it nothing more is staged or launched than the prefill's own.
 static int prefill_batch_impl(ze_engine* e, const int32_t* seqs, int n, const int32_t* lens, const int32_t* input_ids,
                               const void* image_embeds, const int32_t* n_image_rows, const int32_t* position_ids,
-                              const int32_t* rope_deltas, const int32_t* score_from, float* out_logps, void* stream) {
+                              const int32_t* rope_deltas, const int32_t* score_from, float* out_logps,
+                              const ze_score_detail_out* detail, void* stream) {
     if (!e || !seqs || !lens || !input_ids || !position_ids || !rope_deltas || n <= 0)
         return ze_fail(e, ZE_ERR_INVALID, "bad prefill arguments");
     const ze_config& c = e->cfg;
@@ -919,7 +920,7 @@ static int prefill_batch_impl(ze_engine* e, const int32_t* seqs, int n, const in
         }
         prefill_logits(e, xr.data(), lo.data(), n, s);
     }
-    if (n_scored > 0) ZE_TRY(ze_score_rows(e, n_scored, out_logps, s));
+    if (n_scored > 0) ZE_TRY(ze_score_rows(e, n_scored, out_logps, detail, s));
     ze_timer_end(e, th, s);
     ZE_KCHECK();
     row0 = 0;
@@ -935,7 +936,7 @@ static int prefill_batch_impl(ze_engine* e, const int32_t* seqs, int n, const in
 extern "C" int ze_prefill_batch(ze_engine* e, const int32_t* seqs, int n, const int32_t* lens, const int32_t* input_ids,
                                 const void* image_embeds, const int32_t* n_image_rows, const int32_t* position_ids,
                                 const int32_t* rope_deltas, void* stream) {
-    return prefill_batch_impl(e, seqs, n, lens, input_ids, image_embeds, n_image_rows, position_ids, rope_deltas, nullptr, nullptr, stream);
+    return prefill_batch_impl(e, seqs, n, lens, input_ids, image_embeds, n_image_rows, position_ids, rope_deltas, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int ze_score_batch(ze_engine* e, const int32_t* seqs, int n, const int32_t* lens, const int32_t* input_ids,
@@ -943,7 +944,21 @@ extern "C" int ze_score_batch(ze_engine* e, const int32_t* seqs, int n, const in
                               const int32_t* rope_deltas, const int32_t* score_from, float* out_logps, void* stream) {
     if (!out_logps) return ze_fail(e, ZE_ERR_INVALID, "ze_score_batch needs an output buffer");
     return prefill_batch_impl(e, seqs, n, lens, input_ids, image_embeds, n_image_rows, position_ids, rope_deltas, score_from, out_logps,
-                              stream);
+                              nullptr, stream);
+}
+
+extern "C" int ze_score_batch_detail(ze_engine* e, const int32_t* seqs, int n, const int32_t* lens, const int32_t* input_ids,
+                                     const void* image_embeds, const int32_t* n_image_rows, const int32_t* position_ids,
+                                     const int32_t* rope_deltas, const int32_t* score_from, int top_n, float* out_logps,
+                                     float* out_entropy, int32_t* out_rank, int32_t* out_top_ids, float* out_top_logprobs, void* stream) {
+    if (!out_logps) return ze_fail(e, ZE_ERR_INVALID, "ze_score_batch_detail needs an output buffer");
+    if (top_n < 0 || top_n > ZE_MAX_TOP_LOGPROBS) return ze_fail(e, ZE_ERR_INVALID, "top_n must be in [0, 20]");
+    if (!out_top_ids != !out_top_logprobs || (out_top_ids && top_n < 1))
+        return ze_fail(e, ZE_ERR_INVALID, "the top arrays are both null, or both set with top_n >= 1");
+    ze_score_detail_out d;
+    d.top_n = out_top_ids ? top_n : 0, d.entropy = out_entropy, d.rank = out_rank, d.top_ids = out_top_ids, d.top_lps = out_top_logprobs;
+    return prefill_batch_impl(e, seqs, n, lens, input_ids, image_embeds, n_image_rows, position_ids, rope_deltas, score_from, out_logps,
+                              &d, stream);
 }
 
 // ================================================================== decode
@@ -2033,6 +2048,21 @@ extern "C" int ze_op_token_logprob(ze_engine* e, const void* logits, int rows, i
         return ze_fail(e, ZE_ERR_INVALID, "bad token_logprob arguments");
     hipSetDevice(e->device);
     ze_launch_token_logprob((const bf16_t*)logits, ld, vocab, targets, out, rows, (hipStream_t)stream);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
+extern "C" int ze_op_score_detail(ze_engine* e, const void* logits, int rows, int vocab, int ld, const int32_t* targets, int top_n,
+                                  float* out_logprob, float* out_entropy, int32_t* out_rank, int32_t* out_top_ids,
+                                  float* out_top_logprobs, void* stream) {
+    if (!e || !logits || !targets || !out_logprob || rows < 0 || vocab <= 0 || ld < vocab || ld % 8)
+        return ze_fail(e, ZE_ERR_INVALID, "bad score_detail arguments");
+    if (top_n < 0 || top_n > ZE_MAX_TOP_LOGPROBS) return ze_fail(e, ZE_ERR_INVALID, "top_n must be in [0, 20]");
+    if (!out_top_ids != !out_top_logprobs || (out_top_ids && top_n < 1))
+        return ze_fail(e, ZE_ERR_INVALID, "the top arrays are both null, or both set with top_n >= 1");
+    hipSetDevice(e->device);
+    ze_launch_score_detail((const bf16_t*)logits, ld, vocab, targets, out_top_ids ? top_n : 0, out_logprob, out_entropy, out_rank,
+                           out_top_ids, out_top_logprobs, rows, (hipStream_t)stream);
     ZE_KCHECK();
     return ZE_OK;
 }

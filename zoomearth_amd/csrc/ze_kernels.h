@@ -346,6 +346,10 @@ void ze_launch_rope_kv_batch(bf16_t* qkv, int n, int heads, int kv_heads, int D,
                              size_t cache_seq_stride, int max_ctx, hipStream_t s);
 void ze_launch_token_logprob(const bf16_t* logits, int ld, int vocab, const int* targets, float* out, int rows,
                              hipStream_t s);
+// k_score_detail (ze_score_detail.hip): k_token_logprob's rows and targets; beside out_lp (the same bits) the entropy, the rank of
+// the target and the top_n first entries of (value descending, id ascending) per row.  out_ent, out_rank, out_ids + out_tlp may be null
+void ze_launch_score_detail(const bf16_t* logits, int ld, int vocab, const int* targets, int top_n, float* out_lp, float* out_ent,
+                            int* out_rank, int* out_ids, float* out_tlp, int rows, hipStream_t s);
 void ze_launch_sample_batch(const float* logits, int vocab, uint8_t* seen_base, float penalty, ze_seq_dev* st,
                             const int* seq_ids, int n, const int* eos_ids, int n_eos, int pad_id, int ignore_eos,
                             int advance_ctx, int sample, int32_t* out_tokens_base, int max_gen, float* ws,

@@ -4,7 +4,8 @@
 //   k_rmsnorm_gather   y[r] = final norm of x[table[r]], dense rows -- the arithmetic of k_rmsnorm (ze_rmsnorm.h), the same bits
 //   lm_head            ze_launch_gemm over the dense rows in chunks of the free MLP workspace, as ze_score chunks its rows:
 //                      bf16 logits, K in sequence on every tile, so a row's logits do not depend on the chunk it falls into
-//   k_token_logprob    fp32 log-softmax pick of the target id, a function of the row alone
+//   k_token_logprob    fp32 log-softmax pick of the target id, a function of the row alone; where ze_score_batch_detail asks for
+//                      entropy, rank or alternatives, k_score_detail (ze_score_detail.hip) in its place: the same pick and more
 // Zero scored rows launch nothing.
 #include "ze_engine.h"
 #include "ze_rmsnorm.h"
@@ -42,7 +43,8 @@ int ze_score_chunk_rows(const ze_engine* e, int rows) {
 }
 
 // out[r] = log_softmax(lm_head(final_norm(e->th[rows[r]])))[targets[r]] for the n entries of e->tscore, after the pass's layers
-int ze_score_rows(ze_engine* e, int n, float* out, hipStream_t s) {
+// detail (ze_score_batch_detail): k_score_detail in k_token_logprob's place, its outputs packed as out
+int ze_score_rows(ze_engine* e, int n, float* out, const ze_score_detail_out* detail, hipStream_t s) {
     if (n <= 0) return ZE_OK;
     const ze_config& c = e->cfg;
     const int H = c.hidden, ldl = (c.vocab + 7) & ~7;
@@ -53,7 +55,14 @@ int ze_score_rows(ze_engine* e, int n, float* out, hipStream_t s) {
     for (int r0 = 0; r0 < n; r0 += chunk) {
         const int m = std::min(chunk, n - r0);
         ze_launch_gemm(ZE_EPI_NONE, e->ty + (size_t)r0 * H, H, e->lm_head, H, nullptr, nullptr, 0, e->ta, ldl, nullptr, m, c.vocab, H, s);
-        ze_launch_token_logprob(e->ta, ldl, c.vocab, targets + r0, out + r0, m, s);
+        if (detail && detail->any()) {
+            const ze_score_detail_out& d = *detail;
+            ze_launch_score_detail(e->ta, ldl, c.vocab, targets + r0, d.top_n, out + r0, d.entropy ? d.entropy + r0 : nullptr,
+                                   d.rank ? d.rank + r0 : nullptr, d.top_ids ? d.top_ids + (size_t)r0 * d.top_n : nullptr,
+                                   d.top_lps ? d.top_lps + (size_t)r0 * d.top_n : nullptr, m, s);
+        } else {
+            ze_launch_token_logprob(e->ta, ldl, c.vocab, targets + r0, out + r0, m, s);
+        }
     }
     return ZE_OK;
 }

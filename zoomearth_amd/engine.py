@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Iterable, Optional, Sequence
+from typing import Iterable, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -39,6 +39,22 @@ def _ptr(t):
 def _i32(a):
     a = np.ascontiguousarray(np.asarray(a, dtype=np.int32))
     return a, a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+class ScoreDetail(NamedTuple):
+    """What score_batch_detail returns per scored position, packed in chain order (chain i: [offsets[i], offsets[i + 1])); the
+    members that were not asked for are None."""
+    logps: torch.Tensor                    # f32 [count]
+    entropy: Optional[torch.Tensor]        # f32 [count]
+    rank: Optional[torch.Tensor]           # int32 [count], 0 = the arg-max
+    top_ids: Optional[torch.Tensor]        # int32 [count, top_n]
+    top_logprobs: Optional[torch.Tensor]   # f32 [count, top_n]
+    offsets: list
+
+    def chain(self, i: int) -> "ScoreDetail":
+        """The entries of chain i alone."""
+        a, b = self.offsets[i], self.offsets[i + 1]
+        return ScoreDetail(*(None if x is None else x[a:b] for x in self[:5]), [0, b - a])
 
 
 class Engine:
@@ -610,6 +626,22 @@ class Engine:
                                                  logits.stride(0), _ptr(targets), _ptr(out), self._stream()))
         return out
 
+    def op_score_detail(self, logits: torch.Tensor, targets: torch.Tensor, top_n: int = 0) -> "ScoreDetail":
+        """The kernel of score_batch_detail alone (ze_op_score_detail) on bf16 logits [rows, vocab] (row stride % 8 == 0): per row
+        the log-probability of its target (the bits of op_token_logprob), the entropy, the target's rank and, for top_n > 0, the
+        top_n first ids of (value descending, id ascending) with their log-probabilities."""
+        assert logits.dtype == torch.bfloat16 and logits.dim() == 2 and logits.stride(1) == 1
+        assert targets.dtype == torch.int32 and targets.is_contiguous()
+        rows, n = int(logits.shape[0]), int(top_n)
+        lp = torch.empty(rows, dtype=torch.float32, device=self.device)
+        ent = torch.empty(rows, dtype=torch.float32, device=self.device)
+        rank = torch.empty(rows, dtype=torch.int32, device=self.device)
+        ids = torch.empty((rows, n), dtype=torch.int32, device=self.device) if n > 0 else None
+        tlp = torch.empty((rows, n), dtype=torch.float32, device=self.device) if n > 0 else None
+        self._check(self.lib.ze_op_score_detail(self.h, _ptr(logits), rows, int(logits.shape[1]), int(logits.stride(0)), _ptr(targets),
+                                                n, _ptr(lp), _ptr(ent), _ptr(rank), _ptr(ids), _ptr(tlp), self._stream()))
+        return ScoreDetail(lp, ent, rank, ids, tlp, [0, rows])
+
     def _batch_args(self, seqs, ids_list, embeds_list, pos_list, deltas):
         """The arguments ze_prefill_batch and ze_score_batch share, from per-chain lists: (n, seqs, lens, ids, embeds, image rows,
         positions, deltas) as the C ABI takes them, and the arrays the pointers point into (alive while the caller holds them)."""
@@ -651,6 +683,36 @@ class Engine:
         out = torch.empty(max(int(offsets[-1]), 1), dtype=torch.float32, device=self.device)
         self._check(self.lib.ze_score_batch(self.h, sp, n, lp, ip, _ptr(emb), nrp, pp, dp, sfp, _ptr(out), self._stream()))
         return out[:int(offsets[-1])], offsets.tolist()
+
+    def score_batch_detail(self, seqs, ids_list, embeds_list, pos_list, deltas, score_from=None, top_n: int = 0,
+                           entropy: bool = False, rank: bool = False) -> "ScoreDetail":
+        """score_batch() with more per scored position (ze_score_batch_detail): `logps` as score_batch gives them, bit for bit, and,
+        where asked, `entropy` (f32), `rank` of the next id (int32, 0 = the arg-max) and the `top_n` (<= MAX_TOP_LOGPROBS) best ids
+        with their log-probabilities (`top_ids` int32 / `top_logprobs` f32, [count, top_n], (value descending, id ascending), places
+        a row cannot fill (-1, -inf)).  All on the device, packed as `logps`; what was not asked for is None.  Nothing asked: the
+        launches of score_batch."""
+        (n, sp, lp, ip, emb, nrp, pp, dp), alive = self._batch_args(seqs, ids_list, embeds_list, pos_list, deltas)
+        lens = alive[1]
+        sf = np.zeros(n, dtype=np.int32) if score_from is None else np.asarray(score_from, dtype=np.int32).reshape(-1)
+        if len(sf) != n:
+            raise ValueError(f"score_from has {len(sf)} entries for {n} chains")
+        sf, sfp = _i32(sf)
+        counts = np.clip(lens.astype(np.int64) - 1 - np.clip(sf, 0, None), 0, None)
+        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        total, tn = int(offsets[-1]), int(top_n)
+        want_top = 0 < tn <= MAX_TOP_LOGPROBS   # (a value outside the range is the library's error)
+
+        def buf(dtype, *shape):
+            return torch.empty((max(total, 1),) + shape, dtype=dtype, device=self.device)
+        out = buf(torch.float32)
+        ent = buf(torch.float32) if entropy else None
+        rk = buf(torch.int32) if rank else None
+        ids = buf(torch.int32, tn) if want_top else None
+        tlp = buf(torch.float32, tn) if want_top else None
+        self._check(self.lib.ze_score_batch_detail(self.h, sp, n, lp, ip, _ptr(emb), nrp, pp, dp, sfp, tn, _ptr(out), _ptr(ent), _ptr(rk),
+                                                   _ptr(ids), _ptr(tlp), self._stream()))
+        cut = lambda x: None if x is None else x[:total]
+        return ScoreDetail(cut(out), cut(ent), cut(rk), cut(ids), cut(tlp), offsets.tolist())
 
     def decode_step(self, seq: int, token: int = -1, want_logits: bool = True):
         logits = torch.empty(self.config.text.vocab_size, dtype=torch.float32, device=self.device) if want_logits else None

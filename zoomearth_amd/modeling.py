@@ -202,14 +202,22 @@ class ZoomEarthForConditionalGeneration:
         score_from = k: columns t < k are not computed and stay 0 (the trainer keeps `[:, prompt_length - 1:]` only, so
         k = prompt_length - 1 skips the final norm, the lm_head and the log-softmax of every prompt position); shape, layout
         and padding rules are unchanged.  The rows run together through `score_sequences`."""
-        e, cfg = self.engine, self.config
+        e = self.engine
+        items, where, shape = self._score_items(input_ids, attention_mask, pixel_values, image_grid_thw, image_keys, score_from)
+        out = torch.zeros(shape, dtype=torch.float32, device=e.device)
+        for (b, cols), lp in zip(where, self.score_sequences(items, share_prefix=share_prefix, min_shared=min_shared)):
+            out[b, torch.as_tensor(cols, device=e.device)] = lp
+        return out.to(input_ids.device) if input_ids.device.type != "cpu" else out.cpu()
+
+    def _score_items(self, input_ids, attention_mask, pixel_values, image_grid_thw, image_keys, score_from):
+        """The ScoreItems of a padded batch, where each lands ((row, columns) per item) and the result shape (B, L - 1)."""
+        cfg = self.config
         ids_cpu = input_ids.cpu().numpy()
         mask = attention_mask.cpu().numpy().astype(bool) if attention_mask is not None else np.ones_like(ids_cpu, bool)
         grids = image_grid_thw.cpu().numpy().tolist() if image_grid_thw is not None else []
         keys = list(image_keys) if image_keys is not None else [None] * len(grids)
         rows_per = [g[0] * g[1] * g[2] for g in grids]
         offs = np.concatenate([[0], np.cumsum(rows_per)]).astype(int)
-        out = torch.zeros((ids_cpu.shape[0], max(ids_cpu.shape[1] - 1, 0)), dtype=torch.float32, device=e.device)
         gi = 0
         items, where = [], []
         for b in range(ids_cpu.shape[0]):
@@ -229,20 +237,48 @@ class ZoomEarthForConditionalGeneration:
             feats = [self._features(pixel_values[offs[i]:offs[i + 1]], grids[i], keys[i]) for i in my]
             items.append(ScoreItem(ids, [grids[i] for i in my], feats, [keys[i] for i in my], first))
             where.append((b, cols))
-        for (b, cols), lp in zip(where, self.score_sequences(items, share_prefix=share_prefix, min_shared=min_shared)):
-            out[b, torch.as_tensor(cols, device=e.device)] = lp
-        return out.to(input_ids.device) if input_ids.device.type != "cpu" else out.cpu()
+        return items, where, (ids_cpu.shape[0], max(ids_cpu.shape[1] - 1, 0))
 
     @torch.no_grad()
-    def score_sequences(self, items, share_prefix: bool = True, min_shared: int = 64):
+    def per_token_details(self, input_ids, attention_mask=None, pixel_values=None, image_grid_thw=None, image_keys=None,
+                          score_from: Optional[int] = None, top_n: int = 0, entropy: bool = True, rank: bool = False,
+                          share_prefix: bool = True, min_shared: int = 64, **kw):
+        """per_token_logps with more per position, from the same passes (`score_sequences` with a request): a dict with `logps`
+        f32 [B, L - 1] (the bits of per_token_logps) and, where asked, `entropy` f32 [B, L - 1] (the policy's per-token entropy a GRPO
+        trainer logs and masks on), `rank` int32 [B, L - 1] and `top_ids` int32 / `top_logprobs` f32 [B, L - 1, top_n].  The padding
+        rules are those of per_token_logps: columns of padded positions and columns before score_from hold 0 (rank -1, top ids -1,
+        top log-probabilities -inf)."""
+        e = self.engine
+        items, where, shape = self._score_items(input_ids, attention_mask, pixel_values, image_grid_thw, image_keys, score_from)
+        out = dict(logps=torch.zeros(shape, dtype=torch.float32, device=e.device))
+        if entropy:
+            out["entropy"] = torch.zeros(shape, dtype=torch.float32, device=e.device)
+        if rank:
+            out["rank"] = torch.full(shape, -1, dtype=torch.int32, device=e.device)
+        if top_n:
+            out["top_ids"] = torch.full(shape + (top_n,), -1, dtype=torch.int32, device=e.device)
+            out["top_logprobs"] = torch.full(shape + (top_n,), float("-inf"), dtype=torch.float32, device=e.device)
+        res = self.score_sequences(items, share_prefix=share_prefix, min_shared=min_shared, top_n=top_n, entropy=entropy, rank=rank)
+        for (b, cols), d in zip(where, res):
+            c = torch.as_tensor(cols, device=e.device)
+            for name in out:
+                out[name][b, c] = getattr(d, name)
+        return {k: (v.to(input_ids.device) if input_ids.device.type != "cpu" else v.cpu()) for k, v in out.items()}
+
+    @torch.no_grad()
+    def score_sequences(self, items, share_prefix: bool = True, min_shared: int = 64, top_n: int = 0, entropy: bool = False,
+                        rank: bool = False):
         """Scores many sequences in as few passes as the engine's limits allow: one f32 tensor per ScoreItem, on the device,
         with the log-probability of the next id at positions item.score_from .. len(ids) - 2 -- the bits `Engine.score` of
         the sequence alone gives there.  The plan (score_plan.plan_score_passes) packs the sequences into `score_batch`
         passes of at most max_prefill_rows rows and max_seqs chains; with share_prefix, sequences with a common prompt (the G
         generations of a sample) prefill it once: one of them whole, in an earlier pass, the others copy its K/V rows
         (`seq_copy_prefix`, bit-identical) and prefill their tails.  The chain slots are scratch: cached chains of generate()
-        are forgotten.  `last_score_stats` tells what the call did."""
+        are forgotten.  `last_score_stats` tells what the call did.
+        top_n / entropy / rank: with any of them the passes go through `score_batch_detail` and every item gets a ScoreDetail
+        (`logps` the same bits; the members not asked for None) instead of the tensor; with none, nothing changes."""
         e, cfg = self.engine, self.config
+        detail = bool(top_n) or entropy or rank
         plan = plan_score_passes([PlanItem(it.ids, list(it.keys) if it.keys is not None else [None] * len(it.grids), it.score_from)
                                   for it in items], e.max_prefill_rows, e.max_seqs, cfg.image_token_id, share_prefix, min_shared)
         self._chains.clear()
@@ -265,11 +301,15 @@ class ZoomEarthForConditionalGeneration:
                 pos_l.append(pos[:, en.start:])
                 dl.append(delta)
                 sf.append(it.score_from - en.start)
-            flat, off = e.score_batch(slots, ids_l, emb_l, pos_l, dl, sf)
+            if detail:
+                det = e.score_batch_detail(slots, ids_l, emb_l, pos_l, dl, sf, top_n=top_n, entropy=entropy, rank=rank)
+                off = det.offsets
+            else:
+                flat, off = e.score_batch(slots, ids_l, emb_l, pos_l, dl, sf)
             stats["rows_per_pass"].append(sum(len(x) for x in ids_l))
             stats["scored_rows"] += off[-1]
             for k, en in enumerate(entries):
-                out[en.item] = flat[off[k]:off[k + 1]]
+                out[en.item] = det.chain(k) if detail else flat[off[k]:off[k + 1]]
         self.last_score_stats = stats
         return out
 

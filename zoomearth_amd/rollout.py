@@ -40,6 +40,7 @@ class Rollout:
     n_prompt1: int = 0               # stage-1 prompt length in tokens
     images: list = field(default_factory=list)   # images of the FINAL prompt, in order
     logps: Optional[object] = None   # f32 tensor: log p of every token of the final sequence from position n_prompt1 on
+    entropies: Optional[object] = None   # f32 tensor aligned with logps: the policy's entropy at those positions (entropies=True)
     # sampled_logps: the decode-time log-probability of every sampled id of the stage (the policy's own `old_per_token_logps` of
     # the completion positions, grpo_trainer.py:660-683), from the step that drew it -- no extra pass
     completion1_logps: List[float] = field(default_factory=list)
@@ -50,7 +51,7 @@ class Rollout:
 def rollout_two_stage(model, processor, samples, num_generations: int = 4, temperature: float = 0.7,
                       max_new_tokens: int = 800, seed: int = 0, max_view: int = 512, with_logps: bool = True,
                       burst: int = 8, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                      min_p: Optional[float] = None, sampled_logps: bool = False) -> List[Rollout]:
+                      min_p: Optional[float] = None, sampled_logps: bool = False, entropies: bool = False) -> List[Rollout]:
     """samples: dicts with `prompt` (the stage-1 prompt text, one `<|vision_start|><|image_pad|><|vision_end|>` block),
     `image` (the tile: DeviceImage or PIL) and `bbox` (the dataset's reference box; empty = non-cropping question).
     top_k / top_p / min_p: the sampling filters of the reference's generation step (GRPOConfig top_k / top_p / min_p,
@@ -58,6 +59,7 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
     sampled_logps: fill completion1_logps / completion2_logps with the log-probabilities the decode steps computed for their own
     samples (the model's distribution, before temperature and filters); independent of with_logps, which scores the final
     sequences with batched passes of their own.
+    entropies: with with_logps, fill Rollout.entropies from the same planned scoring call (no further pass).
     Returns len(samples) * num_generations rollouts, sample-major."""
     sched = ChainScheduler(model, processor, do_sample=True, temperature=temperature, seed=seed, burst=burst,
                            top_k=top_k, top_p=top_p, min_p=min_p, logprobs=0 if sampled_logps else None)
@@ -127,6 +129,10 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
             items.append(ScoreItem(ids, grids, feats, keys, min(max(ro.n_prompt1 - 1, 0), max(len(ids) - 1, 0))))
         # ONE planned call for all rollouts: many sequences per pass, the G generations of a sample share their stage-1 prompt's
         # rows, and only the positions from the stage-1 prompt's end on go through the lm_head (model.score_sequences)
-        for ro, lp in zip(scored, model.score_sequences(items)):
-            ro.logps = lp.cpu()
+        if entropies:
+            for ro, d in zip(scored, model.score_sequences(items, entropy=True)):
+                ro.logps, ro.entropies = d.logps.cpu(), d.entropy.cpu()
+        else:
+            for ro, lp in zip(scored, model.score_sequences(items)):
+                ro.logps = lp.cpu()
     return out

@@ -22,7 +22,7 @@ import contextlib
 import os
 import time
 from collections import OrderedDict, deque
-from dataclasses import dataclass, field
+from dataclasses import InitVar, dataclass, field
 from typing import Any, Callable, List, Optional
 
 import numpy as np
@@ -71,6 +71,11 @@ class Request:
     temperature: Optional[float] = None
     seed: Optional[int] = None
     repetition_penalty: Optional[float] = None
+    # vLLM's `prompt_logprobs=N` (None = off; 0 = the prompt's own tokens only; 1..20 = that many best alternatives as well): the
+    # request's prefill pass scores its prompt positions (ze_score_batch_detail).  An init-only argument kept as a plain attribute,
+    # like its three result lists below: `dataclasses.fields(Request)` stays the list of what every request carries into its decode
+    # steps, and a request that does not ask is the object it was
+    prompt_logprobs: InitVar[Optional[int]] = None
     # filled by the scheduler
     slot: int = -1
     n_prompt: int = 0
@@ -80,6 +85,12 @@ class Request:
     # model's own distribution at its step, and the step's best alternatives as (id, logprob), best first
     token_logprobs: List[float] = field(default_factory=list)
     top_logprobs: List[list] = field(default_factory=list)
+    # with `prompt_logprobs`: one entry per prompt token, there before on_done runs -- the token's log-probability given the ids in
+    # front of it, its 0-based rank, and the best alternatives at its place as (id, logprob), best first.  None at position 0 and
+    # wherever the predicting row was not computed by the request's own pass (a cached prefix of its slot)
+    def __post_init__(self, prompt_logprobs):
+        self.prompt_logprobs = prompt_logprobs
+        self.prompt_token_logprobs, self.prompt_ranks, self.prompt_top_logprobs = [], [], []
 
 
 class GrammarCache:
@@ -457,7 +468,10 @@ class ChainScheduler:
 
     def _plan_sharing(self, prepared):
         """Decides, for every fresh chain of the round, where its leading K/V rows come from; returns the pass-A items."""
-        fresh = [p for p in prepared if p["reuse"] == 0 and p["keys"] and all(k is not None for k in p["keys"])]
+        # (a chain that asked for prompt log-probabilities computes every row itself: it takes no prefix and, within its round, is
+        # no anchor either -- an anchor's prefix goes through a pass of its own; alive or parked it donates like any other chain)
+        fresh = [p for p in prepared if p["reuse"] == 0 and p["keys"] and all(k is not None for k in p["keys"])
+                 and not p["req"]._chain.wants_prompt_logprobs]
         if not fresh:
             return []
         donors = {}   # first image key -> [(slot, ids, keys)]: chains that hold their prompt's K/V rows right now
@@ -602,7 +616,17 @@ class ChainScheduler:
                 else:
                     for it in marked:
                         e.mark_seen(it["req"].slot, it["ids"])
-            e.prefill_batch(slots, ids_l, emb_l, pos_l, dl)
+            asking = [k for k, it in enumerate(ok) if it["final"] and it["req"]._chain.wants_prompt_logprobs]
+            if asking:
+                # the scoring form of the pass: the askers from their first new row on, everybody else from the last row, which
+                # contributes nothing -- their tokens and state are those of prefill_batch
+                sf = [0 if k in asking else len(ids_l[k]) - 1 for k in range(len(ok))]
+                top = max(ok[k]["req"]._chain.prompt_logprobs for k in asking)
+                det = e.score_batch_detail(slots, ids_l, emb_l, pos_l, dl, score_from=sf, top_n=top, rank=True)
+                for k in asking:
+                    self._attach_prompt_logprobs(ok[k]["req"], ok[k]["ids"], ok[k]["reuse"], det.chain(k))
+            else:
+                e.prefill_batch(slots, ids_l, emb_l, pos_l, dl)
         except Exception as ex:
             self._fail_all([it["req"] for it in ok], ex)
             return
@@ -630,6 +654,7 @@ class ChainScheduler:
             sampled=sampled, effective_penalty=penalty,
             top_k=int(pick("top_k") or 0), top_p=float(1.0 if top_p is None else top_p), min_p=float(pick("min_p") or 0.0),
             logprobs=None if logprobs is None else int(logprobs),
+            prompt_logprobs=None if getattr(req, "prompt_logprobs", None) is None else int(req.prompt_logprobs),
             presence_penalty=float(pick("presence_penalty") or 0.0), frequency_penalty=float(pick("frequency_penalty") or 0.0),
             min_new_tokens=int(pick("min_new_tokens") or 0), logit_bias=pick("logit_bias") or {},
             no_repeat_ngram_size=int(getattr(req, "no_repeat_ngram_size", None) or 0),
@@ -670,6 +695,20 @@ class ChainScheduler:
                 self.engine.set_grammar(req.slot, None)
             except Exception:
                 pass
+
+    @staticmethod
+    def _attach_prompt_logprobs(req, ids, reuse: int, det) -> None:
+        """The scored positions of the request's pass into its prompt lists: new row j predicts prompt token reuse + j + 1."""
+        n, N = len(ids), req._chain.prompt_logprobs
+        req._prompt_ids = list(ids)
+        lps, ranks = det.logps.cpu().tolist(), det.rank.cpu().tolist()
+        tids = det.top_ids.cpu().tolist() if det.top_ids is not None else None
+        tlps = det.top_logprobs.cpu().tolist() if det.top_logprobs is not None else None
+        req.prompt_token_logprobs, req.prompt_ranks, req.prompt_top_logprobs = [None] * n, [None] * n, [None] * n
+        for j, (lp, rk) in enumerate(zip(lps, ranks)):
+            t = reuse + j + 1
+            req.prompt_token_logprobs[t], req.prompt_ranks[t] = float(lp), int(rk)
+            req.prompt_top_logprobs[t] = [(int(i), float(v)) for i, v in zip(tids[j][:N], tlps[j][:N]) if int(i) >= 0] if N and tids else []
 
     @staticmethod
     def _attach_logprobs(req, lp, n: int) -> None:

@@ -17,6 +17,9 @@ vLLM's top-level `guided_regex` (a pattern) and `guided_choice` (a list of strin
 automaton on the device masks every step (`zoomearth_amd/grammar.py`); a pattern that does not compile is a 400.
 `logprobs: true` (with `top_logprobs: 0..20`) adds `choices[0].logprobs.content`, one entry per completion token, from the
 decode step's own logits (the model's distribution, before repetition penalty, temperature and filters).
+vLLM's top-level `prompt_logprobs: 0..20` adds a top-level `prompt_logprobs` list: null for the first prompt token, then per token
+`{id: {logprob, rank, decoded_token}}` for the token itself and that many best alternatives, from the request's own prefill pass
+(`ze_score_batch_detail`).
 Prompt: the Qwen2.5-VL chat template (`<|im_start|>role\\n ... <|im_end|>\\n`, an image item becomes
 `<|vision_start|><|image_pad|><|vision_end|>`, a default system turn when the conversation has none, then the
 generation prompt `<|im_start|>assistant\\n`).  temperature 0 / absent -> greedy, else temperature sampling.
@@ -108,6 +111,7 @@ class _Parsed:
     top_p: float = 1.0
     min_p: float = 0.0
     logprobs: Optional[int] = None
+    prompt_logprobs: Optional[int] = None
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     logit_bias: dict = field(default_factory=dict)
@@ -210,6 +214,14 @@ class ChatServer:
             if not (0 <= top <= 20):
                 raise BadRequest(f"top_logprobs must be in [0, 20], got {top}")
         p.logprobs = (int(top or 0) if lp else None)
+        # vLLM's `prompt_logprobs` (0 .. 20): None = no list in the response
+        plp = req.get("prompt_logprobs")
+        if plp is not None:
+            if isinstance(plp, bool) or not isinstance(plp, int):
+                raise BadRequest(f"prompt_logprobs must be an integer, got {plp!r}")
+            if not (0 <= plp <= 20):
+                raise BadRequest(f"prompt_logprobs must be in [0, 20], got {plp}")
+            p.prompt_logprobs = int(plp)
         # OpenAI's `presence_penalty` / `frequency_penalty` ([-2, 2]) and `logit_bias` ({"id": bias in [-100, 100]}, at most 300
         # entries), vLLM's `min_tokens`: applied on the device to every step's logits, greedy requests included
         for name in ("presence_penalty", "frequency_penalty"):
@@ -311,7 +323,27 @@ class ChatServer:
             content.append(item)
         return {"content": content}
 
-    def _response(self, p: _Parsed, out, n_in: int, lp=None) -> dict:
+    def _prompt_logprobs_list(self, p: _Parsed, ids, plp) -> list:
+        """vLLM's `prompt_logprobs`: null for the first prompt token (and wherever the position was not scored), then per token
+        {id: {logprob, rank (1-based), decoded_token}} for the token itself and the N best alternatives at its place.
+        plp = (log-probability, 0-based rank, [(id, logprob), ...] best first) per prompt position."""
+        tok = self.processor.tokenizer
+
+        def entry(i, v, rank):
+            return {"logprob": float(v), "rank": int(rank), "decoded_token": tok.decode([int(i)], skip_special_tokens=False)}
+
+        out = []
+        for t, i in enumerate(ids):
+            if t >= len(plp[0]) or plp[0][t] is None:
+                out.append(None)
+                continue
+            item = {str(int(i)): entry(i, plp[0][t], plp[1][t] + 1)}
+            for place, (j, v) in enumerate((plp[2][t] or [])[: p.prompt_logprobs]):
+                item.setdefault(str(int(j)), entry(j, v, place + 1))
+            out.append(item)
+        return out
+
+    def _response(self, p: _Parsed, out, n_in: int, lp=None, prompt=None) -> dict:
         eos = set(self.model.config.eos_token_ids)
         pad = self.model.config.pad_token_id
         out = out[: p.max_tokens]
@@ -343,6 +375,8 @@ class ChatServer:
             c = res["choices"][0]
             res["choices"][0] = {"index": c["index"], "message": c["message"], "logprobs": self._logprobs_block(p, ids, lp),
                                  "finish_reason": c["finish_reason"]}
+        if p.prompt_logprobs is not None and prompt is not None:
+            res["prompt_logprobs"] = self._prompt_logprobs_list(p, prompt[0], prompt[1:])
         return res
 
     def _run(self, batch):
@@ -377,7 +411,10 @@ class ChatServer:
 
     # ------------------------------------------------------------------ entry points
     def complete(self, req: dict) -> dict:
-        return self._run([self._parse(req)])[0]
+        p = self._parse(req)
+        if p.prompt_logprobs is not None:   # the prompt is scored by the scheduler's prefill pass
+            return self.submit(req).result()
+        return self._run([p])[0]
 
     def complete_many(self, reqs) -> list:
         """The requests as ONE batch (all must be greedy with the model's own repetition penalty; at most max_seqs of them)."""
@@ -391,6 +428,8 @@ class ChatServer:
                              "no_repeat_ngram_size / guided_regex / guided_choice are not batched")
         if len(batch) > self.max_batch:
             raise BadRequest(f"batch of {len(batch)} exceeds max_seqs = {self.max_batch}")
+        if any(p.prompt_logprobs is not None for p in batch):
+            raise BadRequest("requests with prompt_logprobs go through submit() / complete()")
         return self._run(batch)
 
     def submit(self, req: dict):
@@ -421,7 +460,10 @@ class ChatServer:
         from .scheduler import Request
 
         def done(req, tokens, text):
-            p.future.set_result(self._response(p, tokens, req.n_prompt, (req.token_logprobs, req.top_logprobs)))
+            prompt = None
+            if p.prompt_logprobs is not None:
+                prompt = (req._prompt_ids, req.prompt_token_logprobs, req.prompt_ranks, req.prompt_top_logprobs)
+            p.future.set_result(self._response(p, tokens, req.n_prompt, (req.token_logprobs, req.top_logprobs), prompt))
             return None
 
         def failed(req, ex):
@@ -434,7 +476,7 @@ class ChatServer:
             own["repetition_penalty"] = p.repetition_penalty
         return Request(prompt=p.prompt, images=[DeviceImage.from_pil(im, self.model.engine) for im in p.pil_images],
                        max_new_tokens=max(1, min(p.max_tokens, self.model.engine.max_ctx)), on_done=done, on_error=failed,
-                       logprobs=p.logprobs, presence_penalty=p.presence_penalty, frequency_penalty=p.frequency_penalty,
+                       logprobs=p.logprobs, prompt_logprobs=p.prompt_logprobs, presence_penalty=p.presence_penalty, frequency_penalty=p.frequency_penalty,
                        logit_bias=p.logit_bias, min_new_tokens=p.min_tokens, stop_ids=p.stop_records(self.processor.tokenizer),
                        no_repeat_ngram_size=p.no_repeat_ngram_size, guided_regex=p.guided_regex, guided_choice=p.guided_choice, **own)
 
