@@ -187,6 +187,24 @@ int ze_seq_len(ze_engine* e, int seq);
  * prefill computes a row independently of what else shares the pass, so this is bit-identical to prefilling the whole
  * prompt into dst_seq. */
 int ze_seq_copy_prefix(ze_engine* e, int dst_seq, int src_seq, int n_tokens, void* stream);
+/* Parallel sampling (several completions of one prompt: HF's num_return_sequences, vLLM's SamplingParams(n=...), the G generations
+ * of a GRPO group): chain `src_seq`, prefilled and not stepped since, n times.  Every dst_seqs[i] becomes the chain src_seq is --
+ * exactly what a ze_prefill of the whole prompt into that slot would have left -- so ze_chain_begin can follow at once.  One launch
+ * (ze_fork.hip, k_kv_fork) loads every 16-byte piece of the source's cached K/V rows, of its last-position logits row and of its
+ * repetition-penalty set ONCE and stores it to all n destinations: the prompt's marks travel with the chain, the caller does not
+ * re-mark.  Per destination the context length, the rope delta and the split row are the source's; its per-chain requests are
+ * cleared (the caller installs each sibling's own, then draws); the decode attention reads the prompt rows from the source -- or
+ * from the source's own holder when that one covers them -- so one copy of the prompt is streamed for all siblings, and
+ * ze_seq_retire / ze_seq_reset / ze_seq_truncate of the source move the readers as they do for ze_seq_copy_prefix.
+ * Contract: let d be a destination and P a chain that ran ze_prefill / ze_prefill_batch on the whole prompt itself, with the same
+ * marks (ze_seq_mark_seen), the same installed requests and the same sample_stream.  Then the K/V rows, the first token, every later
+ * token and every recorded log-probability of d are bit-identical to P's -- in both decode families, whatever else shares the
+ * bursts, and whether or not the source is still alive.
+ * Everything is checked before anything is enqueued or changed; after an error no chain has changed.  ZE_ERR_INVALID: dst_seqs
+ * NULL or n <= 0, a destination equal to the source or named twice, a source without cached rows, a source whose logits row is
+ * not that of its last cached row any more (a decode step, ze_chain_begin / ze_generate*, ze_seq_truncate or a copy into it ran
+ * since its ze_prefill* / ze_score*).  ZE_ERR_NOTFOUND: a slot out of range.  dst_seqs is a host array. */
+int ze_seq_fork(ze_engine* e, int src_seq, const int32_t* dst_seqs, int n, void* stream);
 
 /* replaces: the prefill forward of Qwen2_5_VLForConditionalGeneration (HF:...:1185-1253,1308-1400): embed,
  * image scatter, M-RoPE, decoder layers, final norm, lm_head on the last position.

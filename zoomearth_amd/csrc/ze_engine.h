@@ -225,6 +225,11 @@ struct ze_engine {
     int32_t* out_tokens = nullptr;
     std::vector<int> ctx_host, delta_host;
     std::vector<int> split_host;   // round 6: the chains' split rows (ze_seq_dev::split), host truth
+    // ze_seq_fork: the chain's row of dlogits holds the logits of its LAST cached row and nothing has drawn from it -- set where a
+    // prefill / scoring pass (or a fork) leaves the chain, cleared by whatever draws for it, steps it or changes its rows; and the
+    // token those passes pushed into the chain state (the prompt's last id)
+    std::vector<char> logits_fresh;
+    std::vector<int> tok_host;
     int* bmate = nullptr;          // [max_seqs] per row of the batched step: the row it shares its prefix parts with, or -1 (upload_batch)
     int live_parts_long = 0;       // 384-key parts of the batch's longest chain under its split (the pipelined attention's grid extent)
     // Shared-prefix hints, (source chain << 16) | P per chain slot.  pfx_host is the truth, kept by whatever call changes it

@@ -283,6 +283,8 @@ extern "C" int ze_engine_create(const ze_config* cfg, int device_id, ze_engine**
     e->prefix_hints = c.max_seqs < 32768 && c.max_ctx < 65536;  // (ze_tune knob 17 = 1: every chain reads its own rows, for A/B runs)
     e->delta_host.assign(c.max_seqs, 0);
     e->split_host.assign(c.max_seqs, 0);
+    e->logits_fresh.assign(c.max_seqs, 0);
+    e->tok_host.assign(c.max_seqs, 0);
     e->graphs.assign(c.max_seqs, nullptr);
     e->graph_key.assign(c.max_seqs, ze_step_key{});
     chk(ze_requests_create(e));

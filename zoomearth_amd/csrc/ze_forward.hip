@@ -391,6 +391,7 @@ extern "C" int ze_seq_reset(ze_engine* e, int seq, void* stream) {
     e->ctx_host[seq] = 0;
     e->delta_host[seq] = 0;
     e->split_host[seq] = 0;
+    e->logits_fresh[seq] = 0;
     prefix_source_gone(e, seq, 0);
     e->pfx_host[seq] = 0;
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)seq * e->cfg.vocab, 0, e->cfg.vocab, s));
@@ -449,6 +450,7 @@ extern "C" int ze_seq_truncate(ze_engine* e, int seq, int keep_len, void* stream
     if (keep_len < 0 || keep_len > e->ctx_host[seq]) return ze_fail(e, ZE_ERR_INVALID, "keep_len out of range");
     hipSetDevice(e->device);
     e->ctx_host[seq] = keep_len;
+    e->logits_fresh[seq] = 0;
     if (keep_len < e->split_host[seq]) e->split_host[seq] = 0;   // (the image block itself is cut: the rest is a chain without one)
     prefix_source_gone(e, seq, keep_len);   // rows from keep_len on will be rewritten
     if ((e->pfx_host[seq] & 0xffff) > keep_len) e->pfx_host[seq] = 0;
@@ -472,6 +474,7 @@ extern "C" int ze_seq_copy_prefix(ze_engine* e, int dst_seq, int src_seq, int n_
     ZE_KCHECK();
     e->ctx_host[dst_seq] = n_tokens;
     e->delta_host[dst_seq] = 0;
+    e->logits_fresh[dst_seq] = 0;
     // the split row travels with the rows: the copy holds the source's first image block iff it reaches past its end (the same
     // tokens, the same split -- however a chain came by its rows)
     e->split_host[dst_seq] = (e->split_host[src_seq] > 0 && e->split_host[src_seq] <= n_tokens) ? e->split_host[src_seq] : 0;
@@ -489,6 +492,55 @@ extern "C" int ze_seq_copy_prefix(ze_engine* e, int dst_seq, int src_seq, int n_
     ZE_HIP(hipMemsetAsync(e->seen + (size_t)dst_seq * c.vocab, 0, c.vocab, s));
     ze_requests_clear(e, dst_seq, s);
     return push_state(e, dst_seq, s, 0, 0, 0);
+}
+
+// The whole chain `src_seq`, n times (include/zoomearth.h): validation first -- after an error nothing was enqueued or changed --
+// then the destination table, ONE launch of k_kv_fork (ze_fork.hip: K/V rows, logits row, seen-set), and per destination the host
+// state ze_seq_copy_prefix keeps, with the rope delta and the prompt's last id handed on (no prefill follows).
+extern "C" int ze_seq_fork(ze_engine* e, int src_seq, const int32_t* dst_seqs, int n, void* stream) {
+    ZE_TRY(check_seq(e, src_seq));
+    if (!dst_seqs || n <= 0) return ze_fail(e, ZE_ERR_INVALID, "fork needs a table of n > 0 destination chains");
+    for (int i = 0; i < n; ++i) {
+        ZE_TRY(check_seq(e, dst_seqs[i]));
+        if (dst_seqs[i] == src_seq) return ze_fail(e, ZE_ERR_INVALID, "source and destination chain are the same");
+        for (int j = 0; j < i; ++j)
+            if (dst_seqs[j] == dst_seqs[i]) return ze_fail(e, ZE_ERR_INVALID, "a destination chain appears twice");
+    }
+    const int rows = e->ctx_host[src_seq];
+    if (rows <= 0) return ze_fail(e, ZE_ERR_INVALID, "the source chain is empty");
+    if (!e->logits_fresh[src_seq])
+        return ze_fail(e, ZE_ERR_INVALID, "the source chain's logits are not those of its last row (it drew, stepped or changed since its prefill)");
+    if (n > e->prefill_rows) return ze_fail(e, ZE_ERR_NOMEM, "more destinations than the id buffer holds");
+    const ze_config& c = e->cfg;
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    // the destination slots travel as kernel arguments into the prefill's id buffer, in stream order behind whatever still reads it
+    // (ze_seq_mark_seen's way: no allocation, no staging buffer to wait for)
+    ze_launch_set_ints(e->tsrc, dst_seqs, n, s);
+    const size_t head_stride = (size_t)c.max_ctx * e->head_dim, seq_stride = (size_t)c.kv_heads * head_stride;
+    ze_launch_kv_fork(e->kcache, e->vcache, (size_t)c.max_seqs * seq_stride, seq_stride, head_stride, c.layers, c.kv_heads, e->head_dim,
+                      src_seq, e->tsrc, n, rows, e->dlogits, e->seen, c.vocab, s);
+    ZE_KCHECK();
+    // the decode attention reads the prompt from the source -- or the source's own holder, when that one covers the rows (the rule
+    // of ze_seq_copy_prefix): one copy of the prompt is streamed for all siblings
+    // (looked up per destination, behind prefix_source_gone: a destination that WAS the source's holder is none afterwards)
+    for (int i = 0; i < n; ++i) {
+        const int d = dst_seqs[i];
+        e->ctx_host[d] = rows;
+        e->delta_host[d] = e->delta_host[src_seq];
+        e->split_host[d] = e->split_host[src_seq];
+        e->tok_host[d] = e->tok_host[src_seq];
+        e->logits_fresh[d] = 1;
+        prefix_source_gone(e, d, 0);
+        if (!e->pfx_copy_ev[d]) ZE_HIP(hipEventCreateWithFlags(&e->pfx_copy_ev[d], hipEventDisableTiming));
+        ZE_HIP(hipEventRecord(e->pfx_copy_ev[d], s));  // (a holder other chains may be pointed at only once this is over)
+        const int hs = e->pfx_host[src_seq];
+        const int holder = (hs != 0 && (hs & 0xffff) >= rows) ? (hs >> 16) : src_seq;
+        e->pfx_host[d] = (e->prefix_hints && rows < 65536 && holder != d) ? ((holder << 16) | rows) : 0;
+        ze_requests_clear(e, d, s);
+        ZE_TRY(push_state(e, d, s, e->tok_host[d], 0, 0));
+    }
+    return ZE_OK;
 }
 
 extern "C" int ze_seq_len(ze_engine* e, int seq) {
@@ -813,6 +865,8 @@ static int prefill_impl(ze_engine* e, int seq, const int32_t* input_ids, int len
                               hipMemcpyDeviceToDevice, s));
     e->ctx_host[seq] = past + len;
     e->delta_host[seq] = rope_delta;
+    e->logits_fresh[seq] = 1;  // (ze_prefill and ze_score alike: the chain is "as after ze_prefill")
+    e->tok_host[seq] = input_ids[len - 1];
     return push_state(e, seq, s, input_ids[len - 1], 0, 0);
 }
 
@@ -927,6 +981,8 @@ static int prefill_batch_impl(ze_engine* e, const int32_t* seqs, int n, const in
     for (int i = 0; i < n; ++i) {
         e->ctx_host[seqs[i]] += lens[i];
         e->delta_host[seqs[i]] = rope_deltas[i];
+        e->logits_fresh[seqs[i]] = 1;
+        e->tok_host[seqs[i]] = input_ids[row0 + lens[i] - 1];
         ZE_TRY(push_state(e, seqs[i], s, input_ids[row0 + lens[i] - 1], 0, 0));
         row0 += lens[i];
     }
@@ -1041,6 +1097,7 @@ extern "C" int ze_decode_step(ze_engine* e, int seq, int token, float* out_logit
     if (token >= c.vocab) return ze_fail(e, ZE_ERR_INVALID, "token id out of range");
     hipStream_t s = (hipStream_t)stream;
     hipSetDevice(e->device);
+    e->logits_fresh[seq] = 0;
     if (token >= 0) ze_launch_set_ints(&(e->st_dev + seq)->token, &token, 1, s);
     const int th = ze_timer_begin(e, 3, s);
     ZE_TRY(ze_enqueue_decode_step(e, seq, 1.0f, 1, false, ze_sample_opts{}, s));
@@ -1147,6 +1204,7 @@ static int op_sample(ze_engine* e, int seq, const float* logits, float repetitio
     const ze_config& c = e->cfg;
     hipSetDevice(e->device);
     // n_gen is set so the sampled token lands in out_tokens[index] of this chain's slot
+    e->logits_fresh[seq] = 0;
     ZE_TRY(push_state(e, seq, s, 0, 0, 0));
     if (index) ze_launch_set_ints(&(e->st_dev + seq)->n_gen, &index, 1, s);
     ze_launch_sample(logits, c.vocab, e->seen + (size_t)seq * c.vocab, repetition_penalty, e->st_dev + seq, e->eos_dev,
@@ -1197,6 +1255,7 @@ static int capture_step(ze_engine* e, F enqueue, hipGraphExec_t* exec) {
 static int first_token(ze_engine* e, int q, float pen, int ign, const ze_sample_opts& so, hipStream_t s) {
     const ze_config& c = e->cfg;
     const float* row = e->dlogits + (size_t)q * c.vocab;
+    e->logits_fresh[q] = 0;  // (the draw marks the seen-set and moves the chain state: no longer what the prefill left)
     ze_launch_sample(ze_requests_rows(e, row, nullptr, q, 1, s), c.vocab, e->seen + (size_t)q * c.vocab, pen, e->st_dev + q, e->eos_dev,
                      c.n_eos, c.pad_token_id, ign, 0, e->out_tokens + (size_t)q * c.max_ctx, e->dsample, so, s);
     ze_requests_after_token(e, row, nullptr, q, 1, s);
@@ -1644,6 +1703,7 @@ extern "C" int ze_decode_batch(ze_engine* e, const int32_t* seqs, int n, const i
     ZE_TRY(ensure_fragments(e, s));
     ZE_TRY(upload_batch(e, seqs, n, s));
     set_live_parts(e, seqs, n, 1);
+    for (int i = 0; i < n; ++i) e->logits_fresh[seqs[i]] = 0;
     if (tokens) {
         for (int i = 0; i < n; ++i) {
             if (tokens[i] >= c.vocab) return ze_fail(e, ZE_ERR_INVALID, "token id out of range");
@@ -1692,7 +1752,7 @@ static int run_burst(ze_engine* e, const std::vector<int>& active, int steps, co
         else
             ZE_TRY(enqueue_decode_batch(e, na, pen, ign, 1, bso, s));
     }
-    for (int q : active) e->ctx_host[q] += steps;
+    for (int q : active) e->ctx_host[q] += steps, e->logits_fresh[q] = 0;
     return ZE_OK;
 }
 

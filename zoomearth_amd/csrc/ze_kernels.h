@@ -287,6 +287,11 @@ void ze_launch_attn_decode_stream(const bf16_t* q, int q_row_stride, const bf16_
 // first n_tokens cached K/V rows of chain src -> chain dst (all layers / kv heads); strides in elements
 void ze_launch_kv_copy_prefix(bf16_t* kcache, bf16_t* vcache, size_t layer_stride, size_t seq_stride, size_t head_stride,
                               int layers, int kv_heads, int D, int src, int dst, int n_tokens, hipStream_t s);
+// fork (ze_fork.hip): the same rows of chain src -> the n chains of the device table dst_dev, each piece loaded once, and with them
+// the source's logits row (f32 [vocab] per slot) and seen-set (u8 [vocab] per slot), in one launch
+void ze_launch_kv_fork(bf16_t* kcache, bf16_t* vcache, size_t layer_stride, size_t seq_stride, size_t head_stride, int layers, int kv_heads,
+                       int D, int src, const int* dst_dev, int n, int n_tokens, float* logits, uint8_t* seen, int vocab, hipStream_t s);
+int ze_kv_fork_blocks(int runs, int n_vec);  // blocks per run of that launch
 
 // ---- sampling
 // Request of one chain slot (ze_seq_set_sampling): 16 bytes, one load per workgroup.  penalty = 0: the slot has no request (a

@@ -571,6 +571,13 @@ class Engine:
         """Chain `dst` becomes the first n_tokens cached tokens of chain `src` (shared prompt prefix: K/V rows copied)."""
         self._check(self.lib.ze_seq_copy_prefix(self.h, dst, src, n_tokens, self._stream()))
 
+    def seq_fork(self, src: int, dsts):
+        """Every chain of `dsts` becomes the prefilled chain `src` -- K/V rows, last-position logits and repetition-penalty marks, in
+        one launch -- exactly as if it had prefilled the whole prompt itself: `chain_begin` can follow at once, after the chain's
+        own requests are installed (the fork clears the slot's previous ones).  `src` must not have drawn a token since its prefill."""
+        a, p = _i32(list(dsts))
+        self._check(self.lib.ze_seq_fork(self.h, int(src), p, len(a), self._stream()))
+
     def seq_len(self, seq: int) -> int:
         return self._check(self.lib.ze_seq_len(self.h, seq))
 

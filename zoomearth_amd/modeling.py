@@ -449,14 +449,23 @@ class ZoomEarthForConditionalGeneration:
     def generate(self, input_ids=None, attention_mask=None, pixel_values=None, image_grid_thw=None,
                  mm_token_type_ids=None, image_keys=None, max_new_tokens: int = 20, do_sample: bool = False,
                  num_beams: int = 1, temperature=None, top_p=None, top_k=None, repetition_penalty=None,
-                 ignore_eos: bool = False, logprobs: Optional[int] = None, **kw):
-        """`logprobs`: None returns the id tensor; an int in 0 .. 20 returns a GenerateOutput with the log-probability of every
+                 ignore_eos: bool = False, logprobs: Optional[int] = None, num_return_sequences: int = 1, **kw):
+        """`num_return_sequences` = k > 1 (sampling only, as in HF): k completions per input row, returned batch-major as HF lays them
+        out -- rows (b0 r0, b0 r1, ..., b1 r0, ...) of a [batch * k, len] result, log-probabilities likewise.  Each input row is
+        prefilled once and forked on the device (`Engine.seq_fork`); the completions are bit for bit those of a call on
+        `input_ids.repeat_interleave(k, 0)`: row b * k + r draws on stream b * k + r.
+        `logprobs`: None returns the id tensor; an int in 0 .. 20 returns a GenerateOutput with the log-probability of every
         generated token under the model's own distribution (the step's fp32 logits, before repetition penalty, temperature
         and filters) and that many best alternatives per step, computed on the device inside the decode step.
         `guided_regex` / `guided_choice` (vLLM's; with `tokenizer=`): every row is held to the pattern by a token automaton on the
         device (zoomearth_amd/grammar.py), set after each chain's prefill where the token rules are set."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not part of the ZoomEarth path (num_beams=1 everywhere)")
+        k = num_return_sequences
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"`num_return_sequences` has to be a strictly positive integer, but is {k}")
+        if k > 1 and not do_sample:
+            raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {k}).")
         if logprobs is not None:
             if isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer)) or not (0 <= logprobs <= MAX_TOP_LOGPROBS):
                 raise ValueError(f"`logprobs` has to be None or an integer in [0, {MAX_TOP_LOGPROBS}], but is {logprobs}")
@@ -473,7 +482,7 @@ class ZoomEarthForConditionalGeneration:
         top_k = top_k if top_k is not None else getattr(gc, "top_k", None)
         top_p = top_p if top_p is not None else getattr(gc, "top_p", None)
         temperature = temperature if temperature is not None else getattr(gc, "temperature", None)
-        if do_sample and top_k == 1:
+        if do_sample and top_k == 1 and k == 1:
             do_sample = False  # a one-token nucleus is the arg-max
         min_p = kw.get("min_p") if kw.get("min_p") is not None else getattr(gc, "min_p", None)
         filt_kw = {}
@@ -502,7 +511,7 @@ class ZoomEarthForConditionalGeneration:
         gid = self.engine.grammar_create(guided) if guided is not None else None
         try:
             return self._generate_rows(_Rows(ids_cpu, mask, grids, keys, offs, pixel_values, input_ids), chain, gid, max_new_tokens,
-                                       ignore_eos, sample_kw, stop_strings, kw.get("tokenizer"))
+                                       ignore_eos, sample_kw, stop_strings, kw.get("tokenizer"), int(k))
         finally:
             if gid is not None:   # the grammar lives for the call: off the chains, then off the engine
                 for slot in range(self.engine.max_seqs):
@@ -510,16 +519,19 @@ class ZoomEarthForConditionalGeneration:
                         self.engine.set_grammar(slot, None)
                 self.engine.grammar_destroy(gid)
 
-    def _generate_rows(self, rows: _Rows, chain: ChainRequest, gid, max_new_tokens, ignore_eos, sample_kw, stop_strings, tokenizer):
+    def _generate_rows(self, rows: _Rows, chain: ChainRequest, gid, max_new_tokens, ignore_eos, sample_kw, stop_strings, tokenizer,
+                       k: int = 1):
         e, cfg = self.engine, self.config
         ids_cpu, mask, grids, keys, offs, pixel_values, input_ids = rows
         pen, logprobs = chain.effective_penalty, chain.logprobs
         gi = 0
         outs = []
         nrows = ids_cpu.shape[0]
-        batched = nrows > 1
-        if batched and nrows > e.max_seqs:
-            raise ValueError(f"batch of {nrows} rows needs max_seqs >= {nrows} (engine has {e.max_seqs})")
+        # k completions per row (num_return_sequences): always the batched path; input row b is prefilled into slot b * k and forked
+        # into the k - 1 slots behind it, so the chains sit in the slots -- and draw on the streams -- of the repeated batch
+        batched = nrows > 1 or k > 1
+        if batched and nrows * k > e.max_seqs:
+            raise ValueError(f"batch of {nrows * k} rows needs max_seqs >= {nrows * k} (engine has {e.max_seqs})")
         if batched:  # every row gets its own chain slot; the decode steps then run as one batch
             self._chains.clear()
             self._next_slot = 0
@@ -538,7 +550,7 @@ class ZoomEarthForConditionalGeneration:
                 raise ValueError("Image features and image tokens do not match")
             my_grids = [grids[i] for i in my]
             my_keys = [keys[i] for i in my]
-            slot, reuse = (b, 0) if batched else self._pick_slot(ids, my_keys)
+            slot, reuse = (b * k, 0) if batched else self._pick_slot(ids, my_keys)
             pre = np.asarray(ids[:reuse]) == cfg.image_token_id
             n_img_reused = int((pre & ~np.concatenate([[False], pre[:-1]])).sum()) if reuse else 0
             feats = [self._features(pixel_values[offs[i]:offs[i + 1]], grids[i], keys[i]) for i in my[n_img_reused:]]
@@ -577,6 +589,12 @@ class ZoomEarthForConditionalGeneration:
             if pen != 1.0:
                 for slot, _, _, _, _, ids in pending:
                     e.mark_seen(slot, ids)
+            if k > 1:   # the marks travel with the fork; every sibling gets its own request installed, like a row of its own
+                for slot, _, _, _, _, ids in list(pending):
+                    e.seq_fork(slot, list(range(slot + 1, slot + k)))
+                    pending += [(slot + r, None, None, None, None, ids) for r in range(1, k)]
+                pending.sort(key=lambda item: item[0])
+                slots = [item[0] for item in pending]
             for slot, _, _, _, _, ids in pending:
                 chain.install(e, slot, ids, gid)
             outs = e.generate_batch(slots, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw)
@@ -596,6 +614,8 @@ class ZoomEarthForConditionalGeneration:
                     outs[b] = list(t[:min(cuts)])
         width = max(len(t) for t in outs)
         pad = cfg.pad_token_id
+        if k > 1:   # (HF's expand_inputs_for_generation: every input row k times, in place)
+            ids_cpu, nrows = np.repeat(ids_cpu, k, axis=0), nrows * k
         res = torch.full((ids_cpu.shape[0], ids_cpu.shape[1] + width), pad, dtype=torch.long)
         res[:, : ids_cpu.shape[1]] = torch.from_numpy(ids_cpu)
         for b, t in enumerate(outs):

@@ -11,7 +11,8 @@ the final prompt + completion ids from the stage-1 prompt length on (`_get_per_t
 :660-683).
 
 Here all G x len(samples) chains advance together (sampled decoding at a temperature, one random stream per chain:
-`seed`, stream = sample * G + g for stage 1 and the same + G * len(samples) for stage 2), stage 2 continues on the chain
+`seed`, stream = sample * G + g for stage 1 and the same + G * len(samples) for stage 2; the G generations of a sample are one
+`Request(n=G)`: one prefill, forked on the device), stage 2 continues on the chain
 slot of stage 1 with the cached stage-1 prompt reused, and scoring runs through `ze_score_batch` (`model.score_sequences`: all
 rollouts in one planned call, scored from the stage-1 prompt's end, the generations of a sample sharing its rows).
 The gradient side of the step is out of scope.
@@ -102,9 +103,20 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
                            stream_id=n * G + ro.sample * G + ro.generation, on_done=done2, on_error=fail(ro))
         return done
 
-    for ro in out:
-        sched.submit(Request(prompt=ro.prompt1, images=[views[ro.sample][1]], max_new_tokens=max_new_tokens,
-                             stream_id=ro.sample * G + ro.generation, on_done=stage1_done(ro), on_error=fail(ro)))
+    # stage 1: ONE request per sample with n = G completions (Request.n): the prompt is prefilled once and forked on the device,
+    # completion g draws on stream sample * G + g.  (More generations than the engine has chain slots go in several such requests.)
+    cap = sched.engine.max_seqs
+    for i in range(n):
+        for g0 in range(0, G, cap):
+            group = out[i * G + g0: i * G + min(g0 + cap, G)]
+
+            def done(req, tokens, text, group=group):
+                return stage1_done(group[req.index])(req, tokens, text)
+
+            def failed(req, ex, group=group):
+                fail(group[req.index])(req, ex)
+            sched.submit(Request(prompt=samples[i]["prompt"], images=[views[i][1]], max_new_tokens=max_new_tokens,
+                                 stream_id=i * G + g0, n=len(group), on_done=done, on_error=failed))
     sched.run()
 
     if with_logps:

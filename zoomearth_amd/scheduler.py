@@ -19,6 +19,7 @@ for every engine of one regime; engines of different regimes agree within bf16 r
 from __future__ import annotations
 
 import contextlib
+import copy
 import os
 import time
 from collections import OrderedDict, deque
@@ -76,6 +77,11 @@ class Request:
     # like its three result lists below: `dataclasses.fields(Request)` stays the list of what every request carries into its decode
     # steps, and a request that does not ask is the object it was
     prompt_logprobs: InitVar[Optional[int]] = None
+    # parallel sampling (vLLM's `n`, HF's `num_return_sequences`): that many completions of the prompt, a sampled request only.  The
+    # prompt is prefilled once and forked on the device (ze_seq_fork); completion i draws on stream `stream_id + i`, and on_done /
+    # on_error run once per completion with a request object of its own that carries `.index` = i and `.parent` = this request (a
+    # follow-up returned for it continues on that completion's slot).  Init-only like prompt_logprobs, and for the same reason
+    n: InitVar[int] = 1
     # filled by the scheduler
     slot: int = -1
     n_prompt: int = 0
@@ -88,8 +94,9 @@ class Request:
     # with `prompt_logprobs`: one entry per prompt token, there before on_done runs -- the token's log-probability given the ids in
     # front of it, its 0-based rank, and the best alternatives at its place as (id, logprob), best first.  None at position 0 and
     # wherever the predicting row was not computed by the request's own pass (a cached prefix of its slot)
-    def __post_init__(self, prompt_logprobs):
+    def __post_init__(self, prompt_logprobs, n=1):
         self.prompt_logprobs = prompt_logprobs
+        self.n, self.index, self.parent = n, 0, None
         self.prompt_token_logprobs, self.prompt_ranks, self.prompt_top_logprobs = [], [], []
 
 
@@ -235,7 +242,7 @@ class ChainScheduler:
         self._features = OrderedDict()     # image key -> ViT features (LRU)
         self._feature_cap = feature_cache
         self.stats = dict(bursts=0, steps=0, chain_steps=0, prefill_rows=0, admitted=0, vit_calls=0, shared_rows=0,
-                          reused_generated_rows=0, overlapped_passes=0)
+                          reused_generated_rows=0, overlapped_passes=0, forked_chains=0, forked_rows=0)
         # Overlap of the two kinds of work on one GPU: while a burst of decode steps runs on the caller's stream
         # (ze_decode_burst_begin: enqueued, not awaited), ONE prefill pass of the admission round -- its ViT call included --
         # is enqueued on a side stream; the burst is collected afterwards (ze_decode_burst_end) and the chains whose pass
@@ -260,12 +267,59 @@ class ChainScheduler:
 
     # ------------------------------------------------------------------ queue
     def submit(self, req: Request) -> None:
+        n = getattr(req, "n", 1)
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not (1 <= n <= self.engine.max_seqs):
+            raise ValueError(f"`n` has to be an integer in [1, {self.engine.max_seqs}] (the engine's chain slots), but is {n!r}")
+        if n > 1:
+            sampled = self.do_sample if req.do_sample is None else bool(req.do_sample)
+            temperature = self.temperature if req.temperature is None else float(req.temperature)
+            if not (sampled and temperature > 0.0):
+                raise ValueError(f"n = {n} completions need a sampled request (do_sample with a temperature > 0): greedy ones are all the same")
         self.waiting.append(req)
+
+    # -- parallel sampling: one request, n completions
+    @staticmethod
+    def _completion(req: Request, i: int) -> Request:
+        """The request object of completion i of `req`: its fields, `index`, `parent`, the stream `stream_id + i`, results of its own."""
+        c = copy.copy(req)
+        c.n, c.index, c.parent, c.stream_id, c.slot = 1, i, req, req.stream_id + i, -1
+        c.tokens, c.text, c.token_logprobs, c.top_logprobs = [], "", [], []
+        return c
+
+    @staticmethod
+    def _take_forks(req):
+        """The siblings `req` (an anchor) still has to fork, each with its pinned slot; they are nobody's afterwards."""
+        forks = getattr(req, "_forks", None) or []
+        if forks:
+            req._forks = []
+        return forks
+
+    def _fork(self, req, ids, keys) -> None:
+        """Behind the anchor's pass, on its stream: its pinned siblings become the chain it is (ze_seq_fork: K/V rows, logits, marks)
+        and wait with it for their first draw.  A failure is the siblings' alone -- slots back, on_error each; the anchor goes on."""
+        forks = self._take_forks(req)
+        if not forks:
+            return
+        try:
+            self.engine.seq_fork(req.slot, [k.slot for k in forks])
+        except Exception as ex:
+            self._fail_all(forks, ex)
+            return
+        for k in forks:
+            k._chain, k.n_prompt = req._chain, req.n_prompt
+            if req._chain.wants_prompt_logprobs:   # computed once, by the anchor's pass: shared by reference
+                k._prompt_ids = req._prompt_ids
+                k.prompt_token_logprobs, k.prompt_ranks, k.prompt_top_logprobs = (req.prompt_token_logprobs, req.prompt_ranks,
+                                                                                  req.prompt_top_logprobs)
+            self._ready.append((k, ids, keys))
+        self.stats["forked_chains"] += len(forks)
+        self.stats["forked_rows"] += len(forks) * len(ids)
 
     def pending_requests(self):
         """Every request the scheduler holds, whatever its state (a caller that gives up on the engine fails them all)."""
         reqs = [l.req for l in self.live.values()] + list(self.waiting) + [r for r, _, _ in self._ready]
         reqs += [it["req"] for g in list(self._groups) + [self._carry] for it in g if it.get("final", True)]
+        reqs += [k for r in list(reqs) for k in (getattr(r, "_forks", None) or [])]   # (siblings that wait for their anchor's pass)
         return reqs
 
     def busy(self) -> bool:
@@ -366,6 +420,12 @@ class ChainScheduler:
                 req.slot = self.free.pop()
             self.waiting.popleft()
             last_img = self._first_image_key(req)
+            if getattr(req, "n", 1) > 1:
+                # n completions: completion 0 is the anchor -- it takes the slot and goes through the round like any request --
+                # and carries the others until its pass has run (below: slots; _prefill: the fork)
+                kids = [self._completion(req, i) for i in range(req.n)]
+                kids[0].slot, kids[0]._forks = req.slot, kids[1:]
+                req = kids[0]
             try:
                 req._chain = self._resolve(req)   # once per request: every later stage of the chain's life reads it
                 inp = self.processor(text=[req.prompt], images=list(req.images) or None, return_tensors="pt")
@@ -391,6 +451,21 @@ class ChainScheduler:
                 prepared.append(dict(req=req, ids=ids, grids=grids, keys=keys, reuse=reuse, n_reused=n_reused, copy_from=None,
                                      upto=len(ids), final=True))
                 rows_planned += len(ids) - reuse
+                if getattr(req, "_forks", None):
+                    # The siblings' slots leave `free` NOW and are in nobody's reach until the fork takes them: a slot that is
+                    # only remembered while it sits in `free` is handed to the next newcomer (free.pop() is LIFO; items carried
+                    # over chunks of admit_chunk_rows live across several calls).  Siblings without a slot become ordinary
+                    # requests of the same prompt and stream at the head of the queue: the shared-prefix path brings them in
+                    # later, with the same bits.
+                    forks, overflow = [], []
+                    for k in req._forks:
+                        if self.free:
+                            k.slot = self.free.pop()
+                            forks.append(k)
+                        else:
+                            overflow.append(k)
+                    req._forks = forks
+                    self.waiting.extendleft(reversed(overflow))
             except Exception as ex:  # a malformed request must not take the batch down
                 self._fail(req, ex)
         if not prepared and not self._carry:
@@ -638,6 +713,7 @@ class ChainScheduler:
             req, ids, keys = it["req"], it["ids"], it["keys"]
             req.n_prompt = len(ids)
             self._ready.append((req, tuple(ids), tuple(keys)))
+            self._fork(req, tuple(ids), tuple(keys))
 
     def _resolve(self, req) -> ChainRequest:
         """The request's optional fields merged with the scheduler's defaults: its own value, else the scheduler's, else off.  A
@@ -893,6 +969,9 @@ class ChainScheduler:
             req.slot = -1
 
     def _fail(self, req: Request, ex: Exception) -> None:
+        forks = self._take_forks(req)
+        if forks:   # an anchor takes the siblings it still carries with it: one error per completion
+            return self._fail_all([req] + forks, ex)
         self._release(req)
         if req.on_error:
             req.on_error(req, ex)
@@ -902,6 +981,7 @@ class ChainScheduler:
     def _fail_all(self, reqs, ex: Exception) -> None:
         """Every request of `reqs` gets the error; the ones without an `on_error` re-raise it once all slots are back."""
         unhandled = False
+        reqs = [r for req in reqs for r in [req] + self._take_forks(req)]
         for req in reqs:
             self._release(req)
             if req.on_error:

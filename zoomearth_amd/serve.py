@@ -6,7 +6,11 @@
 Request: the subset that client sends -- `messages` with `role` in {system, user, assistant} and `content` either a
 string or a list of `{"type": "text", "text": ...}` / `{"type": "image_url", "image_url": {"url": "data:image/...;
 base64,..."}}` items, plus `max_tokens`, `temperature`, `seed`, `top_p` and the vLLM extensions `top_k` (-1 / 0 = off) and
-`min_p` (`n` must be 1, `stream` is not offered); the three filters apply to sampled requests, each request its own.
+`min_p` (`stream` is not offered); the three filters apply to sampled requests, each request its own.
+`n` in [1, 16]: that many completions of the prompt, sampled requests only (n > 1 at temperature 0 / absent is a 400, vLLM's rule).
+The prompt is prefilled once and forked on the device (`ze_seq_fork`); the response carries `n` choices with `index` 0 .. n-1, each
+with its own `finish_reason`, `logprobs` and stop-string cut; choice i draws from random stream i of the request's `seed` (choice 0
+is what n = 1 returns); `usage.completion_tokens` sums the choices, `prompt_tokens` counts once, `prompt_logprobs` appears once.
 vLLM's `repetition_penalty` (finite, > 0; absent = the checkpoint's generation_config) is per request too.
 `presence_penalty` / `frequency_penalty` ([-2, 2]), `logit_bias` (at most 300 `"id": bias` entries in [-100, 100]) and vLLM's
 `min_tokens` adjust every step's logits on the device, each request its own values, greedy requests included.
@@ -42,6 +46,7 @@ from dataclasses import dataclass, field
 from typing import Any, Optional
 
 DEFAULT_SYSTEM = "You are a helpful assistant."
+MAX_N = 16   # completions per request (`n`)
 IMAGE_PLACEHOLDER = "<|vision_start|><|image_pad|><|vision_end|>"
 
 
@@ -121,6 +126,7 @@ class _Parsed:
     no_repeat_ngram_size: int = 0
     guided_regex: Optional[str] = None
     guided_choice: Optional[list] = None
+    n: int = 1
     future: Any = None
 
     def guided(self) -> bool:
@@ -170,14 +176,22 @@ class ChatServer:
     def _parse(self, req: dict) -> _Parsed:
         if req.get("stream"):
             raise BadRequest("stream=true is not offered")
-        if int(req.get("n", 1) or 1) != 1:
-            raise BadRequest("n must be 1")
+        n = req.get("n")
+        if n is not None and (isinstance(n, bool) or not isinstance(n, int)):
+            raise BadRequest(f"n must be an integer, got {n!r}")
+        if n is not None and not (1 <= n <= MAX_N):
+            raise BadRequest(f"n must be in [1, {MAX_N}], got {n}")
         p = _Parsed(req)
+        p.n = int(n or 1)
         p.prompt, p.pil_images = build_prompt(req.get("messages"))
         p.max_tokens = int(req.get("max_tokens") or req.get("max_completion_tokens") or 1024)
         t = req.get("temperature")
         p.sample = t is not None and float(t) > 0.0
         p.temperature = float(t) if p.sample else None
+        if p.n > self.max_batch:
+            raise BadRequest(f"n = {p.n} exceeds the engine's {self.max_batch} chain slots")
+        if p.n > 1 and not p.sample:
+            raise BadRequest(f"n = {p.n} needs temperature > 0: greedy completions would all be the same")
         p.seed = int(req.get("seed") or 0)
         # vLLM's `repetition_penalty`: None = the model's own (generation_config)
         rp = req.get("repetition_penalty")
@@ -379,6 +393,17 @@ class ChatServer:
             res["prompt_logprobs"] = self._prompt_logprobs_list(p, prompt[0], prompt[1:])
         return res
 
+    @staticmethod
+    def _merge_choices(parts, n_in: int) -> dict:
+        """The one-choice responses of a request's n completions, in index order, as one response: n indexed choices, the usage
+        summed over them with the prompt counted once; id, created and the top-level prompt_logprobs are the first one's."""
+        res = parts[0]
+        for i, r in enumerate(parts[1:], 1):
+            res["choices"].append({**r["choices"][0], "index": i})
+        done = sum(r["usage"]["completion_tokens"] for r in parts)
+        res["usage"] = {"prompt_tokens": n_in, "completion_tokens": done, "total_tokens": n_in + done}
+        return res
+
     def _run(self, batch):
         """One processor + generate call for the parsed requests of `batch` (all greedy without logit adjustments, or a single
         request: generate() gives every row of a call the same sampling settings and adjustments)."""
@@ -412,7 +437,7 @@ class ChatServer:
     # ------------------------------------------------------------------ entry points
     def complete(self, req: dict) -> dict:
         p = self._parse(req)
-        if p.prompt_logprobs is not None:   # the prompt is scored by the scheduler's prefill pass
+        if p.prompt_logprobs is not None or p.n > 1:   # the scheduler's work: the scoring prefill pass, the fork of n completions
             return self.submit(req).result()
         return self._run([p])[0]
 
@@ -428,8 +453,8 @@ class ChatServer:
                              "no_repeat_ngram_size / guided_regex / guided_choice are not batched")
         if len(batch) > self.max_batch:
             raise BadRequest(f"batch of {len(batch)} exceeds max_seqs = {self.max_batch}")
-        if any(p.prompt_logprobs is not None for p in batch):
-            raise BadRequest("requests with prompt_logprobs go through submit() / complete()")
+        if any(p.prompt_logprobs is not None or p.n > 1 for p in batch):
+            raise BadRequest("requests with prompt_logprobs or n > 1 go through submit() / complete()")
         return self._run(batch)
 
     def submit(self, req: dict):
@@ -455,15 +480,20 @@ class ChatServer:
     def _request(self, p: _Parsed):
         """The scheduler's Request of a parsed one: its fields under the scheduler's names, the budget clamped to the KV capacity
         (per request: never fails its batch), its future resolved by the callbacks.  A sampled request carries its own temperature
-        and seed, and random stream 0: what it would draw running alone."""
+        and seed, and random stream 0: what it would draw running alone.  With n > 1 the scheduler calls `done` once per completion
+        (stream `index`); the future resolves with the n-th."""
         from .image import DeviceImage
         from .scheduler import Request
 
+        parts = [None] * p.n
+
         def done(req, tokens, text):
             prompt = None
-            if p.prompt_logprobs is not None:
+            if p.prompt_logprobs is not None and req.index == 0:
                 prompt = (req._prompt_ids, req.prompt_token_logprobs, req.prompt_ranks, req.prompt_top_logprobs)
-            p.future.set_result(self._response(p, tokens, req.n_prompt, (req.token_logprobs, req.top_logprobs), prompt))
+            parts[req.index] = self._response(p, tokens, req.n_prompt, (req.token_logprobs, req.top_logprobs), prompt)
+            if all(r is not None for r in parts) and not p.future.done():
+                p.future.set_result(parts[0] if p.n == 1 else self._merge_choices(parts, req.n_prompt))
             return None
 
         def failed(req, ex):
@@ -478,7 +508,7 @@ class ChatServer:
                        max_new_tokens=max(1, min(p.max_tokens, self.model.engine.max_ctx)), on_done=done, on_error=failed,
                        logprobs=p.logprobs, prompt_logprobs=p.prompt_logprobs, presence_penalty=p.presence_penalty, frequency_penalty=p.frequency_penalty,
                        logit_bias=p.logit_bias, min_new_tokens=p.min_tokens, stop_ids=p.stop_records(self.processor.tokenizer),
-                       no_repeat_ngram_size=p.no_repeat_ngram_size, guided_regex=p.guided_regex, guided_choice=p.guided_choice, **own)
+                       no_repeat_ngram_size=p.no_repeat_ngram_size, guided_regex=p.guided_regex, guided_choice=p.guided_choice, n=p.n, **own)
 
     def _dispatch(self):
         """Running-batch admission (the concurrency model of the reference's src/eval/infer_vllm.py:244-271, where the
