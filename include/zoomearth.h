@@ -206,6 +206,45 @@ int ze_seq_copy_prefix(ze_engine* e, int dst_seq, int src_seq, int n_tokens, voi
  * since its ze_prefill* / ze_score*).  ZE_ERR_NOTFOUND: a slot out of range.  dst_seqs is a host array. */
 int ze_seq_fork(ze_engine* e, int src_seq, const int32_t* dst_seqs, int n, void* stream);
 
+/* ---- prefix cache: a pool of K/V blocks that outlives its chains (vLLM's enable_prefix_caching; zoomearth_amd/csrc/ze_prefix.hip).
+ * ze_seq_copy_prefix and ze_seq_fork share rows only while a chain that holds them is alive.  The pool keeps rows without a chain
+ * slot: n_blocks blocks, each `block_rows` consecutive cached rows of one chain for every layer and KV head, K and V both
+ * (block_rows * 2 * layers * kv_heads * 256 bytes).  The engine stores and returns bits; WHICH tokens a block holds, which block is
+ * free and which one is evicted is the caller's business (zoomearth_amd/prefix_cache.py).  A prefix's K/V rows depend on the
+ * prefix alone, so loading them is bit-identical to prefilling them -- the standard of ze_seq_copy_prefix.
+ * One pool per engine.  block_rows: a multiple of 8, at most max_ctx.  ZE_ERR_INVALID: a bad size, or the engine has a pool already;
+ * ZE_ERR_NOMEM: the device allocation failed (the engine stays usable, without a pool). */
+int ze_prefix_pool_create(ze_engine* e, int n_blocks, int block_rows);
+/* Waits for the saves and loads in flight, then frees the pool (none: nothing happens). */
+int ze_prefix_pool_destroy(ze_engine* e);
+/* The pool's sizes (0, 0 without a pool) and the engine's weight generation; any of the three may be NULL.  The generation moves
+ * whenever the K/V rows of given tokens stop being what they were: ze_load_weight, ze_weights_fill_synthetic, ze_weights_invalidate,
+ * ze_weights_broadcast, ze_weights_quantize_fp8, a change of ze_set_fp8_activations, a change of the decode family
+ * (ze_set_decode_regime).  Every block then counts as unsaved: a refreshed policy never reads rows of the old one. */
+int ze_prefix_pool_info(ze_engine* e, int* n_blocks, int* block_rows, unsigned* generation);
+/* Rows [row0, row0 + n * block_rows) of chain `seq` go into the n pool blocks blocks[0 .. n) (a host array; any ids in any order), in
+ * one launch (k_kv_save).  ZE_ERR_INVALID: no pool, row0 no multiple of block_rows, rows past ze_seq_len(seq), a block named twice;
+ * ZE_ERR_NOTFOUND: a block id or the slot out of range.  Checked before anything is enqueued or changed.
+ * Stream order: the caller runs the save behind whatever wrote the rows (on the stream of those decode steps, or once they are
+ * over) and ahead of whatever overwrites the slot next -- as for the source of ze_seq_copy_prefix.  The engine records an event
+ * behind every save, and the save itself waits, on `stream`, for every earlier save and for the loads still reading these blocks. */
+int ze_prefix_save(ze_engine* e, int seq, int row0, const int32_t* blocks, int n, void* stream);
+/* The first n_rows rows of the chain whose blocks are blocks[0 .. n_blocks), in order, become rows [0, n_rows) of the n chains
+ * dst_seqs[0 .. n), in one launch (k_kv_load: every 16-byte piece is read once and stored n times); n_rows may end inside the last
+ * block, whose remaining rows are written nowhere.  Afterwards the destinations are exactly what a prefill of those rows into
+ * dst_seqs[0], then ze_seq_copy_prefix(dst_seqs[i], dst_seqs[0], n_rows) for every i >= 1, would have left: the context length, the
+ * cleared repetition-penalty set and per-chain requests, the split row (`split_row`: the row behind the first image block of those
+ * tokens, 0 = none -- the caller knows the tokens), and the prefix hint of destinations 1 .. n-1, which names destination 0 -- the
+ * decode attention streams one copy for siblings admitted together; ze_seq_retire / ze_seq_reset / ze_seq_truncate move the
+ * readers as ever.  A prefill of the tail follows (ze_prefill / ze_prefill_batch with the chain's rope delta).
+ * ZE_ERR_INVALID: no pool, not (n_blocks - 1) * block_rows < n_rows <= n_blocks * block_rows, n_rows > max_ctx, split_row outside
+ * [0, n_rows], a destination named twice, a block that was not saved under the current generation; ZE_ERR_NOTFOUND: a block id or
+ * a slot out of range.  Checked before anything is enqueued or changed (the ze_seq_fork contract).
+ * Stream order: the load runs on the admission stream ahead of the tail's prefill; it waits, on `stream`, for the saves that wrote
+ * its blocks and for every earlier load, and a later save into one of these blocks waits for it. */
+int ze_prefix_load(ze_engine* e, const int32_t* blocks, int n_blocks, int n_rows, int split_row, const int32_t* dst_seqs, int n,
+                   void* stream);
+
 /* replaces: the prefill forward of Qwen2_5_VLForConditionalGeneration (HF:...:1185-1253,1308-1400): embed,
  * image scatter, M-RoPE, decoder layers, final norm, lm_head on the last position.
  * input_ids: host int32 [len] = the NEW tokens appended after the `ze_seq_len` cached ones (image placeholders

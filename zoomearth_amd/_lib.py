@@ -109,6 +109,11 @@ _SIGS = {
     "ze_seq_len": (C.c_int, [_P, C.c_int]),
     "ze_seq_copy_prefix": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "ze_seq_fork": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_int, _P]),
+    "ze_prefix_pool_create": (C.c_int, [_P, C.c_int, C.c_int]),
+    "ze_prefix_pool_destroy": (C.c_int, [_P]),
+    "ze_prefix_pool_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
+    "ze_prefix_save": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _P]),
+    "ze_prefix_load": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _P]),
     "ze_prefill": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_int, _P, C.c_int, C.POINTER(C.c_int32), C.c_int,
                              _P, _P]),
     "ze_score": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_int, _P, C.c_int, C.POINTER(C.c_int32), C.c_int,

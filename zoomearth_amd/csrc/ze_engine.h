@@ -171,6 +171,24 @@ struct ze_requests {
     ze_grammar_bufs gr_bufs() const { return ze_grammar_bufs{gr_dev, gr_desc}; }
 };
 
+// Prefix cache (ze_prefix.hip): a pool of K/V blocks independent of the chain slots.  data: [n_blocks][layers][kv_heads][K|V]
+// [block_rows][head_dim] bf16.  Per block, host truth: the generation it was saved under (0 = never; ze_engine::prefix_generation),
+// the number of the save that wrote it and of the last load that reads it.  saves / loads: the events behind the last ZE_PREFIX_RING
+// calls of each kind (call number -> entry number % ring), what the stream order of ze_prefix_save / ze_prefix_load is built from;
+// ids_save / ids_load: the device lists their kernels read (ids_load: a call's block ids, then its destination slots; ids_cap + max_seqs ints).
+enum { ZE_PREFIX_RING = 64 };
+struct ze_prefix_pool {
+    int n_blocks = 0, block_rows = 0, ids_cap = 0;
+    size_t block_elems = 0;
+    bf16_t* data = nullptr;
+    int *ids_save = nullptr, *ids_load = nullptr;
+    struct call { hipEvent_t ev = nullptr; uint64_t seq = 0; };
+    std::vector<call> saves, loads;
+    uint64_t n_saves = 0, n_loads = 0;
+    std::vector<unsigned> saved_gen;
+    std::vector<uint64_t> saved_seq, read_seq;
+};
+
 struct ze_engine {
     ze_config cfg{};
     int device = 0;
@@ -243,6 +261,10 @@ struct ze_engine {
     std::vector<hipEvent_t> pfx_copy_ev;
     bool prefix_hints = true;      // the hint fits its 16 + 16 bits (ze_tune knob 17 = 1: every chain reads its own rows)
     ze_requests req;  // per-chain requests (above)
+    // prefix cache: the pool (null = none) and the generation of the weights -- bumped by whatever changes what a K/V row of given
+    // tokens would be (ze_prefix_weights_changed), so that a block saved under another generation is never loaded
+    ze_prefix_pool* prefix_pool = nullptr;
+    unsigned prefix_generation = 1;
     // captured single-chain decode step per slot, and the key it was captured under (ze_step_key_of)
     std::vector<hipGraphExec_t> graphs;
     std::vector<ze_step_key> graph_key;
@@ -418,4 +440,12 @@ int ensure_fragments(ze_engine* e, hipStream_t s);
 void sync_prefix(ze_engine* e, const int32_t* seqs, int n, hipStream_t s);
 void upload_mates(ze_engine* e, const int32_t* seqs, int n, hipStream_t s);
 void set_live_parts(ze_engine* e, const int32_t* seqs, int n, int steps);
+// chain bookkeeping shared with ze_prefix.hip: the readers of rows >= keep of chain `seq` move to another holder; the chain state
+// of `seq` goes to the device in stream order
+void prefix_source_gone(ze_engine* e, int seq, int keep);
+int push_state(ze_engine* e, int seq, hipStream_t s, int token, int n_gen, int finished);
+// ---- prefix cache (ze_prefix.hip)
+void ze_prefix_pool_free(ze_engine* e);   // (ze_engine_destroy: the device is idle)
+// the K/V rows of given tokens are no longer what they were: every pool block counts as unsaved from now on
+inline void ze_prefix_weights_changed(ze_engine* e) { ++e->prefix_generation; }
 #pragma GCC visibility pop

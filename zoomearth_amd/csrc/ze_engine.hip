@@ -16,6 +16,7 @@ static int ze_bound_device = -1;  // the launch-policy caches (hipFuncSetAttribu
 // quantises again) and captured decode graphs, which bake the weight pointers in, are re-captured.
 void ze_weights_changed(ze_engine* e) {
     e->frag_ready = false;
+    ze_prefix_weights_changed(e);
     if (e->fp8_ready) {
         e->fp8_ready = false;
         e->fp8_act = false;  // goes with the fp8 weights: the caller quantises and switches it on again
@@ -452,6 +453,7 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
     for (void* p : dev)
         if (p) hipFree(p);
     ze_requests_free(e);
+    ze_prefix_pool_free(e);
     if (e->pfx_dev) hipFree(e->pfx_dev);
     if (e->arena_p) hipFree(e->arena_p);
     if (e->qkv_epi_dev) hipFree(e->qkv_epi_dev);

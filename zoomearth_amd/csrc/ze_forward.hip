@@ -339,7 +339,7 @@ static bool prefix_copy_done(ze_engine* e, int d) {
 // the one among them with the longest prefix WHOSE COPY HAS LANDED (its own rows hold the same bits), which goes back to reading
 // its own rows; readers it does not cover -- and all of them when no copy has landed yet -- go back to their own rows as well
 // (a chain joins a decode step only behind its own prefill pass, so its own rows are always good by then)
-static void prefix_source_gone(ze_engine* e, int seq, int keep) {
+void prefix_source_gone(ze_engine* e, int seq, int keep) {
     int leader = -1, lead_p = 0;
     const int n = (int)e->pfx_host.size();
     for (int d = 0; d < n; ++d) {
@@ -369,7 +369,7 @@ void sync_prefix(ze_engine* e, const int32_t* seqs, int n, hipStream_t s) {
     if (m) ze_launch_scatter_ints(e->pfx_dev, idx, val, m, s);
 }
 
-static int push_state(ze_engine* e, int seq, hipStream_t s, int token, int n_gen, int finished) {
+int push_state(ze_engine* e, int seq, hipStream_t s, int token, int n_gen, int finished) {
     ze_seq_dev st;
     memset(&st, 0, sizeof(st));
     st.ctx = e->ctx_host[seq];
@@ -2499,6 +2499,7 @@ extern "C" int ze_weights_quantize_fp8(ze_engine* e, void* stream) {
     ZE_HIP(hipStreamSynchronize(s));
     e->fp8_ready = true;
     e->frag_ready = false;  // the bf16 copies were replaced by the dequantised values
+    ze_prefix_weights_changed(e);
     ++ze_tune_epoch;  // captured decode steps hold the bf16 streams
     return ZE_OK;
 }
@@ -2510,6 +2511,7 @@ extern "C" int ze_set_fp8_activations(ze_engine* e, int on) {
     if (e->fp8_act != (on != 0)) {
         e->fp8_act = on != 0;
         ++ze_tune_epoch;  // captured decode steps bake the choice of kernels in
+        ze_prefix_weights_changed(e);   // (the passes compute other K/V rows from now on)
     }
     return ZE_OK;
 }
@@ -2543,7 +2545,10 @@ extern "C" int ze_set_decode_regime(ze_engine* e, int regime) {
     if (regime != e->decode_regime) {
         const bool was = e->wide_regime();
         e->decode_regime = regime;
-        if (was != e->wide_regime()) e->frag_ready = false;  // the other family's weight copies are built on its first step
+        if (was != e->wide_regime()) {
+            e->frag_ready = false;         // the other family's weight copies are built on its first step
+            ze_prefix_weights_changed(e);  // (rows the decode steps wrote are the other family's, equal within bf16 rounding only)
+        }
         ++ze_tune_epoch;  // captured batched steps bake the kernel family in
     }
     return e->wide_regime() ? 1 : 0;

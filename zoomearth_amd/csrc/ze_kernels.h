@@ -292,6 +292,13 @@ void ze_launch_kv_copy_prefix(bf16_t* kcache, bf16_t* vcache, size_t layer_strid
 void ze_launch_kv_fork(bf16_t* kcache, bf16_t* vcache, size_t layer_stride, size_t seq_stride, size_t head_stride, int layers, int kv_heads,
                        int D, int src, const int* dst_dev, int n, int n_tokens, float* logits, uint8_t* seen, int vocab, hipStream_t s);
 int ze_kv_fork_blocks(int runs, int n_vec);  // blocks per run of that launch
+// prefix cache (ze_prefix.hip): rows [row0, row0 + nb * block_rows) of chain seq -> the nb pool blocks of the device list ids_dev, and
+// the first n_rows rows of the listed blocks -> rows from 0 on of the n chains of dst_dev (each piece loaded once); the pool is
+// [block][layer][kv head][K|V][block_rows][D]
+void ze_launch_kv_save(const bf16_t* kcache, const bf16_t* vcache, size_t layer_stride, size_t seq_stride, size_t head_stride, int layers,
+                       int kv_heads, int D, int seq, int row0, bf16_t* pool, const int* ids_dev, int nb, int block_rows, hipStream_t s);
+void ze_launch_kv_load(bf16_t* kcache, bf16_t* vcache, size_t layer_stride, size_t seq_stride, size_t head_stride, int layers, int kv_heads,
+                       int D, const bf16_t* pool, const int* ids_dev, int block_rows, const int* dst_dev, int n, int n_rows, hipStream_t s);
 
 // ---- sampling
 // Request of one chain slot (ze_seq_set_sampling): 16 bytes, one load per workgroup.  penalty = 0: the slot has no request (a

@@ -578,6 +578,32 @@ class Engine:
         a, p = _i32(list(dsts))
         self._check(self.lib.ze_seq_fork(self.h, int(src), p, len(a), self._stream()))
 
+    # -- prefix cache: the engine's pool of K/V blocks (zoomearth_amd/prefix_cache.py decides what is in them)
+    def prefix_pool_create(self, n_blocks: int, block_rows: int) -> None:
+        self._check(self.lib.ze_prefix_pool_create(self.h, int(n_blocks), int(block_rows)))
+
+    def prefix_pool_destroy(self) -> None:
+        self._check(self.lib.ze_prefix_pool_destroy(self.h))
+
+    def prefix_pool_info(self):
+        """(n_blocks, block_rows, generation): the pool's sizes (0, 0 without one) and the engine's weight generation."""
+        nb, br, gen = C.c_int(), C.c_int(), C.c_uint()
+        self._check(self.lib.ze_prefix_pool_info(self.h, C.byref(nb), C.byref(br), C.byref(gen)))
+        return nb.value, br.value, gen.value
+
+    def prefix_save(self, seq: int, row0: int, blocks, stream=None) -> None:
+        """Rows [row0, row0 + len(blocks) * block_rows) of chain `seq` into the pool blocks `blocks`."""
+        a, p = _i32(list(blocks))
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else self._stream()
+        self._check(self.lib.ze_prefix_save(self.h, int(seq), int(row0), p, len(a), st))
+
+    def prefix_load(self, blocks, n_rows: int, split_row: int, dsts) -> None:
+        """The first n_rows rows held by `blocks` become the chains `dsts`: the first as if it had prefilled them, the others as if
+        they had copied them from it (`seq_copy_prefix`); the tail's prefill follows."""
+        a, p = _i32(list(blocks))
+        d, dp = _i32(list(dsts))
+        self._check(self.lib.ze_prefix_load(self.h, p, len(a), int(n_rows), int(split_row), dp, len(d), self._stream()))
+
     def seq_len(self, seq: int) -> int:
         return self._check(self.lib.ze_seq_len(self.h, seq))
 

@@ -52,7 +52,8 @@ class Rollout:
 def rollout_two_stage(model, processor, samples, num_generations: int = 4, temperature: float = 0.7,
                       max_new_tokens: int = 800, seed: int = 0, max_view: int = 512, with_logps: bool = True,
                       burst: int = 8, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                      min_p: Optional[float] = None, sampled_logps: bool = False, entropies: bool = False) -> List[Rollout]:
+                      min_p: Optional[float] = None, sampled_logps: bool = False, entropies: bool = False,
+                      prefix_cache=None) -> List[Rollout]:
     """samples: dicts with `prompt` (the stage-1 prompt text, one `<|vision_start|><|image_pad|><|vision_end|>` block),
     `image` (the tile: DeviceImage or PIL) and `bbox` (the dataset's reference box; empty = non-cropping question).
     top_k / top_p / min_p: the sampling filters of the reference's generation step (GRPOConfig top_k / top_p / min_p,
@@ -61,9 +62,13 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
     samples (the model's distribution, before temperature and filters); independent of with_logps, which scores the final
     sequences with batched passes of their own.
     entropies: with with_logps, fill Rollout.entropies from the same planned scoring call (no further pass).
+    prefix_cache: a PrefixCache of the model's engine (zoomearth_amd/prefix_cache.py) that the caller keeps between calls: the rows
+    of the chains of one call stay in its pool, and the next call on the same samples prefills only what it does not hold (the
+    trainer's `enable_prefix_caching=True`); a weight refresh between the calls empties it.
     Returns len(samples) * num_generations rollouts, sample-major."""
     sched = ChainScheduler(model, processor, do_sample=True, temperature=temperature, seed=seed, burst=burst,
-                           top_k=top_k, top_p=top_p, min_p=min_p, logprobs=0 if sampled_logps else None)
+                           top_k=top_k, top_p=top_p, min_p=min_p, logprobs=0 if sampled_logps else None,
+                           **({} if prefix_cache is None else {"prefix_cache": prefix_cache}))
     n, G = len(samples), int(num_generations)
     out = [Rollout(sample=i, generation=g, prompt1=samples[i]["prompt"]) for i in range(n) for g in range(G)]
     views = {}

@@ -170,7 +170,8 @@ class ChainScheduler:
                  min_shared: int = 64, reuse_generated: bool = True, overlap: Optional[bool] = None, hold_below: int = 0,
                  admit_chunk_rows: int = 0, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  min_p: Optional[float] = None, logprobs: Optional[int] = None, presence_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, logit_bias: Optional[dict] = None, min_new_tokens: Optional[int] = None):
+                 frequency_penalty: Optional[float] = None, logit_bias: Optional[dict] = None, min_new_tokens: Optional[int] = None,
+                 prefix_cache_rows: int = 0, prefix_cache_block_rows: int = 32, prefix_cache=None):
         self.model, self.processor, self.engine = model, processor, model.engine
         # Logit adjustments: the defaults of requests that name none (None = off).  Written into the slot's rows of the engine's
         # tables next to the filter, with zero counts, for fresh slots and for follow-ups on a parked slot alike; requests with and
@@ -243,6 +244,22 @@ class ChainScheduler:
         self._feature_cap = feature_cache
         self.stats = dict(bursts=0, steps=0, chain_steps=0, prefill_rows=0, admitted=0, vit_calls=0, shared_rows=0,
                           reused_generated_rows=0, overlapped_passes=0, forked_chains=0, forked_rows=0)
+        # Prefix cache (zoomearth_amd/prefix_cache.py): K/V rows that outlive their chains.  The sharing above needs a donor that is
+        # alive or parked; with a cache, a chain that retires leaves the full blocks of its rows in the engine's pool, and a later
+        # fresh chain whose prompt starts with them loads them (ze_prefix_load) and prefills only its tail -- the second HTTP request
+        # of a question, the next question of a tile sent after the first has finished, the next rollout of the same samples.
+        # `prefix_cache_rows` = 0 (the default): no pool, no call, today's path.  `prefix_cache`: a PrefixCache of this engine that
+        # outlives the scheduler (rollout_two_stage hands the same one to every call).
+        self.prefix_cache, self._owns_prefix_cache = prefix_cache, False
+        if prefix_cache is None and int(prefix_cache_rows) > 0:
+            from .prefix_cache import PrefixCache
+            self.prefix_cache = PrefixCache(self.engine, int(prefix_cache_rows), int(prefix_cache_block_rows))
+            self._owns_prefix_cache = True   # (close() gives the pool back; a cache handed in is its owner's)
+        if self.prefix_cache is not None:
+            self.prefix_cache.unpin_all()   # (loads a previous scheduler of this engine planned and never ran)
+            self.stats.update(prefix_cache_hit_rows=0, prefix_cache_saved_rows=0, prefix_cache_evicted_blocks=0,
+                              prefix_cache_save_errors=0)
+            self.prefix_cache_last_error = None
         # Overlap of the two kinds of work on one GPU: while a burst of decode steps runs on the caller's stream
         # (ze_decode_burst_begin: enqueued, not awaited), ONE prefill pass of the admission round -- its ViT call included --
         # is enqueued on a side stream; the burst is collected afterwards (ze_decode_burst_end) and the chains whose pass
@@ -264,6 +281,13 @@ class ChainScheduler:
             self._trace_ev = dict(base=torch.cuda.Event(enable_timing=True), t0=time.perf_counter(), passes=[])
             self._trace_ev["base"].record(torch.cuda.current_stream(self.engine.device))
         model._chains.clear()              # the scheduler owns every chain slot while it runs
+
+    def close(self) -> None:
+        """Gives back what the scheduler created on the engine: the prefix pool of `prefix_cache_rows` (a `prefix_cache` object
+        handed in stays its owner's).  A scheduler without a cache has nothing to close."""
+        if self._owns_prefix_cache and self.prefix_cache is not None:
+            self.prefix_cache.close()
+        self.prefix_cache, self._owns_prefix_cache = None, False
 
     # ------------------------------------------------------------------ queue
     def submit(self, req: Request) -> None:
@@ -531,6 +555,8 @@ class ChainScheduler:
                 ev.record(self._side)
                 self._pass_done.extend([ev] * (len(self._ready) - n0))
         except Exception as ex:
+            for it in group:
+                self._unpin(it)
             self._fail_all([it["req"] for it in group if it["req"].slot >= 0 and it["req"].slot not in self.live
                             and not any(r is it["req"] for r, _, _ in self._ready)], ex)
 
@@ -547,7 +573,15 @@ class ChainScheduler:
         # no anchor either -- an anchor's prefix goes through a pass of its own; alive or parked it donates like any other chain)
         fresh = [p for p in prepared if p["reuse"] == 0 and p["keys"] and all(k is not None for k in p["keys"])
                  and not p["req"]._chain.wants_prompt_logprobs]
+        cache = self.prefix_cache
+        if cache is not None:
+            # what the pool holds of every fresh chain's prompt (text-only prompts too: the pool needs no image to group by)
+            for p in prepared:
+                if p["reuse"] == 0 and not p["req"]._chain.wants_prompt_logprobs:
+                    p["cache"] = cache.match(p["ids"], p["keys"])
         if not fresh:
+            if cache is not None:
+                self._plan_cache(prepared)
             return []
         donors = {}   # first image key -> [(slot, ids, keys)]: chains that hold their prompt's K/V rows right now
         taken = {p["req"].slot for p in prepared}
@@ -572,18 +606,44 @@ class ChainScheduler:
                         rest = [q for q in rest if q is not p]
                 if not rest:
                     break
-            if len(rest) < 2:
+            if cache is not None:
+                # a live holder first (the decode attention shares it), then the round's own anchor; the pool where it covers more
+                # rows than the donor does, or as many as the anchor's pass would compute
+                n = self._anchor_prefix(rest)[0]
+                for p in members:
+                    self._plan_cache([p], floor=n if any(q is p for q in rest) else None)
+                rest = [p for p in rest if not p.get("cached")]
+            n, ni = self._anchor_prefix(rest)
+            if not n:
                 continue
             ref = rest[0]                                   # no donor yet: the first member's prefix is prefilled alone
-            n = min(self._prefix_len(ref["ids"], p["ids"]) for p in rest[1:])
-            ni = self._images_in(ref["ids"], n)
-            if n < self.min_shared or any(tuple(p["keys"][:ni]) != tuple(ref["keys"][:ni]) for p in rest[1:]):
-                continue
             anchors.append(dict(ref, upto=n, final=False))
             ref.update(reuse=n, n_reused=ni, copy_from=-1)   # -1: the rows are already in its own slot after pass A
             for p in rest[1:]:
                 p.update(copy_from=ref["req"].slot, reuse=n, n_reused=ni)
+        if cache is not None:
+            self._plan_cache([p for p in prepared if not any(q is p for q in fresh)])
         return anchors
+
+    def _anchor_prefix(self, rest):
+        """(rows, images) of the prefix the first of `rest` would prefill alone for the others to copy; (0, 0): no such prefix."""
+        if len(rest) < 2:
+            return 0, 0
+        ref = rest[0]
+        n = min(self._prefix_len(ref["ids"], p["ids"]) for p in rest[1:])
+        ni = self._images_in(ref["ids"], n)
+        if n < self.min_shared or any(tuple(p["keys"][:ni]) != tuple(ref["keys"][:ni]) for p in rest[1:]):
+            return 0, 0
+        return n, ni
+
+    def _plan_cache(self, items, floor=None) -> None:
+        """The items whose prompt the pool covers for more rows than their planned source does (and for `floor` rows at least) take
+        them from the pool; the match stays pinned until its load is enqueued (or the request fails)."""
+        for p in items:
+            m = p.get("cache")
+            if m and not p.get("cached") and m.rows > p["reuse"] and m.rows >= (floor or 0):
+                self.prefix_cache.pin(m)
+                p.update(copy_from=None, reuse=m.rows, n_reused=m.images, cached=m)
 
     def _reusable(self, slot, ids, keys):
         """(cached prefix length, images inside it) when the slot's parked chain is a strict prefix of `ids`.  With
@@ -641,10 +701,16 @@ class ChainScheduler:
         e = self.engine
         slots, ids_l, emb_l, pos_l, dl = [], [], [], [], []
         ok = []
+        # members of the pass with the same match in the prefix cache: ONE ze_prefix_load for all of them, at the first one's turn
+        loads = {}
+        for it in group:
+            if it.get("cached") and it["req"].slot >= 0:
+                loads.setdefault((it["cached"].blocks, it["cached"].rows), dict(items=[], state=None))["items"].append(it)
         for it in group:
             req, ids, grids, keys, reuse, n_reused, upto = (it["req"], it["ids"], it["grids"], it["keys"], it["reuse"],
                                                            it["n_reused"], it["upto"])
             if req.slot < 0:
+                self._unpin(it)
                 continue                                       # failed earlier in this round (pass A)
             if it["copy_from"] is not None and e.seq_len(it["copy_from"] if it["copy_from"] >= 0 else req.slot) < reuse:
                 # the donor's rows are gone (its pass failed; _fail resets the slot, so a stale context of the slot's
@@ -658,7 +724,9 @@ class ChainScheduler:
                 for k in keys[n_reused:n_upto]:
                     self._features.move_to_end(k)
                 emb = (torch.cat(feats) if len(feats) > 1 else feats[0]) if feats else None
-                if it["copy_from"] is None:
+                if it.get("cached"):
+                    self._load_cached(loads[(it["cached"].blocks, it["cached"].rows)], it)
+                elif it["copy_from"] is None:
                     if reuse:
                         e.seq_truncate(req.slot, reuse)       # a follow-up on its own slot: keep the cached prompt
                     else:
@@ -675,6 +743,7 @@ class ChainScheduler:
                 dl.append(delta)
                 ok.append(it)
             except Exception as ex:
+                self._unpin(it)
                 self._fail(req, ex)
         if not ok:
             return
@@ -712,8 +781,52 @@ class ChainScheduler:
         for it in final:
             req, ids, keys = it["req"], it["ids"], it["keys"]
             req.n_prompt = len(ids)
+            req.cached_tokens = it["reuse"]                     # rows the request did not compute: a donor's, the pool's, its own slot's
             self._ready.append((req, tuple(ids), tuple(keys)))
             self._fork(req, tuple(ids), tuple(keys))
+
+    # -- prefix cache
+    def _unpin(self, it) -> None:
+        m = it.pop("cached", None)
+        if m:
+            self.prefix_cache.unpin(m)
+
+    def _load_cached(self, load, it) -> None:
+        """The pool's rows into the slots of every member of the pass that shares `it`'s match: enqueued once, at the turn of the
+        first member to get this far, on the admission stream in front of the tails' pass; a failure is every member's."""
+        if load["state"] is None:
+            m, cfg = it["cached"], self.model.config
+            end = getattr(cfg, "vision_end_token_id", None)
+            # (the split row a prefill of these tokens notes: the row behind their first image block)
+            split = next((t + 1 for t in range(m.rows) if it["ids"][t] == end), 0) if end is not None and end >= 0 else 0
+            slots = [it["req"].slot] + [q["req"].slot for q in load["items"] if q is not it and q["req"].slot >= 0]
+            try:
+                self.prefix_cache.load(m, slots, split if split < 65536 else 0)
+                load["state"] = True
+                self.stats["prefix_cache_hit_rows"] += m.rows * len(slots)
+            except Exception as ex:
+                load["state"] = ex
+        self._unpin(it)
+        if load["state"] is not True:
+            raise load["state"]
+
+    def _save_to_cache(self, slot: int, ids, keys, n_rows: int) -> None:
+        """A chain leaves its slot: the full blocks of its first n_rows rows that the pool does not hold yet are copied there, before
+        the slot is retired or reset.  The decode steps that wrote the rows are over (the burst was collected), so the copy runs on
+        the admission stream, ahead of whatever that stream writes into the slot next."""
+        cache = self.prefix_cache
+        if cache is None or n_rows < cache.block_rows:
+            return
+        try:
+            evicted = cache.stats["evicted_blocks"]
+            saved = cache.save(slot, ids, keys, n_rows, stream=self._side)
+            self.stats["prefix_cache_saved_rows"] += saved
+            self.stats["prefix_cache_evicted_blocks"] += cache.stats["evicted_blocks"] - evicted
+        except Exception as ex:
+            # the cache is an optimisation -- a chain that cannot be saved is recomputed next time and no request fails for it -- but
+            # the failure is counted and kept, not lost
+            self.stats["prefix_cache_save_errors"] += 1
+            self.prefix_cache_last_error = ex
 
     def _resolve(self, req) -> ChainRequest:
         """The request's optional fields merged with the scheduler's defaults: its own value, else the scheduler's, else off.  A
@@ -813,6 +926,8 @@ class ChainScheduler:
                     break
         for req, ids, keys in self._ready[:keep_from]:
             req._chain.install(self.engine, req.slot, ids)
+            if self.prefix_cache is not None:
+                req._prefilled = (ids, keys)   # (_release: the rows of a chain that got this far are worth keeping)
             try:
                 self._set_grammar(req)
             except Exception as ex:   # no grammar to be had (a bad pattern, or all in use): this request fails, the round goes on
@@ -945,6 +1060,18 @@ class ChainScheduler:
             self.parked[slot] = (l.ids, l.keys, tuple(req.tokens[:max(0, cached)]))
             self.waiting.appendleft(follow)
         else:
+            if self.prefix_cache is not None:
+                # the prompt's rows and, under reuse_generated, those of the generated tokens that went through the model (all but
+                # the last one sampled; up to the first id that could open or close an image block): what `parked` keeps
+                gen, cfg = [], self.model.config
+                if self.reuse_generated:
+                    special = (cfg.image_token_id, getattr(cfg, "vision_start_token_id", None), getattr(cfg, "vision_end_token_id", None))
+                    for t in req.tokens[:max(0, min(self.engine.seq_len(slot) - len(l.ids), len(req.tokens) - 1))]:
+                        if t in special:
+                            break
+                        gen.append(int(t))
+                req._prefilled = None
+                self._save_to_cache(slot, list(l.ids) + gen, l.keys, len(l.ids) + len(gen))
             self._retire_slot(slot)
             self.free.append(slot)
 
@@ -960,6 +1087,10 @@ class ChainScheduler:
         if req.slot >= 0:
             self._drop_grammar(req)
             self.parked.pop(req.slot, None)
+            done = getattr(req, "_prefilled", None)
+            if self.prefix_cache is not None and done is not None:   # a chain that ran: its prompt's rows are good
+                req._prefilled = None
+                self._save_to_cache(req.slot, done[0], done[1], min(len(done[0]), self.engine.seq_len(req.slot)))
             try:
                 self._retire_slot(req.slot)
                 self.engine.seq_reset(req.slot)   # nothing may copy a prefix from what the slot held before
@@ -995,6 +1126,9 @@ class ChainScheduler:
 def run_requests(model, processor, requests, **kw) -> None:
     """Convenience: every request through one scheduler, to completion."""
     s = ChainScheduler(model, processor, **kw)
-    for r in requests:
-        s.submit(r)
-    s.run()
+    try:
+        for r in requests:
+            s.submit(r)
+        s.run()
+    finally:
+        s.close()

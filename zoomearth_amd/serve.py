@@ -161,8 +161,13 @@ class ChatServer:
     """Holds the model / processor pair; turns OpenAI request dicts into response dicts, one at a time
     (`complete`), as an explicit batch (`complete_many`) or through the batching dispatcher (`submit`)."""
 
-    def __init__(self, model, processor, model_id: str = "ZoomEarth", batch_window_s: float = 0.01, max_batch=None):
+    def __init__(self, model, processor, model_id: str = "ZoomEarth", batch_window_s: float = 0.01, max_batch=None,
+                 prefix_cache_rows: int = 0):
         self.model, self.processor, self.model_id = model, processor, model_id
+        # --prefix-cache-rows N: the K/V rows of finished requests stay in a pool of N rows (zoomearth_amd/prefix_cache.py), and a
+        # later request whose prompt starts with them -- stage 2 of a question, the next question of a tile -- prefills only its
+        # tail; `usage.prompt_tokens_details.cached_tokens` reports the rows it did not compute.  0: no pool, today's responses.
+        self.prefix_cache_rows, self.prefix_cache = int(prefix_cache_rows), None
         self._lock = threading.Lock()  # the engine is single-stream
         self.batch_window_s = batch_window_s
         self.max_batch = int(max_batch or getattr(model.engine, "max_seqs", 1))
@@ -401,7 +406,10 @@ class ChatServer:
         for i, r in enumerate(parts[1:], 1):
             res["choices"].append({**r["choices"][0], "index": i})
         done = sum(r["usage"]["completion_tokens"] for r in parts)
+        details = parts[0]["usage"].get("prompt_tokens_details")
         res["usage"] = {"prompt_tokens": n_in, "completion_tokens": done, "total_tokens": n_in + done}
+        if details is not None:
+            res["usage"]["prompt_tokens_details"] = details
         return res
 
     def _run(self, batch):
@@ -476,6 +484,13 @@ class ChatServer:
         with self._cv:
             self._stop = True
             self._cv.notify()
+        if self.prefix_cache is not None:   # the dispatcher ends first (it may be in the middle of a step), then the pool goes
+            worker = self._worker
+            if worker is not None and worker is not threading.current_thread():
+                worker.join()
+            with self._lock:
+                self.prefix_cache.close()
+                self.prefix_cache = None
 
     def _request(self, p: _Parsed):
         """The scheduler's Request of a parsed one: its fields under the scheduler's names, the budget clamped to the KV capacity
@@ -492,6 +507,8 @@ class ChatServer:
             if p.prompt_logprobs is not None and req.index == 0:
                 prompt = (req._prompt_ids, req.prompt_token_logprobs, req.prompt_ranks, req.prompt_top_logprobs)
             parts[req.index] = self._response(p, tokens, req.n_prompt, (req.token_logprobs, req.top_logprobs), prompt)
+            if self.prefix_cache is not None:   # OpenAI's field: the prompt rows this request did not compute
+                parts[req.index]["usage"]["prompt_tokens_details"] = {"cached_tokens": int(getattr(req, "cached_tokens", 0))}
             if all(r is not None for r in parts) and not p.future.done():
                 p.future.set_result(parts[0] if p.n == 1 else self._merge_choices(parts, req.n_prompt))
             return None
@@ -534,7 +551,13 @@ class ChatServer:
                 new, self._queue = self._queue, []
             with self._lock:
                 if sched is None:
-                    sched = ChainScheduler(self.model, self.processor, do_sample=False, max_batch=self.max_batch, burst=8)
+                    kw = {}
+                    if self.prefix_cache_rows > 0:   # (the cache outlives a scheduler that had to be replaced)
+                        if self.prefix_cache is None:
+                            from .prefix_cache import PrefixCache
+                            self.prefix_cache = PrefixCache(self.model.engine, self.prefix_cache_rows)
+                        kw["prefix_cache"] = self.prefix_cache
+                    sched = ChainScheduler(self.model, self.processor, do_sample=False, max_batch=self.max_batch, burst=8, **kw)
                     self.scheduler = sched
                 for p in new:
                     try:
@@ -594,11 +617,15 @@ def main():  # pragma: no cover
     ap.add_argument("--served_model_name", default="ZoomEarth")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8000)
+    ap.add_argument("--prefix-cache-rows", type=int, default=0,
+                    help="keep the K/V rows of finished requests in a pool of this many rows (0 = off); later requests that start "
+                         "with them prefill only their tail and report usage.prompt_tokens_details.cached_tokens")
     args = ap.parse_args()
     model = ZoomEarthForConditionalGeneration.from_pretrained(args.model_name)
     processor = ZoomEarthProcessor.from_pretrained(args.model_name, trust_remote_code=True, max_pixels=128 * 128 * 28 * 28)
     processor.tokenizer.padding_side = "left"
-    uvicorn.run(create_app(ChatServer(model, processor, args.served_model_name)), host=args.host, port=args.port)
+    uvicorn.run(create_app(ChatServer(model, processor, args.served_model_name, prefix_cache_rows=args.prefix_cache_rows)),
+                host=args.host, port=args.port)
 
 
 if __name__ == "__main__":  # pragma: no cover
