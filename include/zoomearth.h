@@ -94,6 +94,10 @@ int ze_weights_fill_synthetic(ze_engine* e, uint64_t seed, float std, float matr
                               float norm_jitter);
 /* Number of HF tensors still missing (0 = ready); names of missing tensors are in ze_last_error(). */
 int ze_weights_missing(ze_engine* e);
+/* replaces: `param.shape` of a named parameter.  The logical shape of an HF tensor the engine knows, by its key in either layout:
+ * rows x cols (a vector has cols = 1) and its kind (0 projection matrix, 1 norm weight, 2 bias, 3 embedding table / lm_head);
+ * ZE_ERR_NOTFOUND for a key it has none for (a tied lm_head among them).  Any out pointer may be NULL. */
+int ze_weight_shape(ze_engine* e, const char* name, int* rows, int* cols, int* kind);
 /* The packed bf16 weight arena (one contiguous device allocation): lets the host broadcast it once over
  * RCCL/xGMI with torch.distributed and checksum it.  Does not transfer ownership. */
 int ze_weights_arena(ze_engine* e, void** dev_ptr, size_t* bytes);
@@ -108,6 +112,47 @@ int ze_weights_invalidate(ze_engine* e);
  * src/eval/infer.py:147-151,171 -- the checkpoint is read from disk once).  RCCL is not linked: the symbol must already be
  * loaded in the process (ZE_ERR_NOTFOUND otherwise).  Derived weight copies are dropped as after ze_load_weight. */
 int ze_weights_broadcast(ze_engine* e, void* nccl_comm, int root, void* stream);
+
+/* ------------------------------------------------------------------ LoRA adapters */
+/* A LoRA adapter is a low-rank delta merged into the weight arena on the device: while adapter X is active, every tensor it names
+ * holds bf16(W + scale * B @ A) (fp32, k ascending, no fused multiply-add, one round-to-nearest-even), computed from a bf16 snapshot
+ * of the base tensor (the base store), so every switch is one pass per tensor and -1 returns the base bits exactly.  No forward
+ * kernel knows about adapters; with none active nothing new is launched.  Up to ZE_MAX_ADAPTERS adapters are resident, one is active.
+ *
+ * Base-weight writes: ze_load_weight, ze_weights_fill_synthetic, ze_weights_invalidate and ze_weights_broadcast make the arena's
+ * contents -- merged tensors included -- the new base: afterwards no adapter is active and the base store is dropped; the resident
+ * adapters stay loaded.  K/V rows computed under other weights (chains, prefix-pool blocks saved by the caller's own keys) are
+ * the caller's to drop, as they are for ze_load_weight; the prefix pool's generation moves on with every switch.
+ * ze_weights_quantize_fp8 replaces the arena's bf16 values by the dequantised ones and leaves the base store alone: a switch after it
+ * merges from the unquantised base (the caller quantises again); a tensor first snapshotted after it has the dequantised values as base. */
+#define ZE_MAX_ADAPTERS 8
+#define ZE_LORA_MAX_RANK 128
+/* replaces: PeftModel.from_pretrained(model, dir) / model.add_adapter (src/train/SFT.py `--lora_r 8`; the peft_config of
+ * src/train/RL/src/open-r1-multimodal/src/open_r1/trainer/grpo_trainer.py): a resident, inactive, empty adapter.  ZE_ERR_NOMEM when
+ * ZE_MAX_ADAPTERS are resident. */
+int ze_lora_create(ze_engine* e, int* adapter);
+/* replaces: the lora_A / lora_B parameters of one PEFT LoraLayer.  `name` is the HF key of the BASE tensor in either checkpoint
+ * layout (as ze_load_weight); it has to be a projection matrix of the decoder or the vision tower (q/k/v and gate/up under their own
+ * names) -- the embedding table, lm_head, norms and biases are ZE_ERR_INVALID.  host_A [r, cols] and host_B [rows, r] of `dtype`
+ * are converted exactly to fp32; the call carries r only and READS r * cols and rows * r elements from them -- the caller sizes its
+ * arrays by ze_weight_shape (Engine.lora_add checks both shapes against it).  ZE_ERR_INVALID: 1 <= r <= ZE_LORA_MAX_RANK violated, the tensor added twice to this adapter, the
+ * adapter is the active one (deactivate first).  ZE_ERR_NOTFOUND: unknown tensor or adapter. */
+int ze_lora_add(ze_engine* e, int adapter, const char* name, int dtype, int r, float scale, const void* host_A, const void* host_B);
+/* replaces: PeftModel.delete_adapter.  ZE_ERR_INVALID while it is the active one. */
+int ze_lora_destroy(ze_engine* e, int adapter);
+/* replaces: PeftModel.set_adapter(name), and -- adapter = -1, the base weights -- `with model.disable_adapter():` as the GRPO trainer
+ * uses it for the reference log-probabilities (grpo_trainer.py:679).  Snapshots into the base store whatever a resident adapter
+ * names and the store does not hold yet, restores every tensor the previous adapter touched and the new one does not, merges every
+ * tensor of the new one from the store; then drops the derived weight copies, the captured graphs and the prefix pool's generation
+ * as ze_load_weight does (an FP8 engine quantises again) and synchronises `stream`.  Activating what is active does nothing. */
+int ze_lora_activate(ze_engine* e, int adapter, void* stream);
+/* replaces: PeftModel.active_adapter / peft_config: the active adapter (-1 = none), the resident ones, the bytes of the base store. */
+int ze_lora_info(ze_engine* e, int* active, int* n_resident, size_t* base_store_bytes);
+/* The merge kernel alone on device buffers (replaces: LoraLayer.merge, W += scale * B @ A, for one tensor): base_bf16 [rows, cols]
+ * row-major, A f32 [r, cols], B f32 [rows, r]; logical row i goes to row (mode 0: offset + i; mode 1, the gate/up interleave:
+ * (i / 16) * 32 + i % 16 + offset) of dst_bf16, leading dimension ld >= cols; columns cols .. ld are not touched.  r = 0 copies. */
+int ze_op_lora_merge(ze_engine* e, const void* base_bf16, int rows, int cols, const float* A, const float* B, int r, float scale,
+                     void* dst_bf16, int ld, int mode, int offset, void* stream);
 
 /* ------------------------------------------------------------------ image front-end (K0-K2) */
 /* replaces: `Image.open(image_fp).convert("RGB")` arriving on the device (src/eval/infer.py:215,237 + the `.to(device)`

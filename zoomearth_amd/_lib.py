@@ -84,10 +84,17 @@ _SIGS = {
     "ze_load_weight": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_int64), _P]),
     "ze_weights_fill_synthetic": (C.c_int, [_P, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float]),
     "ze_weights_missing": (C.c_int, [_P]),
+    "ze_weight_shape": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ze_weights_arena": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "ze_weights_invalidate": (C.c_int, [_P]),
     "ze_set_decode_regime": (C.c_int, [_P, C.c_int]),
     "ze_weights_broadcast": (C.c_int, [_P, _P, C.c_int, _P]),
+    "ze_lora_create": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "ze_lora_add": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_float, _P, _P]),
+    "ze_lora_destroy": (C.c_int, [_P, C.c_int]),
+    "ze_lora_activate": (C.c_int, [_P, C.c_int, _P]),
+    "ze_lora_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "ze_op_lora_merge": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ze_tile_upload": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "ze_op_crop_resize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int32), _P, C.c_int, C.c_int, _P]),
     "ze_smart_resize": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int),

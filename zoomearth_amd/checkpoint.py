@@ -81,3 +81,54 @@ def write_safetensors(path: str, tensors: dict, bf16: bool = False) -> None:
         f.write(hj)
         for b in blobs:
             f.write(b)
+
+
+# ---------------------------------------------------------------------------------------------------------------- PEFT LoRA adapters
+_ADAPTER_REJECTS = (("use_dora", lambda v: bool(v)), ("fan_in_fan_out", lambda v: bool(v)), ("bias", lambda v: v not in (None, "none")),
+                    ("modules_to_save", lambda v: bool(v)), ("peft_type", lambda v: v is not None and str(v).upper() != "LORA"))
+
+
+def _alpha_of(cfg: dict, module: str):
+    """PEFT's rule: the first `alpha_pattern` key that equals the module name or matches it as a suffix (`.*\\.key$`), else lora_alpha."""
+    import re
+    for key, alpha in (cfg.get("alpha_pattern") or {}).items():
+        if key == module or re.match(rf".*\.{key}$", module):
+            return alpha
+    return cfg.get("lora_alpha", 8)
+
+
+def read_adapter(adapter_dir: str):
+    """A PEFT LoRA adapter directory (adapter_config.json + adapter_model.safetensors) -> (config dict, {base key: (A, B, r, scale)}).
+
+    replaces: PeftModel.from_pretrained's reading of the adapter (the reference trains ZoomEarth with `--lora_r 8`).  Keys
+    `base_model.model.<module>.lora_A[.<adapter name>].weight` / `...lora_B...` name the base tensor `<module>.weight`; A is [r, in], B
+    [out, r], r each tensor's own; scale = alpha / r, or alpha / sqrt(r) with use_rslora, alpha from `alpha_pattern` where a pattern
+    matches the module, else `lora_alpha`.  What the merge does not implement is refused with a ValueError naming the field."""
+    import math
+    import re
+    with open(os.path.join(adapter_dir, "adapter_config.json"), encoding="utf-8") as f:
+        cfg = json.load(f)
+    for field, bad in _ADAPTER_REJECTS:
+        if bad(cfg.get(field)):
+            raise ValueError(f"{adapter_dir}: adapter_config.json has {field} = {cfg.get(field)!r}, which the LoRA merge does not support")
+    halves = {}
+    pat = re.compile(r"^base_model\.model\.(.+)\.lora_([AB])(?:\.[^.]+)?\.weight$")
+    for name, arr in iter_safetensors(os.path.join(adapter_dir, "adapter_model.safetensors")):
+        m = pat.match(name)
+        if not m:
+            raise ValueError(f"{adapter_dir}: unexpected tensor {name} in adapter_model.safetensors")
+        if m.group(2) in halves.setdefault(m.group(1), {}):
+            raise ValueError(f"{adapter_dir}: lora_{m.group(2)} of {m.group(1)} appears twice (more than one adapter name in the file)")
+        halves[m.group(1)][m.group(2)] = arr
+    out = {}
+    for module, ab in halves.items():
+        if "A" not in ab or "B" not in ab:
+            raise ValueError(f"{adapter_dir}: {module} has lora_{'A' if 'A' in ab else 'B'} without lora_{'B' if 'A' in ab else 'A'}")
+        shape = lambda x: x[0].shape if isinstance(x, tuple) else x.shape   # noqa: E731
+        (r, _), (_, rb) = shape(ab["A"]), shape(ab["B"])
+        if r != rb:
+            raise ValueError(f"{adapter_dir}: {module}: lora_A has rank {r}, lora_B rank {rb}")
+        alpha = _alpha_of(cfg, module)
+        scale = alpha / math.sqrt(r) if cfg.get("use_rslora") else alpha / r
+        out[module + ".weight"] = (ab["A"], ab["B"], int(r), float(scale))
+    return cfg, out

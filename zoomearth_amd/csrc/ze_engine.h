@@ -189,6 +189,25 @@ struct ze_prefix_pool {
     std::vector<uint64_t> saved_seq, read_seq;
 };
 
+// LoRA adapters (ze_lora.hip).  An adapter is a set of (A fp32 [r, cols], B fp32 [rows, r], scale) per base tensor, resident on the
+// device; the active one is merged into the arena.  store: the bf16 row-major snapshot of every tensor a resident adapter names,
+// taken from the arena while it held the base bits -- what every merge and restore reads; dropped by any base-weight write.
+struct ze_lora_tensor {
+    float *A = nullptr, *B = nullptr;
+    int r = 0;
+    float scale = 0.f;
+};
+struct ze_lora_adapter {
+    bool used = false;
+    std::map<std::string, ze_lora_tensor> t;  // by canonical tensor name
+};
+struct ze_lora {
+    ze_lora_adapter ad[ZE_MAX_ADAPTERS];
+    int active = -1;
+    std::map<std::string, bf16_t*> store;
+    size_t store_bytes = 0;
+};
+
 struct ze_engine {
     ze_config cfg{};
     int device = 0;
@@ -202,6 +221,7 @@ struct ze_engine {
     std::set<std::string> loaded;
     void* staging = nullptr;
     size_t staging_bytes = 0;
+    ze_lora* lora = nullptr;  // adapters and the base store (null until the first ze_lora_create)
     ze_linear patch_embed, merger0, merger2;
     bf16_t* ln_q = nullptr;
     std::vector<ze_vit_block> vb;
@@ -448,4 +468,11 @@ int push_state(ze_engine* e, int seq, hipStream_t s, int token, int n_gen, int f
 void ze_prefix_pool_free(ze_engine* e);   // (ze_engine_destroy: the device is idle)
 // the K/V rows of given tokens are no longer what they were: every pool block counts as unsaved from now on
 inline void ze_prefix_weights_changed(ze_engine* e) { ++e->prefix_generation; }
+// an HF checkpoint key of either layout as the key of ze_engine::dests (ze_engine.hip)
+std::string ze_canonical_name(const char* name);
+// ---- LoRA adapters (ze_lora.hip)
+void ze_lora_free(ze_engine* e);          // (ze_engine_destroy)
+// the arena was written from outside the adapters (load, synthetic fill, invalidate, broadcast): its contents are the base now --
+// no adapter is active and the base store is dropped; resident adapters stay
+void ze_lora_base_written(ze_engine* e);
 #pragma GCC visibility pop

@@ -454,6 +454,7 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
         if (p) hipFree(p);
     ze_requests_free(e);
     ze_prefix_pool_free(e);
+    ze_lora_free(e);
     if (e->pfx_dev) hipFree(e->pfx_dev);
     if (e->arena_p) hipFree(e->arena_p);
     if (e->qkv_epi_dev) hipFree(e->qkv_epi_dev);
@@ -478,7 +479,7 @@ extern "C" int ze_sync(ze_engine* e, void* stream) {
 }
 
 // ------------------------------------------------------------------ weights
-static std::string canonical_name(const char* name) {
+std::string ze_canonical_name(const char* name) {
     std::string n(name);
     if (n.rfind("visual.", 0) == 0) return "model." + n;  // 4.49-era layout
     if (n.rfind("model.layers.", 0) == 0 || n.rfind("model.embed_tokens.", 0) == 0 || n.rfind("model.norm.", 0) == 0)
@@ -490,7 +491,7 @@ extern "C" int ze_load_weight(ze_engine* e, const char* name, int dtype, int ndi
                               const void* host_ptr) {
     if (e) ze_weights_changed(e);
     if (!e || !name || !shape || !host_ptr) return ze_fail(e, ZE_ERR_INVALID, "null argument");
-    const std::string cn = canonical_name(name);
+    const std::string cn = ze_canonical_name(name);
     if (cn == "lm_head.weight" && e->cfg.tie_word_embeddings) {
         e->loaded.insert(cn);
         return ZE_OK;  // tied: embed_tokens is the lm_head
@@ -505,6 +506,7 @@ extern "C" int ze_load_weight(ze_engine* e, const char* name, int dtype, int ndi
     const size_t esz = dtype == ZE_F32 ? 4 : 2;
     if (dtype != ZE_F32 && dtype != ZE_F16 && dtype != ZE_BF16) return ze_fail(e, ZE_ERR_INVALID, "bad dtype");
     hipSetDevice(e->device);
+    ze_lora_base_written(e);  // (only now: a refused call writes nothing and leaves the adapters' base store alone)
     const int rows_per = (int)std::max<size_t>(1, e->staging_bytes / ((size_t)d.cols * esz));
     for (int r0 = 0; r0 < d.rows; r0 += rows_per) {
         const int nr = std::min(rows_per, d.rows - r0);
@@ -517,9 +519,19 @@ extern "C" int ze_load_weight(ze_engine* e, const char* name, int dtype, int ndi
     return ZE_OK;
 }
 
+extern "C" int ze_weight_shape(ze_engine* e, const char* name, int* rows, int* cols, int* kind) {
+    if (!e || !name) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    auto it = e->dests.find(ze_canonical_name(name));
+    if (it == e->dests.end()) return ze_fail(e, ZE_ERR_NOTFOUND, std::string("unknown weight: ") + name);
+    if (rows) *rows = it->second.rows;
+    if (cols) *cols = it->second.cols;
+    if (kind) *kind = it->second.kind;
+    return ZE_OK;
+}
+
 extern "C" int ze_weights_fill_synthetic(ze_engine* e, uint64_t seed, float std_, float matrix_gain, float bias_std,
                                          float norm_jitter) {
-    if (e) ze_weights_changed(e);
+    if (e) ze_weights_changed(e), ze_lora_base_written(e);
     if (!e) return ze_fail(e, ZE_ERR_INVALID, "null engine");
     hipSetDevice(e->device);
     for (auto& kv : e->dests) {
@@ -569,6 +581,7 @@ extern "C" int ze_weights_invalidate(ze_engine* e) {
     if (!e) return ze_fail(e, ZE_ERR_INVALID, "null engine");
     for (auto& kv : e->dests) e->loaded.insert(kv.first);
     ze_weights_changed(e);
+    ze_lora_base_written(e);
     return ZE_OK;
 }
 
@@ -584,6 +597,7 @@ extern "C" int ze_weights_broadcast(ze_engine* e, void* nccl_comm, int root, voi
     if (!fn) return ze_fail(e, ZE_ERR_NOTFOUND, "ncclBroadcast is not loaded in this process (load librccl before calling)");
     hipSetDevice(e->device);
     ze_weights_changed(e);
+    ze_lora_base_written(e);
     const size_t bytes = e->arena_used * sizeof(bf16_t);
     const int rc = fn(e->arena, e->arena, bytes, /*ncclUint8*/ 1, root, nccl_comm, (hipStream_t)stream);
     if (rc != 0) return ze_fail(e, ZE_ERR_HIP, "ncclBroadcast failed with code " + std::to_string(rc));

@@ -180,6 +180,87 @@ class Engine:
         """After writing through weights_arena() (broadcast, weight refresh): derived copies and graphs are rebuilt."""
         self._check(self.lib.ze_weights_invalidate(self.h))
 
+    # ------------------------------------------------------------------ LoRA adapters
+    def lora_create(self) -> int:
+        """A resident, inactive, empty adapter (ze_lora_create); at most 8 per engine."""
+        a = C.c_int()
+        self._check(self.lib.ze_lora_create(self.h, C.byref(a)))
+        return int(a.value)
+
+    def lora_add(self, adapter: int, name: str, A, B, scale: float) -> None:
+        """The delta of one base tensor (ze_lora_add): `name` its HF key, A [r, cols] and B [rows, r] numpy float32 / float16 or
+        (uint16, 'bf16') pairs of one dtype, W' = bf16(W + scale * B @ A).  The shapes are checked against the base tensor."""
+        def raw(x):
+            if isinstance(x, tuple):
+                return np.ascontiguousarray(x[0], dtype=np.uint16), _lib.ZE_BF16
+            x = np.ascontiguousarray(x)
+            if x.dtype not in _NP2ZE:
+                x = x.astype(np.float32)
+            return x, _NP2ZE[x.dtype]
+
+        def f32(x, dt):   # exact: bf16 bits are the upper half of the float32 word
+            return (x.astype(np.uint32) << 16).view(np.float32) if dt == _lib.ZE_BF16 else x.astype(np.float32)
+        (a, da), (b, db) = raw(A), raw(B)
+        if da != db:      # (the call carries one dtype)
+            a, b, da = f32(a, da), f32(b, db), _lib.ZE_F32
+        if a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[1]:
+            raise ValueError(f"LoRA shapes for {name}: A {a.shape} has to be [r, cols] and B {b.shape} [rows, r]")
+        if name != "lm_head.weight":   # (tied: no tensor of its own; the engine refuses it by name)
+            rows, cols, _kind = self.weight_shape(name)
+            if b.shape[0] != rows or a.shape[1] != cols:
+                raise ValueError(f"LoRA shape mismatch for {name}: B @ A is {b.shape[0]} x {a.shape[1]}, the tensor is {rows} x {cols}")
+        self._check(self.lib.ze_lora_add(self.h, int(adapter), name.encode(), da, int(a.shape[0]), float(scale),
+                                         a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+
+    def weight_shape(self, name: str):
+        """(rows, cols, kind) of an HF tensor by its key in either layout (ze_weight_shape): kind 0 projection matrix, 1 norm weight,
+        2 bias, 3 embedding table / lm_head.  A key the engine has no tensor for raises."""
+        r, c, k = C.c_int(), C.c_int(), C.c_int()
+        self._check(self.lib.ze_weight_shape(self.h, name.encode(), C.byref(r), C.byref(c), C.byref(k)))
+        return int(r.value), int(c.value), int(k.value)
+
+    def lora_load(self, tensors) -> int:
+        """A new adapter from {base key: (A, B, r, scale)} (checkpoint.read_adapter's second result); returns its id.  On an error
+        the half-built adapter is destroyed."""
+        a = self.lora_create()
+        try:
+            for name, (A, B, _r, scale) in tensors.items():
+                self.lora_add(a, name, A, B, scale)
+        except Exception:
+            self.lora_destroy(a)
+            raise
+        return a
+
+    def lora_activate(self, adapter: Optional[int]) -> None:
+        """Merges adapter `adapter` into the weight arena, None = the base weights (ze_lora_activate): one pass per tensor from the
+        base store, then everything derived from the weights is dropped as after a weight load.  K/V rows and ViT features computed
+        under the previous weights are the caller's to drop."""
+        self._check(self.lib.ze_lora_activate(self.h, -1 if adapter is None else int(adapter), self._stream()))
+
+    def lora_destroy(self, adapter: int) -> None:
+        self._check(self.lib.ze_lora_destroy(self.h, int(adapter)))
+
+    def lora_info(self):
+        """(active adapter or None, resident adapters, bytes of the base store)."""
+        a, n, b = C.c_int(), C.c_int(), C.c_size_t()
+        self._check(self.lib.ze_lora_info(self.h, C.byref(a), C.byref(n), C.byref(b)))
+        return (None if a.value < 0 else int(a.value)), int(n.value), int(b.value)
+
+    def op_lora_merge(self, base: torch.Tensor, A: Optional[torch.Tensor], B: Optional[torch.Tensor], scale: float, dst: torch.Tensor,
+                      ld: int, mode: int = 0, offset: int = 0) -> None:
+        """The merge kernel alone (ze_op_lora_merge): base bf16 [rows, cols], A f32 [r, cols], B f32 [rows, r] (both None: r = 0, a
+        copy), dst a bf16 buffer the mapped rows fit into, leading dimension ld."""
+        rows, cols = int(base.shape[0]), int(base.shape[1])
+        r = 0 if A is None else int(A.shape[0])
+        assert base.dtype == torch.bfloat16 and dst.dtype == torch.bfloat16 and base.is_contiguous()
+        assert r == 0 or (A.dtype == torch.float32 and B.dtype == torch.float32 and A.is_contiguous() and B.is_contiguous()
+                          and tuple(A.shape) == (r, cols) and tuple(B.shape) == (rows, r))
+        last = (offset + rows - 1) if mode == 0 else ((rows - 1) // 16 * 32 + (rows - 1) % 16 + offset)
+        assert ld >= cols and offset >= 0 and last * ld + cols <= dst.numel(), "the mapped rows do not fit into dst"
+        self._use(base, A, B, dst)
+        self._check(self.lib.ze_op_lora_merge(self.h, _ptr(base), rows, cols, _ptr(A), _ptr(B), r, float(scale), _ptr(dst), int(ld),
+                                              int(mode), int(offset), self._stream()))
+
     # ------------------------------------------------------------------ front-end
     def crop_resize(self, tile: torch.Tensor, box: Sequence[int], out_wh: Sequence[int]) -> torch.Tensor:
         """PIL `tile.crop(box).resize(out_wh, BICUBIC)` on a device u8 [H, W, 3] tensor."""

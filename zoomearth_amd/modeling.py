@@ -27,8 +27,9 @@ import torch
 
 from . import processor as _processor
 from .chain_request import ChainRequest
-from .checkpoint import iter_checkpoint
+from .checkpoint import iter_checkpoint, read_adapter
 from .config import ModelConfig
+from .scheduler import KEEP_ADAPTER
 from .score_plan import PlanItem, plan_score_passes, score_columns
 from .engine import MAX_LOGIT_BIAS, MAX_RULE_INTS, MAX_RULE_LEN, MAX_RULE_WORDS, MAX_TOP_LOGPROBS, Engine
 
@@ -66,6 +67,27 @@ class _Rows(NamedTuple):
     input_ids: torch.Tensor
 
 
+class adapter_scope:
+    """`with adapter_scope(model, name_or_None):` runs the block under that adapter (None = the base weights) and puts the previously
+    active one back on exit, also on an exception.  KEEP_ADAPTER: nothing is switched.  A switch that changes nothing launches
+    nothing (ze_lora_activate).  Not for a model whose ChainScheduler has live chains: their K/V rows belong to the weights that made
+    them (the scheduler's own `set_adapter` refuses then; this does not know of it)."""
+
+    def __init__(self, model, adapter):
+        self.model, self.adapter = model, adapter
+
+    def __enter__(self):
+        if self.adapter is not KEEP_ADAPTER:
+            self.before = self.model.active_adapter
+            self.model.set_adapter(self.adapter)
+        return self.model
+
+    def __exit__(self, *exc):
+        if self.adapter is not KEEP_ADAPTER:
+            self.model.set_adapter(self.before)
+        return False
+
+
 class ZoomEarthForConditionalGeneration:
     def __init__(self, config: ModelConfig, engine: Engine, generation_config=None):
         self.config = config
@@ -77,6 +99,7 @@ class ZoomEarthForConditionalGeneration:
         self._chains = OrderedDict()      # slot -> (prompt ids tuple, image keys tuple)
         self._next_slot = 0
         self.reuse_prefix = True
+        self._adapters = {}               # adapter name -> engine adapter id (which one is active is the ENGINE's state)
         _processor.set_default_engine(engine)
 
     # ------------------------------------------------------------------ construction
@@ -86,7 +109,27 @@ class ZoomEarthForConditionalGeneration:
         """broadcast=True under WORLD_SIZE > 1 (one rank per GPU): only rank 0 reads the safetensors, the other ranks
         receive the packed weight arena in ONE collective (accel.broadcast_engine_weights: RCCL over xGMI) -- where the
         reference has every rank read the checkpoint itself (/root/reference/src/eval/infer.py:147-151).  The seconds the
-        collective took are left in `model.weight_broadcast_s`."""
+        collective took are left in `model.weight_broadcast_s`.
+        A PEFT adapter directory (adapter_config.json, no config.json): the base model named by its `base_model_name_or_path` -- or
+        by the `base=` keyword -- is loaded as above, then the adapter is loaded and activated (`load_adapter`, `set_adapter`); under
+        broadcast every rank applies it itself after the base broadcast (A / B are a few MB)."""
+        base = kw.pop("base", None)
+        if os.path.exists(os.path.join(path, "adapter_config.json")) and not os.path.exists(os.path.join(path, "config.json")):
+            if base is None:
+                with open(os.path.join(path, "adapter_config.json"), encoding="utf-8") as f:
+                    base = json.load(f).get("base_model_name_or_path")
+            if not base:
+                raise ValueError(f"{path}: adapter_config.json names no base_model_name_or_path (pass base=)")
+            model = cls.from_pretrained(base, torch_dtype=torch_dtype, device=device, max_seqs=max_seqs, max_ctx=max_ctx,
+                                        max_patches=max_patches, max_tile_side=max_tile_side, max_prefill_rows=max_prefill_rows,
+                                        broadcast=broadcast, **kw)
+            try:
+                model.load_adapter(path)
+                model.set_adapter("default")
+            except Exception:
+                model.engine.close()
+                raise
+            return model
         config = ModelConfig.from_pretrained(path)
         dev = 0 if device is None else (device.index or 0 if isinstance(device, torch.device) else int(device))
         if device is None and "LOCAL_RANK" in os.environ:  # (more local ranks than GPUs: ranks share GPUs, accel.Accelerator)
@@ -139,7 +182,9 @@ class ZoomEarthForConditionalGeneration:
     def clone_lane(self, **engine_kw):
         """A second engine on the same GPU with a copy of this model's weights (device-to-device), for a further LANE of
         question chains: its own KV cache, workspaces, scheduler thread and HIP stream, so that the prefill / ViT rounds of
-        one lane overlap the decode bursts of the other (src/eval/infer.py --lanes; bench.py --lanes)."""
+        one lane overlap the decode bursts of the other (src/eval/infer.py --lanes; bench.py --lanes).
+        A lane cloned while a LoRA adapter is active takes the MERGED weights as its base: it has no adapters of its own, and
+        nothing can take the delta out of it again."""
         e = self.engine
         kw = dict(device=e.device.index or 0, max_seqs=e.max_seqs, max_ctx=e.max_ctx, max_patches=e.max_patches,
                   max_tile_side=int(e.zcfg.max_tile_side), max_prefill_rows=int(e.zcfg.max_prefill_rows))
@@ -158,7 +203,51 @@ class ZoomEarthForConditionalGeneration:
         lane.config, lane.engine, lane.generation_config = self.config, e2, gen
         lane._vit_cache, lane._chains, lane._next_slot, lane.reuse_prefix = OrderedDict(), OrderedDict(), 0, True
         lane.weight_broadcast_s = 0.0
+        lane._adapters = {}
         return lane
+
+    # ------------------------------------------------------------------ LoRA adapters
+    def load_adapter(self, path_or_tensors, adapter_name: str = "default"):
+        """replaces: PeftModel.from_pretrained / load_adapter.  A PEFT LoRA directory (checkpoint.read_adapter) or its tensors
+        {base key: (A, B, r, scale)}: resident on the device under `adapter_name`, not active until `set_adapter`."""
+        if adapter_name in self._adapters:
+            raise ValueError(f"adapter {adapter_name!r} is already loaded")
+        tensors = read_adapter(path_or_tensors)[1] if isinstance(path_or_tensors, (str, os.PathLike)) else path_or_tensors
+        self._adapters[adapter_name] = self.engine.lora_load(tensors)
+        return adapter_name
+
+    @property
+    def active_adapter(self):
+        """The name of the adapter merged into the engine's weights, None for the base weights.  Read from the engine: a base-weight
+        write (load_state_dict, fill_synthetic, weights_invalidate, a broadcast) under an active adapter leaves none active."""
+        adapters = getattr(self, "_adapters", None)
+        if not adapters:
+            return None
+        active = self.engine.lora_info()[0]
+        return next((name for name, a in adapters.items() if a == active), None)
+
+    def set_adapter(self, name) -> None:
+        """replaces: PeftModel.set_adapter; None = the base weights.  Cached ViT features and chains belong to the weights that made
+        them: every switch forgets them.  The chains of a running ChainScheduler on this model are not known here: switch through
+        the scheduler (`ChainScheduler(adapter=)`, `set_adapter`), which refuses while chains are live, never under it."""
+        if name is not None and name not in self._adapters:
+            raise ValueError(f"no adapter {name!r} (loaded: {sorted(self._adapters)})")
+        if name == self.active_adapter:
+            return
+        self.engine.lora_activate(None if name is None else self._adapters[name])
+        self._vit_cache.clear()
+        self._chains.clear()
+
+    def disable_adapter(self):
+        """replaces: `with model.disable_adapter():` (the reference policy of the GRPO step, grpo_trainer.py:679)."""
+        return adapter_scope(self, None)
+
+    def delete_adapter(self, name) -> None:
+        if name not in self._adapters:
+            raise ValueError(f"no adapter {name!r}")
+        if name == self.active_adapter:
+            self.set_adapter(None)
+        self.engine.lora_destroy(self._adapters.pop(name))
 
     @property
     def device(self):
@@ -193,8 +282,11 @@ class ZoomEarthForConditionalGeneration:
     # ------------------------------------------------------------------ rollout scoring
     @torch.no_grad()
     def per_token_logps(self, input_ids, attention_mask=None, pixel_values=None, image_grid_thw=None,
-                        image_keys=None, score_from: Optional[int] = None, share_prefix: bool = True, min_shared: int = 64, **kw):
+                        image_keys=None, score_from: Optional[int] = None, share_prefix: bool = True, min_shared: int = 64,
+                        adapter=KEEP_ADAPTER, **kw):
         """Log-probability of every token given its prefix: f32 [B, L - 1], column t = log p(input_ids[:, t + 1]).
+        adapter: a loaded adapter's name or None (the base weights, the GRPO step's reference policy) to score under; the previously
+        active one is back afterwards.
         Same result layout as `_get_per_token_logps(model, input_ids, attention_mask, pixel_values=...,
         image_grid_thw=...)` of the reference's GRPO trainer (src/train/RL/src/open-r1-multimodal/src/open_r1/
         trainer/grpo_trainer.py:494-504), which it calls without gradients for the old policy and the reference
@@ -203,10 +295,11 @@ class ZoomEarthForConditionalGeneration:
         k = prompt_length - 1 skips the final norm, the lm_head and the log-softmax of every prompt position); shape, layout
         and padding rules are unchanged.  The rows run together through `score_sequences`."""
         e = self.engine
-        items, where, shape = self._score_items(input_ids, attention_mask, pixel_values, image_grid_thw, image_keys, score_from)
-        out = torch.zeros(shape, dtype=torch.float32, device=e.device)
-        for (b, cols), lp in zip(where, self.score_sequences(items, share_prefix=share_prefix, min_shared=min_shared)):
-            out[b, torch.as_tensor(cols, device=e.device)] = lp
+        with adapter_scope(self, adapter):   # (the ViT features of _score_items belong to the adapter too)
+            items, where, shape = self._score_items(input_ids, attention_mask, pixel_values, image_grid_thw, image_keys, score_from)
+            out = torch.zeros(shape, dtype=torch.float32, device=e.device)
+            for (b, cols), lp in zip(where, self.score_sequences(items, share_prefix=share_prefix, min_shared=min_shared)):
+                out[b, torch.as_tensor(cols, device=e.device)] = lp
         return out.to(input_ids.device) if input_ids.device.type != "cpu" else out.cpu()
 
     def _score_items(self, input_ids, attention_mask, pixel_values, image_grid_thw, image_keys, score_from):
@@ -267,7 +360,15 @@ class ZoomEarthForConditionalGeneration:
 
     @torch.no_grad()
     def score_sequences(self, items, share_prefix: bool = True, min_shared: int = 64, top_n: int = 0, entropy: bool = False,
-                        rank: bool = False):
+                        rank: bool = False, adapter=KEEP_ADAPTER):
+        """`_score_sequences` under `adapter` (a loaded adapter's name, or None for the base weights); the previously active adapter is
+        back afterwards.  The items' ViT features are the caller's: for an adapter that touches the vision tower they have to come
+        from the same weights."""
+        with adapter_scope(self, adapter):
+            return self._score_sequences(items, share_prefix, min_shared, top_n, entropy, rank)
+
+    def _score_sequences(self, items, share_prefix: bool = True, min_shared: int = 64, top_n: int = 0, entropy: bool = False,
+                         rank: bool = False):
         """Scores many sequences in as few passes as the engine's limits allow: one f32 tensor per ScoreItem, on the device,
         with the log-probability of the next id at positions item.score_from .. len(ids) - 2 -- the bits `Engine.score` of
         the sequence alone gives there.  The plan (score_plan.plan_score_passes) packs the sequences into `score_batch`

@@ -42,6 +42,7 @@ class Rollout:
     images: list = field(default_factory=list)   # images of the FINAL prompt, in order
     logps: Optional[object] = None   # f32 tensor: log p of every token of the final sequence from position n_prompt1 on
     entropies: Optional[object] = None   # f32 tensor aligned with logps: the policy's entropy at those positions (entropies=True)
+    ref_logps: Optional[object] = None   # f32 tensor aligned with logps: the same positions under the base weights (ref_logps=True)
     # sampled_logps: the decode-time log-probability of every sampled id of the stage (the policy's own `old_per_token_logps` of
     # the completion positions, grpo_trainer.py:660-683), from the step that drew it -- no extra pass
     completion1_logps: List[float] = field(default_factory=list)
@@ -53,7 +54,7 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
                       max_new_tokens: int = 800, seed: int = 0, max_view: int = 512, with_logps: bool = True,
                       burst: int = 8, top_k: Optional[int] = None, top_p: Optional[float] = None,
                       min_p: Optional[float] = None, sampled_logps: bool = False, entropies: bool = False,
-                      prefix_cache=None) -> List[Rollout]:
+                      prefix_cache=None, ref_logps: bool = False) -> List[Rollout]:
     """samples: dicts with `prompt` (the stage-1 prompt text, one `<|vision_start|><|image_pad|><|vision_end|>` block),
     `image` (the tile: DeviceImage or PIL) and `bbox` (the dataset's reference box; empty = non-cropping question).
     top_k / top_p / min_p: the sampling filters of the reference's generation step (GRPOConfig top_k / top_p / min_p,
@@ -65,7 +66,15 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
     prefix_cache: a PrefixCache of the model's engine (zoomearth_amd/prefix_cache.py) that the caller keeps between calls: the rows
     of the chains of one call stay in its pool, and the next call on the same samples prefills only what it does not hold (the
     trainer's `enable_prefix_caching=True`); a weight refresh between the calls empties it.
+    ref_logps: with with_logps and a LoRA adapter active, one more planned scoring call runs under `model.disable_adapter()` and
+    fills Rollout.ref_logps -- the reference-policy log-probabilities of the KL term, which the reference's trainer gets from the
+    same model with the adapter disabled (grpo_trainer.py:672-684).  With no adapter active it raises: the reference policy would
+    be the policy itself.
     Returns len(samples) * num_generations rollouts, sample-major."""
+    if ref_logps and model.active_adapter is None:
+        raise ValueError("ref_logps=True needs an active LoRA adapter: without one the reference policy is the policy itself")
+    if ref_logps and not with_logps:
+        raise ValueError("ref_logps=True needs with_logps=True")
     sched = ChainScheduler(model, processor, do_sample=True, temperature=temperature, seed=seed, burst=burst,
                            top_k=top_k, top_p=top_p, min_p=min_p, logprobs=0 if sampled_logps else None,
                            **({} if prefix_cache is None else {"prefix_cache": prefix_cache}))
@@ -126,7 +135,7 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
 
     if with_logps:
         from .modeling import ScoreItem
-        scored, items = [], []
+        scored, items, pixel_rows = [], [], []
         for ro in out:
             if ro.error:
                 continue
@@ -142,6 +151,8 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
             for g in grids:
                 offs.append(offs[-1] + g[0] * g[1] * g[2])
             feats = [model._features(inp["pixel_values"][offs[i]:offs[i + 1]], grids[i], keys[i]) for i in range(len(grids))]
+            if ref_logps:
+                pixel_rows.append([inp["pixel_values"][offs[i]:offs[i + 1]] for i in range(len(grids))])
             scored.append(ro)
             items.append(ScoreItem(ids, grids, feats, keys, min(max(ro.n_prompt1 - 1, 0), max(len(ids) - 1, 0))))
         # ONE planned call for all rollouts: many sequences per pass, the G generations of a sample share their stage-1 prompt's
@@ -152,4 +163,11 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
         else:
             for ro, lp in zip(scored, model.score_sequences(items)):
                 ro.logps = lp.cpu()
+        if ref_logps:
+            with model.disable_adapter():
+                # (the items' ViT features come from the adapter's vision tower: recomputed under the base weights)
+                base_items = [it._replace(feats=[model._features(pv, g, k) for pv, g, k in zip(pvs, it.grids, it.keys)])
+                              for it, pvs in zip(items, pixel_rows)]
+                for ro, lp in zip(scored, model.score_sequences(base_items)):
+                    ro.ref_logps = lp.cpu()
     return out

@@ -31,6 +31,10 @@ import torch
 
 from .chain_request import ChainRequest
 
+# the default of every `adapter=` argument, here and in modeling.py (which imports this module, so the sentinel lives on this side):
+# leave the model's LoRA adapter as it is
+KEEP_ADAPTER = object()
+
 
 @dataclass
 class Request:
@@ -171,7 +175,7 @@ class ChainScheduler:
                  admit_chunk_rows: int = 0, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  min_p: Optional[float] = None, logprobs: Optional[int] = None, presence_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, logit_bias: Optional[dict] = None, min_new_tokens: Optional[int] = None,
-                 prefix_cache_rows: int = 0, prefix_cache_block_rows: int = 32, prefix_cache=None):
+                 prefix_cache_rows: int = 0, prefix_cache_block_rows: int = 32, prefix_cache=None, adapter=KEEP_ADAPTER):
         self.model, self.processor, self.engine = model, processor, model.engine
         # Logit adjustments: the defaults of requests that name none (None = off).  Written into the slot's rows of the engine's
         # tables next to the filter, with zero counts, for fresh slots and for follow-ups on a parked slot alike; requests with and
@@ -281,6 +285,22 @@ class ChainScheduler:
             self._trace_ev = dict(base=torch.cuda.Event(enable_timing=True), t0=time.perf_counter(), passes=[])
             self._trace_ev["base"].record(torch.cuda.current_stream(self.engine.device))
         model._chains.clear()              # the scheduler owns every chain slot while it runs
+        # LoRA adapter: a loaded adapter's name, None for the base weights, or (the default) whatever the model has active.  Set here,
+        # before any chain exists, and fixed for the scheduler's life: the K/V rows of every chain belong to it.
+        if adapter is not KEEP_ADAPTER:
+            self.set_adapter(adapter)
+
+    def set_adapter(self, adapter) -> None:
+        """Switches the model's LoRA adapter for this scheduler.  Refused while chains are live or being admitted; a switch drops the
+        ViT feature LRU and the parked chains, whose rows came from the other weights (a prefix cache is flushed by the engine's
+        generation)."""
+        if adapter == self.model.active_adapter:
+            return
+        if self.live or self._ready or self._groups or self._carry or self.waiting:
+            raise RuntimeError("the LoRA adapter cannot change while chains are live or waiting")
+        self.model.set_adapter(adapter)
+        self._features.clear()
+        self.parked.clear()   # (a parked slot belongs to a waiting follow-up: there is none)
 
     def close(self) -> None:
         """Gives back what the scheduler created on the engine: the prefix pool of `prefix_cache_rows` (a `prefix_cache` object

@@ -587,7 +587,11 @@ def create_app(server: ChatServer):
 
     @app.get("/v1/models")
     def models():
-        return {"object": "list", "data": [{"id": server.model_id, "object": "model", "owned_by": "zoomearth-mi355x"}]}
+        card = {"id": server.model_id, "object": "model", "owned_by": "zoomearth-mi355x"}
+        adapter = getattr(server.model, "active_adapter", None)
+        if adapter is not None:
+            card["adapter"] = adapter
+        return {"object": "list", "data": [card]}
 
     @app.post("/v1/chat/completions")
     async def chat(request: Request):
@@ -606,6 +610,7 @@ def create_app(server: ChatServer):
 
 def main():  # pragma: no cover
     import argparse
+    import os
 
     import uvicorn
 
@@ -620,8 +625,11 @@ def main():  # pragma: no cover
     ap.add_argument("--prefix-cache-rows", type=int, default=0,
                     help="keep the K/V rows of finished requests in a pool of this many rows (0 = off); later requests that start "
                          "with them prefill only their tail and report usage.prompt_tokens_details.cached_tokens")
+    ap.add_argument("--lora", default=None, help="a PEFT LoRA adapter directory: loaded and activated at start (listed by /v1/models)")
     args = ap.parse_args()
     model = ZoomEarthForConditionalGeneration.from_pretrained(args.model_name)
+    if args.lora:
+        model.set_adapter(model.load_adapter(args.lora, os.path.basename(os.path.normpath(args.lora)) or "default"))
     processor = ZoomEarthProcessor.from_pretrained(args.model_name, trust_remote_code=True, max_pixels=128 * 128 * 28 * 28)
     processor.tokenizer.padding_side = "left"
     uvicorn.run(create_app(ChatServer(model, processor, args.served_model_name, prefix_cache_rows=args.prefix_cache_rows)),
