@@ -688,6 +688,39 @@ int ze_op_quantize_fp8(ze_engine* e, void* w_bf16, int rows, int cols, void* q_o
 int ze_op_linear_mx(ze_engine* e, const void* a8, const void* sa, const void* w8, const void* sw, const void* bias, void* c,
                     int M, int N, int K, int swiglu, void* stream);
 
+/* MXFP4 decode weights (opt-in, REDUCED PRECISION, never the headline configuration): the 4-bit member of the switch above.
+ * Format (OCP MXFP4; restated in numpy by tests/mxfp4_ref.py): W [N, K] is cut into blocks of 32 consecutive k of a row; per block
+ * amax = max |w|, e = floor(log2(amax)) - 2 clamped to [-125, 125] -- the range in which every code * 2^e is a normal bf16 -- and
+ * e = 0 for an all-zero block; the scale byte is e + 127 (E8M0).  An element is w / 2^e rounded to the nearest of {0, 0.5, 1, 1.5,
+ * 2, 3, 4, 6} (E2M1), ties to the even code, magnitudes above 6 saturate to 6, the sign is kept (-0 is code 8).  Canonical layout,
+ * the only one this interface speaks: q u8 [N, K / 2] with the even k in the low nibble, scale u8 [N, K / 32]; the dequantised value
+ * bf16(code * 2^e) is exact.  4.25 bits per weight.
+ * ze_weights_quantize_mxfp4 quantises the tensors ze_weights_quantize_fp8 does (the decoder's projections, an untied lm_head),
+ * REPLACES their bf16 values by the dequantised ones and makes the batch-1 decode GEMVs (ze_decode_step, ze_generate, a single-chain
+ * burst) read the 4-bit stream; prefill, scoring, both batched decode families, the ViT and the fragment-major copies compute from
+ * the dequantised bf16 arena: one model whichever kernel serves a token.  A tensor whose K is not a multiple of 32 keeps its bf16
+ * stream (none of the 3B / 7B decoder tensors: K = 2048 / 11008 and 3584 / 18944).  Life cycle as the FP8 switch: captured graphs
+ * and fragment copies are dropped, the prefix pool's generation moves; any base-weight write (load, fill, arena hand-out, broadcast)
+ * and any adapter switch drops the stream -- quantise again, from the merged arena after a switch (the base store keeps the values
+ * from before the quantisation, as for FP8); the stream's memory is kept for that until the engine is destroyed.  The two formats
+ * exclude each other: this call on an FP8 engine, and ze_weights_quantize_fp8 on an MXFP4 engine, return ZE_ERR_INVALID and change
+ * nothing; ze_set_fp8_activations stays refused without FP8 weights.
+ * ze_op_quantize_mxfp4: the quantiser on one matrix, w bf16 [rows, cols] (device, 16-byte aligned, overwritten with the dequantised
+ * values), q_out u8 [rows, cols / 2] (16-byte aligned), scale_out u8 [rows, cols / 32]; cols % 32 != 0 is ZE_ERR_INVALID, nothing written.
+ * ze_op_gemv4: ze_op_gemv with the MXFP4 stream as W (q4 / scale_e8m0 in the canonical layout, fp32 accumulation, every prologue
+ * and epilogue of ze_op_gemv; there are no FP8 activations on this stream).  K % 32 != 0 is ZE_ERR_INVALID, an x that does not
+ * fit the LDS stage ZE_ERR_NOMEM: outputs untouched, no other kernel runs in its place.
+ * ze_weight_format: which stream the batch-1 decode reads now. */
+#define ZE_WEIGHTS_BF16 0
+#define ZE_WEIGHTS_FP8 1
+#define ZE_WEIGHTS_MXFP4 2
+int ze_weights_quantize_mxfp4(ze_engine* e, void* stream);
+int ze_op_quantize_mxfp4(ze_engine* e, void* w_bf16, int rows, int cols, void* q_out, void* scale_out, void* stream);
+int ze_op_gemv4(ze_engine* e, int epi, const void* q4, const void* scale_e8m0, const void* x_bf16, const void* norm_w, float eps,
+                const void* bias_bf16, int N, int K, void* out_bf16, float* out_f32, const uint8_t* seen, float penalty,
+                int32_t* out_token, int seq, int layer, const void* embed, int token, void* embed_out, void* stream);
+int ze_weight_format(ze_engine* e);
+
 /* ------------------------------------------------------------------ unit ops for parity tests (K3-K22) */
 /* C[M,N] = A[M,K] * W[N,K]^T (+bias[N]) ; bf16 in, fp32 accumulate, bf16 out (one rounding).  act: 0 none, 1 exact GELU,
  * 2 none through the weight-streaming launcher of the batched decode step (split-K; for measurements),

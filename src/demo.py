@@ -17,12 +17,13 @@ from zoomearth_amd.modeling import ZoomEarthForConditionalGeneration  # noqa: E4
 from zoomearth_amd.processor import ZoomEarthProcessor  # noqa: E402
 
 MODEL_PATH = os.environ.get("ZOOMEARTH_MODEL", "")
+WEIGHT_FORMAT = os.environ.get("ZOOMEARTH_WEIGHT_FORMAT") or None   # "fp8" / "mxfp4": reduced-precision decode weights, opt-in
 _STATE = {}
 
 
 def _load():
     if "model" not in _STATE:
-        _STATE["model"] = ZoomEarthForConditionalGeneration.from_pretrained(MODEL_PATH)
+        _STATE["model"] = ZoomEarthForConditionalGeneration.from_pretrained(MODEL_PATH, weight_format=WEIGHT_FORMAT)
         _STATE["processor"] = ZoomEarthProcessor.from_pretrained(MODEL_PATH)
     return _STATE["processor"], _STATE["model"]
 

@@ -22,6 +22,8 @@ e = Engine(cfg, max_seqs=B, max_ctx=2048, max_patches=2048, max_tile_side=1024, 
 e.fill_synthetic(0)
 if os.environ.get("ZE_FP8") in ("1", "2"):  # FP8 decoder weights: the batched step streams fp8 fragments (knob 10 = 1: bf16 copies)
     e.quantize_fp8()
+if os.environ.get("ZE_MXFP4") == "1":  # MXFP4 decoder weights: the batched step computes from the dequantised bf16 copies
+    e.quantize_mxfp4()
 if os.environ.get("ZE_FP8") == "2":  # ... and FP8 activations at the two norm sites (fp8 x fp8 MFMA)
     e.set_fp8_activations(True)
 print(f"model {cfg.name}, fp8 = {os.environ.get('ZE_FP8', '0')} (1 weights, 2 weights + activations)", flush=True)

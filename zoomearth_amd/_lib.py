@@ -180,6 +180,11 @@ _SIGS = {
     "ze_weights_quantize_fp8": (C.c_int, [_P, _P]),
     "ze_set_fp8_activations": (C.c_int, [_P, C.c_int]),
     "ze_op_quantize_fp8": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "ze_weights_quantize_mxfp4": (C.c_int, [_P, _P]),
+    "ze_op_quantize_mxfp4": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "ze_op_gemv4": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_float, _P, C.c_int, C.c_int, _P, _P, _P, C.c_float,
+                              C.POINTER(C.c_int32), C.c_int, C.c_int, _P, C.c_int, _P, _P]),
+    "ze_weight_format": (C.c_int, [_P]),
     "ze_op_linear_mx": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ze_op_linear": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ze_op_rmsnorm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P]),

@@ -30,6 +30,10 @@ struct ze_linear {
     uint8_t* w8 = nullptr;
     float* scale8 = nullptr;
     int ld8 = 0;
+    // MXFP4 decode copy (ze_weights_quantize_mxfp4): E2M1 codes [n, k / 2] + E8M0 block scales [n, k / 32], null = none (the two
+    // formats exclude each other; a tensor whose k is not a multiple of 32 keeps its bf16 stream)
+    uint8_t* w4 = nullptr;
+    uint8_t* scale4 = nullptr;
     // MFMA-fragment-major copy for the batched decode step (ze_launch_pack_fragments), null = none
     bf16_t* wf = nullptr;
     // qkv only, row-streaming regime: rows (and bias) permuted per head for the rope + KV-append epilogue (ze_launch_permute_qkv)
@@ -229,6 +233,8 @@ struct ze_engine {
     ze_linear lm_head8;          // fp8 copy of an untied lm_head (w / ld unused)
     uint8_t* arena8 = nullptr;    // fp8 decode weights (0 until ze_weights_quantize_fp8)
     bool fp8_ready = false;
+    uint8_t* arena4 = nullptr;    // MXFP4 decode weights: codes, then the block scales (0 until ze_weights_quantize_mxfp4)
+    bool mx4_ready = false;       // never together with fp8_ready
     bool fp8_act = false;         // ze_set_fp8_activations: qkv / gate-up inputs quantised to E4M3 per row (needs fp8_ready)
     uint8_t* ty8p = nullptr;      // prefill with FP8 activations: the normalised rows as E4M3 bytes, row-major [rows, hidden]
     float* ty8p_scale = nullptr;  // ... and their scales (block-scaled MFMA GEMM, ze_gemm.hip: k_gemm_ring_mx)

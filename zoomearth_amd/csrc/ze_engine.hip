@@ -12,7 +12,7 @@ extern int ze_live_engines;  // ze_gemv.hip (read by the launch policy of the ei
 static int ze_bound_device = -1;  // the launch-policy caches (hipFuncSetAttribute, CU count) are per process: one GPU per process
 
 // Every weight mutation (load, synthetic fill, arena hand-out for a broadcast / RL refresh) invalidates the derived
-// copies: the fragment-major decode copy is rebuilt on the next batched step, the fp8 stream is dropped (the caller
+// copies: the fragment-major decode copy is rebuilt on the next batched step, the fp8 / MXFP4 stream is dropped (the caller
 // quantises again) and captured decode graphs, which bake the weight pointers in, are re-captured.
 void ze_weights_changed(ze_engine* e) {
     e->frag_ready = false;
@@ -29,6 +29,16 @@ void ze_weights_changed(ze_engine* e) {
         e->lm_head8.w8 = nullptr;
         e->lm_head8.scale8 = nullptr;
         e->lm_head8.wf8 = nullptr;
+    }
+    if (e->mx4_ready) {
+        e->mx4_ready = false;
+        for (auto& L : e->tl)
+            for (ze_linear* l : {&L.qkv, &L.o, &L.gate_up, &L.down}) {
+                l->w4 = nullptr;
+                l->scale4 = nullptr;
+            }
+        e->lm_head8.w4 = nullptr;
+        e->lm_head8.scale4 = nullptr;
     }
     ++ze_tune_epoch;
 }
@@ -448,7 +458,7 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
                    e->st_dev, e->seen, e->out_tokens, e->fe_tmp, e->fe_img, e->fe_coef, e->vx, e->vh, e->vy, e->vqkv,
                    e->vo, e->va, e->vz, e->vz2, e->vcos, e->vsin, e->vperm, e->vinv, e->vtiles_win, e->vtiles_full,
                    e->th, e->ty, e->tqkv, e->to, e->ta, e->tsrc, e->tpos, e->ttiles, e->ttile_aux, e->trow_aux, e->tscore, e->dh, e->dq, e->dattn, e->dact,
-                   e->dlogits, e->dpartial, e->dsample, e->atickets, e->gslab, e->gtickets, e->pslab, e->ptickets, e->bh, e->by, e->bqkv, e->bo, e->ba, e->bseq, e->bmate, e->blogits, e->bpartial, e->bsample, e->arena8, e->arena_f, e->arena_f8,
+                   e->dlogits, e->dpartial, e->dsample, e->atickets, e->gslab, e->gtickets, e->pslab, e->ptickets, e->bh, e->by, e->bqkv, e->bo, e->ba, e->bseq, e->bmate, e->blogits, e->bpartial, e->bsample, e->arena8, e->arena4, e->arena_f, e->arena_f8,
                    e->ty8, e->ty8_scale, e->damax, e->ty8p, e->ty8p_scale, e->xl_dev};
     for (void* p : dev)
         if (p) hipFree(p);

@@ -736,6 +736,8 @@ ze_linear lm_head_linear(const ze_engine* e, bool decode) {
         l.w8 = e->lm_head8.w8;
         l.scale8 = e->lm_head8.scale8;
         l.ld8 = e->lm_head8.ld8;
+        l.w4 = e->lm_head8.w4;
+        l.scale4 = e->lm_head8.scale4;
     }
     return l;
 }
@@ -750,6 +752,10 @@ ze_gemv_args gemv_args_of(const ze_engine* e, const ze_linear& lin, int N, int K
         a.W8 = lin.w8;
         a.scale8 = lin.scale8;
         a.ldw8 = lin.ld8;
+    }
+    if (e->mx4_ready && lin.w4) {
+        a.W4 = lin.w4;
+        a.scale4 = lin.scale4;
     }
     a.N = N;
     a.K = K;
@@ -2341,13 +2347,16 @@ extern "C" int ze_op_kv_read(ze_engine* e, int seq, int layer, int start, int n,
 // ONE launch of the single-chain decode GEMV family (ze_launch_gemv: k_gemv, bf16 or FP8 stream) on the caller's device operands,
 // every epilogue and prologue reachable -- the product path calls the launcher only from ze_enqueue_decode_step / ze_prefill, with
 // the model's own shapes.  epi = the ZE_GV_* code.  A shape the launcher refuses is an error, never another kernel.
-extern "C" int ze_op_gemv(ze_engine* e, int epi, const void* w_bf16, const void* w8, const void* scale8, const void* x_bf16,
-                          const void* norm_w, float eps, const void* bias_bf16, int act8, int N, int K, void* out_bf16,
-                          float* out_f32, const uint8_t* seen, float penalty, int32_t* out_token, int seq, int layer,
-                          const void* embed, int token, void* embed_out, void* stream) {
-    if (!e || (!w_bf16 && !w8) || (w8 && !scale8) || (!x_bf16 && !embed)) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+// (w4 / scale4 non-null: the MXFP4 stream of ze_op_gemv4)
+static int op_gemv_any(ze_engine* e, int epi, const void* w_bf16, const void* w8, const void* scale8, const void* w4, const void* scale4,
+                       const void* x_bf16, const void* norm_w, float eps, const void* bias_bf16, int act8, int N, int K, void* out_bf16,
+                       float* out_f32, const uint8_t* seen, float penalty, int32_t* out_token, int seq, int layer,
+                       const void* embed, int token, void* embed_out, void* stream) {
+    if (!e || (!w_bf16 && !w8 && !w4) || (w8 && !scale8) || (w4 && !scale4) || (!x_bf16 && !embed))
+        return ze_fail(e, ZE_ERR_INVALID, "null argument");
     if (epi < ZE_GV_QKV_ROPE || epi > ZE_GV_PLAIN) return ze_fail(e, ZE_ERR_INVALID, "unknown epilogue");
     if (N < 2 || N % 2 || K < 8 || K % 8) return ze_fail(e, ZE_ERR_INVALID, "N must be even, K a multiple of 8");
+    if (w4 && K % 32) return ze_fail(e, ZE_ERR_INVALID, "the MXFP4 stream needs K % 32 == 0 (one scale per 32 elements)");
     if (epi == ZE_GV_SWIGLU && N % 32) return ze_fail(e, ZE_ERR_INVALID, "SwiGLU: N = 2 * width with width % 16 == 0");
     if (epi == ZE_GV_LOGITS ? !out_f32 : !out_bf16) return ze_fail(e, ZE_ERR_INVALID, "null output");
     if (act8 && (!w8 || !norm_w)) return ze_fail(e, ZE_ERR_INVALID, "act8 goes with the FP8 stream and the norm prologue");
@@ -2386,6 +2395,8 @@ extern "C" int ze_op_gemv(ze_engine* e, int epi, const void* w_bf16, const void*
     a.W8 = (const uint8_t*)w8;
     a.scale8 = (const float*)scale8;
     a.ldw8 = K;
+    a.W4 = (const uint8_t*)w4;
+    a.scale4 = (const uint8_t*)scale4;
     a.N = N;
     a.K = K;
     a.x = (const bf16_t*)x_bf16;
@@ -2431,6 +2442,23 @@ extern "C" int ze_op_gemv(ze_engine* e, int epi, const void* w_bf16, const void*
     return r;
 }
 
+extern "C" int ze_op_gemv(ze_engine* e, int epi, const void* w_bf16, const void* w8, const void* scale8, const void* x_bf16,
+                          const void* norm_w, float eps, const void* bias_bf16, int act8, int N, int K, void* out_bf16,
+                          float* out_f32, const uint8_t* seen, float penalty, int32_t* out_token, int seq, int layer,
+                          const void* embed, int token, void* embed_out, void* stream) {
+    return op_gemv_any(e, epi, w_bf16, w8, scale8, nullptr, nullptr, x_bf16, norm_w, eps, bias_bf16, act8, N, K, out_bf16, out_f32, seen,
+                       penalty, out_token, seq, layer, embed, token, embed_out, stream);
+}
+
+// the same launch with the MXFP4 stream as W (ze_gemv4.hip): q4 u8 [N, K / 2], scale_e8m0 u8 [N, K / 32]
+extern "C" int ze_op_gemv4(ze_engine* e, int epi, const void* q4, const void* scale_e8m0, const void* x_bf16, const void* norm_w, float eps,
+                           const void* bias_bf16, int N, int K, void* out_bf16, float* out_f32, const uint8_t* seen, float penalty,
+                           int32_t* out_token, int seq, int layer, const void* embed, int token, void* embed_out, void* stream) {
+    if (!q4 || !scale_e8m0) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    return op_gemv_any(e, epi, nullptr, nullptr, nullptr, q4, scale_e8m0, x_bf16, norm_w, eps, bias_bf16, 0, N, K, out_bf16, out_f32, seen,
+                       penalty, out_token, seq, layer, embed, token, embed_out, stream);
+}
+
 // fp32 logits of n hidden rows through the lm_head pass of the prefill paths (ze_launch_logits_rows: k_logits_multi, final RMSNorm
 // fused, one pass over W per eight rows).  A K the launcher refuses (eight staged rows do not fit in LDS) is ZE_ERR_NOMEM.
 extern "C" int ze_op_logits_rows(ze_engine* e, const void* w_bf16, const void* norm_w, float eps, const void* x_bf16, float* out_f32,
@@ -2463,6 +2491,7 @@ static int quantize_linear(ze_engine* e, ze_linear& l, int rows, int cols, uint8
 
 extern "C" int ze_weights_quantize_fp8(ze_engine* e, void* stream) {
     if (!e) return ze_fail(e, ZE_ERR_INVALID, "null engine");
+    if (e->mx4_ready) return ze_fail(e, ZE_ERR_INVALID, "the engine streams MXFP4 decode weights: the two formats exclude each other");
     if (e->fp8_ready) return ZE_OK;  // (a weight change clears the flag: ze_weights_changed)
     const ze_config& c = e->cfg;
     hipStream_t s = (hipStream_t)stream;
@@ -2502,6 +2531,77 @@ extern "C" int ze_weights_quantize_fp8(ze_engine* e, void* stream) {
     ze_prefix_weights_changed(e);
     ++ze_tune_epoch;  // captured decode steps hold the bf16 streams
     return ZE_OK;
+}
+
+// ================================================================== MXFP4 decode weights
+// The life cycle of the fp8 switch above, line by line, with the 4-bit stream in the fp8 stream's place; only the batch-1 GEMVs read
+// it (gemv_args_of), every other path computes from the dequantised bf16 arena.
+static bool mx4_takes(const ze_linear& l, int cols) { return cols % 32 == 0 && l.ld % 8 == 0; }
+
+extern "C" int ze_weights_quantize_mxfp4(ze_engine* e, void* stream) {
+    if (!e) return ze_fail(e, ZE_ERR_INVALID, "null engine");
+    if (e->fp8_ready) return ze_fail(e, ZE_ERR_INVALID, "the engine streams FP8 decode weights: the two formats exclude each other");
+    if (e->mx4_ready) return ZE_OK;  // (a weight change clears the flag: ze_weights_changed)
+    const ze_config& c = e->cfg;
+    hipStream_t s = (hipStream_t)stream;
+    hipSetDevice(e->device);
+    const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nqkv = nq + 2 * c.kv_heads * hd, ip = e->text_ipad;
+    const bool head = !c.tie_word_embeddings;  // a tied lm_head is the embedding table: it stays bf16
+    if (head) {
+        e->lm_head8.w = e->lm_head;
+        e->lm_head8.ld = H;
+    }
+    // (tensor, rows, cols) in stream order; a tensor whose K is not a multiple of 32 keeps its bf16 stream
+    std::vector<std::tuple<ze_linear*, int, int>> todo;
+    for (int li = 0; li < c.layers; ++li) {
+        ze_text_layer& L = e->tl[li];
+        todo.emplace_back(&L.qkv, nqkv, H);
+        todo.emplace_back(&L.o, H, nq);
+        todo.emplace_back(&L.gate_up, 2 * ip, H);
+        todo.emplace_back(&L.down, H, ip);
+    }
+    if (head) todo.emplace_back(&e->lm_head8, c.vocab, H);
+    size_t codes = 0, scales = 0;
+    for (auto& t : todo) {
+        if (!mx4_takes(*std::get<0>(t), std::get<2>(t))) continue;
+        codes += (size_t)std::get<1>(t) * (std::get<2>(t) / 2);   // rows of K / 2 bytes: a multiple of 16
+        scales += (size_t)std::get<1>(t) * (std::get<2>(t) / 32);
+    }
+    if (!e->arena4) ZE_HIP(hipMalloc((void**)&e->arena4, codes + scales + 256));  // re-quantisation reuses it
+    uint8_t* cur4 = e->arena4;
+    uint8_t* curs = e->arena4 + codes;
+    for (auto& t : todo) {
+        ze_linear& l = *std::get<0>(t);
+        const int rows = std::get<1>(t), cols = std::get<2>(t);
+        if (!mx4_takes(l, cols)) continue;
+        l.w4 = cur4;
+        l.scale4 = curs;
+        cur4 += (size_t)rows * (cols / 2);
+        curs += (size_t)rows * (cols / 32);
+        ze_launch_quantize_mxfp4(l.w, rows, cols, l.ld, l.w4, l.scale4, s);
+    }
+    ZE_KCHECK();
+    ZE_HIP(hipStreamSynchronize(s));
+    e->mx4_ready = true;
+    e->frag_ready = false;  // the bf16 copies were replaced by the dequantised values
+    ze_prefix_weights_changed(e);
+    ++ze_tune_epoch;  // captured decode steps hold the bf16 streams
+    return ZE_OK;
+}
+
+extern "C" int ze_op_quantize_mxfp4(ze_engine* e, void* w_bf16, int rows, int cols, void* q_out, void* scale_out, void* stream) {
+    if (!e || !w_bf16 || !q_out || !scale_out || rows <= 0 || cols <= 0 || cols % 32)
+        return ze_fail(e, ZE_ERR_INVALID, "bad argument (cols must be a multiple of 32)");
+    if (((uintptr_t)w_bf16 | (uintptr_t)q_out) % 16) return ze_fail(e, ZE_ERR_INVALID, "w_bf16 and q_out must be 16-byte aligned");
+    hipSetDevice(e->device);
+    ze_launch_quantize_mxfp4((bf16_t*)w_bf16, rows, cols, cols, (uint8_t*)q_out, (uint8_t*)scale_out, (hipStream_t)stream);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
+extern "C" int ze_weight_format(ze_engine* e) {
+    if (!e) return ze_fail(e, ZE_ERR_INVALID, "null engine");
+    return e->mx4_ready ? ZE_WEIGHTS_MXFP4 : e->fp8_ready ? ZE_WEIGHTS_FP8 : ZE_WEIGHTS_BF16;
 }
 
 extern "C" int ze_set_fp8_activations(ze_engine* e, int on) {

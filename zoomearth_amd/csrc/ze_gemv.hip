@@ -12,6 +12,7 @@
 #include "ze_gemv_kernel.h"
 
 bool ze_launch_gemv8(int epi, const ze_gemv_args& a, hipStream_t s);
+bool ze_launch_gemv4(int epi, const ze_gemv_args& a, hipStream_t s);
 
 // overrides set through ze_tune(): [0] down variant, [1] gate_up variant, [2] grid cap, [3] fused attention block
 int ze_gemv_knobs[24] = {0};
@@ -24,6 +25,7 @@ bool ze_launch_gemv(int epi, const ze_gemv_args& a, hipStream_t s) {
     if ((size_t)((a.K + 511) / 512 + 2) * 1024 > 60000) return false;  // x must fit the LDS stage
     const bool long_k = a.K > 4096;
     const bool many_rows = a.N >= 8192;
+    if (a.W4) return ze_launch_gemv4(epi, a, s);  // MXFP4 weight stream (ze_gemv4.hip)
     if (a.W8) return ze_launch_gemv8(epi, a, s);  // fp8 weight stream (ze_gemv8.hip)
     switch (epi) {
         // (K split over the waves -- 1280 one-pair workgroups, five per CU -- measured 8.2 us against 6.9: every workgroup

@@ -1,5 +1,5 @@
 // The decode weight-streaming kernel template (k_gemv) and its launch helper, shared by the bf16 instantiations
-// (ze_gemv.hip) and the fp8 ones (ze_gemv8.hip).  Two translation units on purpose: instantiations of one template
+// (ze_gemv.hip), the fp8 ones (ze_gemv8.hip) and the MXFP4 ones (ze_gemv4.hip).  Separate translation units on purpose: instantiations of one template
 // compiled together share register-allocation context, and adding the fp8 variants to the bf16 unit moved the
 // dominant bf16 kernel by +2 % (16.1 vs 15.8 us) with an unchanged instruction mix.
 #pragma once
@@ -21,6 +21,45 @@ __device__ __forceinline__ uint4 load_w16(const bf16_t* p) {
 #endif
 }
 
+// what one lane holds of one weight row for one chunk: 16 B of the stream -- and, for the MXFP4 stream, the E8M0 byte of the ONE
+// 32-element block those 16 B are
+template <int WB>
+struct wtrip {
+    uint4 q;
+};
+template <>
+struct wtrip<4> {
+    uint4 q;
+    uint32_t s;
+};
+
+// two E2M1 codes (byte `b` of w: low nibble first) times the block scale 2^e -> two f32, exact.  Default: gfx950's packed
+// conversion, one instruction per pair.  -DZE_FP4_BITS: measurement build that constructs the floats with integer shifts (the
+// other candidate of DESIGN.md 7j; both are exact, so no test tells them apart).
+typedef float f32x2_w __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2_w fp4x2_to_f32(uint32_t w, float scale, int b) {
+#ifdef ZE_FP4_BITS
+    const uint32_t n = w >> (8 * b);
+    f32x2_w r;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const uint32_t c = (n >> (4 * h)) & 15u, m = c & 7u;
+        // m >= 2: 1.x * 2^(m / 2 - 1), the exponent and the mantissa bit are the code's own bits; m < 2: 0 or 0.5
+        const uint32_t bits = (m >= 2u) ? 0x3F000000u + (m << 22) : m * 0x3F000000u;
+        const float v = __uint_as_float(bits | ((c & 8u) << 28)) * scale;
+        if (h == 0) r.x = v; else r.y = v;
+    }
+    return r;
+#else
+    switch (b) {  // the byte select is an instruction modifier: a constant after unrolling
+        case 0: return __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 0);
+        case 1: return __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 1);
+        case 2: return __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 2);
+        default: return __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 3);
+    }
+#endif
+}
+
 template <int PAIRS>
 struct epi_in {
     float b1[PAIRS], b2[PAIRS];  // bias of the two rows
@@ -38,13 +77,17 @@ struct epi_in {
 //  the boundary whatever the issue structure, so the remaining lever is hiding the fixed part across launches.)
 // WB: bits per weight.  16: bf16 rows.  8: OCP E4M3 rows with a per-row power-of-two scale (ze_quant.hip): a 16-B load
 // carries 16 weights, a chunk is 1024 elements, the conversion is v_cvt_pk_f32_fp8 in registers, and the row's dot
-// product is scaled once (exactly) in the epilogue.
+// product is scaled once (exactly) in the epilogue.  4: OCP MXFP4 rows (ze_quant.hip: E2M1 codes, low nibble = even k, one E8M0
+// scale per 32 elements): a 16-B load carries exactly one scale block, a chunk is 2048 elements, the lane loads its block's scale
+// byte beside the codes, v_cvt_scalef32_pk_f32_fp4 yields the dequantised pair (code * 2^e, exact) and the inner loop is the fp8
+// one.  x sits in LDS with the four 16-B pieces of a lane's 32 elements 1 KiB apart, so that each ds_read_b128 of a wave is one
+// contiguous KiB (a lane-major 64-B stride would put four lanes of every 16-lane group on one bank slot).
 template <int EPI, int PAIRS, int KSPLIT, int CH, int WB = 16>
 __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     bf16_t* xs = reinterpret_cast<bf16_t*>(smem);
     const int K = a.K;
-    constexpr int CSH = (WB == 8) ? 10 : 9;       // log2(elements per chunk): 64 lanes x 16 B of weights
+    constexpr int CSH = (WB == 4) ? 11 : (WB == 8) ? 10 : 9;  // log2(elements per chunk): 64 lanes x 16 B of weights
     constexpr int CE = 1 << CSH, EPL = CE / 64;   // elements per chunk / per lane
     const int nch = (K + CE - 1) >> CSH;          // the last chunk may be partial
     const int Kp = nch << CSH;
@@ -69,10 +112,21 @@ __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
         pos = ctx + a.st->rope_delta;
     }
 
-    // weight rows are addressed in BYTES (bf16: 2 per element, fp8: 1)
+    // weight rows are addressed in BYTES (bf16: 2 per element, fp8: 1, MXFP4: two elements per byte, rows of K / 2)
     constexpr int WBYTES = WB / 8;
-    const uint8_t* Wb = (WB == 8) ? a.W8 : reinterpret_cast<const uint8_t*>(a.W);
-    const size_t ldb = (WB == 8) ? (size_t)a.ldw8 : (size_t)a.ldw * 2;
+    const uint8_t* Wb = (WB == 4) ? a.W4 : (WB == 8) ? a.W8 : reinterpret_cast<const uint8_t*>(a.W);
+    const size_t ldb = (WB == 4) ? (size_t)(K >> 1) : (WB == 8) ? (size_t)a.ldw8 : (size_t)a.ldw * 2;
+    // one weight load of a lane: element offset `off` of row `wr` (MXFP4: with the scale byte of block off / 32)
+    auto load_w = [&](const uint8_t* wr, int off, wtrip<WB>& w) {
+        if constexpr (WB == 4) {
+            w.q = load_w16(reinterpret_cast<const bf16_t*>(wr + (off >> 1)));
+            w.s = a.scale4[((size_t)(wr - Wb) >> 4) + (off >> 5)];  // a row is K / 2 bytes = 16 bytes per scale block
+        } else {
+            w.q = load_w16(reinterpret_cast<const bf16_t*>(wr + off * WBYTES));
+        }
+    };
+    // MXFP4: 16-B vector v of x lives at slot (chunk, piece v & 3, lane) -- see the note on WB above
+    auto xslot = [](int v) { return (WB == 4) ? ((v & ~255) | ((v & 3) << 6) | ((v >> 2) & 63)) : v; };
     auto rows_of = [&](int p0, const uint8_t* (&wrow)[2 * PAIRS], int (&r1)[PAIRS], int (&r2)[PAIRS]) {
 #pragma unroll
         for (int i = 0; i < PAIRS; ++i) {
@@ -91,12 +145,12 @@ __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
             wrow[2 * i + 1] = Wb + (size_t)r2[i] * ldb;
         }
     };
-    auto load_full = [&](const uint8_t* const (&wrow)[2 * PAIRS], int c0, uint4 (&w)[CH][2 * PAIRS]) {
+    auto load_full = [&](const uint8_t* const (&wrow)[2 * PAIRS], int c0, wtrip<WB> (&w)[CH][2 * PAIRS]) {
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
-            const int off = min(((c0 + u * c_step) << CSH) + lane_off, last_off) * WBYTES;
+            const int off = min(((c0 + u * c_step) << CSH) + lane_off, last_off);
 #pragma unroll
-            for (int i = 0; i < 2 * PAIRS; ++i) w[u][i] = load_w16(reinterpret_cast<const bf16_t*>(wrow[i] + off));
+            for (int i = 0; i < 2 * PAIRS; ++i) load_w(wrow[i], off, w[u][i]);
         }
     };
     auto load_epi = [&](const int (&r1)[PAIRS], const int (&r2)[PAIRS], epi_in<PAIRS>& e) {
@@ -142,7 +196,7 @@ __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
     // (the first trip may run past the last chunk: those loads re-read the row's last 16 B and meet the all-zero
     //  chunk kept behind x in LDS, so every wave -- not only those with a full first trip -- streams from t = 0)
     const bool pre = p_first < P;  // wave-uniform
-    uint4 wpre[CH][2 * PAIRS];
+    wtrip<WB> wpre[CH][2 * PAIRS];
     const uint8_t* wrow0[2 * PAIRS];
     int r10[PAIRS], r20[PAIRS];
     epi_in<PAIRS> e0;
@@ -157,7 +211,7 @@ __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
     auto stage_x = [&](int v, uint4 q) {
         if (v * 8 >= K) q = make_uint4(0, 0, 0, 0);
         if (a.embed && blockIdx.x == 0 && v * 8 < K) *reinterpret_cast<uint4*>(a.embed_out + v * 8) = q;
-        *reinterpret_cast<uint4*>(xs + v * 8) = q;
+        *reinterpret_cast<uint4*>(xs + xslot(v) * 8) = q;
         const uint32_t u[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) ss += bf16lo(u[j]) * bf16lo(u[j]) + bf16hi(u[j]) * bf16hi(u[j]);
@@ -177,7 +231,7 @@ __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
         const float inv = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)K + a.eps);
         __syncthreads();
         for (int v = tid; v < (K >> 3); v += 256) {
-            const uint4 q = *reinterpret_cast<const uint4*>(xs + v * 8);
+            const uint4 q = *reinterpret_cast<const uint4*>(xs + xslot(v) * 8);
             const uint4 g = (v == tid) ? g0 : *reinterpret_cast<const uint4*>(a.norm_w + v * 8);
             const uint32_t u[4] = {q.x, q.y, q.z, q.w}, gw[4] = {g.x, g.y, g.z, g.w};
             uint32_t o[4];
@@ -185,7 +239,7 @@ __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
             for (int j = 0; j < 4; ++j)
                 o[j] = pack_bf16x2(bf16_round(bf16lo(u[j]) * inv) * bf16lo(gw[j]),
                                    bf16_round(bf16hi(u[j]) * inv) * bf16hi(gw[j]));
-            *reinterpret_cast<uint4*>(xs + v * 8) = make_uint4(o[0], o[1], o[2], o[3]);
+            *reinterpret_cast<uint4*>(xs + xslot(v) * 8) = make_uint4(o[0], o[1], o[2], o[3]);
         }
         if constexpr (WB == 8) {
             if (a.act8) {  // FP8 activations: the row's E4M3 quantisation (per-row power-of-two scale), kept as bf16 in LDS
@@ -231,18 +285,44 @@ __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
     int best_i = 0x7fffffff;
     // one pair set (2*PAIRS rows); `w0` / `ein` optionally hold its already-issued first trip and epilogue operands
     auto pair_set = [&](int p0, const uint8_t* const (&wrow)[2 * PAIRS], const int (&r1)[PAIRS], const int (&r2)[PAIRS],
-                        auto have_first, uint4 (&w0)[CH][2 * PAIRS], epi_in<PAIRS>& ein) {
+                        auto have_first, wtrip<WB> (&w0)[CH][2 * PAIRS], epi_in<PAIRS>& ein) {
         typedef float f32x2_t __attribute__((ext_vector_type(2)));
         float acc[2 * PAIRS];
-        f32x2_t acc2[2 * PAIRS];  // fp8 path: even / odd elements accumulate separately (v_pk_fma_f32)
+        f32x2_t acc2[2 * PAIRS];  // fp8 / MXFP4 paths: even / odd elements accumulate separately (v_pk_fma_f32)
 #pragma unroll
         for (int i = 0; i < 2 * PAIRS; ++i) {
             acc[i] = 0.f;
             acc2[i] = f32x2_t{0.f, 0.f};
         }
-        auto fma_chunk = [&](int c, const uint4 (&wc)[2 * PAIRS]) {
+        auto fma_chunk = [&](int c, const wtrip<WB> (&wc)[2 * PAIRS]) {
             c = min(c, nch);  // chunk nch is the zero chunk
-            if constexpr (WB == 8) {
+            if constexpr (WB == 4) {
+                // 32 weights per lane, all of one scale block: word j of the load holds elements 8j .. 8j+7, byte b of it the pair
+                // (8j + 2b, 8j + 2b + 1) = word b of x piece j.  The scale byte becomes the float 2^e (byte << 23: 2 <= byte <= 252).
+                f32x2_t xf[16];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint4 xp = *reinterpret_cast<const uint4*>(xs + (c << CSH) + (j << 9) + (lane << 3));
+                    const uint32_t xu[4] = {xp.x, xp.y, xp.z, xp.w};
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) xf[4 * j + b] = f32x2_t{bf16lo(xu[b]), bf16hi(xu[b])};
+                }
+#pragma unroll
+                for (int i = 0; i < 2 * PAIRS; ++i) {
+                    const uint32_t wu[4] = {wc[i].q.x, wc[i].q.y, wc[i].q.z, wc[i].q.w};
+                    const float sc = __uint_as_float(wc[i].s << 23);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        acc2[i] = __builtin_elementwise_fma(fp4x2_to_f32(wu[j], sc, 0), xf[4 * j], acc2[i]);
+                        acc2[i] = __builtin_elementwise_fma(fp4x2_to_f32(wu[j], sc, 1), xf[4 * j + 1], acc2[i]);
+                        acc2[i] = __builtin_elementwise_fma(fp4x2_to_f32(wu[j], sc, 2), xf[4 * j + 2], acc2[i]);
+                        acc2[i] = __builtin_elementwise_fma(fp4x2_to_f32(wu[j], sc, 3), xf[4 * j + 3], acc2[i]);
+                    }
+                    // one row at a time: left alone, the scheduler converts every row of the set first and keeps 32 floats per
+                    // row alive (185 VGPRs at two pairs, half the occupancy of the family)
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            } else if constexpr (WB == 8) {
                 // 16 weights per lane: word j of the load holds elements 4j .. 4j+3.  x comes as two 16-B LDS reads and
                 // is widened to f32 pairs once for all rows of the set; a weight word costs two v_cvt_pk_f32_fp8 and
                 // two packed FMAs (the stream is otherwise VALU-co-limited: 2.5 scalar ops per weight measured 20 %
@@ -255,7 +335,7 @@ __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
                 for (int j = 0; j < 8; ++j) xf[j] = f32x2_t{bf16lo(xu[j]), bf16hi(xu[j])};
 #pragma unroll
                 for (int i = 0; i < 2 * PAIRS; ++i) {
-                    const uint32_t wu[4] = {wc[i].x, wc[i].y, wc[i].z, wc[i].w};
+                    const uint32_t wu[4] = {wc[i].q.x, wc[i].q.y, wc[i].q.z, wc[i].q.w};
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)wu[j], false);
@@ -269,7 +349,7 @@ __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
                 const uint32_t xu[4] = {xq.x, xq.y, xq.z, xq.w};
 #pragma unroll
                 for (int i = 0; i < 2 * PAIRS; ++i) {
-                    const uint32_t wu[4] = {wc[i].x, wc[i].y, wc[i].z, wc[i].w};
+                    const uint32_t wu[4] = {wc[i].q.x, wc[i].q.y, wc[i].q.z, wc[i].q.w};
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         acc[i] = fmaf(bf16lo(wu[j]), bf16lo(xu[j]), acc[i]);
@@ -288,21 +368,21 @@ __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
         }
         // full trips: CH chunks x 2*PAIRS rows of independent 16-B loads per lane, no conditions at all
         for (; c0 + (CH - 1) * c_step < nch; c0 += CH * c_step) {
-            uint4 w[CH][2 * PAIRS];
+            wtrip<WB> w[CH][2 * PAIRS];
             load_full(wrow, c0, w);
 #pragma unroll
             for (int u = 0; u < CH; ++u) fma_chunk(c0 + u * c_step, w[u]);
         }
         // tail: the remaining (< CH) chunks of this wave, guarded by wave-uniform (scalar) conditions only
         if (CH > 1 && c0 < nch) {
-            uint4 w[CH > 1 ? CH - 1 : 1][2 * PAIRS];
+            wtrip<WB> w[CH > 1 ? CH - 1 : 1][2 * PAIRS];
 #pragma unroll
             for (int u = 0; u < CH - 1; ++u) {
                 const int c = c0 + u * c_step;
                 if (c < nch) {
-                    const int off = min((c << CSH) + lane_off, last_off) * WBYTES;
+                    const int off = min((c << CSH) + lane_off, last_off);
 #pragma unroll
-                    for (int i = 0; i < 2 * PAIRS; ++i) w[u][i] = load_w16(reinterpret_cast<const bf16_t*>(wrow[i] + off));
+                    for (int i = 0; i < 2 * PAIRS; ++i) load_w(wrow[i], off, w[u][i]);
                 }
             }
 #pragma unroll
@@ -311,7 +391,7 @@ __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
                 if (c < nch) fma_chunk(c, w[u]);
             }
         }
-        if constexpr (WB == 8) {
+        if constexpr (WB != 16) {
 #pragma unroll
             for (int i = 0; i < 2 * PAIRS; ++i) acc[i] = acc2[i].x + acc2[i].y;
         }
@@ -418,7 +498,7 @@ extern int ze_gemv_knobs[24];
 template <int EPI, int PAIRS, int KSPLIT, int CH, int WB = 16>
 static void launch_gemv_cfg(const ze_gemv_args& a, hipStream_t s) {
     const int P = a.N / 2;
-    constexpr int CE = (WB == 8) ? 1024 : 512;
+    constexpr int CE = (WB == 4) ? 2048 : (WB == 8) ? 1024 : 512;
     const int nch = (a.K + CE - 1) / CE;
     const size_t lds = (size_t)(nch + 1) * CE * 2 + 4 * 2 * PAIRS * sizeof(float) + 64;
     int grid = (KSPLIT == 1) ? ze_cdiv(P, 4 * PAIRS) : ze_cdiv(P, PAIRS);

@@ -224,6 +224,10 @@ struct ze_gemv_args {
     const uint8_t* seen;
     float penalty;
     float* amax_ws;
+    // MXFP4 weight stream (non-null W4 selects it; K % 32 == 0): E2M1 codes [N, K / 2], low nibble = even k, and one E8M0 scale
+    // byte per 32 elements [N, K / 32] -- the canonical layout of include/zoomearth.h, dense rows
+    const uint8_t* W4;
+    const uint8_t* scale4;
 };
 // returns false when x[K] does not fit the LDS stage
 bool ze_launch_gemv(int epi, const ze_gemv_args& a, hipStream_t s);
@@ -234,6 +238,9 @@ bool ze_launch_logits_rows(const bf16_t* W, int ldw, int N, int K, const bf16_t*
 // per-row power-of-two-scale E4M3 quantisation of a bf16 matrix [rows, ld] (cols valid): writes the fp8 bytes
 // [rows, ld8], the scales, and REPLACES the bf16 values by the dequantised ones (exactly representable)
 void ze_launch_quantize_rows(bf16_t* w, int rows, int cols, int ld, uint8_t* q, int ld8, float* scale, hipStream_t s);
+// OCP MXFP4 quantisation of a bf16 matrix [rows, ld] (cols valid, cols % 32 == 0): E2M1 codes q [rows, cols / 2], E8M0 scales
+// [rows, cols / 32], and the bf16 values REPLACED by the dequantised ones (ze_quant.hip states the format)
+void ze_launch_quantize_mxfp4(bf16_t* w, int rows, int cols, int ld, uint8_t* q, uint8_t* scale, hipStream_t s);
 
 // ---- attention
 // Varlen flash attention (prefill / ViT). Tiles: host-built list of (q_start, q_end, kv_start, kv_end) int4 rows.

@@ -30,11 +30,16 @@ static int time_launches(ze_engine* e, hipStream_t s, int warm, int iters, F lau
     return r;
 }
 
-// algorithmic bytes of a weight matrix: bf16, or the FP8 copy (1 byte per weight + one fp32 scale per row)
+// algorithmic bytes of a weight matrix as launch `g` streams it: bf16, the FP8 copy (1 byte per weight + one fp32 scale per row), or
+// the MXFP4 copy (half a byte per weight + one scale byte per 32 weights)
 static double weight_bytes(double rows, double cols, bool fp8) { return fp8 ? rows * cols + rows * 4.0 : rows * cols * 2.0; }
+static double weight_bytes(double rows, double cols, const ze_gemv_args& g) {
+    if (g.W4) return rows * cols * 0.5 + rows * cols / 32.0;
+    return weight_bytes(rows, cols, g.W8 != nullptr);
+}
 
 // The weight-streaming kernels of the SINGLE-CHAIN decode step (chain slot 0), one kind per call, with the arguments
-// ze_enqueue_decode_step gives them: a quantised engine streams the FP8 copy, with FP8 activations where the step has them.
+// ze_enqueue_decode_step gives them: a quantised engine streams its FP8 or MXFP4 copy, with FP8 activations where the step has them.
 extern "C" int ze_profile_decode_kernel(ze_engine* e, int which, int iters, float* avg_us, double* bytes_per_launch,
                                         void* stream) {
     if (!e || !avg_us || !bytes_per_launch || iters <= 0) return ze_fail(e, ZE_ERR_INVALID, "bad argument");
@@ -56,31 +61,31 @@ extern "C" int ze_profile_decode_kernel(ze_engine* e, int which, int iters, floa
                 g.norm_w = L.in_norm; g.eps = c.rms_eps; g.bias = L.qkv.bias; g.out_bf16 = e->dq; g.st = e->st_dev; g.cosT = e->cosT;
                 g.sinT = e->sinT; g.kcache = e->kc(li, 0); g.vcache = e->vc(li, 0);
                 g.heads = c.heads; g.kv_heads = c.kv_heads; g.max_ctx = c.max_ctx; g.act8 = e->fp8_act ? 1 : 0;
-                bytes = weight_bytes(nqkv, H, g.W8 != nullptr);
+                bytes = weight_bytes(nqkv, H, g);
                 ze_launch_gemv(ZE_GV_QKV_ROPE, g, s);
                 break;
             case 1:
                 g = gemv_args_of(e, L.o, H, nq, e->dattn);
                 g.out_bf16 = e->dh;
-                bytes = weight_bytes(H, nq, g.W8 != nullptr);
+                bytes = weight_bytes(H, nq, g);
                 ze_launch_gemv(ZE_GV_RESIDUAL, g, s);
                 break;
             case 2:
                 g = gemv_args_of(e, L.gate_up, 2 * ip, H, e->dh);
                 g.norm_w = L.post_norm; g.eps = c.rms_eps; g.out_bf16 = e->dact; g.act8 = e->fp8_act ? 1 : 0;
-                bytes = weight_bytes(2.0 * c.intermediate, H, g.W8 != nullptr);
+                bytes = weight_bytes(2.0 * c.intermediate, H, g);
                 ze_launch_gemv(ZE_GV_SWIGLU, g, s);
                 break;
             case 3:
                 g = gemv_args_of(e, L.down, H, ip, e->dact);
                 g.out_bf16 = e->dh;
-                bytes = weight_bytes(H, c.intermediate, g.W8 != nullptr);
+                bytes = weight_bytes(H, c.intermediate, g);
                 ze_launch_gemv(ZE_GV_RESIDUAL, g, s);
                 break;
             default:
                 g = gemv_args_of(e, lm_head_linear(e, true), c.vocab, H, e->dh);
                 g.norm_w = e->final_norm; g.eps = c.rms_eps; g.out_f32 = e->dlogits;
-                bytes = weight_bytes(c.vocab, H, g.W8 != nullptr);
+                bytes = weight_bytes(c.vocab, H, g);
                 ze_launch_gemv(ZE_GV_LOGITS, g, s);
                 break;
         }

@@ -961,6 +961,27 @@ class Engine:
         """Switch the decoder's linear layers to FP8 (E4M3, per-row power-of-two scales): see ze_weights_quantize_fp8."""
         self._check(self.lib.ze_weights_quantize_fp8(self.h, self._stream()))
 
+    def quantize_mxfp4(self):
+        """Switch the decoder's linear layers to MXFP4 (E2M1 codes, one E8M0 scale per 32 weights; reduced precision, opt-in): the
+        batch-1 decode reads the 4-bit stream, every other path the dequantised bf16 values.  See ze_weights_quantize_mxfp4."""
+        self._check(self.lib.ze_weights_quantize_mxfp4(self.h, self._stream()))
+
+    WEIGHT_FORMATS = ("bf16", "fp8", "mxfp4")
+
+    @property
+    def weight_format(self) -> str:
+        """The weight stream the batch-1 decode reads now: "bf16", "fp8" or "mxfp4" (the engine's state: a weight write or an
+        adapter switch returns it to "bf16")."""
+        return self.WEIGHT_FORMATS[self._check(self.lib.ze_weight_format(self.h))]
+
+    def set_weight_format(self, fmt) -> None:
+        """Quantise the loaded weights to `fmt` ("fp8" / "mxfp4"; None or "bf16": leave them).  The formats exclude each other."""
+        if fmt in (None, "bf16"):
+            return
+        if fmt not in self.WEIGHT_FORMATS:
+            raise ValueError(f"weight_format {fmt!r}: one of {self.WEIGHT_FORMATS}")
+        self.quantize_fp8() if fmt == "fp8" else self.quantize_mxfp4()
+
     def set_fp8_activations(self, on: bool = True):
         """FP8 x FP8 batched decode (qkv and gate/up inputs quantised per row): see ze_set_fp8_activations.  Needs
         quantize_fp8() first; a weight change switches it off again."""
@@ -982,6 +1003,15 @@ class Engine:
         q = torch.empty((rows, cols), dtype=torch.uint8, device=self.device)
         sc = torch.empty(rows, dtype=torch.float32, device=self.device)
         self._check(self.lib.ze_op_quantize_fp8(self.h, _ptr(w), rows, cols, _ptr(q), _ptr(sc), self._stream()))
+        return q, sc
+
+    def op_quantize_mxfp4(self, w: torch.Tensor):
+        """w bf16 [rows, cols] on the device (overwritten with the dequantised values) -> (u8 codes [rows, cols / 2], low nibble =
+        even k; u8 E8M0 scales [rows, cols / 32]).  cols % 32 == 0."""
+        rows, cols = w.shape
+        q = torch.empty((rows, cols // 2), dtype=torch.uint8, device=self.device)
+        sc = torch.empty((rows, cols // 32), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.ze_op_quantize_mxfp4(self.h, _ptr(w), rows, cols, _ptr(q), _ptr(sc), self._stream()))
         return q, sc
 
     # ------------------------------------------------------------------ unit ops (parity tests)
@@ -1063,6 +1093,23 @@ class Engine:
                                         n, k, None if f32 else _ptr(out), _ptr(out) if f32 else None, _ptr(seen), penalty,
                                         C.byref(tok) if argmax else None, seq, layer, _ptr(embed), int(token), _ptr(embed_out),
                                         self._stream()))
+        return (out, int(tok.value)) if argmax else out
+
+    def op_gemv4(self, epi: int, x, q4, scale4, norm_w=None, eps: float = 1e-6, bias=None, out=None, argmax: bool = False, seen=None,
+                 penalty: float = 1.0, seq: int = 0, layer: int = 0, embed=None, token: int = -1, embed_out=None):
+        """op_gemv with the MXFP4 stream as W (ze_op_gemv4): q4 u8 [N, K / 2], scale4 u8 [N, K / 32] as op_quantize_mxfp4 returns."""
+        n, k = q4.shape[0], q4.shape[1] * 2
+        if out is None:
+            t = self.config.text
+            shape, dt = {self.GV_SWIGLU: (n // 2, torch.bfloat16), self.GV_LOGITS: (n, torch.float32),
+                         self.GV_QKV_ROPE: (t.hidden_size, torch.bfloat16)}.get(epi, (n, torch.bfloat16))
+            out = torch.empty(shape, dtype=dt, device=self.device)
+        tok = C.c_int32(-1)
+        f32 = epi == self.GV_LOGITS
+        self._check(self.lib.ze_op_gemv4(self.h, epi, _ptr(q4), _ptr(scale4), _ptr(x), _ptr(norm_w), eps, _ptr(bias), n, k,
+                                         None if f32 else _ptr(out), _ptr(out) if f32 else None, _ptr(seen), penalty,
+                                         C.byref(tok) if argmax else None, seq, layer, _ptr(embed), int(token), _ptr(embed_out),
+                                         self._stream()))
         return (out, int(tok.value)) if argmax else out
 
     def op_logits_rows(self, x: torch.Tensor, w: torch.Tensor, norm_w: torch.Tensor, eps: float = 1e-6, out=None) -> torch.Tensor:

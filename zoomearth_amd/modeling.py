@@ -112,8 +112,12 @@ class ZoomEarthForConditionalGeneration:
         collective took are left in `model.weight_broadcast_s`.
         A PEFT adapter directory (adapter_config.json, no config.json): the base model named by its `base_model_name_or_path` -- or
         by the `base=` keyword -- is loaded as above, then the adapter is loaded and activated (`load_adapter`, `set_adapter`); under
-        broadcast every rank applies it itself after the base broadcast (A / B are a few MB)."""
+        broadcast every rank applies it itself after the base broadcast (A / B are a few MB).
+        weight_format="fp8" / "mxfp4" (reduced precision, opt-in; default bf16): the decoder's linear layers are quantised once the
+        weights -- with the adapter merged, if the path is one -- are in place (Engine.set_weight_format); `set_adapter` quantises
+        again after every switch, since a switch returns the engine to bf16."""
         base = kw.pop("base", None)
+        weight_format = kw.pop("weight_format", None)
         if os.path.exists(os.path.join(path, "adapter_config.json")) and not os.path.exists(os.path.join(path, "config.json")):
             if base is None:
                 with open(os.path.join(path, "adapter_config.json"), encoding="utf-8") as f:
@@ -125,6 +129,7 @@ class ZoomEarthForConditionalGeneration:
                                         broadcast=broadcast, **kw)
             try:
                 model.load_adapter(path)
+                model.weight_format = weight_format
                 model.set_adapter("default")
             except Exception:
                 model.engine.close()
@@ -167,6 +172,12 @@ class ZoomEarthForConditionalGeneration:
                     setattr(gen, k, v)
         model = cls(config, engine, gen)
         model.weight_broadcast_s = bcast_s
+        try:
+            engine.set_weight_format(weight_format)
+        except Exception:
+            engine.close()
+            raise
+        model.weight_format = weight_format
         return model
 
     @classmethod
@@ -235,6 +246,7 @@ class ZoomEarthForConditionalGeneration:
         if name == self.active_adapter:
             return
         self.engine.lora_activate(None if name is None else self._adapters[name])
+        self.engine.set_weight_format(getattr(self, "weight_format", None))   # (the switch dropped the quantised stream)
         self._vit_cache.clear()
         self._chains.clear()
 

@@ -591,6 +591,9 @@ def create_app(server: ChatServer):
         adapter = getattr(server.model, "active_adapter", None)
         if adapter is not None:
             card["adapter"] = adapter
+        engine = getattr(server.model, "engine", None)
+        if engine is not None and hasattr(engine, "weight_format"):
+            card["weight_format"] = engine.weight_format   # "bf16", or the reduced-precision decode stream: "fp8" / "mxfp4"
         return {"object": "list", "data": [card]}
 
     @app.post("/v1/chat/completions")
@@ -626,8 +629,11 @@ def main():  # pragma: no cover
                     help="keep the K/V rows of finished requests in a pool of this many rows (0 = off); later requests that start "
                          "with them prefill only their tail and report usage.prompt_tokens_details.cached_tokens")
     ap.add_argument("--lora", default=None, help="a PEFT LoRA adapter directory: loaded and activated at start (listed by /v1/models)")
+    ap.add_argument("--weight-format", default="bf16", choices=["bf16", "fp8", "mxfp4"],
+                    help="decode weight stream: fp8 / mxfp4 quantise the decoder's linear layers (reduced precision, opt-in; "
+                         "reported by /v1/models)")
     args = ap.parse_args()
-    model = ZoomEarthForConditionalGeneration.from_pretrained(args.model_name)
+    model = ZoomEarthForConditionalGeneration.from_pretrained(args.model_name, weight_format=args.weight_format)
     if args.lora:
         model.set_adapter(model.load_adapter(args.lora, os.path.basename(os.path.normpath(args.lora)) or "default"))
     processor = ZoomEarthProcessor.from_pretrained(args.model_name, trust_remote_code=True, max_pixels=128 * 128 * 28 * 28)
