@@ -774,6 +774,62 @@ int ze_op_embed_scatter(ze_engine* e, const int32_t* input_ids, int len, const v
 int ze_op_mrope_kv(ze_engine* e, int seq, int layer, void* qkv_bf16, int T, const int32_t* position_ids, int past, void* stream);
 int ze_op_rope_kv_decode(ze_engine* e, const int32_t* seqs, int n, int layer, void* qkv_bf16, void* stream);
 int ze_op_kv_read(ze_engine* e, int seq, int layer, int start, int n, void* out_k, void* out_v, void* stream);
+
+/* ------------------------------------------------------------------ speculative decoding by prompt lookup (zoomearth_amd/csrc/ze_spec.hip)
+ * replaces: HF generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=g) (HF:generation/candidate_generator.py,
+ * PromptLookupCandidateGenerator) and vLLM's `ngram` speculative method (speculative_config = {"method": "ngram", ...}).  Lossless: a
+ * chain's tokens and K/V rows are bit for bit those of plain ze_decode_burst steps of the fragment family (decode family 0), which
+ * agree with the single-chain GEMV family only within bf16 rounding, as the two batched families do (ze_set_decode_regime).
+ *
+ * A speculating chain owns up to k + 1 consecutive rows of a burst's step: row 0 is fed its last token at position ctx, row j draft
+ * id j - 1 at position ctx + j.  The qkv launch appends row j's K/V at cache row ctx + j; the decode attention treats every row as an
+ * entry of its own that reads the first ctx + j + 1 keys of the chain's slot (parts cut by the row's own length; the chain's prefix
+ * hint applies to every row); everything else is row-wise.  Row j's logits are bit-identical to those of a plain family-0 step of the
+ * chain alone at position ctx + j after feeding the tokens before it one by one.  A step has at most 64 rows: one per chain without
+ * speculation, k + 1 per speculating chain; more is ZE_ERR_INVALID.
+ *   drafter (k_spec_draft, one workgroup per chain, on the device): the history is the prompt ids given here followed by the generated
+ *     ids; for g = max_ngram down to min_ngram the MOST RECENT earlier occurrence of the last g ids that has an id behind it is looked
+ *     for, the first g with one wins; the draft is what follows it, at most k ids, cut at the end of the history and at the cache rows
+ *     and token slots the chain has left (max_ctx).  No occurrence: the chain contributes one row, as without speculation.
+ *   accept pass (k_spec_accept, one workgroup per chain): for row j = 0, 1, ... the greedy arg-max under the repetition penalty
+ *     against the seen-set as of row j (the arithmetic and tie rule of ze_op_sample_greedy) is emitted and marked seen; the walk stops
+ *     behind the last row, behind a token that differs from draft id j, behind an EOS id, or when the chain's room is used up.  The
+ *     chain's context length grows by the emitted tokens; the K/V of rejected rows stay as dead rows beyond it (as after
+ *     ze_seq_truncate).  No host synchronisation inside a burst.
+ * ze_decode_burst / _begin / _end: when any chain of the burst speculates, every step is draft -> row table -> family-0 step ->
+ * accept; chains without speculation ride along with one row and their usual sampler.  A burst of `steps` steps emits up to
+ * steps x (k + 1) tokens per speculating chain (n_generated reports it; a caller with a token budget trims).  How far a speculating
+ * chain came is known on the device alone until ze_decode_burst_end has read it back: between ze_decode_burst_begin and its _end
+ * ze_seq_len reports the length before the burst, and a second ze_decode_burst_begin that names the chain is ZE_ERR_INVALID.  Greedy only: a
+ * speculating chain may carry a repetition penalty (the call's, or its own ze_seq_set_sampling mode 0) and nothing else.
+ * ze_seq_set_speculation: k = 0 clears; 1 <= k <= 8 and 1 <= min_ngram <= max_ngram <= 8, n_prompt in [0, max_ctx], ids inside the
+ * vocabulary -- anything else is ZE_ERR_INVALID.  ZE_ERR_INVALID too, and nothing changes: the engine runs the row-streaming family
+ * (decode family 1 has no multi-row kernels); the chain has a sampled request, a sampling filter, a logit adjust, token rules, a
+ * grammar or a log-probability request -- and each of those setters refuses a chain that speculates.  prompt_ids is a host array (as
+ * the context of ze_seq_set_token_rules, whose per-slot history buffer it shares).  Set after the chain's prefill; cleared wherever
+ * the sampling filter is (ze_seq_reset, ze_seq_truncate, ze_seq_copy_prefix / ze_seq_fork / ze_prefix_load into the slot).  The
+ * buffers come with the first request (64 logits rows among them); ZE_ERR_NOMEM if that fails, and the engine stays usable. */
+int ze_seq_set_speculation(ze_engine* e, int seq, int k, int min_ngram, int max_ngram, const int32_t* prompt_ids, int n_prompt, void* stream);
+/* The chain's counters since its request was set: speculative steps it took part in, draft ids proposed, draft ids accepted (tokens
+ * emitted = steps + accepted).  All zero for a chain without a request.  Any out pointer may be NULL.  Waits for `stream`. */
+int ze_chain_spec_stats(ze_engine* e, int seq, int* steps, int* drafted, int* accepted, void* stream);
+/* The drafter alone (HF: PromptLookupCandidateGenerator.get_candidates; vLLM: NgramProposer): hist_ids int32 [rows, ld] device, row r
+ * holding hist_lens[r] ids (device int32 [rows]); out_draft int32 [rows, k] device (-1 behind the draft), out_len int32 [rows]. */
+int ze_op_spec_draft(ze_engine* e, const int32_t* hist_ids, const int32_t* hist_lens, int rows, int ld, int k, int min_ngram,
+                     int max_ngram, int32_t* out_draft, int32_t* out_len, void* stream);
+/* The accept pass alone (HF: the greedy branch of _speculative_sampling / assisted decoding's longest-matching-prefix rule; vLLM's
+ * ngram method with greedy verification), everything on the device: chain c owns rows c * (k + 1) .. c * (k + 1) + draft_len[c] of
+ * logits f32 [n_chains * (k + 1), ld] and the ids draft[c * k .. ); seen uint8 [n_chains, vocab] (nonzero = penalised; updated with
+ * the emitted ids) or NULL (no penalty); repetition_penalty f32 [n_chains] and room int32 [n_chains] (the tokens the chain may still
+ * emit, >= 1) are device arrays; out_tokens int32 [n_chains, k + 1] (-1 behind the emitted ids), out_count / out_finished int32
+ * [n_chains] (finished: an EOS id of the config was emitted; never with ignore_eos). */
+int ze_op_spec_accept(ze_engine* e, const float* logits, int n_chains, int vocab, int ld, int k, const int32_t* draft,
+                      const int32_t* draft_len, uint8_t* seen, const float* repetition_penalty, const int32_t* room, int ignore_eos,
+                      int32_t* out_tokens, int32_t* out_count, int32_t* out_finished, void* stream);
+/* The row contract alone (HF / vLLM: the verification forward of a speculative step): chain `seq` is fed tokens[0 .. r) (host) at r
+ * consecutive positions in ONE family-0 step -- teacher forcing as ze_decode_batch, the cache grows by r rows; out_logits f32
+ * [r, vocab] device or NULL.  r <= 64. */
+int ze_op_decode_rows(ze_engine* e, int seq, const int32_t* tokens, int r, float* out_logits, void* stream);
 /* The attention of one batched decode step, alone (K16 at decode: HF:modeling_qwen2_5_vl.py:606-639 on the rows of the KV cache):
  * qkv_bf16 [n, (heads + 2 kv_heads) x 128] = the chains' projections after ze_op_rope_kv_decode (their k / v are row ctx of the
  * cache); out_bf16 [n, heads x 128] = softmax(q K^T / sqrt(128)) V over rows 0 .. ctx, per head, with the step's own kernel. */

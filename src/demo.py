@@ -18,6 +18,9 @@ from zoomearth_amd.processor import ZoomEarthProcessor  # noqa: E402
 
 MODEL_PATH = os.environ.get("ZOOMEARTH_MODEL", "")
 WEIGHT_FORMAT = os.environ.get("ZOOMEARTH_WEIGHT_FORMAT") or None   # "fp8" / "mxfp4": reduced-precision decode weights, opt-in
+# ZOOMEARTH_SPECULATIVE=K: speculative decoding by prompt lookup, K draft ids per step (lossless, greedy).  Off by default: at batch 1
+# it trades the single-chain step for the batched family's, and DESIGN 7k has the figures that decide whether that pays
+SPECULATIVE = int(os.environ.get("ZOOMEARTH_SPECULATIVE") or 0)
 _STATE = {}
 
 
@@ -29,7 +32,8 @@ def _load():
 
 
 def chat_batch(prompts, imgs, processor, model):
-    return H.chat_batch(prompts, imgs, processor, model, do_sample=False)
+    extra = dict(prompt_lookup_num_tokens=SPECULATIVE) if SPECULATIVE > 0 else {}
+    return H.chat_batch(prompts, imgs, processor, model, do_sample=False, **extra)
 
 
 def chat(prompt, image_fp):

@@ -32,6 +32,13 @@ class ChainRequest:
     no_repeat_ngram_size: int = 0
     stop_ids: Sequence = ()
     bad_words_ids: Sequence = ()
+    # speculative decoding by prompt lookup (HF's prompt_lookup_num_tokens / max_matching_ngram_size, vLLM's ngram method): up to
+    # that many draft ids per step, looked up in prompt + generated ids by their last ngram_max .. ngram_min ids; 0 = off.  Greedy
+    # only: the front-ends refuse it together with a sampled mode, a filter, log-probabilities, logit adjustments, token rules or a
+    # grammar, as the engine does
+    speculative_tokens: int = 0
+    ngram_min: int = 1
+    ngram_max: int = 3
 
     @property
     def wants_logprobs(self) -> bool:
@@ -40,6 +47,18 @@ class ChainRequest:
     @property
     def wants_prompt_logprobs(self) -> bool:
         return self.prompt_logprobs is not None
+
+    def speculation_conflict(self, grammar: bool = False) -> Optional[str]:
+        """What of this request speculation excludes (the engine's rule, ze_seq_set_speculation), or None."""
+        if self.sampled:
+            return "sampling"
+        if self.logprobs is not None:
+            return "logprobs"
+        if self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or self.logit_bias or self.min_new_tokens > 0:
+            return "logit adjustments"
+        if self.stop_ids or self.bad_words_ids or self.no_repeat_ngram_size > 0:
+            return "token rules"
+        return "guided decoding" if grammar else None
 
     def install(self, engine, slot: int, prompt_ids, grammar: Optional[int] = None) -> None:
         """The request into `slot`, whose reset / truncate / prefix copy cleared the previous chain's, before the first draw.  The
@@ -59,3 +78,5 @@ class ChainRequest:
                                    context=list(prompt_ids) if bans else None)
         if grammar is not None:
             engine.set_grammar(slot, grammar)
+        if self.speculative_tokens > 0:   # (last: the engine checks the slot's other requests)
+            engine.set_speculation(slot, self.speculative_tokens, list(prompt_ids), self.ngram_min, self.ngram_max)

@@ -624,7 +624,12 @@ __device__ __forceinline__ void aw_run_part(const bf16_t* __restrict__ qsrc, con
 
 // SPLIT (round 6, not the shipped form): the split-row partition and the paired prefix parts are an instantiation of their own, so that
 // the shipped kernel is the round-5 code to the instruction (the disabled branches cost it 1-2 % in a same-box A/B: 83.1 -> 85.0 us).
-template <int MB, int ROUNDS, bool SPLIT = false>
+// ROWS (speculative decoding, ze_spec.hip): a step's rows may name a chain more than once -- row bz then reads the first
+// ctx + row_off[bz] + 1 keys of its chain's slot (row_off[bz] < 0, a dead row: the keys the chain has).  Every row is an entry of its own
+// in the work list (its own partials, ticket and merge), its parts a function of its own length alone, exactly as for a chain of that
+// length.  Again an instantiation of its own, compiled in a unit of its own (ze_attn_rows.hip, which includes this file: this unit's
+// code is what it was); the offsets arrive in the `mate` argument, which the unsplit form does not use.
+template <int MB, int ROUNDS, bool SPLIT = false, bool ROWS = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k_attn_decode_wave_long(
     const bf16_t* __restrict__ q, int q_row_stride, const bf16_t* __restrict__ kcache, const bf16_t* __restrict__ vcache,
     size_t cache_seq_stride, const ze_seq_dev* __restrict__ st_base, const int* __restrict__ seq_ids, int heads, int kv_heads,
@@ -637,8 +642,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
     const int bz = blockIdx.y;
     const int xr = (int)((blockIdx.x + (unsigned)(x_rot & 15) * ((unsigned)bz >> (x_rot >> 4))) % gridDim.x);  // (k_attn_decode_wave)
     const int kvh = xr % kv_heads, part = xr / kv_heads;
+    static_assert(!(SPLIT && ROWS), "the offsets travel in the mate argument");
     const int seq = seq_ids[bz];
-    const int ctx = st_base[seq].ctx + 1;
+    const int ctx = ROWS ? min(st_base[seq].ctx + 1 + max(mate[bz], 0), max_ctx) : st_base[seq].ctx + 1;
     // Round 6: the chain's SPLIT ROW (ze_seq_dev::split: the end of its first image block -- a property of the chain's own tokens,
     // set when they are prefilled or copied, never of the batch) cuts the parts: [0, split) in PART-key pieces, then [split, ctx) in
     // PART-key pieces.  The rows below the split are what the questions of a tile share, so a PREFIX part holds no row of the chain's
@@ -800,6 +806,23 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
 
 extern int ze_gemv_knobs[24];
 
+#ifdef ZE_ATTN_ROWS_UNIT
+// the pipelined kernel's ROWS form over the n rows of a step; `parts`: the 384-key parts the longest row can have (the grid's extent)
+void ze_launch_attn_decode_rows(const bf16_t* q, int q_row_stride, const bf16_t* kcache, const bf16_t* vcache, size_t cache_seq_stride,
+                                bf16_t* out, int out_row_stride, const ze_seq_dev* st, const int* seq_ids, const int* row_off, int n, int heads,
+                                int kv_heads, int max_ctx, float scale, float* ws_partial, unsigned* tickets, int parts, const int* prefix,
+                                hipStream_t s) {
+    constexpr int rounds = AW_LONG_ROUNDS;
+    const int wparts = (max_ctx + AW_PART - 1) / AW_PART;   // slots per row of the partial buffer, as the plain launch lays it out
+    const int lparts = (max_ctx + rounds * AW_TOK - 1) / (rounds * AW_TOK);
+    const int lg = std::min(lparts, std::max(1, parts));
+    const int xrot = ze_gemv_knobs[16] > 0 ? ze_gemv_knobs[16] : (3 | (2 << 4));
+    k_attn_decode_wave_long<8, rounds, false, true><<<dim3(kv_heads * lg, n), 256, 4 * 3 * AW_VSTAGE, s>>>(
+        q, q_row_stride, kcache, vcache, cache_seq_stride, st, seq_ids, heads, kv_heads, max_ctx, scale * 1.4426950408889634f, ws_partial, wparts,
+        tickets, out, out_row_stride, xrot, prefix, row_off, 0);
+}
+#else
+
 // (measurements: ze_tune knob 16 = step | shift << 4 overrides the grid rotation of the pipelined kernel; 0 = the shipped 3 | 2 << 4)
 static int xrot_knob() { return ze_gemv_knobs[16] > 0 ? ze_gemv_knobs[16] : (3 | (2 << 4)); }
 
@@ -858,3 +881,4 @@ void ze_launch_attn_decode_stream(const bf16_t* q, int q_row_stride, const bf16_
                                                                               seq_ids, heads, kv_heads, max_ctx, sl, ws_partial,
                                                                               max_parts, tickets, out, out_row_stride, chunk);
 }
+#endif  // ZE_ATTN_ROWS_UNIT

@@ -212,6 +212,27 @@ struct ze_lora {
     size_t store_bytes = 0;
 };
 
+// Speculative decoding by prompt lookup (ze_spec.hip; the steps themselves: ze_forward.hip).  host: the truth per slot (k = 0: off);
+// table: the per-slot device words the drafter and the accept pass read (ZE_SP_WORDS ints: k, min_ngram, max_ngram, prompt ids, then
+// the counters steps / drafted / accepted), written in stream order by the setter; n_spec = slots with a request.  While it is 0 no
+// burst launches anything for it.  The prompt ids live in the context history of the token rules (ze_requests::tr_ctx: the two
+// requests exclude each other per chain).  Everything below comes with the first request: the row table of a speculative step --
+// row_seq / row_off / row_tok [64]: the chain slot of a row, its offset behind the chain's context (< 0: a dead row) and the id it
+// is fed -- the burst's chains (ZE_SP_CHAIN_WORDS ints each: slot, first row, rows, penalty bits), their draft lengths, and the
+// step's own logits rows, attention partials and tickets (a step may have more rows than the engine has slots).
+enum { ZE_SP_WORDS = 8, ZE_SP_CHAIN_WORDS = 4, ZE_SP_MAX_ROWS = 64, ZE_SP_MAX_K = 8 };
+struct ze_spec {
+    struct chain_host { int k = 0, min_ngram = 0, max_ngram = 0, n_prompt = 0; };
+    std::vector<chain_host> host;
+    std::vector<char> pending;   // the chain took part in a ze_decode_burst_begin whose _end has not read its length back yet
+    int n_spec = 0;
+    int* table = nullptr;
+    int *row_seq = nullptr, *row_off = nullptr, *row_tok = nullptr, *chains = nullptr, *dlen = nullptr;
+    float *logits = nullptr, *partial = nullptr;
+    unsigned* tickets = nullptr;
+    bool on(int seq) const { return !host.empty() && host[seq].k > 0; }
+};
+
 struct ze_engine {
     ze_config cfg{};
     int device = 0;
@@ -287,6 +308,8 @@ struct ze_engine {
     std::vector<hipEvent_t> pfx_copy_ev;
     bool prefix_hints = true;      // the hint fits its 16 + 16 bits (ze_tune knob 17 = 1: every chain reads its own rows)
     ze_requests req;  // per-chain requests (above)
+    ze_spec spec;     // speculative decoding (above)
+    const int* brow_off = nullptr;  // set while a speculative step is enqueued: its rows' offsets (batch_qkv, batch_attention)
     // prefix cache: the pool (null = none) and the generation of the weights -- bumped by whatever changes what a K/V row of given
     // tokens would be (ze_prefix_weights_changed), so that a block saved under another generation is never loaded
     ze_prefix_pool* prefix_pool = nullptr;
@@ -427,6 +450,25 @@ float ze_penalty_of(const ze_engine* e, const ze_gen_params* p, int seq);
 ze_sample_opts ze_sample_opts_of(ze_engine* e, const ze_gen_params* p, int slot, bool batch = false);
 // n = 0: the single-chain step of chain `seq`; else the batched step of n chains
 ze_step_key ze_step_key_of(const ze_engine* e, int n, int seq, float penalty, int ignore_eos, const ze_sample_opts& so);
+
+// ---- speculative decoding (ze_spec.hip)
+void ze_spec_free(ze_engine* e);
+int ze_spec_alloc(ze_engine* e);   // the buffers of the first request, all or none
+void ze_spec_clear(ze_engine* e, int seq, hipStream_t s);   // wherever ze_requests_clear runs
+// one chain per workgroup of the burst's list (`chains`: ZE_SP_CHAIN_WORDS ints each): the drafter fills the chain's rows of the row
+// table, the accept pass walks them
+struct ze_spec_step {
+    ze_seq_dev* st;
+    const int *table, *chains, *hist_ctx, *eos_ids;
+    int32_t* out_tokens;
+    uint8_t* seen;
+    const float* logits;
+    int *row_off, *row_tok, *dlen;
+    int n_chains, max_ctx, vocab, n_eos, ignore_eos;
+};
+void ze_launch_spec_draft(const ze_spec_step& a, hipStream_t s);
+void ze_launch_spec_accept(const ze_spec_step& a, int first_chain, hipStream_t s);
+void ze_launch_spec_embed(const int* row_tok, int n, const bf16_t* embed, bf16_t* out, int hidden, hipStream_t s);
 
 // ---- the launch sites of the forward passes (ze_forward.hip) that the profilers (ze_profile.hip) time: a projection's launcher is
 // chosen in these functions only, so a profiler cannot launch anything but what the pass launches

@@ -1520,6 +1520,16 @@ static int upload_batch(ze_engine* e, const int32_t* seqs, int n, hipStream_t s)
 // its predecessor k_attn_decode_stream (a workgroup-wide LDS-DMA ring); knob 8 = 1: the 64-token-slice kernel of the
 // single-chain step with a chain dimension (the round-1 form) -- both kept for A/B measurements
 // (q_rows / out_rows: the step's own buffers, or the caller's -- ze_op_attn_decode)
+// whether the step's decode attention is a per-wave kernel (192- or 384-key parts whatever the context): ceil(max_ctx / 192) parts must
+// fit the partial buffer (max(max_splits, 8) parts per chain) and the merge's 64 lanes; 128-wide heads, the q heads of a kv head as
+// MFMA columns.  One predicate for the plain step and for the steps whose rows name a chain more than once (spec_step_ok).
+static bool attn_per_wave(const ze_engine* e) {
+    const ze_config& c = e->cfg;
+    const int wparts = (c.max_ctx + 191) / 192;
+    return ze_gemv_knobs[8] != 2 && ze_gemv_knobs[11] == 0 && wparts <= std::max(e->max_splits, 8) && wparts <= 64 && e->head_dim == 128 &&
+           c.heads / c.kv_heads <= 16;
+}
+
 static void launch_batch_attention(ze_engine* e, int li, int n, bool frag_out, hipStream_t s, const bf16_t* q_rows = nullptr,
                                    bf16_t* out_rows = nullptr) {
     const ze_config& c = e->cfg;
@@ -1528,6 +1538,11 @@ static void launch_batch_attention(ze_engine* e, int li, int n, bool frag_out, h
     const float scale = 1.0f / sqrtf((float)hd);
     const bf16_t* qb = q_rows ? q_rows : e->bqkv;
     bf16_t* ob = out_rows ? out_rows : e->bo;
+    if (e->brow_off && !q_rows) {  // a speculative step (spec_step_ok: the pipelined kernel is the one in force)
+        ze_launch_attn_decode_rows(qb, nqkv, e->kc(li, 0), e->vc(li, 0), seq_stride, ob, frag_out ? -(nq / 32) : nq, e->st_dev, e->bseq, e->brow_off,
+                                   n, c.heads, c.kv_heads, c.max_ctx, scale, e->bpartial, e->atickets, e->live_parts_long, e->pfx_dev, s);
+        return;
+    }
     if (ze_gemv_knobs[8] == 1)
         ze_launch_attn_decode(qb, nqkv, e->kc(li, 0), e->vc(li, 0), seq_stride, ob, frag_out ? -(nq / 32) : nq, e->st_dev,
                               e->bseq, n, c.heads, c.kv_heads, hd, c.max_ctx, scale, e->bpartial, e->max_splits, e->atickets, s);
@@ -1537,8 +1552,7 @@ static void launch_batch_attention(ze_engine* e, int li, int n, bool frag_out, h
         // the per-wave kernel cuts 192-key parts whatever the context: ceil(max_ctx / 192) of them must fit the partial buffer
         // (max(max_splits, 8) parts per chain) and the merge's 64 lanes
         const int wparts = (c.max_ctx + 191) / 192;
-        const bool per_wave = ze_gemv_knobs[8] != 2 && ze_gemv_knobs[11] == 0 && wparts <= std::max(e->max_splits, 8) && wparts <= 64 &&
-                              hd == 128 && c.heads / c.kv_heads <= 16;  // (128-wide heads, the q heads of a kv head as MFMA columns)
+        const bool per_wave = attn_per_wave(e);
         const int chunk = ze_gemv_knobs[11] >= 64 ? ze_gemv_knobs[11] / 32 * 32 : 0;  // 0: a sixth of the chain's context
         const int max_parts = chunk ? (c.max_ctx + chunk - 1) / chunk : 8;           // (at most 8 parts: 128-token floor)
         ze_launch_attn_decode_stream(qb, nqkv, e->kc(li, 0), e->vc(li, 0), seq_stride, ob, frag_out ? -(nq / 32) : nq,
@@ -1600,7 +1614,7 @@ bool batch_qkv(ze_engine* e, int li, int n, hipStream_t s) {
         ze_launch_qkv_rope_oneshot(r.a8q ? (const bf16_t*)e->ty8 : e->by, w8 ? (const bf16_t*)L.qkv.wf8 : L.qkv.wf, L.qkv.bias,
                                    e->bqkv, nqkv, n, H, c.heads, c.kv_heads, e->cosT, e->sinT, e->st_dev, e->bseq,
                                    e->kc(li, 0), e->vc(li, 0), seq_stride, c.max_ctx, s, w8 ? L.qkv.scale8 : nullptr,
-                                   r.a8q ? e->ty8_scale : nullptr);
+                                   r.a8q ? e->ty8_scale : nullptr, e->brow_off);
         return w8;
     }
     // row streaming: projection + M-RoPE + KV append in ONE launch on the permuted rows (same bits as the pair of
@@ -1762,6 +1776,192 @@ static int run_burst(ze_engine* e, const std::vector<int>& active, int steps, co
     return ZE_OK;
 }
 
+// ================================================================== speculative bursts (ze_spec.hip: drafter, accept pass, setter)
+// A step of a burst in which some chain speculates: draft -> row table -> the fragment family's launches over the rows -> the usual
+// sampler for the chains without speculation (the first n_plain rows, one each) -> the accept pass for the others.  Row j of a chain
+// is fed at position ctx + j and every kernel of the family computes a row independently of what shares the step, so its logits are
+// the bits a plain step of the chain alone at that position produces.  The launches are the step's own functions
+// (batch_norm .. batch_lm_head) on the step's own row table, logits, partials and tickets: a step may have more rows than the
+// engine has slots.
+struct spec_layout {
+    int rows = 0, n_plain = 0, n_chains = 0;
+};
+
+// the multi-row forms exist for the fragment kernels and the pipelined attention alone
+static bool spec_step_ok(const ze_engine* e) {
+    const batch_regime r = regime_of(e, 0);
+    const int k8 = ze_gemv_knobs[8], k23 = ze_gemv_knobs[23];
+    // the plain step must be on the very kernel the ROWS form instantiates: per-wave, 384-key parts (knob 8 not 1 / 4), no split rows
+    return r.fr && r.fl && attn_per_wave(e) && k8 != 1 && k8 != 4 && k23 != 2 && k23 != 3;
+}
+
+// the forward pass over the n rows of the row table (ze_spec: row_seq / row_off / row_tok) into the step's own logits rows
+static void enqueue_rows_forward(ze_engine* e, int n, hipStream_t s) {
+    const ze_config& c = e->cfg;
+    ze_spec& q = e->spec;
+    // the step's launch functions read the engine's batch buffers: they are the speculative step's own while this guard lives
+    struct rows_buffers {
+        ze_engine* e;
+        int* bseq;
+        float *blogits, *bpartial;
+        unsigned* atickets;
+        explicit rows_buffers(ze_engine* e_) : e(e_), bseq(e_->bseq), blogits(e_->blogits), bpartial(e_->bpartial), atickets(e_->atickets) {
+            const ze_spec& q = e->spec;
+            e->bseq = q.row_seq, e->blogits = q.logits, e->bpartial = q.partial, e->atickets = q.tickets, e->brow_off = q.row_off;
+        }
+        ~rows_buffers() { e->bseq = bseq, e->blogits = blogits, e->bpartial = bpartial, e->atickets = atickets, e->brow_off = nullptr; }
+        rows_buffers(const rows_buffers&) = delete;
+        rows_buffers& operator=(const rows_buffers&) = delete;
+    } guard(e);
+    ze_launch_spec_embed(q.row_tok, n, e->embed, e->bh, c.hidden, s);
+    for (int li = 0; li < c.layers; ++li) {
+        batch_norm(e, li, n, ZE_NORM_IN, s);
+        batch_qkv(e, li, n, s);
+        batch_attention(e, li, n, s);
+        batch_o(e, li, n, s);
+        batch_norm(e, li, n, ZE_NORM_POST, s);
+        batch_gate_up(e, li, n, s);
+        batch_down(e, li, n, s);
+    }
+    batch_norm(e, 0, n, ZE_NORM_FINAL, s);
+    batch_lm_head(e, 0, n, s);
+}
+
+static int enqueue_spec_step(ze_engine* e, const spec_layout& L, float penalty, int ign, const ze_sample_opts& so, hipStream_t s) {
+    const ze_config& c = e->cfg;
+    ze_spec& q = e->spec;
+    ze_spec_step a;
+    a.st = e->st_dev, a.table = q.table, a.chains = q.chains, a.hist_ctx = e->req.tr_ctx, a.eos_ids = e->eos_dev;
+    a.out_tokens = e->out_tokens, a.seen = e->seen, a.logits = q.logits, a.row_off = q.row_off, a.row_tok = q.row_tok, a.dlen = q.dlen;
+    a.n_chains = L.n_chains, a.max_ctx = c.max_ctx, a.vocab = c.vocab, a.n_eos = c.n_eos, a.ignore_eos = ign;
+    ze_launch_spec_draft(a, s);
+    enqueue_rows_forward(e, L.rows, s);
+    if (L.n_plain > 0) {  // rows 0 .. n_plain - 1: one chain each, and their usual sampler
+        ze_launch_sample_batch(ze_requests_rows(e, q.logits, q.row_seq, 0, L.n_plain, s), c.vocab, e->seen, penalty, e->st_dev, q.row_seq,
+                               L.n_plain, e->eos_dev, c.n_eos, c.pad_token_id, ign, 1, 1, e->out_tokens, c.max_ctx, e->bsample,
+                               e->bsample + (size_t)c.max_seqs * 2 * 128, so, s);
+        ze_requests_after_token(e, q.logits, q.row_seq, 0, L.n_plain, s);
+    }
+    ze_launch_spec_accept(a, L.n_plain, s);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
+// `steps` speculative steps for the chains of a burst; returns the steps enqueued or a negative ze_status
+static int spec_burst(ze_engine* e, const std::vector<int>& chains, int steps, const ze_gen_params* p, float pen, int ign, hipStream_t s) {
+    const ze_config& c = e->cfg;
+    ze_spec& q = e->spec;
+    if (e->wide_regime() || !spec_step_ok(e))
+        return ze_fail(e, ZE_ERR_INVALID, "a speculative burst needs the fragment kernels and the pipelined decode attention (family 0, default ze_tune knobs)");
+    for (size_t i = 0; i < chains.size(); ++i) {
+        for (size_t j = 0; j < i; ++j)
+            if (chains[i] == chains[j]) return ze_fail(e, ZE_ERR_INVALID, "duplicate sequence id in a batch");
+        // how far a speculating chain came in a burst is the device's to know until ze_decode_burst_end has read it back
+        if (q.on(chains[i]) && q.pending[chains[i]])
+            return ze_fail(e, ZE_ERR_INVALID, "a speculating chain of this burst has a burst in flight: ze_decode_burst_end first");
+        if (!q.on(chains[i]) && e->ctx_host[chains[i]] > c.max_ctx) return ze_fail(e, ZE_ERR_NOMEM, "sequence exceeds max_ctx");
+    }
+    const bool call_draws = p->do_sample && p->temperature > 0.f;
+    // the row table: the chains without speculation first (one row each: the sampler's rows), then k + 1 rows per speculating chain
+    std::vector<int> order;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int ch : chains)
+            if ((int)q.on(ch) == pass) order.push_back(ch);
+    spec_layout L;
+    std::vector<int> row_seq, tab;
+    int mx = 0;
+    for (int ch : order) {
+        const int k = q.on(ch) ? q.host[ch].k : 0;
+        const ze_chain_sampling& own = e->req.samp_host[ch];
+        if (k > 0 && (own.penalty > 0.f ? own.temperature > 0.f : call_draws))
+            return ze_fail(e, ZE_ERR_INVALID, "speculation is greedy only: the burst samples a speculating chain");
+        if (k == 0) steps = std::min(steps, c.max_ctx - e->ctx_host[ch]);  // (a speculating chain out of room rides along with dead rows)
+        const float cp = own.penalty > 0.f ? own.penalty : pen;
+        int bits;
+        memcpy(&bits, &cp, sizeof(bits));
+        tab.insert(tab.end(), {ch, L.rows, k + 1, bits});
+        for (int j = 0; j <= k; ++j) row_seq.push_back(ch);
+        L.rows += k + 1;
+        L.n_chains += 1;
+        if (k == 0) L.n_plain += 1;
+    }
+    if (L.rows > ZE_SP_MAX_ROWS) return ze_fail(e, ZE_ERR_INVALID, "more than 64 rows in a speculative step (one per plain chain, k + 1 per speculating chain)");
+    if (steps <= 0) return 0;
+    for (int ch : chains) mx = std::max(mx, std::min(c.max_ctx, e->ctx_host[ch] + steps * ((q.on(ch) ? q.host[ch].k : 0) + 1) + 1));
+    ze_launch_set_ints(q.row_seq, row_seq.data(), L.rows, s);
+    ze_launch_set_ints(q.chains, tab.data(), (int)tab.size(), s);
+    sync_prefix(e, chains.data(), (int)chains.size(), s);
+    e->live_parts = (mx + 191) / 192;   // the attention grid's extent: the longest context any row can reach in this burst
+    e->live_parts_long = (mx + 383) / 384;
+    const ze_sample_opts bso = ze_sample_opts_of(e, p, 0, true);
+    hipGraphExec_t gx = nullptr;
+    if (p->use_graph) {  // the key of a plain step over `rows` rows, and the layout: nothing else decides what the step launches
+        ze_step_key key = ze_step_key_of(e, L.rows, 0, pen, ign, bso);
+        key.n = L.rows | L.n_plain << 8 | L.n_chains << 16 | 1 << 30;
+        if (e->bgraph_epoch != ze_tune_epoch) {
+            for (auto& kv : e->bgraphs) hipGraphExecDestroy(kv.second);
+            e->bgraphs.clear();
+            e->bgraph_epoch = ze_tune_epoch;
+        }
+        auto it = e->bgraphs.find(key);
+        if (it == e->bgraphs.end()) {
+            hipGraphExec_t ex = nullptr;
+            ZE_TRY(capture_step(e, [&](hipStream_t cs) { return enqueue_spec_step(e, L, pen, ign, bso, cs); }, &ex));
+            it = e->bgraphs.emplace(key, ex).first;
+        }
+        gx = it->second;
+    }
+    for (int i = 0; i < steps; ++i) {
+        if (gx)
+            ZE_HIP(hipGraphLaunch(gx, s));
+        else
+            ZE_TRY(enqueue_spec_step(e, L, pen, ign, bso, s));
+    }
+    // a speculating chain's length is the device's to know until ze_decode_burst_end reads it back
+    for (int ch : chains) {
+        if (!q.on(ch)) e->ctx_host[ch] += steps;
+        else q.pending[ch] = 1;
+        e->logits_fresh[ch] = 0;
+    }
+    return steps;
+}
+
+// The row contract alone: chain `seq` is fed tokens[0 .. r) at r consecutive positions in ONE family-0 step (teacher forcing, as
+// ze_decode_batch: no sampling, the cache grows by r rows); out_logits f32 [r, vocab] device
+extern "C" int ze_op_decode_rows(ze_engine* e, int seq, const int32_t* tokens, int r, float* out_logits, void* stream) {
+    ZE_TRY(check_seq(e, seq));
+    const ze_config& c = e->cfg;
+    if (!tokens || r < 1) return ze_fail(e, ZE_ERR_INVALID, "null tokens or r < 1");
+    if (r > ZE_SP_MAX_ROWS) return ze_fail(e, ZE_ERR_INVALID, "more than 64 rows in a step");
+    for (int j = 0; j < r; ++j)
+        if (tokens[j] < 0 || tokens[j] >= c.vocab) return ze_fail(e, ZE_ERR_INVALID, "token id out of range");
+    if (e->ctx_host[seq] + r > c.max_ctx) return ze_fail(e, ZE_ERR_NOMEM, "sequence exceeds max_ctx");
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    ZE_TRY(ensure_fragments(e, s));
+    if (e->wide_regime() || !spec_step_ok(e))
+        return ze_fail(e, ZE_ERR_INVALID, "rows of one chain need the fragment kernels and the pipelined decode attention (family 0, default ze_tune knobs)");
+    ZE_TRY(ze_spec_alloc(e));
+    ze_spec& q = e->spec;
+    std::vector<int> row_seq(r, seq), row_off(r);
+    for (int j = 0; j < r; ++j) row_off[j] = j;
+    ze_launch_set_ints(q.row_seq, row_seq.data(), r, s);
+    ze_launch_set_ints(q.row_off, row_off.data(), r, s);
+    ze_launch_set_ints(q.row_tok, tokens, r, s);
+    sync_prefix(e, &seq, 1, s);
+    e->live_parts = (e->ctx_host[seq] + r + 191) / 192;
+    e->live_parts_long = (e->ctx_host[seq] + r + 383) / 384;
+    enqueue_rows_forward(e, r, s);
+    e->ctx_host[seq] += r;
+    e->logits_fresh[seq] = 0;
+    e->tok_host[seq] = tokens[r - 1];
+    ze_launch_set_ints(&(e->st_dev + seq)->ctx, &e->ctx_host[seq], 1, s);
+    ze_launch_set_ints(&(e->st_dev + seq)->token, &tokens[r - 1], 1, s);
+    ZE_KCHECK();
+    if (out_logits) ZE_HIP(hipMemcpyAsync(out_logits, q.logits, (size_t)r * c.vocab * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return ZE_OK;
+}
+
 // first_token for a chain of a batch; `sample_stream` = the chain's random stream
 static int begin_chain(ze_engine* e, int q, const ze_gen_params* p, int ign, int sample_stream, hipStream_t s) {
     const ze_sample_opts so = ze_sample_opts_of(e, p, q);
@@ -1857,13 +2057,21 @@ extern "C" int ze_decode_burst_begin(ze_engine* e, const int32_t* seqs, int n, i
     hipStream_t s = (hipStream_t)stream;
     ZE_TRY(ensure_fragments(e, s));
     std::vector<int> active(seqs, seqs + n);
+    bool speculative = false;
     for (int q : active) {
         if (q < 0 || q >= c.max_seqs) return ze_fail(e, ZE_ERR_NOTFOUND, "sequence id out of range");
-        steps = std::min(steps, c.max_ctx - e->ctx_host[q]);  // every chain of the burst must have room for all its steps
+        speculative = speculative || e->spec.on(q);
     }
-    if (steps < 0) return ze_fail(e, ZE_ERR_NOMEM, "sequence exceeds max_ctx");
     const float pen = p->repetition_penalty > 0.f ? p->repetition_penalty : 1.0f;
     const int ign = p->ignore_eos ? 1 : 0;
+    if (speculative) {  // some chain of the burst speculates (ze_seq_set_speculation): every step is draft -> rows -> step -> accept
+        const int td = ze_timer_begin(e, 3, s);
+        const int ran = spec_burst(e, active, steps, p, pen, ign, s);
+        ze_timer_end(e, td, s);
+        return ran;
+    }
+    for (int q : active) steps = std::min(steps, c.max_ctx - e->ctx_host[q]);  // every chain of the burst must have room for all its steps
+    if (steps < 0) return ze_fail(e, ZE_ERR_NOMEM, "sequence exceeds max_ctx");
     const int td = ze_timer_begin(e, 3, s);
     if (steps > 0) ZE_TRY(run_burst(e, active, steps, p, pen, ign, ze_sample_opts_of(e, p, 0, true), s));
     ze_timer_end(e, td, s);
@@ -1881,6 +2089,8 @@ extern "C" int ze_decode_burst_end(ze_engine* e, const int32_t* seqs, int n, int
         if (seqs[i] < 0 || seqs[i] >= c.max_seqs) return ze_fail(e, ZE_ERR_NOTFOUND, "sequence id out of range");
         if (n_generated) n_generated[i] = e->bstate_host[seqs[i]].n_gen;
         if (finished) finished[i] = e->bstate_host[seqs[i]].finished;
+        // how far a speculating chain came is decided on the device (the accept pass)
+        if (e->spec.on(seqs[i])) e->ctx_host[seqs[i]] = std::min(e->bstate_host[seqs[i]].ctx, c.max_ctx), e->spec.pending[seqs[i]] = 0;
     }
     return ZE_OK;
 }

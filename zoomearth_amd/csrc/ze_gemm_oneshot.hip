@@ -22,7 +22,10 @@
 typedef __attribute__((ext_vector_type(8))) __bf16 os_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float os_f32x4;
 
-enum { OS_EPI_BIAS = 0, OS_EPI_RESIDUAL = 1, OS_EPI_QKV = 2 };
+// OS_EPI_QKV_ROWS: OS_EPI_QKV for a step whose rows may name a chain more than once (speculative decoding, ze_spec.hip): row r sits
+// row_off[r] positions behind its chain's context -- or nowhere (row_off[r] < 0: no K/V row is written).  An instantiation of its
+// own: the plain step's kernel is the code it was.
+enum { OS_EPI_BIAS = 0, OS_EPI_RESIDUAL = 1, OS_EPI_QKV = 2, OS_EPI_QKV_ROWS = 3 };
 
 struct ze_oneshot_args {
     const bf16_t* Xf;      // activations, fragment-major (k_rmsnorm(frag) / attention merge)
@@ -40,6 +43,7 @@ struct ze_oneshot_args {
     bf16_t *kcache, *vcache;
     size_t cache_seq_stride;
     int heads, kv_heads, max_ctx;
+    const int* row_off;    // OS_EPI_QKV_ROWS: per row, its offset behind the chain's context; < 0 = a dead row
 };
 
 typedef __attribute__((ext_vector_type(2))) __bf16 os_bf16x2;
@@ -68,6 +72,7 @@ __global__ void __launch_bounds__(1024) k_gemm_oneshot(const ze_oneshot_args a) 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fq = lane >> 4;
+    constexpr bool QKV = EPI == OS_EPI_QKV || EPI == OS_EPI_QKV_ROWS;
     const int nb = blockIdx.x;                   // fragment block: 16 weight rows
     const int ns_all = a.K >> 5;
     const int base = ns_all >> 4, rem = ns_all & 15;
@@ -76,7 +81,7 @@ __global__ void __launch_bounds__(1024) k_gemm_oneshot(const ze_oneshot_args a) 
     // ---- epilogue operands first (waves 0 .. MT-1 own row tile `wid` at the end): they ride under the main loads
     // output column of this lane in ORIGINAL order
     int col;
-    if (EPI == OS_EPI_QKV) {
+    if (QKV) {
         const int h = nb >> 3, j = nb & 7;       // head, 8-dim group
         col = h * D + (fr < 8 ? 8 * j + fr : 64 + 8 * j + (fr - 8));
     } else {
@@ -84,14 +89,15 @@ __global__ void __launch_bounds__(1024) k_gemm_oneshot(const ze_oneshot_args a) 
     }
     float bias_v = 0.f;
     float res[4] = {0.f, 0.f, 0.f, 0.f};
-    int seq[4] = {0, 0, 0, 0};
+    int seq[4] = {0, 0, 0, 0}, off[4] = {0, 0, 0, 0};
     if (wid < MT) {
         if (a.bias) bias_v = bf16_to_f32(a.bias[col]);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = min(wid * 16 + fq * 4 + r, a.M - 1);
             if (EPI == OS_EPI_RESIDUAL) res[r] = bf16_to_f32(a.R[(size_t)row * a.ldr + col]);
-            if (EPI == OS_EPI_QKV) seq[r] = a.seq_ids[row];
+            if (QKV) seq[r] = a.seq_ids[row];
+            if (EPI == OS_EPI_QKV_ROWS) off[r] = a.row_off[row];
         }
     }
 
@@ -138,11 +144,11 @@ __global__ void __launch_bounds__(1024) k_gemm_oneshot(const ze_oneshot_args a) 
 
     // chain state of this lane's rows (QKV): a dependent load behind seq_ids, requested while the partials travel
     int ctx[4] = {0, 0, 0, 0}, pos[4] = {0, 0, 0, 0};
-    if (EPI == OS_EPI_QKV && wid < MT) {
+    if (QKV && wid < MT) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            ctx[r] = a.st[seq[r]].ctx;
-            pos[r] = ctx[r] + a.st[seq[r]].rope_delta;
+            ctx[r] = a.st[seq[r]].ctx + (off[r] > 0 ? off[r] : 0);
+            pos[r] = (EPI == OS_EPI_QKV_ROWS ? min(ctx[r], a.max_ctx - 1) : ctx[r]) + a.st[seq[r]].rope_delta;  // (a dead row rotates by a row the table has)
         }
     }
 
@@ -185,7 +191,7 @@ __global__ void __launch_bounds__(1024) k_gemm_oneshot(const ze_oneshot_args a) 
         for (int r = 0; r < 4; ++r) v[r] *= a.ascale[min(wid * 16 + fq * 4 + r, a.M - 1)] * wsc;
     }
     // ---- epilogue: v[r] -> row = wid*16 + fq*4 + r, column `col`
-    if (EPI != OS_EPI_QKV) {
+    if (!QKV) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = wid * 16 + fq * 4 + r;
@@ -204,6 +210,7 @@ __global__ void __launch_bounds__(1024) k_gemm_oneshot(const ze_oneshot_args a) 
         const float mine = bf16_round(v[r] + bias_v);
         const float other = __shfl_xor(mine, 8, 64);  // the rotate_half partner (dims d and d +- 64) sits 8 columns away
         if (row >= a.M) continue;
+        if (EPI == OS_EPI_QKV_ROWS && h >= a.heads && (off[r] < 0 || ctx[r] >= a.max_ctx)) continue;  // a dead row appends nothing
         if (h >= a.heads + a.kv_heads) {          // v head: no rotation, straight into the cache
             a.vcache[(size_t)seq[r] * a.cache_seq_stride + ((size_t)(h - a.heads - a.kv_heads) * a.max_ctx + ctx[r]) * D +
                      (col - h * D)] = f32_to_bf16(mine);
@@ -264,7 +271,8 @@ void ze_launch_gemm_oneshot(int epi, const bf16_t* Xf, const bf16_t* Wf, const b
 void ze_launch_qkv_rope_oneshot(const bf16_t* Xf, const bf16_t* Wf_perm, const bf16_t* bias, bf16_t* q_out, int ldq, int M,
                                 int K, int heads, int kv_heads, const bf16_t* cosT, const bf16_t* sinT,
                                 const ze_seq_dev* st, const int* seq_ids, bf16_t* kcache, bf16_t* vcache,
-                                size_t cache_seq_stride, int max_ctx, hipStream_t s, const float* wscale, const float* ascale) {
+                                size_t cache_seq_stride, int max_ctx, hipStream_t s, const float* wscale, const float* ascale,
+                                const int* row_off) {
     if (M <= 0) return;
     ze_oneshot_args a;
     memset(&a, 0, sizeof(a));
@@ -273,5 +281,7 @@ void ze_launch_qkv_rope_oneshot(const bf16_t* Xf, const bf16_t* Wf_perm, const b
     a.Xf = Xf; a.Wf = Wf_perm; a.bias = bias; a.C = q_out; a.ldc = ldq; a.M = M; a.N = (heads + 2 * kv_heads) * 128; a.K = K;
     a.st = st; a.seq_ids = seq_ids; a.cosT = cosT; a.sinT = sinT; a.kcache = kcache; a.vcache = vcache;
     a.cache_seq_stride = cache_seq_stride; a.heads = heads; a.kv_heads = kv_heads; a.max_ctx = max_ctx;
-    launch_oneshot<OS_EPI_QKV>(a, s);
+    a.row_off = row_off;
+    if (row_off) launch_oneshot<OS_EPI_QKV_ROWS>(a, s);
+    else launch_oneshot<OS_EPI_QKV>(a, s);
 }

@@ -117,7 +117,10 @@ void ze_launch_qkv_rope_oneshot(const bf16_t* Xf, const bf16_t* Wf_perm, const b
                                 int K, int heads, int kv_heads, const bf16_t* cosT, const bf16_t* sinT,
                                 const ze_seq_dev* st, const int* seq_ids, bf16_t* kcache, bf16_t* vcache,
                                 size_t cache_seq_stride, int max_ctx, hipStream_t s, const float* wscale = nullptr,
-                                const float* ascale = nullptr);
+                                const float* ascale = nullptr,
+                                // a step whose rows may name a chain more than once (ze_spec.hip): row r sits row_off[r] positions
+                                // behind its chain's context; row_off[r] < 0: a dead row, which appends no K/V row
+                                const int* row_off = nullptr);
 // block-scaled FP8 GEMM (k_gemm_ring_mx): A8 [M, K] / W8 [N, K] E4M3 bytes with one power-of-two scale per row each; epi
 // ZE_EPI_NONE or ZE_EPI_SWIGLU; false when the shape does not qualify (K % 128, leading dimensions % 16)
 bool ze_launch_gemm_mx(int epi, const uint8_t* A, int lda, const float* sa, const uint8_t* W, int ldw, const float* sw,
@@ -287,6 +290,13 @@ void ze_launch_attn_decode_stream(const bf16_t* q, int q_row_stride, const bf16_
                                   // parts (or -1; symmetric; null = nobody pairs), long_parts = the 384-key parts the batch's longest
                                   // chain has under its split (0: derive from per_wave), use_split = ze_seq_dev::split cuts the parts
                                   const int* mate = nullptr, int long_parts = 0, int use_split = 0);
+// rows that name a chain more than once (ze_attn_rows.hip: the pipelined kernel's ROWS form; speculative decoding): row b reads the
+// first ctx + row_off[b] + 1 keys of chain seq_ids[b] (row_off[b] < 0, a dead row: the keys the chain has); parts = the 384-key parts
+// the longest row can have; ws_partial holds ceil(max_ctx / 192) slots per row, tickets kv_heads per row
+void ze_launch_attn_decode_rows(const bf16_t* q, int q_row_stride, const bf16_t* kcache, const bf16_t* vcache, size_t cache_seq_stride,
+                                bf16_t* out, int out_row_stride, const ze_seq_dev* st, const int* seq_ids, const int* row_off, int n, int heads,
+                                int kv_heads, int max_ctx, float scale, float* ws_partial, unsigned* tickets, int parts, const int* prefix,
+                                hipStream_t s);
 // prefix (per_wave only; per chain SLOT, null = none): (source chain << 16) | P -- rows 0 .. P-1 of the source chain's KV cache
 // hold the same bits as the chain's own (ze_seq_copy_prefix) and are read from the SOURCE, so the questions of one tile stream
 // one copy of their image prefix (Infinity Cache hits)

@@ -85,6 +85,7 @@ static void write_filter(ze_engine* e, int seq, int top_k, float top_p, float mi
 extern "C" int ze_seq_set_sampling_filter(ze_engine* e, int seq, int top_k, float top_p, float min_p, void* stream) {
     ZE_TRY(check_seq(e, seq));
     ZE_TRY(ze_check_filter(e, top_k, top_p, min_p));
+    if ((top_k > 0 || top_p < 1.f || min_p > 0.f) && e->spec.on(seq)) return ze_fail(e, ZE_ERR_INVALID, "the chain speculates (ze_seq_set_speculation): greedy only, no sampling filter");
     hipSetDevice(e->device);
     write_filter(e, seq, top_k, top_p, min_p, (hipStream_t)stream);
     ZE_KCHECK();
@@ -112,6 +113,7 @@ extern "C" int ze_seq_set_sampling(ze_engine* e, int seq, int mode, float temper
         return ze_fail(e, ZE_ERR_INVALID, "temperature must be finite and > 0");
     if (mode >= 0 && !(std::isfinite(repetition_penalty) && repetition_penalty > 0.f))
         return ze_fail(e, ZE_ERR_INVALID, "repetition_penalty must be finite and > 0 (1 = off)");
+    if (mode == 1 && e->spec.on(seq)) return ze_fail(e, ZE_ERR_INVALID, "the chain speculates (ze_seq_set_speculation): greedy only");
     hipSetDevice(e->device);
     hipStream_t s = (hipStream_t)stream;
     if (mode >= 0 && !e->req.samp_dev) {
@@ -146,6 +148,7 @@ static void write_logprobs(ze_engine* e, int seq, int top_n, hipStream_t s) {
 extern "C" int ze_seq_set_logprobs(ze_engine* e, int seq, int top_n, void* stream) {
     ZE_TRY(check_seq(e, seq));
     if (top_n < -1 || top_n > ZE_MAX_TOP_LOGPROBS) return ze_fail(e, ZE_ERR_INVALID, "top_n must be in [-1, 20] (-1 = off)");
+    if (top_n >= 0 && e->spec.on(seq)) return ze_fail(e, ZE_ERR_INVALID, "the chain speculates (ze_seq_set_speculation): no log-probabilities");
     hipSetDevice(e->device);
     ze_requests& q = e->req;
     const size_t entries = (size_t)e->cfg.max_seqs * e->cfg.max_ctx;
@@ -215,6 +218,7 @@ extern "C" int ze_seq_set_logit_adjust(ze_engine* e, int seq, float presence_pen
     h.frequency = frequency_penalty + 0.f;
     h.min_new = min_new_tokens;
     h.n_bias = n_bias;
+    if (h.on() && e->spec.on(seq)) return ze_fail(e, ZE_ERR_INVALID, "the chain speculates (ze_seq_set_speculation): no logit adjust");
     hipSetDevice(e->device);
     hipStream_t s = (hipStream_t)stream;
     ze_requests& q = e->req;
@@ -292,6 +296,7 @@ extern "C" int ze_seq_set_token_rules(ze_engine* e, int seq, int no_repeat_ngram
     ze_requests::rules_host h;
     h.ngram = no_repeat_ngram, h.n_stop_ints = stop_ints, h.n_stop_words = n_stop_words, h.n_ban_ints = ban_ints, h.n_ban_words = n_ban_words;
     h.n_context = h.bans() ? n_context : 0;  // (stop records never look at the context)
+    if (h.on() && e->spec.on(seq)) return ze_fail(e, ZE_ERR_INVALID, "the chain speculates (ze_seq_set_speculation): no token rules");
     hipSetDevice(e->device);
     hipStream_t s = (hipStream_t)stream;
     ze_requests& q = e->req;
@@ -442,6 +447,7 @@ extern "C" int ze_seq_set_grammar(ze_engine* e, int seq, int grammar, int state,
         ZE_TRY(check_grammar(e, grammar));
         if (state < 0 || state >= e->req.gr_tab[grammar].n_states) return ze_fail(e, ZE_ERR_INVALID, "state outside the grammar");
     }
+    if (grammar >= 0 && e->spec.on(seq)) return ze_fail(e, ZE_ERR_INVALID, "the chain speculates (ze_seq_set_speculation): no grammar");
     hipSetDevice(e->device);
     write_grammar(e, seq, grammar, state, (hipStream_t)stream);
     ZE_KCHECK();
@@ -499,6 +505,7 @@ void ze_requests_clear(ze_engine* e, int seq, hipStream_t s) {
     if (q.la_host[seq].on()) write_adjust(e, seq, ze_requests::adjust_host{}, nullptr, nullptr, s);
     if (q.tr_host[seq].on()) write_rules(e, seq, ze_requests::rules_host{}, nullptr, nullptr, s);
     if (q.gr_host[seq] >= 0) write_grammar(e, seq, -1, 0, s);
+    ze_spec_clear(e, seq, s);
 }
 
 void ze_requests_after_token(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s) {

@@ -853,6 +853,87 @@ class Engine:
         self._check(self.lib.ze_generate(self.h, seq, C.byref(p), out, C.byref(n), self._stream()))
         return [int(out[i]) for i in range(n.value)]
 
+    def set_speculation(self, seq: int, k: int, prompt_ids=(), ngram_min: int = 1, ngram_max: int = 3):
+        """Speculative decoding by prompt lookup for chain `seq` (ze_seq_set_speculation; HF's prompt_lookup_num_tokens, vLLM's
+        ngram method): up to `k` draft ids per step, looked up in prompt_ids + the generated ids by the most recent earlier
+        occurrence of the last ngram_max .. ngram_min ids, verified in the same family-0 step.  Lossless and greedy only; k = 0
+        clears.  Set after the chain's prefill; held until the slot is reset, truncated or copied into."""
+        ids, ip = _i32(list(prompt_ids) if k else [])
+        self._check(self.lib.ze_seq_set_speculation(self.h, int(seq), int(k), int(ngram_min), int(ngram_max), ip, len(ids), self._stream()))
+
+    def generate_speculative(self, seqs, max_new_tokens: int, repetition_penalty: float = 1.0, ignore_eos: bool = False,
+                             use_graph: bool = True, burst: int = 8):
+        """Greedy generation for prefilled chains through family-0 bursts (chain_begin + decode_burst), the path chains with
+        set_speculation take: a step emits up to k + 1 tokens per speculating chain.  Returns one id list per chain, trimmed to
+        max_new_tokens -- bit for bit what the same bursts give without speculation."""
+        seqs = [int(s) for s in seqs]
+        p = self.gen_params(repetition_penalty=repetition_penalty, ignore_eos=ignore_eos, use_graph=use_graph)
+        for i, s in enumerate(seqs):
+            self.chain_begin(s, p, i)
+        n_gen, fin, live = {s: 1 for s in seqs}, {s: False for s in seqs}, list(seqs)
+        while live:
+            live = [s for s in live if n_gen[s] < max_new_tokens and not fin[s] and self.seq_len(s) < self.max_ctx]
+            if not live:
+                break
+            left = max_new_tokens - min(n_gen[s] for s in live)
+            ran, ng, f = self.decode_burst(live, max(1, min(int(burst), left)), p)
+            if ran <= 0 or all(a == n_gen[s] for a, s in zip(ng, live)):
+                break
+            for s, a, b in zip(live, ng, f):
+                n_gen[s], fin[s] = a, b
+        return [self.chain_tokens(s, max_new_tokens) for s in seqs]
+
+    def spec_stats(self, seq: int):
+        """(speculative steps, draft ids proposed, draft ids accepted) of chain `seq` since set_speculation."""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        self._check(self.lib.ze_chain_spec_stats(self.h, int(seq), C.byref(a), C.byref(b), C.byref(c), self._stream()))
+        return a.value, b.value, c.value
+
+    def op_spec_draft(self, histories, k: int, ngram_min: int = 1, ngram_max: int = 3):
+        """The drafter alone (ze_op_spec_draft) on a list of id histories; returns one draft (list of ids) per history."""
+        rows = len(histories)
+        ld = max(1, max((len(h) for h in histories), default=1))
+        hist = np.zeros((rows, ld), dtype=np.int32)
+        for r, h in enumerate(histories):
+            hist[r, :len(h)] = h
+        hd = torch.from_numpy(hist).to(self.device)
+        ln = torch.tensor([len(h) for h in histories], dtype=torch.int32, device=self.device)
+        out = torch.empty((rows, int(k)), dtype=torch.int32, device=self.device)
+        on = torch.empty(rows, dtype=torch.int32, device=self.device)
+        self._check(self.lib.ze_op_spec_draft(self.h, _ptr(hd), _ptr(ln), rows, ld, int(k), int(ngram_min), int(ngram_max), _ptr(out), _ptr(on),
+                                              self._stream()))
+        o, n = out.cpu().numpy(), on.cpu().numpy()
+        return [[int(t) for t in o[r, :n[r]]] for r in range(rows)]
+
+    def op_spec_accept(self, logits: torch.Tensor, drafts, k: int, seen: Optional[torch.Tensor] = None, repetition_penalty=1.0, room=None,
+                       ignore_eos: bool = False):
+        """The accept pass alone (ze_op_spec_accept): logits f32 [n * (k + 1), vocab] device, drafts a list of n id lists (<= k each),
+        seen uint8 [n, vocab] device (updated in place) or None.  Returns (emitted ids per chain, finished flags)."""
+        n, k = len(drafts), int(k)
+        assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape[0] == n * (k + 1)
+        d = np.full((n, k), -1, dtype=np.int32)
+        for c, dr in enumerate(drafts):
+            d[c, :len(dr)] = dr
+        dd = torch.from_numpy(d).to(self.device)
+        dl = torch.tensor([len(dr) for dr in drafts], dtype=torch.int32, device=self.device)
+        pen = torch.tensor(np.broadcast_to(np.asarray(repetition_penalty, dtype=np.float32), (n,)).copy(), device=self.device)
+        rm = torch.tensor(np.broadcast_to(np.asarray(k + 1 if room is None else room, dtype=np.int32), (n,)).copy(), device=self.device)
+        out = torch.empty((n, k + 1), dtype=torch.int32, device=self.device)
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device)
+        fin = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._check(self.lib.ze_op_spec_accept(self.h, _ptr(logits), n, int(logits.shape[1]), int(logits.stride(0)), k, _ptr(dd), _ptr(dl),
+                                               _ptr(seen), _ptr(pen), _ptr(rm), int(bool(ignore_eos)), _ptr(out), _ptr(cnt), _ptr(fin),
+                                               self._stream()))
+        o, m, f = out.cpu().numpy(), cnt.cpu().numpy(), fin.cpu().numpy()
+        return [[int(t) for t in o[c, :m[c]]] for c in range(n)], [bool(x) for x in f]
+
+    def decode_rows(self, seq: int, tokens):
+        """Chain `seq` fed `tokens` at consecutive positions in one family-0 step (ze_op_decode_rows); logits f32 [len, vocab]."""
+        tk, tp = _i32(tokens)
+        logits = torch.empty((len(tk), self.config.text.vocab_size), dtype=torch.float32, device=self.device)
+        self._check(self.lib.ze_op_decode_rows(self.h, int(seq), tp, len(tk), _ptr(logits), self._stream()))
+        return logits
+
     def set_decode_regime(self, regime: int = -1) -> int:
         """Kernel family of the batched decode step: 0 fragment kernels (<= 64 chains per step), 1 row streaming (any
         count), -1 by capacity (max_seqs > 64 -> 1).  Returns the family in force."""

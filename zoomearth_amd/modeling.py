@@ -525,6 +525,24 @@ class ZoomEarthForConditionalGeneration:
                 raise ValueError(f"{name}: at most {MAX_RULE_WORDS} sequences of at most {MAX_RULE_LEN} tokens, {MAX_RULE_INTS} ints packed")
         return int(ngram or 0), stop, bad, strings
 
+    @staticmethod
+    def _speculation_request(kw, do_sample, num_return_sequences=1):
+        """(k, largest n-gram) from generate's `prompt_lookup_num_tokens` / `max_matching_ngram_size`; (0, 3) when not asked for."""
+        k, g = kw.get("prompt_lookup_num_tokens"), kw.get("max_matching_ngram_size")
+        if k is None:
+            if g is not None:
+                raise ValueError("`max_matching_ngram_size` needs `prompt_lookup_num_tokens`")
+            return 0, 3
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not (1 <= k <= 8):
+            raise ValueError(f"`prompt_lookup_num_tokens` has to be an integer in [1, 8], but is {k!r}")
+        g = 3 if g is None else g
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not (1 <= g <= 8):
+            raise ValueError(f"`max_matching_ngram_size` has to be an integer in [1, 8], but is {g!r}")
+        if do_sample or num_return_sequences != 1:
+            raise ValueError("`prompt_lookup_num_tokens` is greedy speculative decoding here: it is not supported with "
+                             "`do_sample=True` or `num_return_sequences` > 1.")
+        return int(k), int(g)
+
     def compile_grammar(self, guided_regex=None, guided_choice=None, tokenizer=None):
         """The token automaton (zoomearth_amd.grammar.TokenAutomaton) of vLLM's `guided_regex` (a pattern) or `guided_choice` (a list
         of strings) against `tokenizer`'s vocabulary, padded to the model's; compiled once per pattern and tokenizer (a small memo on
@@ -571,7 +589,11 @@ class ZoomEarthForConditionalGeneration:
         generated token under the model's own distribution (the step's fp32 logits, before repetition penalty, temperature
         and filters) and that many best alternatives per step, computed on the device inside the decode step.
         `guided_regex` / `guided_choice` (vLLM's; with `tokenizer=`): every row is held to the pattern by a token automaton on the
-        device (zoomearth_amd/grammar.py), set after each chain's prefill where the token rules are set."""
+        device (zoomearth_amd/grammar.py), set after each chain's prefill where the token rules are set.
+        `prompt_lookup_num_tokens` = k (HF's; 1 .. 8) with `max_matching_ngram_size` (default 3, as HF's is 2 .. here up to 8):
+        speculative decoding by prompt lookup on the device (Engine.set_speculation), greedy only.  The call goes through the
+        family-0 bursts (Engine.generate_speculative) and returns bit for bit what those bursts return without it -- the batched
+        family's sequence, which agrees with the single-chain path's within bf16 rounding."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not part of the ZoomEarth path (num_beams=1 everywhere)")
         k = num_return_sequences
@@ -611,12 +633,17 @@ class ZoomEarthForConditionalGeneration:
                            min_p=float(min_p or 0.0))
         presence, frequency, min_new, bias = self._logit_adjust_request(kw)
         ngram, stop, bad, stop_strings = self._token_rules_request(kw)
+        spec_k, spec_g = self._speculation_request(kw, do_sample, k)
         # generate's sampling goes through gen_params and Engine.generate(**sample_kw): the chain carries none of its own, no filter
-        chain = ChainRequest(effective_penalty=float(pen), logprobs=logprobs, presence_penalty=presence, frequency_penalty=frequency,
+        chain = ChainRequest(speculative_tokens=spec_k, ngram_max=spec_g, ngram_min=1, effective_penalty=float(pen), logprobs=logprobs, presence_penalty=presence, frequency_penalty=frequency,
                              min_new_tokens=min_new, logit_bias=bias, no_repeat_ngram_size=ngram, stop_ids=stop, bad_words_ids=bad)
         guided = None
         if kw.get("guided_regex") is not None or kw.get("guided_choice") is not None:
             guided = self.compile_grammar(kw.get("guided_regex"), kw.get("guided_choice"), kw.get("tokenizer"))
+        if spec_k:
+            what = chain.speculation_conflict(grammar=guided is not None)
+            if what is not None:
+                raise ValueError(f"`prompt_lookup_num_tokens` is greedy speculative decoding and cannot be combined with {what}")
         if do_sample and temperature is None:
             temperature = 1.0
         sample_kw = dict(do_sample=bool(do_sample), temperature=float(temperature or 1.0),
@@ -649,6 +676,11 @@ class ZoomEarthForConditionalGeneration:
             self._chains.clear()
             self._next_slot = 0
             e.set_decode_regime(-1)  # (a scheduler may have pinned the family to its own capacity)
+        spec = chain.speculative_tokens > 0
+        if spec:   # the family-0 bursts carry the speculative steps (the row-streaming family has no multi-row kernels)
+            if nrows * k > 64:
+                raise ValueError("`prompt_lookup_num_tokens` runs on the fragment kernels: at most 64 rows per call")
+            e.set_decode_regime(0)
         slots = []
         pending = []
         lps = []
@@ -685,7 +717,10 @@ class ZoomEarthForConditionalGeneration:
                 self._chains[slot] = (tuple(ids), tuple(my_keys))
                 self._chains.move_to_end(slot)
                 chain.install(e, slot, ids, gid)  # (the reset / truncate above cleared the slot's previous request)
-                outs.append(e.generate(slot, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw))
+                if spec:
+                    outs.append(e.generate_speculative([slot], max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos)[0])
+                else:
+                    outs.append(e.generate(slot, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw))
                 if logprobs is not None:
                     lps.append(e.chain_logprobs(slot, max_new_tokens))
             slots.append(slot)
@@ -710,7 +745,14 @@ class ZoomEarthForConditionalGeneration:
                 slots = [item[0] for item in pending]
             for slot, _, _, _, _, ids in pending:
                 chain.install(e, slot, ids, gid)
-            outs = e.generate_batch(slots, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw)
+            if spec:   # rows are budgeted as the engine counts them: 1 + k per chain, 64 in a step
+                k_eff = min(chain.speculative_tokens, 64 // len(slots) - 1)
+                if k_eff < chain.speculative_tokens:
+                    for slot, _, _, _, _, ids in pending:
+                        e.set_speculation(slot, k_eff, ids, chain.ngram_min, chain.ngram_max)
+                outs = e.generate_speculative(slots, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos)
+            else:
+                outs = e.generate_batch(slots, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw)
             if logprobs is not None:
                 lps = e.chain_logprobs_batch(slots, logprobs, max_new_tokens)
         if chain.stop_ids or stop_strings:

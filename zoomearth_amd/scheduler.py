@@ -23,6 +23,7 @@ import copy
 import os
 import time
 from collections import OrderedDict, deque
+import dataclasses
 from dataclasses import InitVar, dataclass, field
 from typing import Any, Callable, List, Optional
 
@@ -86,6 +87,10 @@ class Request:
     # on_error run once per completion with a request object of its own that carries `.index` = i and `.parent` = this request (a
     # follow-up returned for it continues on that completion's slot).  Init-only like prompt_logprobs, and for the same reason
     n: InitVar[int] = 1
+    # speculative decoding by prompt lookup (None = the scheduler's default; 0 = off; 1 .. 8 draft ids per step): greedy only -- a
+    # request that names it together with sampling, log-probabilities, logit adjustments, token rules or a grammar is refused.
+    # Init-only like prompt_logprobs, and for the same reason
+    speculative_tokens: InitVar[Optional[int]] = None
     # filled by the scheduler
     slot: int = -1
     n_prompt: int = 0
@@ -98,8 +103,9 @@ class Request:
     # with `prompt_logprobs`: one entry per prompt token, there before on_done runs -- the token's log-probability given the ids in
     # front of it, its 0-based rank, and the best alternatives at its place as (id, logprob), best first.  None at position 0 and
     # wherever the predicting row was not computed by the request's own pass (a cached prefix of its slot)
-    def __post_init__(self, prompt_logprobs, n=1):
+    def __post_init__(self, prompt_logprobs, n=1, speculative_tokens=None):
         self.prompt_logprobs = prompt_logprobs
+        self.speculative_tokens = speculative_tokens
         self.n, self.index, self.parent = n, 0, None
         self.prompt_token_logprobs, self.prompt_ranks, self.prompt_top_logprobs = [], [], []
 
@@ -175,8 +181,18 @@ class ChainScheduler:
                  admit_chunk_rows: int = 0, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  min_p: Optional[float] = None, logprobs: Optional[int] = None, presence_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, logit_bias: Optional[dict] = None, min_new_tokens: Optional[int] = None,
-                 prefix_cache_rows: int = 0, prefix_cache_block_rows: int = 32, prefix_cache=None, adapter=KEEP_ADAPTER):
+                 prefix_cache_rows: int = 0, prefix_cache_block_rows: int = 32, prefix_cache=None, adapter=KEEP_ADAPTER,
+                 speculative_tokens: int = 0, ngram_min: int = 1, ngram_max: int = 3):
         self.model, self.processor, self.engine = model, processor, model.engine
+        # Speculative decoding by prompt lookup: the default of requests that name none (0 = off).  A step of the fragment family
+        # holds 64 rows, one per chain and one more per draft id: a chain's k is lowered when it joins so that the live chains' rows,
+        # and one row for every slot still free, fit (_spec_budget).  Requests that cannot speculate (sampled, log-probabilities,
+        # adjustments, rules, a grammar) ride the same bursts with one row.
+        self.speculative_tokens, self.ngram_min, self.ngram_max = int(speculative_tokens or 0), int(ngram_min), int(ngram_max)
+        if not (0 <= self.speculative_tokens <= 8) or not (1 <= self.ngram_min <= self.ngram_max <= 8):
+            raise ValueError("speculative_tokens has to be in [0, 8] and 1 <= ngram_min <= ngram_max <= 8")
+        if self.speculative_tokens and min(int(max_batch or self.engine.max_seqs), self.engine.max_seqs) > 64:
+            raise ValueError("speculative decoding runs on the fragment kernels: max_batch <= 64")
         # Logit adjustments: the defaults of requests that name none (None = off).  Written into the slot's rows of the engine's
         # tables next to the filter, with zero counts, for fresh slots and for follow-ups on a parked slot alike; requests with and
         # without them share the same bursts.
@@ -858,7 +874,7 @@ class ChainScheduler:
         own = any(getattr(req, k, None) is not None for k in ("do_sample", "temperature", "seed", "repetition_penalty"))
         sampled, penalty = bool(pick("do_sample")), float(pick("repetition_penalty", "penalty"))
         top_p, logprobs = pick("top_p"), pick("logprobs")
-        return ChainRequest(
+        chain = ChainRequest(
             sampling=(sampled, float(pick("temperature")), int(pick("seed")), penalty) if own else None,
             sampled=sampled, effective_penalty=penalty,
             top_k=int(pick("top_k") or 0), top_p=float(1.0 if top_p is None else top_p), min_p=float(pick("min_p") or 0.0),
@@ -868,6 +884,31 @@ class ChainScheduler:
             min_new_tokens=int(pick("min_new_tokens") or 0), logit_bias=pick("logit_bias") or {},
             no_repeat_ngram_size=int(getattr(req, "no_repeat_ngram_size", None) or 0),
             stop_ids=list(getattr(req, "stop_ids", None) or ()), bad_words_ids=list(getattr(req, "bad_words_ids", None) or ()))
+        return self._with_speculation(req, chain)
+
+    def _with_speculation(self, req, chain: ChainRequest) -> ChainRequest:
+        """The request's speculative_tokens, else the scheduler's -- which yields to whatever of the request excludes it, while a
+        request that names both is refused."""
+        own = getattr(req, "speculative_tokens", None)
+        k = self.speculative_tokens if own is None else own
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not (0 <= k <= 8):
+            raise ValueError(f"`speculative_tokens` has to be an integer in [0, 8], but is {k!r}")
+        if not k:
+            return chain
+        what = chain.speculation_conflict(grammar=self._grammar_key(req) is not None)
+        if what is not None:
+            if own is None:
+                return chain
+            raise ValueError(f"`speculative_tokens` is greedy speculative decoding and cannot be combined with {what}")
+        if self.max_batch > 64:
+            raise ValueError("speculative decoding runs on the fragment kernels: max_batch <= 64")
+        return dataclasses.replace(chain, speculative_tokens=int(k), ngram_min=self.ngram_min, ngram_max=self.ngram_max)
+
+    def _spec_budget(self, k: int) -> int:
+        """The k a joining chain gets: the rows of a step, sum of 1 + k over the live chains, stay <= 64 with one row left for every
+        slot that may still fill."""
+        used = sum(1 + l.req._chain.speculative_tokens for l in self.live.values())
+        return max(0, min(int(k), 64 - used - 1 - (self.max_batch - len(self.live) - 1)))
 
     @staticmethod
     def _grammar_key(req):
@@ -945,6 +986,8 @@ class ChainScheduler:
                     keep_from = i
                     break
         for req, ids, keys in self._ready[:keep_from]:
+            if req._chain.speculative_tokens:   # the step's 64 rows: this chain's k as the live set leaves room for it
+                req._chain = dataclasses.replace(req._chain, speculative_tokens=self._spec_budget(req._chain.speculative_tokens))
             req._chain.install(self.engine, req.slot, ids)
             if self.prefix_cache is not None:
                 req._prefilled = (ids, keys)   # (_release: the rows of a chain that got this far are worth keeping)
