@@ -463,6 +463,45 @@ int ze_op_sample_filter(ze_engine* e, const float* logits, int rows, int vocab, 
                         const int32_t* top_k, const float* top_p, const float* min_p, float* out_cut, int32_t* out_kept,
                         void* stream);
 
+/* Entropy filters of one chain: typical-p, epsilon and eta cutoffs (replaces: TypicalLogitsWarper / EpsilonLogitsWarper /
+ * EtaLogitsWarper, HF:generation/logits_process.py, each with min_tokens_to_keep = 1, the tail of HF:generation/utils.py:
+ * _get_logits_processor).  Order: temperature -> top-k -> top-p -> min-p -> typical -> epsilon -> eta; each step works over the
+ * survivors of everything before it, renormalised.  With z_i = score_i / T, e_i = expf(z_i - z_max) and w_i = (uint64) rintf(e_i *
+ * 2^40) as above (z_max the maximum of the row):
+ *   entropy  of a survivor set S: mass M = sum w_i, U = sum u_i with u_i = (uint64) rintf(e_i * (z_max - z_i) * 2^40) and u_i = 0
+ *            where e_i is 0; H(S) = log(M * 2^-40) + U / M, computed once per row (float64) from the two integers.  Both sums are
+ *            integer: the result is a function of the row alone, whatever order the atomics land in and whatever the grid.
+ *   typical  (mass typical_p in (0, 1); 1 = off): s_i = |(z_max - z_i) + log(M * 2^-40) - H| in fp32 (log(M * 2^-40) and H rounded
+ *            to fp32, the operations left to right); target = ceil((double)typical_p * (double)M); token i survives iff the mass
+ *            of the survivors with s_j strictly smaller than s_i is < target; equal s live or die together (HF's
+ *            last_ind = (cumsum < mass).sum()).  Every fp32 step of s is monotone in z, so the survivors are an interval: the band
+ *            [lo, hi] = their smallest and largest z.  The arg-max may be dropped: that is typical sampling.
+ *   epsilon  (epsilon_cutoff in (0, 1); 0 = off): over the band's survivors with mass M2, keep w_i >= ceil((double)eps * (double)M2);
+ *            the largest-z survivor is always kept.
+ *   eta      (eta_cutoff in (0, 1); 0 = off): H3 and M3 over what epsilon left; thr = min(eta, sqrt(eta) * exp(-H3)) in float64;
+ *            keep w_i >= ceil(thr * (double)M3); the largest-z survivor is always kept.
+ * Per chain and step the selection (ze_sample_band.hip, behind the one of ze_sample_filter.hip, whose cut it reads -- or -inf
+ * while no chain of the engine has such a filter) writes cut, ceil (+inf when typical is off) and kept; the draw treats z_i < cut
+ * or z_i > ceil as e_i = 0 and is otherwise the draw of ze_op_sample_temperature, in the same summation order.
+ * ZE_ERR_INVALID -- the state is then unchanged -- for typical_p outside (0, 1], epsilon_cutoff or eta_cutoff outside [0, 1), and on
+ * a chain that speculates (ze_seq_set_speculation refuses a chain that carries this filter, too).  The values travel as kernel
+ * arguments on `stream` into a per-slot device table, no synchronisation; honoured wherever the sampling filter is (a chain whose
+ * effective mode is greedy ignores it) and cleared wherever it is.  While no chain of the engine has one, every sampling step
+ * launches exactly what it launches without this entry, under the graph keys it had. */
+int ze_seq_set_entropy_filter(ze_engine* e, int seq, float typical_p, float epsilon_cutoff, float eta_cutoff, void* stream);
+/* The selection of the whole warper chain alone on caller-supplied rows: as ze_op_sample_filter, with host arrays typical_p /
+ * epsilon_cutoff / eta_cutoff of length `rows` too; out_cut, out_ceil f32 [rows] device, out_kept int32 [rows] device (may be
+ * NULL): row r keeps the out_kept[r] tokens with out_cut[r] <= logits[r, i] / temperature[r] <= out_ceil[r].  Waits for `stream`. */
+int ze_op_sample_band(ze_engine* e, const float* logits, int rows, int vocab, int ld, const float* temperature, const int32_t* top_k,
+                      const float* top_p, const float* min_p, const float* typical_p, const float* epsilon_cutoff,
+                      const float* eta_cutoff, float* out_cut, float* out_ceil, int32_t* out_kept, void* stream);
+/* ze_op_sample_rows under a band per row: host arrays cut / ceil of length `rows` (-inf / +inf = open; not NaN); a sampled row
+ * draws among the tokens with cut[r] <= score / temperature[r] <= ceil[r], a greedy row ignores its band. */
+int ze_op_sample_rows_band(ze_engine* e, const float* logits, int rows, int vocab, int ld, const uint8_t* seen,
+                           const float* temperature, const float* repetition_penalty, const uint64_t* seed,
+                           const int32_t* sample_stream, const int32_t* index, const float* cut, const float* ceil,
+                           int32_t* out_tokens, void* stream);
+
 /* Sampling request of one chain (replaces: the do_sample / temperature / seed / repetition_penalty of ze_gen_params, which a call
  * takes once for all its chains -- as the OpenAI-compatible back-end of src/eval/infer_vllm.py:244-271 takes `temperature`,
  * `seed` and `repetition_penalty` per request).  mode: -1 clear (the chain follows the call's ze_gen_params again; the other

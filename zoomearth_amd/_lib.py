@@ -155,6 +155,13 @@ _SIGS = {
     "ze_op_sample_filter": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P]),
     "ze_seq_set_sampling": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_float, _P]),
+    "ze_seq_set_entropy_filter": (C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_float, _P]),
+    "ze_op_sample_band": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_float), _P, _P, _P, _P]),
+    "ze_op_sample_rows_band": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_float), _P, _P]),
     "ze_op_sample_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                     C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),

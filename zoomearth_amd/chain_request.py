@@ -22,6 +22,10 @@ class ChainRequest:
     top_k: int = 0
     top_p: float = 1.0
     min_p: float = 0.0
+    # HF's typical_p / epsilon_cutoff / eta_cutoff (1.0 / 0.0 / 0.0 = off), behind the three above and written with them
+    typical_p: float = 1.0
+    epsilon_cutoff: float = 0.0
+    eta_cutoff: float = 0.0
     logprobs: Optional[int] = None
     # vLLM's prompt_logprobs: the chain's prefill pass scores its prompt positions (None: a plain prefill); nothing to install
     prompt_logprobs: Optional[int] = None
@@ -68,6 +72,8 @@ class ChainRequest:
             engine.set_sampling(slot, do_sample=do_sample, temperature=temperature, seed=seed, repetition_penalty=penalty)
         if self.sampled and (self.top_k > 0 or self.top_p < 1.0 or self.min_p > 0.0):
             engine.set_sampling_filter(slot, self.top_k, self.top_p, self.min_p)
+        if self.sampled and (self.typical_p < 1.0 or self.epsilon_cutoff > 0.0 or self.eta_cutoff > 0.0):
+            engine.set_entropy_filter(slot, self.typical_p, self.epsilon_cutoff, self.eta_cutoff)
         if self.logprobs is not None:
             engine.set_logprobs(slot, self.logprobs)
         if self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or self.logit_bias or self.min_new_tokens > 0:

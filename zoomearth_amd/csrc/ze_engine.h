@@ -67,7 +67,7 @@ struct ze_step_key {
     unsigned long long seed = 0;
     unsigned tune_epoch = 0;                   // single-chain step only (the batched graphs are flushed when the epoch changes)
     int live_parts = 0, live_parts_long = 0;   // batched step only: the attention grids' extents
-    int sampling_bits = 0;                     // bit 0 = sampling filters, bit 1 = per-chain sampling table, bit 2 = ... with a draw
+    int sampling_bits = 0;                     // bit 0 = sampling filters, bit 1 = per-chain sampling table, bit 2 = ... with a draw, bit 3 = entropy filters
     int lp_mode = 0, la_mode = 0, tr_mode = 0, gr_mode = 0;
     auto tied() const {
         return std::tie(n, penalty, ignore_eos, temperature, seed, tune_epoch, live_parts, live_parts_long, sampling_bits, lp_mode, la_mode,
@@ -89,6 +89,14 @@ struct ze_requests {
     std::vector<filter_host> filt_host;
     int n_filters = 0;
     float *filt_dev = nullptr, *cut_dev = nullptr;
+    // Entropy filters (ze_seq_set_entropy_filter: typical / epsilon / eta), kept like the sampling filters: ent_host the truth,
+    // ent_dev the per-slot table the band selection reads ((typical_p, epsilon_cutoff, eta_cutoff, 0) per slot; all zero = off),
+    // n_entropy = slots with one.  While it is 0 no sampling launch knows about bands at all.  ceil_dev: the ceilings, laid out as
+    // cut_dev.
+    struct entropy_host { float typical_p = 1.f, epsilon = 0.f, eta = 0.f; bool on() const { return typical_p < 1.f || epsilon > 0.f || eta > 0.f; } };
+    std::vector<entropy_host> ent_host;
+    int n_entropy = 0;
+    float *ent_dev = nullptr, *ceil_dev = nullptr;
     // Sampling requests (ze_seq_set_sampling): samp_host is the truth (penalty = 0: the slot has none), samp_dev the per-slot
     // table the per-chain sampling kernels read, allocated by the first request and written in stream order by the setter;
     // n_sampling = slots with a request, n_sampled = those of them that draw (temperature > 0).  While n_sampling is 0 every
@@ -444,6 +452,7 @@ const float* ze_requests_rows(ze_engine* e, const float* logits, const int* seq_
 void ze_requests_logprobs(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s);
 void ze_requests_after_token(ze_engine* e, const float* logits, const int* seq_ids, int slot0, int n, hipStream_t s);
 int ze_check_filter(ze_engine* e, int top_k, float top_p, float min_p);
+int ze_check_entropy_filter(ze_engine* e, float typical_p, float epsilon_cutoff, float eta_cutoff);
 // the sampling options of a launch: see ze_requests.hip
 void ze_attach_filters(ze_engine* e, ze_sample_opts& so, bool batch);
 float ze_penalty_of(const ze_engine* e, const ze_gen_params* p, int seq);

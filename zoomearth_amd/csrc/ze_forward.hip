@@ -1146,21 +1146,22 @@ extern "C" int ze_op_sample_filter(ze_engine* e, const float* logits, int rows, 
 
 // One draw per caller row with a (temperature | greedy, penalty, seed, stream, index) of its own: the per-chain kernels of
 // ze_sample.hip with row = slot, on tables built for the call
-extern "C" int ze_op_sample_rows(ze_engine* e, const float* logits, int rows, int vocab, int ld, const uint8_t* seen,
-                                 const float* temperature, const float* repetition_penalty, const uint64_t* seed,
-                                 const int32_t* sample_stream, const int32_t* index, const int32_t* top_k, const float* top_p,
-                                 const float* min_p, int32_t* out_tokens, void* stream) {
+static int op_sample_rows(ze_engine* e, const float* logits, int rows, int vocab, int ld, const uint8_t* seen,
+                          const float* temperature, const float* repetition_penalty, const uint64_t* seed,
+                          const int32_t* sample_stream, const int32_t* index, const int32_t* top_k, const float* top_p,
+                          const float* min_p, const float* band_cut, const float* band_ceil, int32_t* out_tokens, void* stream) {
     if (!e || !logits || !temperature || !repetition_penalty || !seed || !sample_stream || !index || !out_tokens)
         return ze_fail(e, ZE_ERR_INVALID, "null argument");
     if (rows <= 0 || vocab <= 0 || ld < vocab) return ze_fail(e, ZE_ERR_INVALID, "rows and vocab must be positive, ld >= vocab");
     const bool filters = top_k || top_p || min_p;
     if (filters && !(top_k && top_p && min_p)) return ze_fail(e, ZE_ERR_INVALID, "top_k, top_p and min_p come together or not at all");
-    // one block of 4-byte words: requests (4 per row) | chain states (8) | filters (4) | row ids (1) | cuts (1) | arg-max
-    // partials (256) | chunk sums (128); the 16-byte entries come first, so they stay aligned
+    // one block of 4-byte words: requests (4 per row) | chain states (8) | filters (4) | row ids (1) | cuts (1) | ceilings (1) |
+    // arg-max partials (256) | chunk sums (128); the 16-byte entries come first, so they stay aligned
     const size_t o_samp = 0, o_st = o_samp + 4 * (size_t)rows, o_filt = o_st + 8 * (size_t)rows, o_ids = o_filt + 4 * (size_t)rows,
-                 o_cut = o_ids + rows, o_part = o_cut + rows, o_sum = o_part + 256 * (size_t)rows, words = o_sum + 128 * (size_t)rows;
+                 o_cut = o_ids + rows, o_ceil = o_cut + rows, o_part = o_ceil + rows, o_sum = o_part + 256 * (size_t)rows,
+                 words = o_sum + 128 * (size_t)rows;
     static_assert(sizeof(ze_chain_sampling) == 16 && sizeof(ze_seq_dev) == 32, "table strides");
-    std::vector<int32_t> host(o_cut, 0);
+    std::vector<int32_t> host(o_part, 0);
     bool draws = false;
     for (int r = 0; r < rows; ++r) {
         if (!(std::isfinite(temperature[r]) && temperature[r] >= 0.f)) return ze_fail(e, ZE_ERR_INVALID, "temperature must be finite and >= 0 (0 = greedy)");
@@ -1182,6 +1183,11 @@ extern "C" int ze_op_sample_rows(ze_engine* e, const float* logits, int rows, in
             memcpy(&host[o_filt + 4 * (size_t)r + 1], &top_p[r], sizeof(float));
             memcpy(&host[o_filt + 4 * (size_t)r + 2], &min_p[r], sizeof(float));
         }
+        if (band_cut) {  // the caller's band [cut, ceil] of the row, z = score / temperature
+            if (std::isnan(band_cut[r]) || std::isnan(band_ceil[r])) return ze_fail(e, ZE_ERR_INVALID, "a band is two numbers (-inf / +inf = open)");
+            memcpy(&host[o_cut + r], &band_cut[r], sizeof(float));
+            memcpy(&host[o_ceil + r], &band_ceil[r], sizeof(float));
+        }
     }
     hipSetDevice(e->device);
     hipStream_t s = (hipStream_t)stream;
@@ -1193,9 +1199,65 @@ extern "C" int ze_op_sample_rows(ze_engine* e, const float* logits, int rows, in
     if (r == ZE_OK)
         ze_launch_sample_rows(logits, vocab, ld, seen, reinterpret_cast<const ze_seq_dev*>(dev + o_st), dev + o_ids, rows,
                               reinterpret_cast<const ze_chain_sampling*>(dev + o_samp), draws,
-                              filters ? reinterpret_cast<const float*>(dev + o_filt) : nullptr, reinterpret_cast<float*>(dev + o_cut),
-                              reinterpret_cast<float*>(dev + o_part), reinterpret_cast<float*>(dev + o_sum), out_tokens, s);
+                              filters ? reinterpret_cast<const float*>(dev + o_filt) : nullptr,
+                              filters || band_cut ? reinterpret_cast<float*>(dev + o_cut) : nullptr,
+                              band_cut ? reinterpret_cast<float*>(dev + o_ceil) : nullptr, reinterpret_cast<float*>(dev + o_part), reinterpret_cast<float*>(dev + o_sum), out_tokens, s);
     if (r == ZE_OK && hipGetLastError() != hipSuccess) r = ze_fail(e, ZE_ERR_HIP, "sampling kernel launch failed");
+    if (hipStreamSynchronize(s) != hipSuccess && r == ZE_OK) r = ze_fail(e, ZE_ERR_HIP, "hipStreamSynchronize failed");
+    hipFree(dev);
+    return r;
+}
+
+extern "C" int ze_op_sample_rows(ze_engine* e, const float* logits, int rows, int vocab, int ld, const uint8_t* seen,
+                                 const float* temperature, const float* repetition_penalty, const uint64_t* seed,
+                                 const int32_t* sample_stream, const int32_t* index, const int32_t* top_k, const float* top_p,
+                                 const float* min_p, int32_t* out_tokens, void* stream) {
+    return op_sample_rows(e, logits, rows, vocab, ld, seen, temperature, repetition_penalty, seed, sample_stream, index, top_k, top_p,
+                          min_p, nullptr, nullptr, out_tokens, stream);
+}
+
+// ... under a band per row as ze_op_sample_band (or anyone) found it: the _band draw kernels alone
+extern "C" int ze_op_sample_rows_band(ze_engine* e, const float* logits, int rows, int vocab, int ld, const uint8_t* seen,
+                                      const float* temperature, const float* repetition_penalty, const uint64_t* seed,
+                                      const int32_t* sample_stream, const int32_t* index, const float* cut, const float* ceil,
+                                      int32_t* out_tokens, void* stream) {
+    if (!cut || !ceil) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    return op_sample_rows(e, logits, rows, vocab, ld, seen, temperature, repetition_penalty, seed, sample_stream, index, nullptr,
+                          nullptr, nullptr, cut, ceil, out_tokens, stream);
+}
+
+// The whole warper chain's selection alone, on caller-supplied rows (unit op: the filter of every row, then its band)
+extern "C" int ze_op_sample_band(ze_engine* e, const float* logits, int rows, int vocab, int ld, const float* temperature,
+                                 const int32_t* top_k, const float* top_p, const float* min_p, const float* typical_p,
+                                 const float* epsilon_cutoff, const float* eta_cutoff, float* out_cut, float* out_ceil,
+                                 int32_t* out_kept, void* stream) {
+    if (!e || !logits || !temperature || !top_k || !top_p || !min_p || !typical_p || !epsilon_cutoff || !eta_cutoff || !out_cut || !out_ceil)
+        return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    if (rows <= 0 || vocab <= 0 || ld < vocab) return ze_fail(e, ZE_ERR_INVALID, "rows and vocab must be positive, ld >= vocab");
+    std::vector<float> table((size_t)rows * 8);  // the filter table, then the entropy-filter table
+    for (int r = 0; r < rows; ++r) {
+        if (!(temperature[r] > 0.f)) return ze_fail(e, ZE_ERR_INVALID, "temperature must be positive");
+        ZE_TRY(ze_check_filter(e, top_k[r], top_p[r], min_p[r]));
+        ZE_TRY(ze_check_entropy_filter(e, typical_p[r], epsilon_cutoff[r], eta_cutoff[r]));
+        float* f = &table[4 * (size_t)r];
+        float* g = &table[4 * ((size_t)rows + r)];
+        memcpy(f, &top_k[r], sizeof(int));
+        f[1] = top_p[r], f[2] = min_p[r], f[3] = temperature[r];
+        g[0] = typical_p[r], g[1] = epsilon_cutoff[r], g[2] = eta_cutoff[r], g[3] = temperature[r];
+    }
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    float* dev = nullptr;
+    ZE_HIP(hipMalloc((void**)&dev, table.size() * sizeof(float)));
+    int r = ZE_OK;
+    if (hipMemcpyAsync(dev, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)
+        r = ze_fail(e, ZE_ERR_HIP, "hipMemcpyAsync failed");
+    if (r == ZE_OK) {
+        ze_launch_sample_filter(logits, vocab, ld, nullptr, nullptr, 0, rows, 1.0f, 1.0f, dev, out_cut, out_kept, nullptr, s);
+        ze_launch_sample_band(logits, vocab, ld, nullptr, nullptr, 0, rows, 1.0f, 1.0f, dev + 4 * (size_t)rows, out_cut, out_cut, out_ceil,
+                              out_kept, nullptr, s);
+    }
+    if (r == ZE_OK && hipGetLastError() != hipSuccess) r = ze_fail(e, ZE_ERR_HIP, "selection kernel launch failed");
     if (hipStreamSynchronize(s) != hipSuccess && r == ZE_OK) r = ze_fail(e, ZE_ERR_HIP, "hipStreamSynchronize failed");
     hipFree(dev);
     return r;

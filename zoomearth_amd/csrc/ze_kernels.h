@@ -333,6 +333,11 @@ struct ze_sample_opts {
     // launch); both null unless some chain of the engine has a filter -- then the draw launches exactly what it always did
     const float* filt = nullptr;
     float* cuts = nullptr;
+    // entropy filters (typical / epsilon / eta: ze_sample_band.hip): the per-slot table (typical_p, epsilon_cutoff, eta_cutoff, 0)
+    // and where the step's ceilings go, next to the cuts; both null unless some chain of the engine has one -- with them the step
+    // launches the band selection and the _band draw kernels, without them exactly what it always did
+    const float* ent = nullptr;
+    float* ceils = nullptr;
     // per-chain sampling requests (batched launches only; a single-chain launch resolves its chain's request on the host):
     // the per-slot table, null unless some chain of the engine has a request -- then the step launches exactly what it always
     // did; samp_draws: some chain of the engine has a SAMPLED request, so the draw is launched whatever `temperature` says
@@ -347,13 +352,22 @@ void ze_launch_sample_filter(const float* logits, int vocab, int ld, const uint8
                              int n, float penalty, float temperature, const float* filt, float* out_cut, int* out_kept,
                              const ze_chain_sampling* samp, hipStream_t s);
 void ze_launch_set_filter(float* filt, int slot, int top_k, float top_p, float min_p, float temperature, hipStream_t s);
+// The band of each of n rows (ze_sample_band.hip), rows / slots / samp as above: row b reads ent[slot] and in_cut[b] (null: -inf;
+// may be out_cut) and writes out_cut[b], out_ceil[b] (+inf unless typical ran) and, when given, out_kept[b] (a row without any of
+// the three keeps what the selection before it wrote)
+void ze_launch_sample_band(const float* logits, int vocab, int ld, const uint8_t* seen_base, const int* seq_ids, int slot0, int n,
+                           float penalty, float temperature, const float* ent, const float* in_cut, float* out_cut, float* out_ceil,
+                           int* out_kept, const ze_chain_sampling* samp, hipStream_t s);
+void ze_launch_set_entropy_filter(float* ent, int slot, float typical_p, float epsilon_cutoff, float eta_cutoff, float temperature,
+                                  hipStream_t s);
 void ze_launch_set_sampling(ze_chain_sampling* table, int slot, ze_chain_sampling v, hipStream_t s);
 // One draw per row on caller rows (ze_op_sample_rows): logits [n, ld]; seen [n, vocab] or null; samp / st / filt (or null) have
-// one entry per ROW (ids = 0 .. n-1 on the device); ws_part 2 * 128 * n, ws_sum 128 * n, cuts n floats.  Touches neither seen
-// nor st: out_tokens[row] = the token.
+// one entry per ROW (ids = 0 .. n-1 on the device); ws_part 2 * 128 * n, ws_sum 128 * n, cuts n floats.  ceils (or null; then filt
+// is null): n floats -- the rows are drawn under the caller's band [cuts, ceils].  Touches neither seen nor st: out_tokens[row] =
+// the token.
 void ze_launch_sample_rows(const float* logits, int vocab, int ld, const uint8_t* seen, const ze_seq_dev* st, const int* ids, int n,
-                           const ze_chain_sampling* samp, bool draws, const float* filt, float* cuts, float* ws_part, float* ws_sum,
-                           int32_t* out_tokens, hipStream_t s);
+                           const ze_chain_sampling* samp, bool draws, const float* filt, float* cuts, float* ceils, float* ws_part,
+                           float* ws_sum, int32_t* out_tokens, hipStream_t s);
 // ws: 2 * 128 arg-max partials + 64 spare + 128 chunk sums (floats)
 void ze_launch_sample(const float* logits, int vocab, uint8_t* seen, float penalty, ze_seq_dev* st,
                       const int* eos_ids, int n_eos, int pad_id, int ignore_eos, int advance_ctx,

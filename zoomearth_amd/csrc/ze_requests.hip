@@ -43,6 +43,9 @@ int ze_requests_create(ze_engine* e) {
     q.filt_host.assign(c.max_seqs, ze_requests::filter_host{});
     chk(dev_alloc(e, &q.filt_dev, (size_t)c.max_seqs * 4));
     chk(dev_alloc(e, &q.cut_dev, (size_t)c.max_seqs * 2));
+    q.ent_host.assign(c.max_seqs, ze_requests::entropy_host{});
+    chk(dev_alloc(e, &q.ent_dev, (size_t)c.max_seqs * 4));
+    chk(dev_alloc(e, &q.ceil_dev, (size_t)c.max_seqs * 2));
     q.samp_host.assign(c.max_seqs, ze_chain_sampling{0.f, 0.f, 0ull});
     q.lp_host.assign(c.max_seqs, -1);
     chk(dev_alloc(e, &q.lp_dev, (size_t)c.max_seqs, false));
@@ -57,7 +60,7 @@ int ze_requests_create(ze_engine* e) {
 
 void ze_requests_free(ze_engine* e) {
     const ze_requests& q = e->req;
-    void* dev[] = {q.filt_dev, q.cut_dev, q.samp_dev, q.lp_dev, q.lp_tok, q.lp_top_ids, q.lp_top_lps, q.la_dev, q.la_bias_ids,
+    void* dev[] = {q.filt_dev, q.cut_dev, q.ent_dev, q.ceil_dev, q.samp_dev, q.lp_dev, q.lp_tok, q.lp_top_ids, q.lp_top_lps, q.la_dev, q.la_bias_ids,
                    q.la_bias_vals, q.la_rows, q.la_counts, q.tr_dev, q.tr_stop, q.tr_ban, q.tr_ctx, q.gr_dev, q.gr_desc};
     for (void* p : dev)
         if (p) hipFree(p);
@@ -88,6 +91,34 @@ extern "C" int ze_seq_set_sampling_filter(ze_engine* e, int seq, int top_k, floa
     if ((top_k > 0 || top_p < 1.f || min_p > 0.f) && e->spec.on(seq)) return ze_fail(e, ZE_ERR_INVALID, "the chain speculates (ze_seq_set_speculation): greedy only, no sampling filter");
     hipSetDevice(e->device);
     write_filter(e, seq, top_k, top_p, min_p, (hipStream_t)stream);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
+// ---- entropy filters (typical / epsilon / eta per chain; ze_sample_band.hip the kernel)
+int ze_check_entropy_filter(ze_engine* e, float typical_p, float epsilon_cutoff, float eta_cutoff) {
+    if (!(typical_p > 0.f && typical_p <= 1.f)) return ze_fail(e, ZE_ERR_INVALID, "typical_p must be in (0, 1] (1 = off)");
+    if (!(epsilon_cutoff >= 0.f && epsilon_cutoff < 1.f)) return ze_fail(e, ZE_ERR_INVALID, "epsilon_cutoff must be in [0, 1) (0 = off)");
+    if (!(eta_cutoff >= 0.f && eta_cutoff < 1.f)) return ze_fail(e, ZE_ERR_INVALID, "eta_cutoff must be in [0, 1) (0 = off)");
+    return ZE_OK;
+}
+
+static void write_entropy_filter(ze_engine* e, int seq, float typical_p, float epsilon_cutoff, float eta_cutoff, hipStream_t s) {
+    ze_requests::entropy_host& f = e->req.ent_host[seq];
+    const bool was = f.on();
+    f.typical_p = typical_p, f.epsilon = epsilon_cutoff + 0.f, f.eta = eta_cutoff + 0.f;
+    e->req.n_entropy += (int)f.on() - (int)was;
+    // the table keeps all zeros for "off" (a zero typical_p is no legal value)
+    if (was || f.on()) ze_launch_set_entropy_filter(e->req.ent_dev, seq, f.on() ? typical_p : 0.f, f.epsilon, f.eta, 0.f, s);
+}
+
+extern "C" int ze_seq_set_entropy_filter(ze_engine* e, int seq, float typical_p, float epsilon_cutoff, float eta_cutoff, void* stream) {
+    ZE_TRY(check_seq(e, seq));
+    ZE_TRY(ze_check_entropy_filter(e, typical_p, epsilon_cutoff, eta_cutoff));
+    if ((typical_p < 1.f || epsilon_cutoff > 0.f || eta_cutoff > 0.f) && e->spec.on(seq))
+        return ze_fail(e, ZE_ERR_INVALID, "the chain speculates (ze_seq_set_speculation): greedy only, no entropy filter");
+    hipSetDevice(e->device);
+    write_entropy_filter(e, seq, typical_p, epsilon_cutoff, eta_cutoff, (hipStream_t)stream);
     ZE_KCHECK();
     return ZE_OK;
 }
@@ -500,6 +531,7 @@ extern "C" int ze_op_grammar_advance(ze_engine* e, int grammar, const int32_t* s
 void ze_requests_clear(ze_engine* e, int seq, hipStream_t s) {
     const ze_requests& q = e->req;
     if (q.filt_host[seq].on()) write_filter(e, seq, 0, 1.f, 0.f, s);
+    if (q.ent_host[seq].on()) write_entropy_filter(e, seq, 1.f, 0.f, 0.f, s);
     clear_sampling(e, seq, s);
     write_logprobs(e, seq, -1, s);
     if (q.la_host[seq].on()) write_adjust(e, seq, ze_requests::adjust_host{}, nullptr, nullptr, s);
@@ -525,9 +557,14 @@ void ze_requests_after_token(ze_engine* e, const float* logits, const int* seq_i
 // A sampled launch learns about filters only while some chain of the engine has one: with none set it is today's launch
 // sequence.  `batch`: the cuts of a batched step (one per row) -- otherwise the slot's own word.
 void ze_attach_filters(ze_engine* e, ze_sample_opts& so, bool batch) {
-    if (so.draws() && e->req.n_filters > 0) {
-        so.filt = e->req.filt_dev;
-        so.cuts = batch ? e->req.cut_dev : e->req.cut_dev + e->cfg.max_seqs + so.slot;
+    const ze_requests& q = e->req;
+    if (!so.draws() || q.n_filters + q.n_entropy == 0) return;
+    const size_t at = batch ? 0 : (size_t)e->cfg.max_seqs + so.slot;
+    so.cuts = q.cut_dev + at;
+    if (q.n_filters > 0) so.filt = q.filt_dev;
+    if (q.n_entropy > 0) {  // (the band selection starts from the filter's cut, or from -inf while no chain has a filter)
+        so.ent = q.ent_dev;
+        so.ceils = q.ceil_dev + at;
     }
 }
 
@@ -572,7 +609,7 @@ ze_step_key ze_step_key_of(const ze_engine* e, int n, int seq, float penalty, in
     k.tune_epoch = n ? 0u : ze_tune_epoch;
     k.live_parts = n ? e->live_parts : 0;
     k.live_parts_long = n ? e->live_parts_long : 0;
-    k.sampling_bits = (int)(so.filt != nullptr) | (int)(so.samp != nullptr) << 1 | (int)so.samp_draws << 2;
+    k.sampling_bits = (int)(so.filt != nullptr) | (int)(so.samp != nullptr) << 1 | (int)so.samp_draws << 2 | (int)(so.ent != nullptr) << 3;
     k.lp_mode = q.lp_mode();
     k.la_mode = n ? q.la_mode() : q.la_mode(seq);
     k.tr_mode = n ? q.tr_mode() : q.tr_mode(seq);

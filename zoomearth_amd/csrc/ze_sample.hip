@@ -121,7 +121,7 @@ __device__ __forceinline__ void accept_token(int bi, uint8_t* __restrict__ seen,
 void ze_launch_multinomial(const float* logits, int vocab, int ld, const uint8_t* seen_base, const ze_seq_dev* st,
                            const int* seq_ids, int slot0, int n, float penalty, float temperature,
                            unsigned long long seed, float* ws_part, float* ws_sum, const float* filt, float* cuts,
-                           const ze_chain_sampling* samp, hipStream_t s);
+                           const float* ent, float* ceils, const ze_chain_sampling* samp, hipStream_t s);
 
 void ze_launch_sample(const float* logits, int vocab, uint8_t* seen, float penalty, ze_seq_dev* st,
                       const int* eos_ids, int n_eos, int pad_id, int ignore_eos, int advance_ctx,
@@ -129,7 +129,7 @@ void ze_launch_sample(const float* logits, int vocab, uint8_t* seen, float penal
     k_argmax_partial<<<SAMPLE_BLOCKS, 256, 0, s>>>(logits, vocab, seen, penalty, ws);
     if (so.temperature > 0.f)
         ze_launch_multinomial(logits, vocab, vocab, seen, st, nullptr, so.slot, 1, penalty, so.temperature, so.seed, ws,
-                              ws + 2 * SAMPLE_BLOCKS + 64, so.filt, so.cuts, nullptr, s);
+                              ws + 2 * SAMPLE_BLOCKS + 64, so.filt, so.cuts, so.ent, so.ceils, nullptr, s);
     k_argmax_final<<<1, 64, 0, s>>>(ws, seen, st, eos_ids, n_eos, pad_id, ignore_eos, advance_ctx, out_tokens, vocab);
 }
 
@@ -302,7 +302,7 @@ void ze_launch_sample_batch(const float* logits, int vocab, uint8_t* seen_base, 
             k_argmax_partial_batch<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, seen_base, seq_ids, penalty, ws);
         if (so.draws())
             ze_launch_multinomial(logits, vocab, vocab, seen_base, st, seq_ids, 0, n, penalty, so.temperature, so.seed, ws,
-                                  ws_sum, so.filt, so.cuts, so.samp, s);
+                                  ws_sum, so.filt, so.cuts, so.ent, so.ceils, so.samp, s);
     }
     k_argmax_final_batch<<<n, 64, 0, s>>>(ws, seen_base, st, seq_ids, vocab, eos_ids, n_eos, pad_id, ignore_eos,
                                           advance_ctx, sample, out_tokens_base, max_gen);
@@ -329,10 +329,14 @@ __device__ __forceinline__ float sample_score(const float* lg, const uint8_t* se
     return v;
 }
 
-// e of one token; a token under the chain's filter cut (ze_sample_filter.hip) has none.  cut = -inf: today's value, bit for bit
+// e of one token; a token under the chain's filter cut (ze_sample_filter.hip) has none.  cut = -inf: today's value, bit for bit.
+// BAND (the _band kernels, launched only while some chain of the engine has a typical / epsilon / eta cutoff: ze_sample_band.hip):
+// nor has a token above the chain's ceiling; without it the ceiling is not there at all
+template <bool BAND = false>
 __device__ __forceinline__ float sample_e(const float* lg, const uint8_t* seen, float penalty, float temperature, float zmax,
-                                          float cut, int i) {
+                                          float cut, int i, float ceil = INFINITY) {
     const float z = sample_score(lg, seen, penalty, i) / temperature;
+    if (BAND && z > ceil) return 0.f;
     return z < cut ? 0.f : expf(z - zmax);
 }
 
@@ -346,14 +350,15 @@ __device__ __forceinline__ float sample_zmax(const float* part, float temperatur
 
 // sum of e over this thread's contiguous run, then the 256 run sums in thread order (by thread 0) -> *total;
 // sRun[t] keeps the run sums for the caller
+template <bool BAND = false>
 __device__ __forceinline__ void sample_chunk_sums(const float* lg, const uint8_t* seen, float penalty, float temperature,
                                                   float zmax, float cut, int start, int end, int run, float* sRun,
-                                                  float* total) {
+                                                  float* total, float ceil = INFINITY) {
     const int t = threadIdx.x;
     float acc = 0.f;
     for (int j = 0; j < run; ++j) {
         const int i = start + t * run + j;
-        if (i < end) acc += sample_e(lg, seen, penalty, temperature, zmax, cut, i);
+        if (i < end) acc += sample_e<BAND>(lg, seen, penalty, temperature, zmax, cut, i, ceil);
     }
     sRun[t] = acc;
     __syncthreads();
@@ -366,15 +371,16 @@ __device__ __forceinline__ void sample_chunk_sums(const float* lg, const uint8_t
 }
 
 // chunk sum blockIdx.x of one row -> sums[blockIdx.x]
+template <bool BAND = false>
 __device__ __forceinline__ void softmax_partial_row(const float* __restrict__ lg, int vocab, const uint8_t* __restrict__ seen,
                                                     float penalty, float temperature, const float* __restrict__ part,
-                                                    float* __restrict__ sums, float cut) {
+                                                    float* __restrict__ sums, float cut, float ceil = INFINITY) {
     const float zmax = sample_zmax(part, temperature);
     const int chunk = (vocab + SAMPLE_BLOCKS - 1) / SAMPLE_BLOCKS, run = (chunk + 255) / 256;
     const int start = blockIdx.x * chunk, end = min(vocab, start + chunk);
     __shared__ float sRun[256];
     __shared__ float sTot;
-    sample_chunk_sums(lg, seen, penalty, temperature, zmax, cut, start, end, run, sRun, &sTot);
+    sample_chunk_sums<BAND>(lg, seen, penalty, temperature, zmax, cut, start, end, run, sRun, &sTot, ceil);
     if (threadIdx.x == 0) sums[blockIdx.x] = sTot;
 }
 
@@ -404,10 +410,11 @@ __global__ void __launch_bounds__(256) k_softmax_partial_chain(const float* __re
 }
 
 // the draw of one row (one workgroup): the pick replaces part[0..1]
+template <bool BAND = false>
 __device__ __forceinline__ void multinomial_pick_row(const float* __restrict__ lg, int vocab, const uint8_t* __restrict__ seen,
                                                      const ze_seq_dev* __restrict__ st, float penalty, float temperature,
                                                      unsigned long long seed, float* __restrict__ part,
-                                                     const float* __restrict__ sums, float cut) {
+                                                     const float* __restrict__ sums, float cut, float ceil = INFINITY) {
     const float zmax = sample_zmax(part, temperature);
     const int chunk = (vocab + SAMPLE_BLOCKS - 1) / SAMPLE_BLOCKS, run = (chunk + 255) / 256;
     __shared__ float sRun[256];
@@ -443,7 +450,7 @@ __device__ __forceinline__ void multinomial_pick_row(const float* __restrict__ l
     const int blk = sBlk;
     const float target = sTarget;
     const int start = blk * chunk, end = min(vocab, start + chunk);
-    sample_chunk_sums(lg, seen, penalty, temperature, zmax, cut, start, end, run, sRun, &sTot);
+    sample_chunk_sums<BAND>(lg, seen, penalty, temperature, zmax, cut, start, end, run, sRun, &sTot, ceil);
     if (threadIdx.x == 0) {
         int tok = -1, last_nz = start;
         float cum = 0.f;
@@ -452,7 +459,7 @@ __device__ __forceinline__ void multinomial_pick_row(const float* __restrict__ l
                 for (int j = 0; j < run; ++j) {
                     const int i = start + t * run + j;
                     if (i >= end) break;
-                    const float e = sample_e(lg, seen, penalty, temperature, zmax, cut, i);
+                    const float e = sample_e<BAND>(lg, seen, penalty, temperature, zmax, cut, i, ceil);
                     cum += e;
                     if (cum > target) {
                         tok = i;
@@ -467,7 +474,7 @@ __device__ __forceinline__ void multinomial_pick_row(const float* __restrict__ l
         }
         if (tok < 0) {  // rounding at the very end (or target = -inf): last element of the chunk that carries mass
             tok = last_nz;
-            while (tok > start && !(sample_e(lg, seen, penalty, temperature, zmax, cut, tok) > 0.f)) --tok;
+            while (tok > start && !(sample_e<BAND>(lg, seen, penalty, temperature, zmax, cut, tok, ceil) > 0.f)) --tok;
         }
         part[0] = INFINITY;  // unbeatable arg-max partial: the final kernel adopts the pick
         reinterpret_cast<int*>(part)[1] = tok;
@@ -504,16 +511,89 @@ __global__ void __launch_bounds__(256) k_multinomial_pick_chain(const float* __r
                          ws_sum + (size_t)b * SAMPLE_BLOCKS, cuts ? cuts[b] : -INFINITY);
 }
 
-// samp (batched launches only, seq_ids given): the per-chain forms -- the same passes over the rows, the values per row
+// ---- the draw under a band [cut, ceil] (ze_sample_band.hip): the four kernels above with the ceiling, instantiations of their own
+__global__ void __launch_bounds__(256) k_softmax_partial_band(const float* __restrict__ logits, int vocab,
+                                                              const uint8_t* __restrict__ seen_base,
+                                                              const int* __restrict__ seq_ids, float penalty, float temperature,
+                                                              const float* __restrict__ ws_part, float* __restrict__ ws_sum,
+                                                              const float* __restrict__ cuts, const float* __restrict__ ceils) {
+    const int b = blockIdx.y;
+    softmax_partial_row<true>(logits + (size_t)b * vocab, vocab, seen_base + (seq_ids ? (size_t)seq_ids[b] * vocab : 0), penalty,
+                              temperature, ws_part + (size_t)b * 2 * SAMPLE_BLOCKS, ws_sum + (size_t)b * SAMPLE_BLOCKS, cuts[b], ceils[b]);
+}
+
+__global__ void __launch_bounds__(256) k_softmax_partial_chain_band(const float* __restrict__ logits, int vocab, int ld,
+                                                                    const uint8_t* __restrict__ seen_base,
+                                                                    const int* __restrict__ seq_ids, float penalty,
+                                                                    float temperature, const ze_chain_sampling* __restrict__ samp,
+                                                                    const float* __restrict__ ws_part, float* __restrict__ ws_sum,
+                                                                    const float* __restrict__ cuts, const float* __restrict__ ceils) {
+    const int b = blockIdx.y, slot = seq_ids[b];
+    const ze_chain_sampling r = chain_sampling_of(samp, slot, penalty, temperature, 0ull);
+    if (!(r.temperature > 0.f)) return;
+    softmax_partial_row<true>(logits + (size_t)b * ld, vocab, seen_base ? seen_base + (size_t)slot * vocab : nullptr,
+                              seen_base ? r.penalty : 1.0f, r.temperature, ws_part + (size_t)b * 2 * SAMPLE_BLOCKS,
+                              ws_sum + (size_t)b * SAMPLE_BLOCKS, cuts[b], ceils[b]);
+}
+
+__global__ void __launch_bounds__(256) k_multinomial_pick_band(const float* __restrict__ logits, int vocab,
+                                                               const uint8_t* __restrict__ seen_base,
+                                                               const ze_seq_dev* __restrict__ st_base,
+                                                               const int* __restrict__ seq_ids, int slot0, float penalty,
+                                                               float temperature, unsigned long long seed,
+                                                               float* __restrict__ ws_part, const float* __restrict__ ws_sum,
+                                                               const float* __restrict__ cuts, const float* __restrict__ ceils) {
+    const int b = blockIdx.x, slot = seq_ids ? seq_ids[b] : slot0;
+    multinomial_pick_row<true>(logits + (size_t)b * vocab, vocab, seen_base + (seq_ids ? (size_t)slot * vocab : 0),
+                               seq_ids ? st_base + slot : st_base, penalty, temperature, seed, ws_part + (size_t)b * 2 * SAMPLE_BLOCKS,
+                               ws_sum + (size_t)b * SAMPLE_BLOCKS, cuts[b], ceils[b]);
+}
+
+__global__ void __launch_bounds__(256) k_multinomial_pick_chain_band(const float* __restrict__ logits, int vocab, int ld,
+                                                                     const uint8_t* __restrict__ seen_base,
+                                                                     const ze_seq_dev* __restrict__ st_base,
+                                                                     const int* __restrict__ seq_ids, float penalty,
+                                                                     float temperature, unsigned long long seed,
+                                                                     const ze_chain_sampling* __restrict__ samp,
+                                                                     float* __restrict__ ws_part, const float* __restrict__ ws_sum,
+                                                                     const float* __restrict__ cuts, const float* __restrict__ ceils) {
+    const int b = blockIdx.x, slot = seq_ids[b];
+    const ze_chain_sampling r = chain_sampling_of(samp, slot, penalty, temperature, seed);
+    if (!(r.temperature > 0.f)) return;
+    multinomial_pick_row<true>(logits + (size_t)b * ld, vocab, seen_base ? seen_base + (size_t)slot * vocab : nullptr, st_base + slot,
+                               seen_base ? r.penalty : 1.0f, r.temperature, r.seed, ws_part + (size_t)b * 2 * SAMPLE_BLOCKS,
+                               ws_sum + (size_t)b * SAMPLE_BLOCKS, cuts[b], ceils[b]);
+}
+
+// samp (batched launches only, seq_ids given): the per-chain forms -- the same passes over the rows, the values per row.
+// filt (or null): the filter table -- the selection writes cuts first; ent (or null): the entropy-filter table -- the band selection
+// follows it and writes cuts and ceils; ceils without ent: the caller's own band.  With ceils the draw runs its _band kernels.
 void ze_launch_multinomial(const float* logits, int vocab, int ld, const uint8_t* seen_base, const ze_seq_dev* st,
                            const int* seq_ids, int slot0, int n, float penalty, float temperature,
                            unsigned long long seed, float* ws_part, float* ws_sum, const float* filt, float* cuts,
-                           const ze_chain_sampling* samp, hipStream_t s) {
+                           const float* ent, float* ceils, const ze_chain_sampling* samp, hipStream_t s) {
     if (n <= 0) return;
-    // filt = null (no chain of the engine has a filter): the two launches of the plain draw, nothing else
-    if (!filt) cuts = nullptr;
-    if (cuts)
+    // filt = ent = ceils = null (no chain of the engine has a filter): the two launches of the plain draw, nothing else
+    if (!filt && !ceils) cuts = nullptr;
+    if (filt)
         ze_launch_sample_filter(logits, vocab, ld, seen_base, seq_ids, slot0, n, penalty, temperature, filt, cuts, nullptr, samp, s);
+    if (ent)
+        ze_launch_sample_band(logits, vocab, ld, seen_base, seq_ids, slot0, n, penalty, temperature, ent, filt ? cuts : nullptr, cuts,
+                              ceils, nullptr, samp, s);
+    if (ceils) {
+        if (samp) {
+            k_softmax_partial_chain_band<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, ld, seen_base, seq_ids, penalty, temperature,
+                                                                                samp, ws_part, ws_sum, cuts, ceils);
+            k_multinomial_pick_chain_band<<<n, 256, 0, s>>>(logits, vocab, ld, seen_base, st, seq_ids, penalty, temperature, seed, samp,
+                                                            ws_part, ws_sum, cuts, ceils);
+        } else {
+            k_softmax_partial_band<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, seen_base, seq_ids, penalty, temperature,
+                                                                          ws_part, ws_sum, cuts, ceils);
+            k_multinomial_pick_band<<<n, 256, 0, s>>>(logits, vocab, seen_base, st, seq_ids, slot0, penalty, temperature, seed,
+                                                      ws_part, ws_sum, cuts, ceils);
+        }
+        return;
+    }
     if (samp) {
         k_softmax_partial_chain<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, ld, seen_base, seq_ids, penalty, temperature,
                                                                        samp, ws_part, ws_sum, cuts);
@@ -550,11 +630,11 @@ __global__ void __launch_bounds__(64) k_argmax_final_rows(const float* __restric
 }
 
 void ze_launch_sample_rows(const float* logits, int vocab, int ld, const uint8_t* seen, const ze_seq_dev* st, const int* ids, int n,
-                           const ze_chain_sampling* samp, bool draws, const float* filt, float* cuts, float* ws_part, float* ws_sum,
-                           int32_t* out_tokens, hipStream_t s) {
+                           const ze_chain_sampling* samp, bool draws, const float* filt, float* cuts, float* ceils, float* ws_part,
+                           float* ws_sum, int32_t* out_tokens, hipStream_t s) {
     if (n <= 0) return;
     k_argmax_partial_chain<<<dim3(SAMPLE_BLOCKS, n), 256, 0, s>>>(logits, vocab, ld, seen, ids, 1.0f, samp, ws_part);
-    if (draws) ze_launch_multinomial(logits, vocab, ld, seen, st, ids, 0, n, 1.0f, 0.f, 0ull, ws_part, ws_sum, filt, cuts, samp, s);
+    if (draws) ze_launch_multinomial(logits, vocab, ld, seen, st, ids, 0, n, 1.0f, 0.f, 0ull, ws_part, ws_sum, filt, cuts, nullptr, ceils, samp, s);
     k_argmax_final_rows<<<n, 64, 0, s>>>(ws_part, vocab, out_tokens);
 }
 

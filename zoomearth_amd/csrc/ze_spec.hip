@@ -329,6 +329,7 @@ extern "C" int ze_seq_set_speculation(ze_engine* e, int seq, int k, int min_ngra
     if (r.samp_host[seq].penalty > 0.f && r.samp_host[seq].temperature > 0.f)
         return ze_fail(e, ZE_ERR_INVALID, "speculation is greedy only: the chain has a sampled request (ze_seq_set_sampling)");
     if (r.filt_host[seq].on()) return ze_fail(e, ZE_ERR_INVALID, "speculation is greedy only: the chain has a sampling filter");
+    if (r.ent_host[seq].on()) return ze_fail(e, ZE_ERR_INVALID, "speculation is greedy only: the chain has an entropy filter");
     if (r.la_host[seq].on()) return ze_fail(e, ZE_ERR_INVALID, "speculation excludes a logit adjust on the same chain");
     if (r.tr_host[seq].on()) return ze_fail(e, ZE_ERR_INVALID, "speculation excludes token rules on the same chain");
     if (r.gr_host[seq] >= 0) return ze_fail(e, ZE_ERR_INVALID, "speculation excludes a grammar on the same chain");

@@ -390,6 +390,67 @@ class Engine:
                                                  m.ctypes.data_as(fp), _ptr(cut), _ptr(kept), self._stream()))
         return cut, kept
 
+    def set_entropy_filter(self, seq: int, typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0):
+        """Typical-p / epsilon / eta cutoffs of chain `seq` (HF's warpers in HF's order, behind top-k / top-p / min-p, applied on
+        the device inside the sampled step; 1.0 / 0.0 / 0.0 = off; None counts as off).  Honoured and cleared wherever the
+        sampling filter is; greedy decoding ignores it; a speculating chain refuses it."""
+        self._check(self.lib.ze_seq_set_entropy_filter(self.h, int(seq), float(1.0 if typical_p is None else typical_p),
+                                                       float(epsilon_cutoff or 0.0), float(eta_cutoff or 0.0), self._stream()))
+
+    def sample_band(self, logits: torch.Tensor, temperature, top_k=0, top_p=1.0, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0,
+                    eta_cutoff=0.0):
+        """The selection of the whole warper chain alone (ze_op_sample_band): logits f32 [rows, vocab] (row stride >= vocab), the
+        settings per row (scalars broadcast).  Returns (cut f32 [rows], ceil f32 [rows], kept int32 [rows]): row r keeps the
+        kept[r] tokens with cut[r] <= logits[r] / temperature[r] <= ceil[r]."""
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+        rows = int(logits.shape[0])
+
+        def per_row(v, dtype):
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (rows,)))
+        f = [per_row(v, np.float32) for v in (temperature, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff)]
+        k = per_row(top_k, np.int32)
+        cut = torch.empty(rows, dtype=torch.float32, device=self.device)
+        ceil = torch.empty(rows, dtype=torch.float32, device=self.device)
+        kept = torch.empty(rows, dtype=torch.int32, device=self.device)
+        fp = C.POINTER(C.c_float)
+        ld = int(logits.stride(0)) if rows > 1 else int(logits.shape[1])   # (the stride of a one-row tensor means nothing)
+        self._use(logits)
+        self._check(self.lib.ze_op_sample_band(self.h, _ptr(logits), rows, int(logits.shape[1]), ld, f[0].ctypes.data_as(fp),
+                                               k.ctypes.data_as(C.POINTER(C.c_int32)), *(a.ctypes.data_as(fp) for a in f[1:]),
+                                               _ptr(cut), _ptr(ceil), _ptr(kept), self._stream()))
+        return cut, ceil, kept
+
+    def sample_rows_band(self, logits: torch.Tensor, temperature, cut, ceil, repetition_penalty=1.0, seed=0, sample_stream=0,
+                         index=0, seen: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """sample_rows under a band per row (ze_op_sample_rows_band): a sampled row draws among the tokens with cut[r] <=
+        score / temperature[r] <= ceil[r] (host values, scalars broadcast).  Returns the tokens, int32 [rows]."""
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+        rows, vocab = int(logits.shape[0]), int(logits.shape[1])
+        if seen is not None:
+            assert seen.dtype == torch.uint8 and seen.is_contiguous() and tuple(seen.shape) == (rows, vocab)
+            self._use(seen)
+
+        def per_row(v, dtype):
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (rows,)))
+        t, pen = per_row(temperature, np.float32), per_row(repetition_penalty, np.float32)
+        sd, strm, idx = per_row(seed, np.uint64), per_row(sample_stream, np.int32), per_row(index, np.int32)
+        lo, hi = per_row(cut, np.float32), per_row(ceil, np.float32)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        out = torch.empty(rows, dtype=torch.int32, device=self.device)
+        ld = int(logits.stride(0)) if rows > 1 else vocab   # (the stride of a one-row tensor means nothing)
+        self._use(logits)
+        self._check(self.lib.ze_op_sample_rows_band(
+            self.h, _ptr(logits), rows, vocab, ld, _ptr(seen) if seen is not None else None, t.ctypes.data_as(fp),
+            pen.ctypes.data_as(fp), sd.ctypes.data_as(C.POINTER(C.c_uint64)), strm.ctypes.data_as(ip), idx.ctypes.data_as(ip),
+            lo.ctypes.data_as(fp), hi.ctypes.data_as(fp), _ptr(out), self._stream()))
+        return out
+
+    def _apply_entropy_filter(self, seqs, typical_p, epsilon_cutoff, eta_cutoff):
+        if typical_p is None and epsilon_cutoff is None and eta_cutoff is None:
+            return  # (whatever set_entropy_filter left on the chains stays)
+        for q in seqs:
+            self.set_entropy_filter(int(q), typical_p, epsilon_cutoff, eta_cutoff)
+
     def set_sampling(self, seq: int, do_sample: Optional[bool] = None, temperature: float = 1.0, seed: int = 0,
                      repetition_penalty: float = 1.0):
         """Sampling request of chain `seq` (ze_seq_set_sampling): do_sample False = greedy, True = temperature sampling with the
@@ -844,10 +905,11 @@ class Engine:
 
     def generate(self, seq: int, max_new_tokens: int, repetition_penalty: float = 1.0, ignore_eos: bool = False,
                  use_graph: bool = True, sync_every: int = 16, do_sample: bool = False, temperature: float = 1.0,
-                 seed: int = 0, top_k=None, top_p=None, min_p=None):
+                 seed: int = 0, top_k=None, top_p=None, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
         p = self._gen_params(max_new_tokens, repetition_penalty, ignore_eos, use_graph, sync_every, do_sample,
                              temperature, seed)
         self._apply_filter([seq], top_k, top_p, min_p)
+        self._apply_entropy_filter([seq], typical_p, epsilon_cutoff, eta_cutoff)
         out = (C.c_int32 * max(max_new_tokens, 1))()
         n = C.c_int()
         self._check(self.lib.ze_generate(self.h, seq, C.byref(p), out, C.byref(n), self._stream()))
@@ -948,11 +1010,12 @@ class Engine:
 
     def generate_batch(self, seqs, max_new_tokens: int, repetition_penalty: float = 1.0, ignore_eos: bool = False,
                        sync_every: int = 16, use_graph: bool = True, do_sample: bool = False, temperature: float = 1.0,
-                       seed: int = 0, top_k=None, top_p=None, min_p=None):
+                       seed: int = 0, top_k=None, top_p=None, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
         """Generation for several prefilled chains at once; returns one token list per chain.  top_k / top_p / min_p, when
         given, are set on every chain of the call (set_sampling_filter beforehand for a filter per chain)."""
         sq, sp = _i32(seqs)
         self._apply_filter(sq, top_k, top_p, min_p)
+        self._apply_entropy_filter(sq, typical_p, epsilon_cutoff, eta_cutoff)
         p = self._gen_params(max_new_tokens, repetition_penalty, ignore_eos, use_graph, sync_every, do_sample,
                              temperature, seed)
         out = (C.c_int32 * (len(sq) * max_new_tokens))()

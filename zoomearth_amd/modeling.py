@@ -11,6 +11,8 @@ wrapper); `do_sample=True, temperature=T` draws from softmax(logits / T) with th
 random stream (`seed=` kwarg or `generation_config.seed`); `top_k` / `top_p` / `min_p` (kwargs, then
 `generation_config`) are HF's warpers in HF's order, applied per chain on the device (`Engine.set_sampling_filter`;
 None, `top_k=0`, `top_p=1.0` mean off, `top_k=1` is greedy, out-of-range values raise ValueError as HF does);
+`typical_p` / `epsilon_cutoff` / `eta_cutoff` (kwargs, then `generation_config`) follow them on the device
+(`Engine.set_entropy_filter`; None, 1.0 / 0.0 / 0.0 mean off, values outside (0, 1) raise HF's ValueError);
 `num_beams` must be 1.
 """
 from __future__ import annotations
@@ -526,6 +528,25 @@ class ZoomEarthForConditionalGeneration:
         return int(ngram or 0), stop, bad, strings
 
     @staticmethod
+    def _entropy_filter_request(kw, gc) -> dict:
+        """generate's `typical_p` / `epsilon_cutoff` / `eta_cutoff` (kwargs, then generation_config) as Engine.generate takes them: only
+        the ones that are on (HF's off values: None or 1.0 / 0.0 / 0.0); HF's errors for anything else outside (0, 1)."""
+        out = {}
+        for name, off in (("typical_p", 1.0), ("epsilon_cutoff", 0.0), ("eta_cutoff", 0.0)):
+            v = kw.get(name) if kw.get(name) is not None else getattr(gc, name, None)
+            if v is None:
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"`{name}` has to be a float > 0 and < 1, but is {v}")
+            v = float(v)
+            if v == off:
+                continue
+            if not (0.0 < v < 1.0):
+                raise ValueError(f"`{name}` has to be a float > 0 and < 1, but is {v}")
+            out[name] = v
+        return out
+
+    @staticmethod
     def _speculation_request(kw, do_sample, num_return_sequences=1):
         """(k, largest n-gram) from generate's `prompt_lookup_num_tokens` / `max_matching_ngram_size`; (0, 3) when not asked for."""
         k, g = kw.get("prompt_lookup_num_tokens"), kw.get("max_matching_ngram_size")
@@ -631,6 +652,12 @@ class ZoomEarthForConditionalGeneration:
             # (top_p = 0 keeps HF's min_tokens_to_keep = 1, the arg-max: the smallest positive value does the same)
             filt_kw = dict(top_k=int(top_k or 0), top_p=1.0 if top_p is None else max(float(top_p), 1e-37),
                            min_p=float(min_p or 0.0))
+        ent_kw = self._entropy_filter_request(kw, gc)
+        if ent_kw and kw.get("prompt_lookup_num_tokens") is not None:
+            raise ValueError("`prompt_lookup_num_tokens` is greedy speculative decoding and cannot be combined with "
+                             "`typical_p`, `epsilon_cutoff` or `eta_cutoff`")
+        if do_sample:   # (without do_sample they are ignored, as HF ignores its warpers)
+            filt_kw.update(ent_kw)
         presence, frequency, min_new, bias = self._logit_adjust_request(kw)
         ngram, stop, bad, stop_strings = self._token_rules_request(kw)
         spec_k, spec_g = self._speculation_request(kw, do_sample, k)

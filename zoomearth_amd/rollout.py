@@ -54,11 +54,14 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
                       max_new_tokens: int = 800, seed: int = 0, max_view: int = 512, with_logps: bool = True,
                       burst: int = 8, top_k: Optional[int] = None, top_p: Optional[float] = None,
                       min_p: Optional[float] = None, sampled_logps: bool = False, entropies: bool = False,
-                      prefix_cache=None, ref_logps: bool = False) -> List[Rollout]:
+                      prefix_cache=None, ref_logps: bool = False, typical_p: Optional[float] = None,
+                      epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None) -> List[Rollout]:
     """samples: dicts with `prompt` (the stage-1 prompt text, one `<|vision_start|><|image_pad|><|vision_end|>` block),
     `image` (the tile: DeviceImage or PIL) and `bbox` (the dataset's reference box; empty = non-cropping question).
     top_k / top_p / min_p: the sampling filters of the reference's generation step (GRPOConfig top_k / top_p / min_p,
     open_r1/trainer/grpo_config.py:62-70), applied to every chain of both stages; None = off.
+    typical_p / epsilon_cutoff / eta_cutoff: HF's entropy-adaptive cutoffs of a generation_config, behind the three above on every
+    chain of both stages; None (or 1.0 / 0.0 / 0.0) = off.
     sampled_logps: fill completion1_logps / completion2_logps with the log-probabilities the decode steps computed for their own
     samples (the model's distribution, before temperature and filters); independent of with_logps, which scores the final
     sequences with batched passes of their own.
@@ -76,7 +79,8 @@ def rollout_two_stage(model, processor, samples, num_generations: int = 4, tempe
     if ref_logps and not with_logps:
         raise ValueError("ref_logps=True needs with_logps=True")
     sched = ChainScheduler(model, processor, do_sample=True, temperature=temperature, seed=seed, burst=burst,
-                           top_k=top_k, top_p=top_p, min_p=min_p, logprobs=0 if sampled_logps else None,
+                           top_k=top_k, top_p=top_p, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff,
+                           eta_cutoff=eta_cutoff, logprobs=0 if sampled_logps else None,
                            **({} if prefix_cache is None else {"prefix_cache": prefix_cache}))
     n, G = len(samples), int(num_generations)
     out = [Rollout(sample=i, generation=g, prompt1=samples[i]["prompt"]) for i in range(n) for g in range(G)]

@@ -91,6 +91,11 @@ class Request:
     # request that names it together with sampling, log-probabilities, logit adjustments, token rules or a grammar is refused.
     # Init-only like prompt_logprobs, and for the same reason
     speculative_tokens: InitVar[Optional[int]] = None
+    # HF's typical_p / epsilon_cutoff / eta_cutoff of this request (None = the scheduler's default; 1.0 / 0.0 / 0.0 = off), resolved
+    # like min_p and written with the sampling filter.  Init-only like prompt_logprobs, and for the same reason
+    typical_p: InitVar[Optional[float]] = None
+    epsilon_cutoff: InitVar[Optional[float]] = None
+    eta_cutoff: InitVar[Optional[float]] = None
     # filled by the scheduler
     slot: int = -1
     n_prompt: int = 0
@@ -103,7 +108,8 @@ class Request:
     # with `prompt_logprobs`: one entry per prompt token, there before on_done runs -- the token's log-probability given the ids in
     # front of it, its 0-based rank, and the best alternatives at its place as (id, logprob), best first.  None at position 0 and
     # wherever the predicting row was not computed by the request's own pass (a cached prefix of its slot)
-    def __post_init__(self, prompt_logprobs, n=1, speculative_tokens=None):
+    def __post_init__(self, prompt_logprobs, n=1, speculative_tokens=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
+        self.typical_p, self.epsilon_cutoff, self.eta_cutoff = typical_p, epsilon_cutoff, eta_cutoff
         self.prompt_logprobs = prompt_logprobs
         self.speculative_tokens = speculative_tokens
         self.n, self.index, self.parent = n, 0, None
@@ -182,8 +188,10 @@ class ChainScheduler:
                  min_p: Optional[float] = None, logprobs: Optional[int] = None, presence_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, logit_bias: Optional[dict] = None, min_new_tokens: Optional[int] = None,
                  prefix_cache_rows: int = 0, prefix_cache_block_rows: int = 32, prefix_cache=None, adapter=KEEP_ADAPTER,
-                 speculative_tokens: int = 0, ngram_min: int = 1, ngram_max: int = 3):
+                 speculative_tokens: int = 0, ngram_min: int = 1, ngram_max: int = 3, typical_p: Optional[float] = None,
+                 epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None):
         self.model, self.processor, self.engine = model, processor, model.engine
+        self.typical_p, self.epsilon_cutoff, self.eta_cutoff = typical_p, epsilon_cutoff, eta_cutoff
         # Speculative decoding by prompt lookup: the default of requests that name none (0 = off).  A step of the fragment family
         # holds 64 rows, one per chain and one more per draft id: a chain's k is lowered when it joins so that the live chains' rows,
         # and one row for every slot still free, fit (_spec_budget).  Requests that cannot speculate (sampled, log-probabilities,
@@ -874,10 +882,16 @@ class ChainScheduler:
         own = any(getattr(req, k, None) is not None for k in ("do_sample", "temperature", "seed", "repetition_penalty"))
         sampled, penalty = bool(pick("do_sample")), float(pick("repetition_penalty", "penalty"))
         top_p, logprobs = pick("top_p"), pick("logprobs")
+        typical_p, epsilon_cutoff, eta_cutoff = pick("typical_p"), pick("epsilon_cutoff"), pick("eta_cutoff")
+        for name, v, ok in (("typical_p", typical_p, lambda x: 0.0 < x <= 1.0), ("epsilon_cutoff", epsilon_cutoff, lambda x: 0.0 <= x < 1.0),
+                            ("eta_cutoff", eta_cutoff, lambda x: 0.0 <= x < 1.0)):
+            if v is not None and not ok(float(v)):
+                raise ValueError(f"`{name}` has to be a float > 0 and < 1, but is {v}")
         chain = ChainRequest(
             sampling=(sampled, float(pick("temperature")), int(pick("seed")), penalty) if own else None,
             sampled=sampled, effective_penalty=penalty,
             top_k=int(pick("top_k") or 0), top_p=float(1.0 if top_p is None else top_p), min_p=float(pick("min_p") or 0.0),
+            typical_p=float(1.0 if typical_p is None else typical_p), epsilon_cutoff=float(epsilon_cutoff or 0.0), eta_cutoff=float(eta_cutoff or 0.0),
             logprobs=None if logprobs is None else int(logprobs),
             prompt_logprobs=None if getattr(req, "prompt_logprobs", None) is None else int(req.prompt_logprobs),
             presence_penalty=float(pick("presence_penalty") or 0.0), frequency_penalty=float(pick("frequency_penalty") or 0.0),

@@ -6,7 +6,8 @@
 Request: the subset that client sends -- `messages` with `role` in {system, user, assistant} and `content` either a
 string or a list of `{"type": "text", "text": ...}` / `{"type": "image_url", "image_url": {"url": "data:image/...;
 base64,..."}}` items, plus `max_tokens`, `temperature`, `seed`, `top_p` and the vLLM extensions `top_k` (-1 / 0 = off) and
-`min_p` (`stream` is not offered); the three filters apply to sampled requests, each request its own.
+`min_p` (`stream` is not offered); the three filters apply to sampled requests, each request its own.  So do HF's `typical_p`,
+`epsilon_cutoff` and `eta_cutoff` (in (0, 1); 1.0 / 0.0 / 0.0 = off; anything else is a 400), behind the three on the device.
 `n` in [1, 16]: that many completions of the prompt, sampled requests only (n > 1 at temperature 0 / absent is a 400, vLLM's rule).
 The prompt is prefilled once and forked on the device (`ze_seq_fork`); the response carries `n` choices with `index` 0 .. n-1, each
 with its own `finish_reason`, `logprobs` and stop-string cut; choice i draws from random stream i of the request's `seed` (choice 0
@@ -115,6 +116,9 @@ class _Parsed:
     top_k: int = 0
     top_p: float = 1.0
     min_p: float = 0.0
+    typical_p: float = 1.0
+    epsilon_cutoff: float = 0.0
+    eta_cutoff: float = 0.0
     logprobs: Optional[int] = None
     prompt_logprobs: Optional[int] = None
     presence_penalty: float = 0.0
@@ -134,6 +138,11 @@ class _Parsed:
 
     def rules(self) -> bool:
         return bool(self.stop or self.stop_token_ids or self.no_repeat_ngram_size)
+
+    def entropy_kw(self) -> dict:
+        """typical_p / epsilon_cutoff / eta_cutoff for generate() or a scheduler Request: the ones that are on."""
+        return {k: v for k, v, off in (("typical_p", self.typical_p, 1.0), ("epsilon_cutoff", self.epsilon_cutoff, 0.0),
+                                       ("eta_cutoff", self.eta_cutoff, 0.0)) if v != off}
 
     def adjusts(self) -> bool:
         """The request carries values generate() gives every row of a call alike: it runs alone, or through the dispatcher."""
@@ -224,6 +233,16 @@ class ChatServer:
         if not (0.0 <= p.min_p <= 1.0):
             raise BadRequest(f"min_p must be in [0, 1], got {p.min_p}")
         p.top_k = max(p.top_k, 0)
+        # HF's entropy-adaptive cutoffs under HF's names (vLLM's `typical_p` too): 1.0 / 0.0 / 0.0 = off
+        for name, off in (("typical_p", 1.0), ("epsilon_cutoff", 0.0), ("eta_cutoff", 0.0)):
+            v = req.get(name)
+            if v is None:
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise BadRequest(f"{name} must be a number, got {v!r}")
+            if float(v) != off and not (0.0 < float(v) < 1.0):
+                raise BadRequest(f"{name} must be in (0, 1) or {off} (off), got {v}")
+            setattr(p, name, float(v))
         # OpenAI's `logprobs` (bool) and `top_logprobs` (0 .. 20, only with logprobs): None = no block in the response
         lp, top = req.get("logprobs"), req.get("top_logprobs")
         if lp is not None and not isinstance(lp, bool):
@@ -431,6 +450,7 @@ class ChatServer:
             kw = dict(max_new_tokens=max(p.max_tokens for p in batch), num_beams=1, do_sample=p0.sample)
             if p0.sample:
                 kw.update(temperature=p0.temperature, top_k=p0.top_k, top_p=p0.top_p, min_p=p0.min_p, seed=p0.seed)
+                kw.update(p0.entropy_kw())
             if p0.repetition_penalty is not None:
                 kw.update(repetition_penalty=p0.repetition_penalty)
             kw.update(p0.adjust_kw(self.processor.tokenizer))
@@ -521,7 +541,7 @@ class ChatServer:
                 p.future.set_exception(ex)
 
         own = dict(do_sample=True, temperature=p.temperature, seed=p.seed, stream_id=0, top_k=p.top_k, top_p=p.top_p,
-                   min_p=p.min_p) if p.sample else {}
+                   min_p=p.min_p, **p.entropy_kw()) if p.sample else {}
         if p.repetition_penalty is not None:
             own["repetition_penalty"] = p.repetition_penalty
         return Request(prompt=p.prompt, images=[DeviceImage.from_pil(im, self.model.engine) for im in p.pil_images],
