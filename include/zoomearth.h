@@ -873,6 +873,10 @@ int ze_op_decode_rows(ze_engine* e, int seq, const int32_t* tokens, int r, float
  * qkv_bf16 [n, (heads + 2 kv_heads) x 128] = the chains' projections after ze_op_rope_kv_decode (their k / v are row ctx of the
  * cache); out_bf16 [n, heads x 128] = softmax(q K^T / sqrt(128)) V over rows 0 .. ctx, per head, with the step's own kernel. */
 int ze_op_attn_decode(ze_engine* e, const int32_t* seqs, int n, int layer, const void* qkv_bf16, void* out_bf16, void* stream);
+/* The attention of the SINGLE-CHAIN decode step (ze_decode_step / ze_generate), alone: the same operation on one chain through the
+ * step's own launch -- no chain table, the chain's own device state, the 64-token-slice kernel in its single-chain instantiation.
+ * qkv_bf16 [(heads + 2 kv_heads) x 128] (the q part is read), out_bf16 [heads x 128]; rows 0 .. ctx of `layer`'s cache of `seq`. */
+int ze_op_attn_decode_single(ze_engine* e, int seq, int layer, const void* qkv_bf16, void* out_bf16, void* stream);
 /* ONE launch of the single-chain decode GEMV family (K16-K22 at one token per step: the kernel that streams every decoder weight
  * once per token), alone, on device operands: out[N] = W[N, K] . x[K] with the prologue and epilogue of the decode step.
  *   W       w_bf16 [N, K] bf16, or -- w8 non-null -- the FP8 stream: w8 u8 [N, K] E4M3 bytes and scale8 f32 [N] as ze_op_quantize_fp8

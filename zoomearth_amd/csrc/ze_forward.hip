@@ -1024,6 +1024,17 @@ extern "C" int ze_score_batch_detail(ze_engine* e, const int32_t* seqs, int n, c
 }
 
 // ================================================================== decode
+// decode attention of the single-chain step: no chain table, the chain's own device state, the <24, 1> instantiation of the
+// slice kernel (ze_attn_decode.hip) over rows 0 .. ctx of the chain's cache
+// (q_row / out_row: the step's own buffers, or the caller's -- ze_op_attn_decode_single)
+static void launch_step_attention(ze_engine* e, int li, int seq, hipStream_t s, const bf16_t* q_row = nullptr, bf16_t* out_row = nullptr) {
+    const ze_config& c = e->cfg;
+    const int hd = e->head_dim;
+    const float scale = 1.0f / sqrtf((float)hd);
+    ze_launch_attn_decode(q_row ? q_row : e->dq, 0, e->kc(li, seq), e->vc(li, seq), 0, out_row ? out_row : e->dattn, 0, e->st_dev + seq,
+                          nullptr, 1, c.heads, c.kv_heads, hd, c.max_ctx, scale, e->dpartial, e->max_splits, e->atickets, s);
+}
+
 // One token for chain `seq`: everything is read from the device-side chain state, so the same launch
 // sequence can be captured once into a hipGraph and replayed.
 static int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int ignore_eos, bool sample, const ze_sample_opts& so,
@@ -1031,7 +1042,6 @@ static int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int igno
     const ze_config& c = e->cfg;
     const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nqkv = nq + 2 * c.kv_heads * hd;
     const ze_seq_dev* st = e->st_dev + seq;
-    const float scale = 1.0f / sqrtf((float)hd);
     for (int li = 0; li < c.layers; ++li) {
         const ze_text_layer& L = e->tl[li];
         ze_gemv_args a = gemv_args_of(e, L.qkv, nqkv, H, e->dh);
@@ -1053,8 +1063,7 @@ static int ze_enqueue_decode_step(ze_engine* e, int seq, float penalty, int igno
             a.embed_out = e->dh;
         }
         ze_launch_gemv(ZE_GV_QKV_ROPE, a, s);
-        ze_launch_attn_decode(e->dq, 0, e->kc(li, seq), e->vc(li, seq), 0, e->dattn, 0, st, nullptr, 1, c.heads,
-                              c.kv_heads, hd, c.max_ctx, scale, e->dpartial, e->max_splits, e->atickets, s);
+        launch_step_attention(e, li, seq, s);
         ze_gemv_args o = gemv_args_of(e, L.o, H, nq, e->dattn);
         o.out_bf16 = e->dh;
         ze_launch_gemv(ZE_GV_RESIDUAL, o, s);
@@ -2595,6 +2604,19 @@ extern "C" int ze_op_attn_decode(ze_engine* e, const int32_t* seqs, int n, int l
     sync_prefix(e, seqs, n, s);
     set_live_parts(e, seqs, n, 1);
     launch_batch_attention(e, layer, n, false, s, (const bf16_t*)qkv_bf16, (bf16_t*)out_bf16);
+    ZE_KCHECK();
+    return ZE_OK;
+}
+// The attention of the SINGLE-CHAIN decode step, alone: the step's own launch (launch_step_attention) on the caller's row -- qkv_bf16
+// [(heads + 2 kv_heads) x 128] as ze_op_rope_kv_decode / ze_op_mrope_kv left it, of which the q part is read -- over rows 0 .. ctx of
+// `layer`'s cache of chain `seq`; out_bf16 [heads x 128].  Chain state is not advanced.
+extern "C" int ze_op_attn_decode_single(ze_engine* e, int seq, int layer, const void* qkv_bf16, void* out_bf16, void* stream) {
+    ZE_TRY(check_seq(e, seq));
+    if (!qkv_bf16 || !out_bf16 || layer < 0 || layer >= e->cfg.layers) return ze_fail(e, ZE_ERR_INVALID, "bad attn_decode_single arguments");
+    if (e->head_dim != 128) return ze_fail(e, ZE_ERR_INVALID, "the decode attention needs 128-wide heads");
+    if (e->ctx_host[seq] + 1 > e->cfg.max_ctx) return ze_fail(e, ZE_ERR_NOMEM, "sequence exceeds max_ctx");
+    hipSetDevice(e->device);
+    launch_step_attention(e, layer, seq, (hipStream_t)stream, (const bf16_t*)qkv_bf16, (bf16_t*)out_bf16);
     ZE_KCHECK();
     return ZE_OK;
 }

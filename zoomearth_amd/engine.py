@@ -1206,6 +1206,14 @@ class Engine:
         self._check(self.lib.ze_op_attn_decode(self.h, sp, len(sq), layer, _ptr(qkv), _ptr(out), self._stream()))
         return out
 
+    def op_attn_decode_single(self, seq: int, layer: int, qkv: torch.Tensor) -> torch.Tensor:
+        """the attention of the single-chain decode step, alone: one chain's qkv row [(heads + 2 kv_heads) x 128] -> [heads x 128]"""
+        t = self.config.text
+        assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and qkv.numel() == (t.num_attention_heads + 2 * t.num_key_value_heads) * 128
+        out = torch.empty((t.hidden_size,), dtype=torch.bfloat16, device=self.device)
+        self._check(self.lib.ze_op_attn_decode_single(self.h, int(seq), int(layer), _ptr(qkv), _ptr(out), self._stream()))
+        return out
+
     def op_kv_read(self, seq: int, layer: int, start: int, n: int):
         t = self.config.text
         shape = (t.num_key_value_heads, n, t.hidden_size // t.num_attention_heads)
