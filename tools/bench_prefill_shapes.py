@@ -16,7 +16,9 @@ for kv in (sys.argv[1].split(",") if len(sys.argv) > 1 else []):
 LLM = [("qkv", 2560, 2048, 0), ("o", 2048, 2048, 0), ("gate_up", 22016, 2048, 4), ("down", 2048, 11008, 0)]
 VIT = [("v.qkv", 3840, 1280, 0), ("v.proj", 1280, 1280, 0), ("v.gate_up", 6912, 1280, 4), ("v.down", 1280, 3456, 0)]
 tot = {}
-for group, rows in ((LLM, (1024, 1820, 2304, 3072, 4096, 6144)), (VIT, (1296, 2592, 5184, 12960))):
+# (256 rows: the 64 x 64 ring tiles of qkv / o / down; 12288: o on the 256 x 256 two-stage ring, 384 tiles -- the branches of
+#  ze_launch_gemm's policy the stream's row counts do not reach)
+for group, rows in ((LLM, (256, 1024, 1820, 2304, 3072, 4096, 6144, 12288)), (VIT, (1296, 2592, 5184, 12960))):
     for m in rows:
         line, t_all, f_all = [], 0.0, 0.0
         for name, n, k, act in group:

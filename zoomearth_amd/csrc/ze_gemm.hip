@@ -1169,17 +1169,71 @@ __global__ void __launch_bounds__(512) k_gemm_p8(const bf16_t* __restrict__ A, i
     }
 }
 
-static void launch_p8(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, const bf16_t* R, int ldr,
-                      bf16_t* C, int ldc, const int* c_rows, int M, int N, int K, hipStream_t s, int ksplit = 1,
-                      const ze_gemm_ws& ws = ze_gemm_ws()) {
+// ----------------------------------------------------------------------------------------------------------------
+// Host side.  The operands of one GEMM travel as ONE struct: every public ze_launch_gemm* entry builds it once from its
+// arguments, every launch_* below takes it by reference plus what it decides itself (a slice count, a row block).
+struct gemm_call {
+    int epi;
+    const bf16_t* A;
+    int lda;
+    const bf16_t* W;
+    int ldw;
+    const bf16_t *bias, *R;
+    int ldr;
+    bf16_t* C;
+    int ldc;
+    const int* c_rows;
+    int M, N, K;
+    hipStream_t s;
+    ze_gemm_ws ws;  // the calling engine's split-K workspace (fp32 slabs + per-tile tickets); empty = none
+};
+static gemm_call no_ws(gemm_call c) {
+    c.ws = ze_gemm_ws();
+    return c;
+}
+
+static int ze_cu_count() {
     static int cus = 0;
     if (!cus) {
         int dev = 0;
         hipGetDevice(&dev);
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        cus = std::max(8, cus / 8 * 8);  // (a multiple of 8: a persistent workgroup's tiles keep its XCD label)
     }
-    const int tiles = ze_cdiv(M, 256) * ze_cdiv(N, 256);
+    return cus;
+}
+
+// The one launch site of every kernel form.  lds_attr = the dynamic-LDS ceiling of this kernel instantiation, raised once per
+// process before its first launch (the launch's own LDS size everywhere but launch_frag_mt); 0 = no attribute call.
+template <auto Kernel>
+static bool lds_attr_set = false;
+template <auto Kernel, class... Args>
+static void launch_lds(dim3 grid, dim3 block, size_t lds, size_t lds_attr, hipStream_t s, Args... args) {
+    if (lds_attr && !lds_attr_set<Kernel>) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_attr);
+        lds_attr_set<Kernel> = true;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+}
+
+// The runtime epilogue as a compile-time constant, over the list the call site names -- exactly those kernels get instantiated:
+// f(std::integral_constant<int, E>) for the E that equals epi; false = epi is not in the list, nothing ran.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <int... Es, class F>
+static bool dispatch_epi(int epi, F&& f) {
+    return ((epi == Es ? (f(int_c<Es>()), true) : false) || ...);
+}
+// rows of a skinny launch -> 16-row tiles per workgroup, MT = 1 / 2 / 4
+template <class F>
+static void dispatch_mt(int M, F&& f) {
+    if (M <= 16) f(int_c<1>());
+    else if (M <= 32) f(int_c<2>());
+    else f(int_c<4>());
+}
+
+static void launch_p8(const gemm_call& c, int ksplit = 1) {
+    const int cus = std::max(8, ze_cu_count() / 8 * 8);  // (a multiple of 8: a persistent workgroup's tiles keep its XCD label)
+    const int tiles = ze_cdiv(c.M, 256) * ze_cdiv(c.N, 256);
     // Persistent workgroups (a tile's first half-tiles requested behind the previous tile's epilogue) -- unless several engines
     // share the GPU (lanes: knob 4 = 1, set by clone_lane / bench.py): a persistent launch holds every CU's LDS until its LAST tile
     // is done, and the other lane's decode kernels wait for all of it (the o projection's 200 workgroups averaged 127 us in the
@@ -1193,41 +1247,21 @@ static void launch_p8(int epi, const bf16_t* A, int lda, const bf16_t* W, int ld
     const int grid = (ze_gemv_knobs[7] == 9 || shared_gpu) ? units : std::min(units, cus);
     // the wide-store epilogue (p8_finish_wide: 16-byte row pieces through 4 KB of LDS per wave) wherever rows are 16-byte
     // aligned; knob 7 = 10: the plain two-byte epilogue, for A/B runs and the bit-equality test
-    const bool sw = epi == ZE_EPI_SWIGLU;
-    const bool wide = ze_gemv_knobs[7] != 10 && (ldc % 8) == 0 && ((size_t)C % 16) == 0 && ((sw ? N / 2 : N) % 8) == 0 &&
-                      (epi != ZE_EPI_RESIDUAL || ((ldr % 8) == 0 && ((size_t)R % 16) == 0));
+    const bool sw = c.epi == ZE_EPI_SWIGLU;
+    const bool wide = ze_gemv_knobs[7] != 10 && (c.ldc % 8) == 0 && ((size_t)c.C % 16) == 0 && ((sw ? c.N / 2 : c.N) % 8) == 0 &&
+                      (c.epi != ZE_EPI_RESIDUAL || ((c.ldr % 8) == 0 && ((size_t)c.R % 16) == 0));
     const size_t lds = wide ? (128 + 32) * 1024 : (128 + 1) * 1024;   // (+ 1 KB: the split-K flag lives behind the K-tile buffers)
     // the blocked walk of the tile grid (k_gemm_p8: `place`): 8 x 4 blocks; knob 21 = 1: the column walk of rounds 3-4, any other
     // value v > 1: blocks of (v >> 8) x (v & 255)
     const int blk = ze_gemv_knobs[21] == 1 ? 0 : (ze_gemv_knobs[21] > 1 ? ze_gemv_knobs[21] : ((8 << 8) | 4));
-#define ZE_P8_LAUNCH(E, WD)                                                                                                    \
-    do {                                                                                                                       \
-        static bool attr_set = false;                                                                                          \
-        if (!attr_set) {                                                                                                       \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_p8<E, WD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            attr_set = true;                                                                                                   \
-        }                                                                                                                      \
-        hipLaunchKernelGGL((k_gemm_p8<E, WD>), dim3(grid), dim3(512), lds, s, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, blk, \
-                           std::max(1, ksplit), ws.slab, ws.tickets);                                                          \
-    } while (0)
-    if (wide) {
-        switch (epi) {
-            case ZE_EPI_NONE: ZE_P8_LAUNCH(ZE_EPI_NONE, true); break;
-            case ZE_EPI_GELU: ZE_P8_LAUNCH(ZE_EPI_GELU, true); break;
-            case ZE_EPI_RESIDUAL: ZE_P8_LAUNCH(ZE_EPI_RESIDUAL, true); break;
-            case ZE_EPI_SWIGLU: ZE_P8_LAUNCH(ZE_EPI_SWIGLU, true); break;
-            case ZE_EPI_F32: ZE_P8_LAUNCH(ZE_EPI_F32, true); break;
-        }
-        return;
-    }
-    switch (epi) {
-        case ZE_EPI_NONE: ZE_P8_LAUNCH(ZE_EPI_NONE, false); break;
-        case ZE_EPI_GELU: ZE_P8_LAUNCH(ZE_EPI_GELU, false); break;
-        case ZE_EPI_RESIDUAL: ZE_P8_LAUNCH(ZE_EPI_RESIDUAL, false); break;
-        case ZE_EPI_SWIGLU: ZE_P8_LAUNCH(ZE_EPI_SWIGLU, false); break;
-        case ZE_EPI_F32: ZE_P8_LAUNCH(ZE_EPI_F32, false); break;
-    }
-#undef ZE_P8_LAUNCH
+    auto go = [&](auto E, auto WD) {
+        launch_lds<k_gemm_p8<E, WD>>(dim3(grid), dim3(512), lds, lds, c.s, c.A, c.lda, c.W, c.ldw, c.bias, c.R, c.ldr, c.C, c.ldc, c.c_rows,
+                                     c.M, c.N, c.K, blk, std::max(1, ksplit), c.ws.slab, c.ws.tickets);
+    };
+    dispatch_epi<ZE_EPI_NONE, ZE_EPI_GELU, ZE_EPI_RESIDUAL, ZE_EPI_SWIGLU, ZE_EPI_F32>(c.epi, [&](auto E) {
+        if (wide) go(E, std::true_type());
+        else go(E, std::false_type());
+    });
 }
 
 // ----------------------------------------------------------------------------------------------------------------
@@ -1409,34 +1443,19 @@ __global__ void __launch_bounds__(512) k_gemm_wstream(const bf16_t* __restrict__
 }
 
 template <int BM, int BN, int SA, int DW, int NK, int E>
-static void launch_wstream_one(const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, const bf16_t* R, int ldr,
-                               bf16_t* C, int ldc, int M, int N, int K, int ksplit, const ze_gemm_ws& ws, hipStream_t s) {
-    const int grid = ze_cdiv(N, BN) * ksplit;
+static void launch_wstream_one(const gemm_call& c, int ksplit) {
+    const int grid = ze_cdiv(c.N, BN) * ksplit;
     const size_t lds = (size_t)SA * BM * 128 + (size_t)2 * BN * 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_wstream<BM, BN, SA, DW, NK, E>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((k_gemm_wstream<BM, BN, SA, DW, NK, E>), dim3(grid), dim3(512), lds, s, A, lda, W, ldw, bias, R, ldr, C,
-                       ldc, M, N, K, ksplit, ws.slab, ws.tickets);
+    launch_lds<k_gemm_wstream<BM, BN, SA, DW, NK, E>>(dim3(grid), dim3(512), lds, lds, c.s, c.A, c.lda, c.W, c.ldw, c.bias, c.R, c.ldr,
+                                                      c.C, c.ldc, c.M, c.N, c.K, ksplit, c.ws.slab, c.ws.tickets);
 }
 
 // The one-pass instances (gate/up with SwiGLU, the lm_head, plain) at the K-step count of the 3B hidden size (K = 2048);
 // false = no instance for this shape (the caller falls back to the ring kernels, which give the same bits).
 template <int BM, int BN, int SA, int DW>
-static bool launch_wstream(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, const bf16_t* R,
-                           int ldr, bf16_t* C, int ldc, int M, int N, int K, const ze_gemm_ws& ws, hipStream_t s) {
-    if (K / GEMM_BK != 32) return false;
-#define ZE_WS_ONE(NK, E) \
-    launch_wstream_one<BM, BN, SA, DW, NK, E>(A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, 1, ws, s); \
-    return true
-    if (epi == ZE_EPI_SWIGLU) { ZE_WS_ONE(32, ZE_EPI_SWIGLU); }
-    if (epi == ZE_EPI_F32) { ZE_WS_ONE(32, ZE_EPI_F32); }
-    if (epi == ZE_EPI_NONE) { ZE_WS_ONE(32, ZE_EPI_NONE); }
-#undef ZE_WS_ONE
-    return false;
+static bool launch_wstream(const gemm_call& c) {
+    if (c.K / GEMM_BK != 32) return false;
+    return dispatch_epi<ZE_EPI_SWIGLU, ZE_EPI_F32, ZE_EPI_NONE>(c.epi, [&](auto E) { launch_wstream_one<BM, BN, SA, DW, 32, E>(c, 1); });
 }
 
 // ----------------------------------------------------------------------------------------------------------------
@@ -1580,28 +1599,29 @@ __global__ void __launch_bounds__(64 * WM * WN) k_gemm_ring_mx(const uint8_t* __
     gemm_finish<BM, BN, EPI, WM, WN>(acc, smem, bias, R, ldr, C, ldc, nullptr, M, N, 1, 0, bid, nwg, bm0, bn0, nullptr, nullptr);
 }
 
+// the operands of the block-scaled form: E4M3 bytes and a power-of-two scale per row of each; no residual, no split K
+struct gemm_mx_call {
+    int epi;
+    const uint8_t* A;
+    int lda;
+    const float* sa;
+    const uint8_t* W;
+    int ldw;
+    const float* sw;
+    const bf16_t* bias;
+    bf16_t* C;
+    int ldc;
+    int M, N, K;
+    hipStream_t s;
+};
 template <int BM, int BN, int ST>
-static void launch_ring_mx(int epi, const uint8_t* A, int lda, const float* sa, const uint8_t* W, int ldw, const float* sw,
-                           const bf16_t* bias, const bf16_t* R, int ldr, bf16_t* C, int ldc, int M, int N, int K, hipStream_t s) {
-    const int grid = ze_cdiv(M, BM) * ze_cdiv(N, BN);
+static void launch_ring_mx(const gemm_mx_call& c) {
+    const int grid = ze_cdiv(c.M, BM) * ze_cdiv(c.N, BN);
     const size_t lds = (size_t)(BM + BN) * 128 * ST;
-#define ZE_MX_LAUNCH(E)                                                                                              \
-    do {                                                                                                             \
-        static bool attr_set = false;                                                                                \
-        if (!attr_set) {                                                                                             \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ring_mx<BM, BN, ST, E, 2, 4>),                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-            attr_set = true;                                                                                         \
-        }                                                                                                            \
-        hipLaunchKernelGGL((k_gemm_ring_mx<BM, BN, ST, E, 2, 4>), dim3(grid), dim3(512), lds, s, A, lda, sa, W, ldw, \
-                           sw, bias, R, ldr, C, ldc, M, N, K);                                                       \
-    } while (0)
-    switch (epi) {
-        case ZE_EPI_NONE: ZE_MX_LAUNCH(ZE_EPI_NONE); break;
-        case ZE_EPI_SWIGLU: ZE_MX_LAUNCH(ZE_EPI_SWIGLU); break;
-        default: break;
-    }
-#undef ZE_MX_LAUNCH
+    dispatch_epi<ZE_EPI_NONE, ZE_EPI_SWIGLU>(c.epi, [&](auto E) {
+        launch_lds<k_gemm_ring_mx<BM, BN, ST, E, 2, 4>>(dim3(grid), dim3(512), lds, lds, c.s, c.A, c.lda, c.sa, c.W, c.ldw, c.sw, c.bias,
+                                                        nullptr, 0, c.C, c.ldc, c.M, c.N, c.K);
+    });
 }
 
 // C = (A8 2^ka) (W8 2^kw)^T (+ bias) (+ SwiGLU): epi NONE or SWIGLU; K a multiple of 128, lda / ldw even.  Tiles as in the
@@ -1610,16 +1630,12 @@ bool ze_launch_gemm_mx(int epi, const uint8_t* A, int lda, const float* sa, cons
                        const bf16_t* bias, bf16_t* C, int ldc, int M, int N, int K, hipStream_t s) {
     if (M <= 0 || N <= 0) return true;
     if (K % 128 != 0 || K / 128 < 2 || (lda & 15) || (ldw & 15) || (epi != ZE_EPI_NONE && epi != ZE_EPI_SWIGLU)) return false;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
+    const gemm_mx_call c{epi, A, lda, sa, W, ldw, sw, bias, C, ldc, M, N, K, s};
+    const int cus = ze_cu_count();
     const int grid4 = ze_cdiv(M, 256) * ze_cdiv(N, 256);
     const bool big = (2 * grid4 >= 3 * cus) || (grid4 <= cus && 10 * grid4 >= 9 * cus);
-    if (big) launch_ring_mx<256, 256, 2>(epi, A, lda, sa, W, ldw, sw, bias, nullptr, 0, C, ldc, M, N, K, s);
-    else launch_ring_mx<128, 256, 3>(epi, A, lda, sa, W, ldw, sw, bias, nullptr, 0, C, ldc, M, N, K, s);
+    if (big) launch_ring_mx<256, 256, 2>(c);
+    else launch_ring_mx<128, 256, 3>(c);
     return true;
 }
 
@@ -1852,62 +1868,38 @@ __global__ void __launch_bounds__(256) k_gemm_skinny(const bf16_t* __restrict__ 
 }
 
 // The split-K workspace (fp32 slabs + per-tile tickets) belongs to the calling engine and travels with every call
-// (ze_gemm_ws); the launch macros below name its two pointers g_slab / g_tickets.
+// (ze_gemm_ws, a member of gemm_call).
 // one ring instantiation, every epilogue
 template <int BM, int BN, int ST, int WM, int WN, bool SPR, bool WIDE = false, bool QKV = false, int BK = GEMM_BK, int KPB = 1>
-static void launch_ring_variant(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias,
-                                const bf16_t* R, int ldr, bf16_t* C, int ldc, const int* c_rows, int M, int N, int K,
-                                hipStream_t s, int ksplit = 1, const ze_gemm_ws& ws = ze_gemm_ws()) {
-    float* g_slab = ws.slab;
-    unsigned* g_tickets = ws.tickets;
-    const int grid = ze_cdiv(M, BM) * ze_cdiv(N, BN) * ksplit;
+static void launch_ring_variant(const gemm_call& c, int ksplit = 1) {
+    const int grid = ze_cdiv(c.M, BM) * ze_cdiv(c.N, BN) * ksplit;
     const size_t lds = (size_t)(BM + BN) * BK * 2 * ST;
-#define ZE_RINGV_LAUNCH(E)                                                                                          \
-    do {                                                                                                            \
-        static bool attr_set = false;                                                                               \
-        if (!attr_set) {                                                                                            \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ring<BM, BN, ST, E, WM, WN, SPR, WIDE, BK, KPB>),  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                              \
-            attr_set = true;                                                                                        \
-        }                                                                                                           \
-        hipLaunchKernelGGL((k_gemm_ring<BM, BN, ST, E, WM, WN, SPR, WIDE, BK, KPB>), dim3(grid), dim3(64 * WM * WN), lds, s, A, \
-                           lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, ksplit, g_slab, g_tickets);          \
-    } while (0)
+    auto go = [&](auto E) {
+        launch_lds<k_gemm_ring<BM, BN, ST, E, WM, WN, SPR, WIDE, BK, KPB>>(dim3(grid), dim3(64 * WM * WN), lds, lds, c.s, c.A, c.lda, c.W, c.ldw,
+                                                                         c.bias, c.R, c.ldr, c.C, c.ldc, c.c_rows, c.M, c.N, c.K, ksplit,
+                                                                         c.ws.slab, c.ws.tickets);
+    };
     if constexpr (QKV) {   // (the decode step's qkv projection with rope + KV append)
-        if (epi == ZE_EPI_QKV_ROPE) ZE_RINGV_LAUNCH(ZE_EPI_QKV_ROPE);
-    } else if constexpr (WIDE) {  // the wide-store epilogue (gemm_finish LDS_EPI): 16-byte row pieces through the idle staging LDS
-        switch (epi) {
-            case ZE_EPI_NONE: ZE_RINGV_LAUNCH(ZE_EPI_NONE); break;
-            case ZE_EPI_GELU: ZE_RINGV_LAUNCH(ZE_EPI_GELU); break;
-            case ZE_EPI_RESIDUAL: ZE_RINGV_LAUNCH(ZE_EPI_RESIDUAL); break;
-            case ZE_EPI_SWIGLU: ZE_RINGV_LAUNCH(ZE_EPI_SWIGLU); break;
-            case ZE_EPI_F32: ZE_RINGV_LAUNCH(ZE_EPI_F32); break;
-        }
+        dispatch_epi<ZE_EPI_QKV_ROPE>(c.epi, go);
     } else {
-        // Every caller without a row scatter and with 16-byte-aligned rows takes the wide-store instantiation of the same tile
-        // (round 4: the two-byte stores of the plain epilogue were a fifth of a 256 x 256 tile's time at K = 1280; same values,
-        // same roundings: the same bits).  knob 7 = 10: plain epilogue everywhere, for A/B runs.  Not for slab-only split-K
-        // launches (no epilogue runs) and not where the staged tile would not fit the ring's LDS.
-        {
-            const bool sw = epi == ZE_EPI_SWIGLU, f32 = epi == ZE_EPI_F32;
+        if constexpr (!WIDE) {
+            // Every caller without a row scatter and with 16-byte-aligned rows takes the wide-store instantiation of the same tile
+            // (WIDE: the wide-store epilogue, gemm_finish LDS_EPI: 16-byte row pieces through the idle staging LDS)
+            // (round 4: the two-byte stores of the plain epilogue were a fifth of a 256 x 256 tile's time at K = 1280; same values,
+            // same roundings: the same bits).  knob 7 = 10: plain epilogue everywhere, for A/B runs.  Not for slab-only split-K
+            // launches (no epilogue runs) and not where the staged tile would not fit the ring's LDS.
+            const bool sw = c.epi == ZE_EPI_SWIGLU, f32 = c.epi == ZE_EPI_F32;
             const size_t stage_b = (size_t)BM * ((sw ? BN / 2 : BN) * (f32 ? 4 : 2) + 16);
-            const bool wide_ok = ze_gemv_knobs[7] != 10 && c_rows == nullptr && !(ksplit > 1 && g_tickets == nullptr) && stage_b <= lds &&
-                                 (ldc % 8) == 0 && ((size_t)C % 16) == 0 && ((sw ? N / 2 : N) % 8) == 0 && (!sw || BN % 32 == 0) &&
-                                 (epi != ZE_EPI_RESIDUAL || ((ldr % 8) == 0 && ((size_t)R % 16) == 0)) && epi != ZE_EPI_QKV_ROPE;
+            const bool wide_ok = ze_gemv_knobs[7] != 10 && c.c_rows == nullptr && !(ksplit > 1 && c.ws.tickets == nullptr) && stage_b <= lds &&
+                                 (c.ldc % 8) == 0 && ((size_t)c.C % 16) == 0 && ((sw ? c.N / 2 : c.N) % 8) == 0 && (!sw || BN % 32 == 0) &&
+                                 (c.epi != ZE_EPI_RESIDUAL || ((c.ldr % 8) == 0 && ((size_t)c.R % 16) == 0)) && c.epi != ZE_EPI_QKV_ROPE;
             if (wide_ok) {
-                launch_ring_variant<BM, BN, ST, WM, WN, SPR, true, false, BK, KPB>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, ksplit, ws);
+                launch_ring_variant<BM, BN, ST, WM, WN, SPR, true, false, BK, KPB>(c, ksplit);
                 return;
             }
         }
-        switch (epi) {
-            case ZE_EPI_NONE: ZE_RINGV_LAUNCH(ZE_EPI_NONE); break;
-            case ZE_EPI_GELU: ZE_RINGV_LAUNCH(ZE_EPI_GELU); break;
-            case ZE_EPI_RESIDUAL: ZE_RINGV_LAUNCH(ZE_EPI_RESIDUAL); break;
-            case ZE_EPI_SWIGLU: ZE_RINGV_LAUNCH(ZE_EPI_SWIGLU); break;
-            case ZE_EPI_F32: ZE_RINGV_LAUNCH(ZE_EPI_F32); break;
-        }
+        dispatch_epi<ZE_EPI_NONE, ZE_EPI_GELU, ZE_EPI_RESIDUAL, ZE_EPI_SWIGLU, ZE_EPI_F32>(c.epi, go);
     }
-#undef ZE_RINGV_LAUNCH
 }
 
 // Round 6, BUILT, MEASURED, NOT SHIPPED (default off; knob 20 = 3 turns it on for A/B runs and its bit-equality test):
@@ -1935,32 +1927,31 @@ static int ze_prefill_split_dropped(int M, int N, int K, int ksplit) {
     return 1;
 }
 
+// the slice count of the weight-streaming split (launch_cfg, stream mode; launch_splitk_two): a function of (N, K) alone -- on tiles
+// BN = 64 columns wide, the only ones stream mode runs on
+static int stream_ksplit(int N, int K, int BN = 64) {
+    int ksplit = 1;
+    const int nk = ze_cdiv(K, GEMM_BK), tiles_n = ze_cdiv(N, BN);
+    while (tiles_n * ksplit < 200 && ksplit < 8 && nk / (ksplit * 2) >= 4) ksplit *= 2;
+    return ksplit;
+}
+
 template <int BM, int BN>
-static void launch_cfg(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias,
-                       const bf16_t* R, int ldr, bf16_t* C, int ldc, const int* c_rows, int M, int N, int K,
-                       hipStream_t s, bool stream_mode, const ze_gemm_ws& ws = ze_gemm_ws()) {
-    float* g_slab = ws.slab;
-    unsigned* g_tickets = ws.tickets;
-    const size_t g_slab_floats = ws.slab_floats;
-    const int g_ticket_cap = ws.ticket_cap;
+static void launch_cfg(const gemm_call& c, bool stream_mode) {
+    const int M = c.M, N = c.N, K = c.K;
+    const ze_gemm_ws& ws = c.ws;
     const int nwg = ze_cdiv(M, BM) * ze_cdiv(N, BN);
     // Split K only in weight-streaming mode (batched decode, few rows): the slice count is a function of (N, K)
     // alone -- computed for ONE row tile -- so a chain's result never depends on how many chains share the step.
     // Prefill / ViT never split: their accumulation order must not depend on M (prefix-KV reuse is bit-exact).
-    int ksplit = 1;
-    if (stream_mode) {
-        const int nk = ze_cdiv(K, GEMM_BK);
-        const int tiles_n = ze_cdiv(N, BN);
-        while (tiles_n * ksplit < 200 && ksplit < 8 && nk / (ksplit * 2) >= 4) ksplit *= 2;
-    } else {
-        ksplit = ze_prefill_ksplit(K, g_slab != nullptr);   // (round 6) a function of K alone: the same on every tile and kernel
-    }
-    if (ksplit > 1 && (!g_slab || (size_t)ksplit * nwg * BM * BN > g_slab_floats || nwg > g_ticket_cap)) {
+    int ksplit = stream_mode ? stream_ksplit(N, K, BN)
+                             : ze_prefill_ksplit(K, ws.slab != nullptr);   // (round 6) a function of K alone: the same on every tile and kernel
+    if (ksplit > 1 && (!ws.slab || (size_t)ksplit * nwg * BM * BN > ws.slab_floats || nwg > ws.ticket_cap)) {
         // never silently: one slice instead of `ksplit` changes the order of every sum of this projection, i.e. a chain's bits
         // would follow the row count.  An engine sizes its slabs for its max_seqs (ze_engine_create), so this is a caller
         // without a workspace (unit ops) or a bug.
         static bool told = false;
-        if (g_slab && !told) {
+        if (ws.slab && !told) {
             told = true;
             fprintf(stderr, "zoomearth: split-K workspace too small for M=%d N=%d K=%d (ksplit %d -> 1): %s\n", M, N, K, ksplit,
                     stream_mode ? "results no longer batch-invariant" : "this call sums K in one run, engine passes in three slices");
@@ -1971,12 +1962,7 @@ static void launch_cfg(int epi, const bf16_t* A, int lda, const bf16_t* W, int l
     // The ring wins where a launch is at most one round of workgroups (few tiles, long K: o / down / merger / ViT
     // proj, 1.3-1.9x) and loses 15-25 % to the register-staged kernel on grids of many rounds, which hide latency
     // with 2-3 co-resident workgroups per CU instead (qkv, gate/up): measured per shape, tools/bench_gemm.py.
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
+    const int cus = ze_cu_count();
     // (weight-streaming mode, rows = chains of a batched decode step: the ring wins at every grid, 5.04 vs 5.32 ms per
     //  step at 64 chains, 3.78 vs 4.17 at 8)
     // Many-tile grids (128 x 128 policy): eight waves (2 x 4) on the LDS-DMA ring, one workgroup per CU, the refill
@@ -1999,33 +1985,27 @@ static void launch_cfg(int epi, const bf16_t* A, int lda, const bf16_t* W, int l
     // knob 7: 3 = register-staged only, 4 = always 256 x 256, 6 = always 128 x 256.
     if (BM == 128 && BN == 128 && (ksplit == 1 || !stream_mode) && K % GEMM_BK == 0 && K / GEMM_BK >= 4 && ze_gemv_knobs[7] != 3 &&
         ze_gemv_knobs[6] == 0) {
-        static int cus8 = 0;
-        if (!cus8) {
-            int dev = 0;
-            hipGetDevice(&dev);
-            if (hipDeviceGetAttribute(&cus8, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus8 <= 0) cus8 = 256;
-        }
         const int grid4 = ze_cdiv(M, 256) * ze_cdiv(N, 256);
-        const bool big = (2 * grid4 >= 3 * cus8) || (grid4 <= cus8 && 10 * grid4 >= 9 * cus8);
+        const bool big = (2 * grid4 >= 3 * cus) || (grid4 <= cus && 10 * grid4 >= 9 * cus);
         // (the 256 x 256 tile runs on the eight-phase kernel; knob 7 = 4: on the two-stage ring, 8: eight-phase at every grid)
-        const bool p8_ok = (lda % 8) == 0 && (ldw % 8) == 0 && (size_t)M * lda < ((size_t)1 << 31) && (size_t)N * ldw < ((size_t)1 << 31);
+        const bool p8_ok = (c.lda % 8) == 0 && (c.ldw % 8) == 0 && (size_t)M * c.lda < ((size_t)1 << 31) && (size_t)N * c.ldw < ((size_t)1 << 31);
         // its grid against the 128 x 256 ring's, in rounds of workgroups: a 128 x 256 tile takes ~0.6 of a 256 x 256 one
         // (measured on the 3B prefill / ViT shapes at 1-13 K rows, tools/bench_prefill_shapes.py: e.g. 192 tiles of 256 x 256 =
         // 0.75 round beat 384 of 128 x 256 = 2 rounds, 215 against 291 us for down at 6144 rows; 128 tiles lose, 210 against 160)
-        const int r8 = ze_cdiv(grid4, cus8), ra = ze_cdiv(2 * grid4, cus8);
+        const int r8 = ze_cdiv(grid4, cus), ra = ze_cdiv(2 * grid4, cus);
         const bool p8_wins = 10 * r8 <= 6 * ra;
         // (a split K -- ze_prefill_ksplit -- rides along: the slab holds ksplit x M_pad x N_pad floats whatever the tile; the 256 x 256
         //  tiles need their own share of the capacity check above, which was made for BM x BN = 128 x 128)
-        const bool fits256 = ksplit == 1 || ((size_t)ksplit * grid4 * 256 * 256 <= g_slab_floats && grid4 <= g_ticket_cap);
-        const bool fits128x256 = ksplit == 1 || ((size_t)ksplit * ze_cdiv(M, 128) * ze_cdiv(N, 256) * 128 * 256 <= g_slab_floats);
+        const bool fits256 = ksplit == 1 || ((size_t)ksplit * grid4 * 256 * 256 <= ws.slab_floats && grid4 <= ws.ticket_cap);
+        const bool fits128x256 = ksplit == 1 || ((size_t)ksplit * ze_cdiv(M, 128) * ze_cdiv(N, 256) * 128 * 256 <= ws.slab_floats);
         if (fits256 && p8_ok && (ze_gemv_knobs[7] == 8 || ((ze_gemv_knobs[7] == 0 || ze_gemv_knobs[7] == 9) && p8_wins)))
-            launch_p8(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, ksplit, ws);
+            launch_p8(c, ksplit);
         else if (fits256 && (ze_gemv_knobs[7] == 4 || (ze_gemv_knobs[7] != 6 && big)))
-            launch_ring_variant<256, 256, 2, 2, 4, true>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, ksplit, ws);
+            launch_ring_variant<256, 256, 2, 2, 4, true>(c, ksplit);
         else if (fits128x256)
-            launch_ring_variant<128, 256, 3, 2, 4, true>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, ksplit, ws);
+            launch_ring_variant<128, 256, 3, 2, 4, true>(c, ksplit);
         else
-            launch_ring_variant<128, 128, 4, 2, 4, true>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, ksplit, ws);
+            launch_ring_variant<128, 128, 4, 2, 4, true>(c, ksplit);
         return;
     }
     const bool ring = ze_gemv_knobs[6] == 2 || (ze_gemv_knobs[6] == 0 && (grid <= cus || stream_mode));
@@ -2038,7 +2018,7 @@ static void launch_cfg(int epi, const bf16_t* A, int lda, const bf16_t* W, int l
         // issue and LDS latency: o 20.4 -> 16.9 us, down 73.4 -> 62.7 (M = 802), 72.7 -> 58.4 (M = 518), ViT proj
         // 15.6 -> 12.4, ViT down 27.3 -> 22.9, merger 37.9 -> 31.4 (1 x 8 waves and the spread refill are 2-8 % behind)
         if (BM == 64 && BN == 128 && (ksplit == 1 || !stream_mode) && ze_gemv_knobs[7] != 3) {
-            launch_ring_variant<64, 128, 4, 2, 4, false>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, ksplit, ws);
+            launch_ring_variant<64, 128, 4, 2, 4, false>(c, ksplit);
             return;
         }
         // the same on 64 x 64 tiles (4 x 2 waves, 16 x 32 per wave: the SwiGLU epilogue pairs two 16-column tiles of a
@@ -2050,42 +2030,21 @@ static void launch_cfg(int epi, const bf16_t* A, int lda, const bf16_t* W, int l
             // (qkv / o of a decode step -- 128-240 tiles of 32 K-steps, at most one workgroup per CU -- with EIGHT stages, 112 KB in
             //  flight per CU instead of 48: 13.8 against 12.9 us; these launches are bound by the per-step chain wait -> barrier ->
             //  fragment reads -> 4 MFMAs, not by bytes in flight)
-            launch_ring_variant<64, 64, 4, 4, 2, false>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, ksplit, ws);
+            launch_ring_variant<64, 64, 4, 4, 2, false>(c, ksplit);
             return;
         }
-#define ZE_RING_LAUNCH(E)                                                                                              \
-    do {                                                                                                               \
-        static bool attr_set = false;                                                                                  \
-        if (!attr_set) {                                                                                               \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ring<BM, BN, STAGES, E>),                        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ring);                            \
-            attr_set = true;                                                                                           \
-        }                                                                                                              \
-        hipLaunchKernelGGL((k_gemm_ring<BM, BN, STAGES, E>), dim3(grid), dim3(256), lds_ring, s, A, lda, W, ldw, bias, \
-                           R, ldr, C, ldc, c_rows, M, N, K, ksplit, g_slab, g_tickets);                                \
-    } while (0)
-        switch (epi) {
-            case ZE_EPI_NONE: ZE_RING_LAUNCH(ZE_EPI_NONE); break;
-            case ZE_EPI_GELU: ZE_RING_LAUNCH(ZE_EPI_GELU); break;
-            case ZE_EPI_RESIDUAL: ZE_RING_LAUNCH(ZE_EPI_RESIDUAL); break;
-            case ZE_EPI_SWIGLU: ZE_RING_LAUNCH(ZE_EPI_SWIGLU); break;
-            case ZE_EPI_F32: ZE_RING_LAUNCH(ZE_EPI_F32); break;
-        }
-#undef ZE_RING_LAUNCH
+        dispatch_epi<ZE_EPI_NONE, ZE_EPI_GELU, ZE_EPI_RESIDUAL, ZE_EPI_SWIGLU, ZE_EPI_F32>(c.epi, [&](auto E) {
+            launch_lds<k_gemm_ring<BM, BN, STAGES, E>>(dim3(grid), dim3(256), lds_ring, lds_ring, c.s, c.A, c.lda, c.W, c.ldw, c.bias, c.R, c.ldr,
+                                                       c.C, c.ldc, c.c_rows, M, N, K, ksplit, ws.slab, ws.tickets);
+        });
         return;
     }
+    // (the register-staged kernel's two LDS buffers fit the default ceiling: no attribute call)
     const size_t lds = (size_t)2 * (BM + BN) * 8 * 16;
-#define ZE_GEMM_LAUNCH(E)                                                                                          \
-    hipLaunchKernelGGL((k_gemm_tn<BM, BN, E>), dim3(grid), dim3(256), lds, s, A, lda, W, ldw, bias, R, ldr, C, ldc, \
-                       c_rows, M, N, K, ksplit, g_slab, g_tickets)
-    switch (epi) {
-        case ZE_EPI_NONE: ZE_GEMM_LAUNCH(ZE_EPI_NONE); break;
-        case ZE_EPI_GELU: ZE_GEMM_LAUNCH(ZE_EPI_GELU); break;
-        case ZE_EPI_RESIDUAL: ZE_GEMM_LAUNCH(ZE_EPI_RESIDUAL); break;
-        case ZE_EPI_SWIGLU: ZE_GEMM_LAUNCH(ZE_EPI_SWIGLU); break;
-        case ZE_EPI_F32: ZE_GEMM_LAUNCH(ZE_EPI_F32); break;
-    }
-#undef ZE_GEMM_LAUNCH
+    dispatch_epi<ZE_EPI_NONE, ZE_EPI_GELU, ZE_EPI_RESIDUAL, ZE_EPI_SWIGLU, ZE_EPI_F32>(c.epi, [&](auto E) {
+        launch_lds<k_gemm_tn<BM, BN, E>>(dim3(grid), dim3(256), lds, 0, c.s, c.A, c.lda, c.W, c.ldw, c.bias, c.R, c.ldr, c.C, c.ldc, c.c_rows,
+                                         M, N, K, ksplit, ws.slab, ws.tickets);
+    });
 }
 
 // Fragment-major operands, no split-K.  What bounds these launches is the memory traffic a CU can keep in flight
@@ -2096,152 +2055,90 @@ static void launch_cfg(int epi, const bf16_t* A, int lda, const bf16_t* W, int l
 // the finer grid: 24.1 us (26.8 at 64 rows per workgroup, 25.1 at 128, 27 on the ring).  Narrow matrices (qkv) take
 // 16 rows per workgroup so that their grid still covers the chip: 5.5 / 8.1 us at 8 / 64 chains (9.8 / 13.9 row-major,
 // 15 on the ring).  lm_head: 96 us at 8 chains (120 on the ring), 140 at 64 (145).
+struct gemm_frag_call {
+    int epi;
+    const bf16_t *Xf, *Wf, *bias, *R;
+    int ldr;
+    bf16_t* C;
+    int ldc;
+    int M, N, K;
+    hipStream_t s;
+    const float *wscale, *ascale;  // FP8 weight fragments / FP8 activation fragments: the scales per row; null = bf16
+};
 template <int TN, int MT, bool W8 = false, bool A8 = false>
-static void launch_frag_mt(int epi, const bf16_t* Xf, const bf16_t* Wf, const bf16_t* bias, const bf16_t* R, int ldr,
-                        bf16_t* C, int ldc, int M, int N, int K, hipStream_t s, int ksplit, const ze_gemm_ws& ws,
-                        const float* wscale = nullptr, const float* ascale = nullptr) {
-    float* g_slab = ws.slab;
-    unsigned* g_tickets = ws.tickets;
-    const int grid = ze_cdiv(N, 16 * TN) * ksplit;
+static void launch_frag_mt(const gemm_frag_call& c) {
+    const int ksplit = 1;  // (no split-K: no workspace)
+    const int grid = ze_cdiv(c.N, 16 * TN) * ksplit;
     // A grid of at most one workgroup per CU asks for more LDS than half a CU has, so that the dispatcher cannot put
     // two of them on one CU and leave another idle (the launch time is the bytes of the busiest CU).
-    static int cus_f = 0;
-    if (!cus_f) {
-        int dev = 0;
-        hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus_f, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus_f <= 0) cus_f = 256;
-    }
-    const size_t lds = (grid <= cus_f) ? (size_t)96 * 1024 : (size_t)16 * TN * 1024;
+    const size_t lds = (grid <= ze_cu_count()) ? (size_t)96 * 1024 : (size_t)16 * TN * 1024;
     const size_t lds_max = (size_t)96 * 1024;
-#define ZE_FRAG_LAUNCH(E)                                                                                           \
-    do {                                                                                                            \
-        static bool attr_set = false;                                                                               \
-        if (!attr_set) {                                                                                            \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_skinny<TN, E, true, MT, false, W8, A8>),      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);                          \
-            attr_set = true;                                                                                        \
-        }                                                                                                           \
-        hipLaunchKernelGGL((k_gemm_skinny<TN, E, true, MT, false, W8, A8>), dim3(grid), dim3(256), lds, s, Xf, 0,   \
-                           Wf, 0, bias, R, ldr,                                                                     \
-                           C, ldc, M, N, K, ksplit, g_slab, g_tickets, wscale, ascale);                             \
-    } while (0)
+    auto go = [&](auto E) {
+        launch_lds<k_gemm_skinny<TN, E, true, MT, false, W8, A8>>(dim3(grid), dim3(256), lds, lds_max, c.s, c.Xf, 0, c.Wf, 0, c.bias, c.R, c.ldr,
+                                                                  c.C, c.ldc, c.M, c.N, c.K, ksplit, nullptr, nullptr, W8 ? c.wscale : nullptr,
+                                                                  A8 ? c.ascale : nullptr);
+    };
     if constexpr (TN % 2 == 0) {
-        if (epi == ZE_EPI_SWIGLU) {
-            ZE_FRAG_LAUNCH(ZE_EPI_SWIGLU);
-            return;
-        }
+        if (dispatch_epi<ZE_EPI_SWIGLU>(c.epi, go)) return;
     }
     if constexpr (A8) return;  // fp8 activations: gate/up only
-    switch (epi) {
-        case ZE_EPI_NONE: ZE_FRAG_LAUNCH(ZE_EPI_NONE); break;
-        case ZE_EPI_RESIDUAL: ZE_FRAG_LAUNCH(ZE_EPI_RESIDUAL); break;
-        case ZE_EPI_F32: ZE_FRAG_LAUNCH(ZE_EPI_F32); break;
-        default: break;
-    }
-#undef ZE_FRAG_LAUNCH
+    dispatch_epi<ZE_EPI_NONE, ZE_EPI_RESIDUAL, ZE_EPI_F32>(c.epi, go);
 }
 
 template <int TN>
-static void launch_frag(int epi, const bf16_t* Xf, const bf16_t* Wf, const bf16_t* bias, const bf16_t* R, int ldr,
-                        bf16_t* C, int ldc, int M, int N, int K, hipStream_t s, int ksplit = 1,
-                        const ze_gemm_ws& ws = ze_gemm_ws(), const float* wscale = nullptr, const float* ascale = nullptr) {
-    if constexpr (TN == 2) {
-        if (wscale && ascale && epi == ZE_EPI_SWIGLU && ksplit == 1) {  // fp8 x fp8
-            if (M <= 16) launch_frag_mt<TN, 1, true, true>(epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, 1, ws, wscale, ascale);
-            else if (M <= 32) launch_frag_mt<TN, 2, true, true>(epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, 1, ws, wscale, ascale);
-            else launch_frag_mt<TN, 4, true, true>(epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, 1, ws, wscale, ascale);
-            return;
+static void launch_frag(const gemm_frag_call& c) {
+    dispatch_mt(c.M, [&](auto MT) {
+        if constexpr (TN == 2) {
+            if (c.wscale && c.ascale && c.epi == ZE_EPI_SWIGLU) {  // fp8 x fp8
+                launch_frag_mt<TN, MT, true, true>(c);
+                return;
+            }
         }
-    }
-    if (wscale) {  // fp8 fragment stream
-        if (M <= 16) launch_frag_mt<TN, 1, true>(epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, ksplit, ws, wscale);
-        else if (M <= 32) launch_frag_mt<TN, 2, true>(epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, ksplit, ws, wscale);
-        else launch_frag_mt<TN, 4, true>(epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, ksplit, ws, wscale);
-        return;
-    }
-    if (M <= 16) launch_frag_mt<TN, 1>(epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, ksplit, ws);
-    else if (M <= 32) launch_frag_mt<TN, 2>(epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, ksplit, ws);
-    else launch_frag_mt<TN, 4>(epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, ksplit, ws);
+        if (c.wscale) launch_frag_mt<TN, MT, true>(c);  // fp8 fragment stream
+        else launch_frag_mt<TN, MT>(c);
+    });
 }
 
 // gate/up (SwiGLU, wide): one workgroup per CU (or a multiple), each with a balanced range of at most three 32-row
 // pairs and ONE pass over the activations
 template <int MT, bool W8 = false, bool A8 = false>
-static void launch_frag_balanced(const bf16_t* Xf, const bf16_t* Wf, const bf16_t* bias, bf16_t* C, int ldc, int M, int N,
-                                 int K, int grid, hipStream_t s, const float* wscale = nullptr, const float* ascale = nullptr) {
+static void launch_frag_balanced(const gemm_frag_call& c, int grid) {
     const size_t lds = (size_t)16 * 6 * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_skinny<6, ZE_EPI_SWIGLU, true, MT, true, W8, A8>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((k_gemm_skinny<6, ZE_EPI_SWIGLU, true, MT, true, W8, A8>), dim3(grid), dim3(256), lds, s, Xf, 0, Wf, 0,
-                       bias, nullptr, 0, C, ldc, M, N, K, 1, nullptr, nullptr, wscale, ascale);
+    launch_lds<k_gemm_skinny<6, ZE_EPI_SWIGLU, true, MT, true, W8, A8>>(dim3(grid), dim3(256), lds, lds, c.s, c.Xf, 0, c.Wf, 0, c.bias,
+                                                                        nullptr, 0, c.C, c.ldc, c.M, c.N, c.K, 1, nullptr, nullptr,
+                                                                        W8 ? c.wscale : nullptr, A8 ? c.ascale : nullptr);
 }
 
 void ze_launch_gemm_frag(int epi, const bf16_t* Xf, const bf16_t* Wf, const bf16_t* bias, const bf16_t* R, int ldr,
                          bf16_t* C, int ldc, int M, int N, int K, hipStream_t s, const float* wscale, const float* ascale) {
     if (M <= 0 || N <= 0) return;
+    const gemm_frag_call c{epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, wscale, ascale};
     // (more than 32 chains only: below that the activation pass is small and the finer 32-row grid wins, 2.84 against
     //  2.91 ms per step at 8 chains; at 64 chains 3.86 against 3.95.  Both forms add an output's K quarters in the same
     //  order, so the choice does not change a chain's result.)
     if (epi == ZE_EPI_SWIGLU && N > 4096 && N % 32 == 0 && M > 32 && ze_gemv_knobs[5] != 2) {
-        static int cus_b = 0;
-        if (!cus_b) {
-            int dev = 0;
-            hipGetDevice(&dev);
-            if (hipDeviceGetAttribute(&cus_b, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus_b <= 0) cus_b = 256;
-        }
+        const int cus = ze_cu_count();
         const int P = N / 32;
-        const int grid = cus_b * ze_cdiv(P, 3 * cus_b);  // at most three pairs per workgroup
-        if (wscale && ascale) launch_frag_balanced<4, true, true>(Xf, Wf, bias, C, ldc, M, N, K, grid, s, wscale, ascale);
-        else if (wscale) launch_frag_balanced<4, true>(Xf, Wf, bias, C, ldc, M, N, K, grid, s, wscale);
-        else launch_frag_balanced<4>(Xf, Wf, bias, C, ldc, M, N, K, grid, s);
+        const int grid = cus * ze_cdiv(P, 3 * cus);  // at most three pairs per workgroup
+        if (wscale && ascale) launch_frag_balanced<4, true, true>(c, grid);
+        else if (wscale) launch_frag_balanced<4, true>(c, grid);
+        else launch_frag_balanced<4>(c, grid);
         return;
     }
-    if (N <= 4096 && epi != ZE_EPI_SWIGLU)
-        launch_frag<1>(epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, 1, ze_gemm_ws(), wscale);
-    else
-        launch_frag<2>(epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, 1, ze_gemm_ws(), wscale, ascale);
+    if (N <= 4096 && epi != ZE_EPI_SWIGLU) launch_frag<1>(c);
+    else launch_frag<2>(c);
 }
 
 // Batched decode: the skinny kernel when the shape allows (M <= 64, whole MFMA slices), else the ring.
 template <int TN, int MT>
-static void launch_skinny_mt(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, const bf16_t* R,
-                          int ldr, bf16_t* C, int ldc, int M, int N, int K, int ksplit, hipStream_t s) {
-    float* g_slab = nullptr;  // never split: no workspace
-    unsigned* g_tickets = nullptr;
-    const int grid = ze_cdiv(N, 16 * TN) * ksplit;
+static void launch_skinny_mt(const gemm_call& c, int ksplit) {
+    const int grid = ze_cdiv(c.N, 16 * TN) * ksplit;
     const size_t lds = (size_t)16 * TN * 1024;
-#define ZE_SKINNY_LAUNCH(E)                                                                                        \
-    do {                                                                                                           \
-        static bool attr_set = false;                                                                              \
-        if (!attr_set) {                                                                                           \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_skinny<TN, E, false, MT>),                   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                             \
-            attr_set = true;                                                                                       \
-        }                                                                                                          \
-        hipLaunchKernelGGL((k_gemm_skinny<TN, E, false, MT>), dim3(grid), dim3(256), lds, s, A, lda, W, ldw, bias,  \
-                           R, ldr, C,                                                                               \
-                           ldc, M, N, K, ksplit, g_slab, g_tickets);                                               \
-    } while (0)
-    switch (epi) {
-        case ZE_EPI_NONE: ZE_SKINNY_LAUNCH(ZE_EPI_NONE); break;
-        case ZE_EPI_GELU: ZE_SKINNY_LAUNCH(ZE_EPI_GELU); break;
-        case ZE_EPI_RESIDUAL: ZE_SKINNY_LAUNCH(ZE_EPI_RESIDUAL); break;
-        case ZE_EPI_F32: ZE_SKINNY_LAUNCH(ZE_EPI_F32); break;
-        default: break;  // SWIGLU pairs 16-row blocks: never routed here
-    }
-#undef ZE_SKINNY_LAUNCH
-}
-
-template <int TN>
-static void launch_skinny(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, const bf16_t* R,
-                          int ldr, bf16_t* C, int ldc, int M, int N, int K, int ksplit, hipStream_t s) {
-    if (M <= 16) launch_skinny_mt<TN, 1>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ksplit, s);
-    else if (M <= 32) launch_skinny_mt<TN, 2>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ksplit, s);
-    else launch_skinny_mt<TN, 4>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ksplit, s);
+    // (never split: no workspace; SWIGLU pairs 16-row blocks: never routed here)
+    dispatch_epi<ZE_EPI_NONE, ZE_EPI_GELU, ZE_EPI_RESIDUAL, ZE_EPI_F32>(c.epi, [&](auto E) {
+        launch_lds<k_gemm_skinny<TN, E, false, MT>>(dim3(grid), dim3(256), lds, lds, c.s, c.A, c.lda, c.W, c.ldw, c.bias, c.R, c.ldr, c.C, c.ldc,
+                                                    c.M, c.N, c.K, ksplit, nullptr, nullptr, nullptr, nullptr);
+    });
 }
 
 // ----------------------------------------------------------------------------------------------------------------
@@ -2300,33 +2197,26 @@ __global__ void __launch_bounds__(64 * WM * WN) k_splitk_reduce(const float* __r
 // through LDS into k_rmsnorm_row's element order -- and also writes the next layer's normalised input.  Bit-identical to the two
 // launches, but M / 4 workgroups are too few to keep the slab reads going: 52.6 us against 48.1 + 3.7 for the pair at 576 rows, 30.7
 // against 21.1 + 3.5 at 128, and the question stream did not move.  DESIGN.md 7f.)
-// the slice count of the weight-streaming split (launch_cfg, stream mode, 64-column tiles): a function of (N, K) alone
-static int stream_ksplit(int N, int K) {
-    int ksplit = 1;
-    const int nk = ze_cdiv(K, GEMM_BK), tiles_n = ze_cdiv(N, 64);
-    while (tiles_n * ksplit < 200 && ksplit < 8 && nk / (ksplit * 2) >= 4) ksplit *= 2;
-    return ksplit;
-}
-
 // long-K projection, more than 64 rows: big tiles on the slices of the one-launch form, then the chip-wide reduction;
 // false = does not apply
 template <int BM, int BN, int ST, bool SPR, int WM = 2, int WN = 4, int BK = GEMM_BK>
-static bool launch_splitk_two(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, const bf16_t* R,
-                              int ldr, bf16_t* C, int ldc, int M, int N, int K, const ze_gemm_ws& ws, hipStream_t s) {
-    if (epi != ZE_EPI_RESIDUAL && epi != ZE_EPI_NONE) return false;
-    const int ksplit = stream_ksplit(N, K);
-    const int nwg = ze_cdiv(M, BM) * ze_cdiv(N, BN);
-    if (ksplit < 2 || K % GEMM_BK != 0 || K / GEMM_BK / ksplit < 4 || !ws.slab || (size_t)ksplit * nwg * BM * BN > ws.slab_floats)
+static bool launch_splitk_two(const gemm_call& c) {
+    if (c.epi != ZE_EPI_RESIDUAL && c.epi != ZE_EPI_NONE) return false;
+    const int ksplit = stream_ksplit(c.N, c.K);
+    const int nwg = ze_cdiv(c.M, BM) * ze_cdiv(c.N, BN);
+    if (ksplit < 2 || c.K % GEMM_BK != 0 || c.K / GEMM_BK / ksplit < 4 || !c.ws.slab || (size_t)ksplit * nwg * BM * BN > c.ws.slab_floats)
         return false;
-    ze_gemm_ws slabs_only = ws;
-    slabs_only.tickets = nullptr;
-    launch_ring_variant<BM, BN, ST, WM, WN, SPR, false, false, BK>(ZE_EPI_NONE, A, lda, W, ldw, nullptr, nullptr, 0, C, ldc, nullptr, M, N, K, s, ksplit, slabs_only);
+    gemm_call slabs_only = c;  // no tickets: every slice parks its sums and leaves; no epilogue runs
+    slabs_only.ws.tickets = nullptr;
+    slabs_only.epi = ZE_EPI_NONE;
+    slabs_only.bias = slabs_only.R = nullptr;
+    slabs_only.ldr = 0;
+    launch_ring_variant<BM, BN, ST, WM, WN, SPR, false, false, BK>(slabs_only, ksplit);
     const int grid = nwg * (BM / (16 * WM)) * (BN / (16 * WN));
-    if (epi == ZE_EPI_RESIDUAL)
-        hipLaunchKernelGGL((k_splitk_reduce<BM, BN, WM, WN, ZE_EPI_RESIDUAL>), dim3(grid), dim3(64 * WM * WN), 0, s, ws.slab, ksplit, bias, R, ldr, C, ldc, M, N);
-    else
-        hipLaunchKernelGGL((k_splitk_reduce<BM, BN, WM, WN, ZE_EPI_NONE>), dim3(grid), dim3(64 * WM * WN), 0, s, ws.slab, ksplit, bias, R, ldr, C, ldc, M, N);
-    return true;
+    return dispatch_epi<ZE_EPI_RESIDUAL, ZE_EPI_NONE>(c.epi, [&](auto E) {
+        launch_lds<k_splitk_reduce<BM, BN, WM, WN, E>>(dim3(grid), dim3(64 * WM * WN), 0, 0, c.s, c.ws.slab, ksplit, c.bias, c.R,
+                                                       c.ldr, c.C, c.ldc, c.M, c.N);
+    });
 }
 
 // dst row p of every 128-row head <- src row head * 128 + dim(p): blocks of 32 = [d0 .. d0 + 15 | 64 + d0 .. 64 + d0 + 15]
@@ -2354,30 +2244,24 @@ void ze_launch_permute_qkv(const bf16_t* W, int ldw, const bf16_t* bias, int n_h
 // K in sequence per output element on every tile: the same bits (test_linear_wide_decode).  false = 64-row tiles already fit one round
 // (or the shape is not a narrow projection): the caller's old rule applies.  knob 13 = 4: off.
 template <bool QKV>
-static bool launch_tall(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, const bf16_t* R, int ldr, bf16_t* C,
-                        int ldc, int M, int N, int K, hipStream_t s) {
-    const int nct = ze_cdiv(N, 64);
+static bool launch_tall(const gemm_call& c) {
+    const int M = c.M, K = c.K, nct = ze_cdiv(c.N, 64);
     if (ze_gemv_knobs[13] == 4 || K % GEMM_BK != 0 || K / GEMM_BK < 4 || M <= 64 || M > 768) return false;
-    if (!QKV && epi != ZE_EPI_NONE && epi != ZE_EPI_RESIDUAL) return false;
+    if (!QKV && c.epi != ZE_EPI_NONE && c.epi != ZE_EPI_RESIDUAL) return false;
     // one workgroup per CU.  Default: six stages in three groups of two K-steps (one barrier per 128 of K; two groups in flight: 16.0 /
     // 11.5 us for qkv / o at 399 rows against 16.4 / 12.1 on the plain four-stage ring, knob 19 = 4; eight stages in four groups of two:
     // level; in two groups of four: 17.8 / 13.6; a plain ring of six or eight stages: 18.9 / 18.2 -- what bounds these launches is what
     // a CU takes in per microsecond, not the depth of its ring)
-#define ZE_TALL_G(BM_, ST_, KPB_) launch_ring_variant<(BM_), 64, ST_, (BM_) / 16, 2, false, false, QKV, GEMM_BK, KPB_>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, nullptr, M, N, K, s)
-#define ZE_TALL_ST(BM_)                                                        \
-    do {                                                                       \
-        const int nk_ = K / GEMM_BK;                                           \
-        if (ze_gemv_knobs[19] == 4 || nk_ % 2) ZE_TALL_G(BM_, 4, 1);           \
-        else ZE_TALL_G(BM_, 6, 2);                                             \
-    } while (0)
-    if (ze_cdiv(M, 64) * nct <= 256) ZE_TALL_ST(64);
-    else if (ze_cdiv(M, 80) * nct <= 256) ZE_TALL_ST(80);
-    else if (ze_cdiv(M, 96) * nct <= 256) ZE_TALL_ST(96);
-    else if (ze_cdiv(M, 112) * nct <= 256) ZE_TALL_ST(112);
-    else if (ze_cdiv(M, 128) * nct <= 256) ZE_TALL_ST(128);
+    auto tall = [&](auto BM) {  // (one run over K: the callers pass no workspace)
+        if (ze_gemv_knobs[19] == 4 || (K / GEMM_BK) % 2) launch_ring_variant<BM, 64, 4, BM / 16, 2, false, false, QKV, GEMM_BK, 1>(c);
+        else launch_ring_variant<BM, 64, 6, BM / 16, 2, false, false, QKV, GEMM_BK, 2>(c);
+    };
+    if (ze_cdiv(M, 64) * nct <= 256) tall(int_c<64>());
+    else if (ze_cdiv(M, 80) * nct <= 256) tall(int_c<80>());
+    else if (ze_cdiv(M, 96) * nct <= 256) tall(int_c<96>());
+    else if (ze_cdiv(M, 112) * nct <= 256) tall(int_c<112>());
+    else if (ze_cdiv(M, 128) * nct <= 256) tall(int_c<128>());
     else return false;
-#undef ZE_TALL_ST
-#undef ZE_TALL_G
     return true;
 }
 
@@ -2387,20 +2271,21 @@ void ze_launch_gemm_qkv_rope(const bf16_t* A, int lda, const bf16_t* Wp, int ldw
                              bf16_t* C, int ldc, int M, int N, int K, hipStream_t s) {
     if (M <= 0 || N <= 0) return;
     const long b64 = (long)ze_cdiv(M, 64) * ze_cdiv(N, 64);
-    const bf16_t* R = reinterpret_cast<const bf16_t*>(dev_args);
-    if (launch_tall<true>(ZE_EPI_QKV_ROPE, A, lda, Wp, ldw, bias_p, R, 0, C, ldc, M, N, K, s)) return;
+    // (the epilogue's arguments ride in the residual pointer)
+    const gemm_call c{ZE_EPI_QKV_ROPE, A, lda, Wp, ldw, bias_p, reinterpret_cast<const bf16_t*>(dev_args), 0, C, ldc, nullptr, M, N, K, s, ze_gemm_ws()};
+    if (launch_tall<true>(c)) return;
     // more than 768 rows (round 6: an engine with more than 768 chain slots -- the one-lane A/B of VERDICT r5 #1b): one round of 128 x 128
     // tiles, the tile ze_launch_gemm gives a prefill pass of this size (9 x 20 = 180 workgroups at 1152 rows); K in sequence: same bits
     if (M > 768 && K % GEMM_BK == 0 && K / GEMM_BK >= 4 && (long)ze_cdiv(M, 128) * ze_cdiv(N, 128) <= 256) {
-        launch_ring_variant<128, 128, 4, 2, 4, true, false, true>(ZE_EPI_QKV_ROPE, A, lda, Wp, ldw, bias_p, R, 0, C, ldc, nullptr, M, N, K, s);
+        launch_ring_variant<128, 128, 4, 2, 4, true, false, true>(c);
         return;
     }
     // (two 64-KB workgroups share a CU: up to 512 tiles stay on 64 x 64 -- 16.4 against 20.8 us at 410 rows, 19.9 / 21.0 at 580, 20.9 /
     //  22.7 at 768; knob 13 = 3: 64 x 128 from 257 tiles on, the rule before)
     if (b64 <= (ze_gemv_knobs[13] == 3 ? 256 : 512))
-        launch_ring_variant<64, 64, 4, 4, 2, false, false, true>(ZE_EPI_QKV_ROPE, A, lda, Wp, ldw, bias_p, R, 0, C, ldc, nullptr, M, N, K, s);
+        launch_ring_variant<64, 64, 4, 4, 2, false, false, true>(c);
     else
-        launch_ring_variant<64, 128, 4, 2, 4, false, false, true>(ZE_EPI_QKV_ROPE, A, lda, Wp, ldw, bias_p, R, 0, C, ldc, nullptr, M, N, K, s);
+        launch_ring_variant<64, 128, 4, 2, 4, false, false, true>(c);
 }
 
 void ze_launch_gemm_p8(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, const bf16_t* R, int ldr,
@@ -2409,33 +2294,42 @@ void ze_launch_gemm_p8(int epi, const bf16_t* A, int lda, const bf16_t* W, int l
     int ks = ze_prefill_ksplit(K, ws.slab != nullptr);   // (as ze_launch_gemm: the direct entry sums like the policy's)
     const long tiles = (long)ze_cdiv(M, 256) * ze_cdiv(N, 256);
     if (ks > 1 && ((size_t)ks * tiles * 256 * 256 > ws.slab_floats || tiles > ws.ticket_cap)) ks = ze_prefill_split_dropped(M, N, K, ks);
-    launch_p8(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, ks, ws);
+    launch_p8({epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, ws}, ks);
 }
 
-void ze_launch_gemm_stream(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias,
-                           const bf16_t* R, int ldr, bf16_t* C, int ldc, int M, int N, int K, const ze_gemm_ws& ws,
-                           hipStream_t s) {
-    if (M <= 0 || N <= 0) return;
+static void launch_stream(const gemm_call& c) {
     // Short, narrow weight matrices (qkv, o: K <= 4096, N <= 4096): the skinny kernel, 16 weight rows per workgroup,
     // no split-K (measured, device time per launch at 8 / 64 chains: qkv 9.8 / 13.9 us against 15.0 / 15.6 on the
     // ring, o 8.9 / 12.9 against 14.0 / 14.9).  With 64 rows per workgroup it loses everywhere the ring streams well
     // (gate/up 43.9 against 27.5 us at 64 chains: its 16-row x 64-B fragment loads use the vector memory path at a
     // fraction of what the LDS-DMA's 128-B rows do), so wide or long matrices stay on the ring.  The choice is a
     // function of (N, K, epilogue) alone: batch-composition invariance.
-    if (M <= 64 && K % 32 == 0 && K <= 4096 && N <= 4096 && epi != ZE_EPI_SWIGLU && ze_gemv_knobs[5] != 1 &&
-        (lda % 8) == 0 && (ldw % 8) == 0) {
-        launch_skinny<1>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, 1, s);
+    if (c.M <= 64 && c.K % 32 == 0 && c.K <= 4096 && c.N <= 4096 && c.epi != ZE_EPI_SWIGLU && ze_gemv_knobs[5] != 1 &&
+        (c.lda % 8) == 0 && (c.ldw % 8) == 0) {
+        dispatch_mt(c.M, [&](auto MT) { launch_skinny_mt<1, MT>(c, 1); });
         return;
     }
     // (64 x 128 tiles and every forced slice count 1 / 2 / 4 lose to this policy at 64 chains: gate/up 27.5 us here,
     //  27.2-59 there; down 21.3 here, 21-67 there)
-    launch_cfg<64, 64>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, nullptr, M, N, K, s, true, ws);
+    launch_cfg<64, 64>(c, true);
+}
+void ze_launch_gemm_stream(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias,
+                           const bf16_t* R, int ldr, bf16_t* C, int ldc, int M, int N, int K, const ze_gemm_ws& ws,
+                           hipStream_t s) {
+    if (M <= 0 || N <= 0) return;
+    launch_stream({epi, A, lda, W, ldw, bias, R, ldr, C, ldc, nullptr, M, N, K, s, ws});
 }
 
-#define ze_ring32_from (ze_gemv_knobs[3] > 0 ? ze_gemv_knobs[3] : 512)  // knob 3: first row count (exclusive) of the 320 x 192 tiles
+static void launch_policy(const gemm_call& c);  // the prefill / ViT policy (ze_launch_gemm, below)
+// knob 3: first row count (exclusive) of the 320 x 192 tiles
+static int ze_ring32_from() { return ze_gemv_knobs[3] > 0 ? ze_gemv_knobs[3] : 512; }
 void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, const bf16_t* R,
                          int ldr, bf16_t* C, int ldc, int M, int N, int K, const ze_gemm_ws& ws, hipStream_t s) {
     if (M <= 0 || N <= 0) return;
+    const gemm_call c{epi, A, lda, W, ldw, bias, R, ldr, C, ldc, nullptr, M, N, K, s, ws};
+    // (the workspace serves the K slices of the long-K branch and travels with the weight-streaming instances; every other tile
+    //  below, and the prefill policy, sums K in one run and gets none)
+    const gemm_call p = no_ws(c);
     // long K (the down projection): eight K slices, reduced in slice order, on the split-K ring (k_gemm_wstream with a
     // split K loses to it at every row count: 36.7 against 34.1 us at 256 rows, 23.4 against 17.4 at 64 -- its K loop alone
     // takes 19 us there, but 256-row tiles make the slab reduction eight times the bytes per reducer)
@@ -2450,28 +2344,22 @@ void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int
         if (ze_gemv_knobs[15] != 6) {
             // 257 .. 384 rows: 192 x 128 tiles -- two row tiles instead of three of 128 (no wasted third), 256 workgroups
             // instead of 192 (every CU), 17 % fewer bytes staged per workgroup; knob 15 = 4: the 128 x 256 tiles there too
-            if (M > 256 && M <= 384 && ze_gemv_knobs[15] != 4 &&
-                launch_splitk_two<192, 128, 3, false, 4, 2>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ws, s)) return;
+            if (M > 256 && M <= 384 && ze_gemv_knobs[15] != 4 && launch_splitk_two<192, 128, 3, false, 4, 2>(c)) return;
             // 513 .. 640 / 641 .. 768 rows: 320 x 128 / 384 x 128 tiles with K-steps of 32 (four stages): two row tiles x 16
             // column tiles x 8 slices = 256 workgroups, one round, where five or six row tiles of 128 x 256 are 320 / 384
             // workgroups -- a second round for a quarter / half of the chip.  knob 15 = 7: off
             // (knob 18, as for gate/up: 0 K-steps of 64 in two stages -- 56.3 -> 53.3 us at 704 rows, level at 576 --, 1 round 4's form)
-            if (M > 512 && M <= 640 && ze_gemv_knobs[15] != 7) {
-                const int f = ze_gemv_knobs[18];
-                if (f == 1 ? launch_splitk_two<320, 128, 4, true, 4, 2, 32>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ws, s)
-                           : launch_splitk_two<320, 128, 2, false, 4, 2>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ws, s)) return;
-            }
-            if (M > 640 && M <= 768 && ze_gemv_knobs[15] != 7) {
-                const int f = ze_gemv_knobs[18];
-                if (f == 1 ? launch_splitk_two<384, 128, 4, true, 4, 2, 32>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ws, s)
-                           : launch_splitk_two<384, 128, 2, false, 4, 2>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ws, s)) return;
-            }
+            auto two_bm = [&](auto BM) {
+                return ze_gemv_knobs[18] == 1 ? launch_splitk_two<BM, 128, 4, true, 4, 2, 32>(c) : launch_splitk_two<BM, 128, 2, false, 4, 2>(c);
+            };
+            if (M > 512 && M <= 640 && ze_gemv_knobs[15] != 7 && two_bm(int_c<320>())) return;
+            if (M > 640 && M <= 768 && ze_gemv_knobs[15] != 7 && two_bm(int_c<384>())) return;
             // (round 5: 128 x 256 without the spread refill 35.7 against 35.1 us at 399 rows, in two stages 43.8)
-            if (M > 256 && launch_splitk_two<128, 256, 3, true>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ws, s)) return;
-            if (M > 128 && M <= 256 && launch_splitk_two<128, 128, 4, true>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ws, s)) return;
-            if (M > 64 && M <= 128 && launch_splitk_two<64, 128, 4, false>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ws, s)) return;
+            if (M > 256 && launch_splitk_two<128, 256, 3, true>(c)) return;
+            if (M > 128 && M <= 256 && launch_splitk_two<128, 128, 4, true>(c)) return;
+            if (M > 64 && M <= 128 && launch_splitk_two<64, 128, 4, false>(c)) return;
         }
-        ze_launch_gemm_stream(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ws, s);
+        launch_stream(c);
         return;
     }
     // One pass over K: K in sequence on every tile, so the choice of tile never changes a result and may follow the row
@@ -2484,7 +2372,7 @@ void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int
     // qkv 21.7 us, o 21.1, gate/up 101.7 on the prefill policy against 38.1 / 22.3 / 129.9 on two blocks of the decode tiles).  K in
     // sequence on every tile: the same bits, so the choice may follow the row count.
     if (M > 768 && epi != ZE_EPI_F32 && ze_gemv_knobs[15] != 9) {
-        ze_launch_gemm(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, nullptr, M, N, K, s);
+        launch_policy(p);
         return;
     }
     const bool ok = K % GEMM_BK == 0 && (lda % 8) == 0 && (ldw % 8) == 0 && (size_t)N * ldw * sizeof(bf16_t) < ((size_t)1 << 31) &&
@@ -2502,7 +2390,8 @@ void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int
         // 513 .. 640 rows (where the question stream spends most of its decode steps: two lanes x 768 slots): 320 x 192 tiles on
         // the ring with K-steps of 32 -- four 32-KB stages, two row tiles x 115 column tiles = 230 workgroups in ONE round, 512
         // staged rows per 320 x 192 outputs -- instead of a 512-row and a 128-row weight-streaming pass.  knob 15 = 7: off
-        if (epi == ZE_EPI_SWIGLU && M > ze_ring32_from && M <= 640 && v != 7 && v != 4) {
+        // 641 .. 768 rows: 384 x 192 tiles the same way (four 36-KB stages, 96 x 96 outputs per wave)
+        if (epi == ZE_EPI_SWIGLU && ((M > ze_ring32_from() && M <= 640) || (M > 640 && M <= 768)) && v != 7 && v != 4) {
             // (round 5: the two-phase loop -- the waves of a SIMD in opposite phases; knob 18 = 1: the plain loop with the spread refill)
             // Round 5.  The launch is bound by what its workgroups take in through LDS-DMA -- with the MFMAs AND the fragment reads compiled
             // out (tools/probes/ring_ablate.sh) it still takes 57.6 of 63.1 us at 576 rows: 230 workgroups x 2 MB = 460 MB at 8 TB/s, the
@@ -2511,30 +2400,28 @@ void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int
             // eight whole 128-byte rows instead of sixteen half lines): 63.7 -> 59.4 us at 576 rows, 77.5 -> 69.1 at 768.  Same MFMAs in
             // the same K order on every form: the same bits.  knob 18: 0 this default, 1 round 4's form (K-steps of 32, four stages,
             // spread refill).
-            const int f = ze_gemv_knobs[18];
-            if (f == 1) launch_ring_variant<320, 192, 4, 4, 2, true, true, false, 32>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, nullptr, M, N, K, s);
-            else launch_ring_variant<320, 192, 2, 4, 2, false, true>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, nullptr, M, N, K, s);
-            return;
-        }
-        // 641 .. 768 rows: 384 x 192 tiles the same way (four 36-KB stages, 96 x 96 outputs per wave)
-        if (epi == ZE_EPI_SWIGLU && M > 640 && M <= 768 && v != 7 && v != 4) {
-            const int f = ze_gemv_knobs[18];
-            if (f == 1) launch_ring_variant<384, 192, 4, 4, 2, true, true, false, 32>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, nullptr, M, N, K, s);
-            else launch_ring_variant<384, 192, 2, 4, 2, false, true>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, nullptr, M, N, K, s);
+            auto ring_bm = [&](auto BM) {
+                if (ze_gemv_knobs[18] == 1) launch_ring_variant<BM, 192, 4, 4, 2, true, true, false, 32>(p);
+                else launch_ring_variant<BM, 192, 2, 4, 2, false, true>(p);
+            };
+            if (M <= 640) ring_bm(int_c<320>());
+            else ring_bm(int_c<384>());
             return;
         }
         // 385 .. 512 rows (round 5): 256 x 192 tiles on K-steps of 64 in two stages WITHOUT the spread refill -- two row tiles x 115
         // column tiles = 230 workgroups staging 1.8 MB each, against 2.4 MB for the 512 x 96 weight-streaming tile (round 4 had tried
         // this tile with the spread refill: 61.9 against 57.4 us at 440 rows).  knob 15 = 8: the weight-streaming tile
         if (epi == ZE_EPI_SWIGLU && M > 384 && M <= 512 && v != 8 && v != 4 && v != 7) {
-            launch_ring_variant<256, 192, 2, 4, 2, false, true>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, nullptr, M, N, K, s);
+            launch_ring_variant<256, 192, 2, 4, 2, false, true>(p);
             return;
         }
         const int blk = (epi == ZE_EPI_SWIGLU && K / GEMM_BK == 32 && v != 5) ? 512 : 256;
         for (int r0 = 0; r0 < M && done; r0 += blk) {
             const int mb = std::min(blk, M - r0);
-            const bf16_t* Ab = A + (size_t)r0 * lda;
-            bf16_t* Cb = C + (size_t)r0 * crow;
+            gemm_call b = c;  // this block of rows
+            b.A += (size_t)r0 * lda;
+            b.C += (size_t)r0 * crow;
+            b.M = mb;
             // 257 .. 384 rows: 192 x 192 tiles on the ring (two row tiles x 115 column tiles = 230 workgroups, one round): a
             // workgroup stages (192 + 192) rows per K-step for 192 x 192 outputs -- 96 FLOP per staged byte against 77 for
             // the 384 x 96 weight-streaming tile, which re-reads ALL the activations in every workgroup.  Same K order per
@@ -2542,26 +2429,26 @@ void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int
             if (mb > 256 && mb <= 384 && epi == ZE_EPI_SWIGLU && v != 4 && r0 == 0 && M <= 384) {
                 // (the refill DMAs spread between the rows of MFMAs: 40.6 against 41.6 us at 344 rows)
                 // (round 5: without the spread refill 41.4 us, in two stages 46.9, against 40.3 as is at 344 rows)
-                launch_ring_variant<192, 192, 3, 4, 2, true, true>(epi, Ab, lda, W, ldw, bias, R, ldr, Cb, ldc, nullptr, mb, N, K, s);
+                launch_ring_variant<192, 192, 3, 4, 2, true, true>(no_ws(b));
                 continue;
             }
             // (tried for 385 .. 512 rows and dropped: 256 x 192 tiles in two stages, 61.9 against 57.4 us at 440 rows)
             // (tried for 385 .. 448 rows and dropped: 224 x 192 tiles on FOUR waves of 112 x 96 outputs -- the only wave grid that
             //  divides 224 rows and keeps the SwiGLU pairs in a wave -- 67.0 against 56.8 us at 440 rows)
-            if (mb > 384) launch_wstream_one<512, 96, 2, 6, 32, ZE_EPI_SWIGLU>(Ab, lda, W, ldw, bias, R, ldr, Cb, ldc, mb, N, K, 1, ws, s);
-            else if (mb > 256) launch_wstream_one<384, 96, 2, 8, 32, ZE_EPI_SWIGLU>(Ab, lda, W, ldw, bias, R, ldr, Cb, ldc, mb, N, K, 1, ws, s);
-            else if (mb > 128) done = launch_wstream<256, 96, 3, 8>(epi, Ab, lda, W, ldw, bias, R, ldr, Cb, ldc, mb, N, K, ws, s);
-            else done = launch_wstream<128, 96, 3, 8>(epi, Ab, lda, W, ldw, bias, R, ldr, Cb, ldc, mb, N, K, ws, s);
-            if (!done && r0 > 0) done = true, ze_launch_gemm(epi, Ab, lda, W, ldw, bias, R, ldr, Cb, ldc, nullptr, mb, N, K, s);
+            if (mb > 384) launch_wstream_one<512, 96, 2, 6, 32, ZE_EPI_SWIGLU>(b, 1);
+            else if (mb > 256) launch_wstream_one<384, 96, 2, 8, 32, ZE_EPI_SWIGLU>(b, 1);
+            else if (mb > 128) done = launch_wstream<256, 96, 3, 8>(b);
+            else done = launch_wstream<128, 96, 3, 8>(b);
+            if (!done && r0 > 0) done = true, launch_policy(no_ws(b));
         }
     }
-    if (!done && N <= 4096 && launch_tall<false>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, s)) return;
-    if (!done) ze_launch_gemm(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, nullptr, M, N, K, s);
+    if (!done && N <= 4096 && launch_tall<false>(p)) return;
+    if (!done) launch_policy(p);
 }
 
-void ze_launch_gemm(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, const bf16_t* R,
-                    int ldr, bf16_t* C, int ldc, const int* c_rows, int M, int N, int K, hipStream_t s, const ze_gemm_ws& ws) {
-    if (M <= 0 || N <= 0) return;
+static void launch_policy(const gemm_call& c) {
+    const int M = c.M, N = c.N, K = c.K;
+    const ze_gemm_ws& ws = c.ws;
     // Many tiles: the largest tile (the register-staged kernel hides latency with several workgroups per CU).
     // Otherwise the largest tile whose grid is one round of at least half the CUs, which then runs on the LDS-DMA
     // ring kernel when K % 64 == 0 (launch_cfg); 64 x 64 tiles for what is left.
@@ -2577,13 +2464,15 @@ void ze_launch_gemm(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw,
         ze_gemv_knobs[7] != 3) {
         int ks_ = ze_prefill_ksplit(K, ws.slab != nullptr);
         if (ks_ > 1 && ((size_t)ks_ * b128 * 128 * 128 > ws.slab_floats || b128 > ws.ticket_cap)) ks_ = ze_prefill_split_dropped(M, N, K, ks_);
-        launch_ring_variant<128, 128, 4, 2, 4, true>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, ks_, ws);
+        launch_ring_variant<128, 128, 4, 2, 4, true>(c, ks_);
         return;
     }
-    if (b128 >= 200)
-        launch_cfg<128, 128>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, false, ws);
-    else if (b64x128 >= 160 || (ringable && (b64x128 >= 128 || b64 > 256)))
-        launch_cfg<64, 128>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, false, ws);
-    else
-        launch_cfg<64, 64>(epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, false, ws);
+    if (b128 >= 200) launch_cfg<128, 128>(c, false);
+    else if (b64x128 >= 160 || (ringable && (b64x128 >= 128 || b64 > 256))) launch_cfg<64, 128>(c, false);
+    else launch_cfg<64, 64>(c, false);
+}
+void ze_launch_gemm(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, const bf16_t* R,
+                    int ldr, bf16_t* C, int ldc, const int* c_rows, int M, int N, int K, hipStream_t s, const ze_gemm_ws& ws) {
+    if (M <= 0 || N <= 0) return;
+    launch_policy({epi, A, lda, W, ldw, bias, R, ldr, C, ldc, c_rows, M, N, K, s, ws});
 }
