@@ -772,6 +772,18 @@ int ze_weight_format(ze_engine* e);
  * 10 the lm_head of that regime: no bias, C is FP32 [M, N] (HF casts the logits to fp32, HF:generation/utils.py:2894). */
 int ze_op_linear(ze_engine* e, const void* a_bf16, const void* w_bf16, const void* bias_bf16, void* c_bf16, int M,
                  int N, int K, int act, void* stream);
+/* The public GEMM launchers of the library, one call, with the operands the engine gives them: leading dimensions of their own
+ * (in elements), the residual epilogue and the output row table.  launcher: 0 ze_launch_gemm with the engine's prefill workspace,
+ * 1 ze_launch_gemm without one (the ViT's call), 2 the eight-phase kernel directly, 3 the weight-streaming launcher of the batched
+ * decode step, 4 the launcher of the row-streaming regime, 5 / 6 the fragment-major skinny / one-shot kernels (a and w packed
+ * inside the call).  epi: 0 none (+bias), 1 exact GELU, 2 residual: C = bf16(r + bf16(A W^T + bias)), r [M, ldr] read at the
+ * INPUT row (r may be c), 3 SwiGLU (as ze_op_linear act 4: C is [M, N / 2]), 4 the fp32 copy of the bf16-rounded value (C is
+ * fp32, ldc in floats).  c_rows (device, may be null; launchers 0-2): row i of the result goes to row c_rows[i] of C.
+ * ZE_ERR_INVALID, nothing launched: a null operand, r null under residual, a leading dimension below its extent, rows of a / w
+ * not 16-byte aligned, K % 8 (launcher 2: K % 64), c_rows on launchers 3-6, the fragment limits (M <= 64, N % 16, K % 32, and
+ * K <= 4096 on launcher 5), GELU on launcher 5, anything but none / residual on launcher 6, SwiGLU with N % 32. */
+int ze_op_gemm(ze_engine* e, int launcher, int epi, const void* a_bf16, int lda, const void* w_bf16, int ldw, const void* bias_bf16,
+               const void* r_bf16, int ldr, void* c, int ldc, const int32_t* c_rows, int M, int N, int K, void* stream);
 /* y = weight * bf16(x * rsqrt(mean(x^2)+eps))  (HF:...modeling_qwen2_5_vl.py:64-79), rows x cols bf16. */
 int ze_op_rmsnorm(ze_engine* e, const void* x_bf16, const void* weight_bf16, void* y_bf16, int rows, int cols,
                   float eps, void* stream);

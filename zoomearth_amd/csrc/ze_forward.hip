@@ -2389,6 +2389,60 @@ extern "C" int ze_op_linear(ze_engine* e, const void* a, const void* w, const vo
     return ZE_OK;
 }
 
+// The public GEMM launchers with the operands the engine gives them: leading dimensions of their own, the residual epilogue, the output
+// row table (tests/test_gpu_gemm_operands.py).  Everything a launcher would not take is refused here, before anything is launched.
+extern "C" int ze_op_gemm(ze_engine* e, int launcher, int epi, const void* a, int lda, const void* w, int ldw, const void* bias,
+                          const void* r, int ldr, void* cmat, int ldc, const int32_t* c_rows, int M, int N, int K, void* stream) {
+    if (!e || !a || !w || !cmat) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    if (launcher < 0 || launcher > 6) return ze_fail(e, ZE_ERR_INVALID, "launcher must be in [0, 6]");
+    if (M <= 0 || N <= 0 || K <= 0) return ze_fail(e, ZE_ERR_INVALID, "M, N, K > 0");
+    const bool frag = launcher == 5 || launcher == 6;
+    bool epi_ok = epi == ZE_EPI_NONE || epi == ZE_EPI_RESIDUAL;  // (the dispatch_epi list of the launcher's kernels, ze_gemm.hip)
+    if (launcher != 6) epi_ok = epi_ok || epi == ZE_EPI_SWIGLU || epi == ZE_EPI_F32 || (launcher != 5 && epi == ZE_EPI_GELU);
+    if (!epi_ok) return ze_fail(e, ZE_ERR_INVALID, "the launcher has no kernel with this epilogue");
+    if (epi == ZE_EPI_RESIDUAL && !r) return ze_fail(e, ZE_ERR_INVALID, "RESIDUAL needs r");
+    if (epi == ZE_EPI_SWIGLU && N % 32) return ze_fail(e, ZE_ERR_INVALID, "SwiGLU: N = 2 * width with width % 16 == 0");
+    if (K % 8) return ze_fail(e, ZE_ERR_INVALID, "K must be a multiple of 8");
+    if (launcher == 2 && (K % 64 || K < 64)) return ze_fail(e, ZE_ERR_INVALID, "eight-phase kernel: K a multiple of 64");
+    if (lda < K || ldw < K || ldc < (epi == ZE_EPI_SWIGLU ? N / 2 : N) || (epi == ZE_EPI_RESIDUAL && ldr < N))
+        return ze_fail(e, ZE_ERR_INVALID, "a leading dimension is below its extent");
+    if (lda % 8 || ldw % 8 || (size_t)a % 16 || (size_t)w % 16)  // (every kernel loads its operands in 16-byte row pieces)
+        return ze_fail(e, ZE_ERR_INVALID, "the rows of a and w start on 16-byte boundaries");
+    if (launcher >= 3 && c_rows) return ze_fail(e, ZE_ERR_INVALID, "the launcher takes no output row table");
+    if (frag && (M > 64 || N % 16 || K % 32 || (launcher == 5 && K > 4096)))
+        return ze_fail(e, ZE_ERR_INVALID, "fragment path: M <= 64, N % 16, K % 32, K <= 4096");
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    const bf16_t *A = (const bf16_t*)a, *W = (const bf16_t*)w, *B = (const bf16_t*)bias;
+    const bf16_t* R = epi == ZE_EPI_RESIDUAL ? (const bf16_t*)r : nullptr;
+    if (!R) ldr = 0;
+    bf16_t* C = (bf16_t*)cmat;
+    if (frag) {  // operands packed here, as ze_op_linear act 3 / 5 does
+        bf16_t *wf = nullptr, *xf = nullptr;
+        const size_t mp = (size_t)(M + 15) / 16 * 16;
+        ZE_HIP(hipMalloc((void**)&wf, ((size_t)N * K + mp * K) * sizeof(bf16_t)));
+        xf = wf + (size_t)N * K;
+        ze_launch_pack_fragments(W, ldw, N, K, wf, s);
+        ze_launch_pack_fragments(A, lda, M, K, xf, s);
+        if (launcher == 6) ze_launch_gemm_oneshot(epi, xf, wf, B, R, ldr, C, ldc, M, N, K, s);
+        else ze_launch_gemm_frag(epi, xf, wf, B, R, ldr, C, ldc, M, N, K, s);
+        hipError_t le = hipGetLastError();
+        hipStreamSynchronize(s);
+        hipFree(wf);
+        if (le != hipSuccess) return ze_fail(e, ZE_ERR_HIP, hipGetErrorString(le));
+        return ZE_OK;
+    }
+    switch (launcher) {
+        case 0: ze_launch_gemm(epi, A, lda, W, ldw, B, R, ldr, C, ldc, c_rows, M, N, K, s, e->prefill_ws()); break;
+        case 1: ze_launch_gemm(epi, A, lda, W, ldw, B, R, ldr, C, ldc, c_rows, M, N, K, s); break;
+        case 2: ze_launch_gemm_p8(epi, A, lda, W, ldw, B, R, ldr, C, ldc, c_rows, M, N, K, s, e->prefill_ws()); break;
+        case 3: ze_launch_gemm_stream(epi, A, lda, W, ldw, B, R, ldr, C, ldc, M, N, K, e->gemm_ws(), s); break;
+        default: ze_launch_gemm_wide(epi, A, lda, W, ldw, B, R, ldr, C, ldc, M, N, K, e->gemm_ws(), s); break;
+    }
+    ZE_KCHECK();
+    return ZE_OK;
+}
+
 extern "C" int ze_op_token_logprob(ze_engine* e, const void* logits, int rows, int vocab, int ld, const int32_t* targets,
                                    float* out, void* stream) {
     if (!logits || !targets || !out || rows < 0 || vocab <= 0 || ld < vocab || ld % 8)

@@ -1246,7 +1246,8 @@ static void launch_p8(const gemm_call& c, int ksplit = 1) {
     const int units = tiles * std::max(1, ksplit);   // (split K: a unit = a K slice of a tile)
     const int grid = (ze_gemv_knobs[7] == 9 || shared_gpu) ? units : std::min(units, cus);
     // the wide-store epilogue (p8_finish_wide: 16-byte row pieces through 4 KB of LDS per wave) wherever rows are 16-byte
-    // aligned; knob 7 = 10: the plain two-byte epilogue, for A/B runs and the bit-equality test
+    // aligned; knob 7 = 10: the plain two-byte epilogue, for A/B runs and tests/test_gpu_gemm_operands.py (both tails against the
+    // same expected bits)
     const bool sw = c.epi == ZE_EPI_SWIGLU;
     const bool wide = ze_gemv_knobs[7] != 10 && (c.ldc % 8) == 0 && ((size_t)c.C % 16) == 0 && ((sw ? c.N / 2 : c.N) % 8) == 0 &&
                       (c.epi != ZE_EPI_RESIDUAL || ((c.ldr % 8) == 0 && ((size_t)c.R % 16) == 0));
@@ -2421,6 +2422,10 @@ void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int
             gemm_call b = c;  // this block of rows
             b.A += (size_t)r0 * lda;
             b.C += (size_t)r0 * crow;
+            // (the residual rows advance with the block, like A and C.  No kernel of this loop reads R today: only SWIGLU / F32 enter it
+            //  by the shipped rule, and under knob 15 = 1 launch_wstream has no RESIDUAL instance, so it returns false at r0 = 0 and the
+            //  WHOLE call goes to launch_policy with the caller's R -- ze_op_gemm therefore takes RESIDUAL at these shapes)
+            if (b.R) b.R += (size_t)r0 * ldr;
             b.M = mb;
             // 257 .. 384 rows: 192 x 192 tiles on the ring (two row tiles x 115 column tiles = 230 workgroups, one round): a
             // workgroup stages (192 + 192) rows per K-step for 192 x 192 outputs -- 96 FLOP per staged byte against 77 for

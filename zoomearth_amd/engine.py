@@ -1292,6 +1292,13 @@ class Engine:
         self._check(self.lib.ze_op_linear(self.h, _ptr(a), _ptr(w), _ptr(bias), _ptr(out), m, n, k, act, self._stream()))
         return out
 
+    def op_gemm(self, launcher: int, epi: int, a, lda: int, w, ldw: int, bias, r, ldr: int, c, ldc: int, c_rows, m: int, n: int,
+                k: int) -> int:
+        """ze_op_gemm on device tensors the caller allocated (padding and sentinels are the caller's): c is written in place.
+        Returns the status code without raising, so that a test can see ZE_ERR_INVALID (-1)."""
+        return int(self.lib.ze_op_gemm(self.h, launcher, epi, _ptr(a), lda, _ptr(w), ldw, _ptr(bias), _ptr(r), ldr, _ptr(c), ldc,
+                                       _ptr(c_rows), m, n, k, self._stream()))
+
     def op_rmsnorm(self, x, w, eps: float):
         out = torch.empty_like(x)
         self._check(self.lib.ze_op_rmsnorm(self.h, _ptr(x), _ptr(w), _ptr(out), x.shape[0], x.shape[1], eps,
