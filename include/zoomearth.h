@@ -981,6 +981,72 @@ int ze_profile_prefill_layer(ze_engine* e, int rows, int layers_run, float avg_u
  * which reset it to 0 when they are done.  A library user who wants a per-engine policy has none to set: value 0 is the only supported
  * production setting. */
 int ze_tune(int knob, int value);
+/* ------------------------------------------------------------------ beam search (zoomearth_amd/csrc/ze_beam.hip)
+ * replaces: GenerationMixin._beam_search with do_sample = False (HF:generation/utils.py:3208-3560: log_softmax, processors and running
+ * scores :3388-3420, _get_top_k_continuations :3077-3129, _get_running_beams_for_next_iteration :3131-3151, _update_finished_beams
+ * :3153-3204, _check_early_stop_heuristic :3008-3052, _beam_search_has_unfinished_sequences :3055-3075, the cache reorder :3477-3489)
+ * and vLLM's use_beam_search.  A GROUP is one prompt with num_beams running hypotheses in num_beams chain slots; every group follows
+ * HF at batch size 1, whatever shares the call.  Per step and group, on the device: lp = log_softmax of the beam's fp32 logits row
+ * (bf16-rounded values, as ze_prefill documents); the repetition penalty on lp for the ids the beam has seen (lp < 0 ? lp * p : lp / p);
+ * + the beam's running score (first step: beam 0 at 0, the others at -1e9).  Candidates are ordered by score descending, then by the
+ * flat index beam * vocab + token ascending (beam = HF's index of the running beam; the tie rule is this library's -- torch.topk has
+ * none -- and equal logits in a row give bit-equal scores).  The next running beams are the best num_beams candidates that are no EOS
+ * id -- HF's top (1 + n_eos) * num_beams with the EOS ones masked; an EOS candidate inside the overall top num_beams is a finished
+ * hypothesis of score cand / n_generated ** length_penalty, merged into the group's num_beams best under HF's early_stopping gates; at
+ * the last step (max_new_tokens, or the step whose token would be fed back at row max_ctx) every candidate counts as finished, as under
+ * HF's MaxLengthCriteria.  A group is done by HF's three conditions.  Slot i then holds the cache, ids, beam indices and seen-set of
+ * the hypothesis that lives there: a parent with children keeps one in its own slot, the others go to the slots whose hypothesis had
+ * none (children in candidate order, free slots ascending), prompt rows are never copied (ze_seq_fork's holder serves them).
+ * early_stopping: 0 = False (heuristic), 1 = True, 2 = "never".  repetition_penalty: 1.0 (or 0) = off. */
+typedef struct ze_beam_params {
+    int32_t num_beams;             /* 1 .. 16 */
+    int32_t num_return_sequences;  /* 1 .. num_beams */
+    int32_t max_new_tokens;
+    float length_penalty;
+    int32_t early_stopping;
+    float repetition_penalty;
+    int32_t use_graph;             /* replay the forward of a step as a hipGraph (the three beam launches follow it on the stream) */
+    int32_t sync_every;            /* host check of the groups' done words, in steps (>= 1) */
+} ze_beam_params;
+/* seqs: host int32 [groups * num_beams]; slot seqs[g * num_beams] of each group is prefilled and not stepped since (the ze_seq_fork
+ * source contract), the call forks it into the group's other slots, then steps: forward of the live groups' rows -> k_beam_rows ->
+ * k_beam_select -> k_beam_reorder, all on `stream`; groups that are done leave the step.  Both decode families.  Outputs (host; the
+ * call waits for the stream): out_tokens int32 [groups, num_return_sequences, max_new_tokens] (pad_token_id behind a hypothesis),
+ * out_len [groups, num_return_sequences], out_scores f32 (HF's sequences_scores; may be NULL), out_beam_indices int32 like out_tokens
+ * (HF's beam_indices, the group's offset g * num_beams included, -1 behind a hypothesis; may be NULL).  Afterwards the slots are
+ * ordinary chains holding the last running beams; ze_seq_reset frees them.
+ * Everything is checked before anything is enqueued or changed.  ZE_ERR_INVALID: a parameter out of range, groups * num_beams >
+ * max_seqs, a slot named twice, more than 64 rows on an engine pinned to decode family 0, a source that is empty or has drawn, stepped
+ * or changed since its prefill, or a slot of the call with a per-chain request a beam step does not serve -- ze_seq_set_sampling,
+ * sampling or entropy filter, log-probabilities, logit adjustment, token rules, grammar, speculation (each keeps working on every chain
+ * outside a beam call).  ZE_ERR_NOTFOUND: a slot out of range.  ZE_ERR_NOMEM: a prompt that fills max_ctx, or the beam tables (they
+ * come with the first call) could not be allocated -- the engine stays usable. */
+int ze_beam_search(ze_engine* e, const int32_t* seqs, int groups, const ze_beam_params* p, int32_t* out_tokens, int32_t* out_len,
+                   float* out_scores, int32_t* out_beam_indices, void* stream);
+/* Unit entry, no model: one beam step (the three launches) on the caller's logits, device f32 [groups * num_beams, ld], row g *
+ * num_beams + j = the beam in slot seqs[g * num_beams + j]; the first `vocab` <= the engine's columns count.  begin != 0 starts a call
+ * (empty finished pools, scores 0 / -1e9, the slots' cached rows as the prompt), begin = 0 continues it with the same groups,
+ * num_beams and max_new_tokens.  The slots' chain states, generated ids and seen-sets move as in ze_beam_search.  Host outputs, any may be
+ * NULL, per row: out_parent = the position in its group of the slot its hypothesis came from, out_token, out_score = the running score,
+ * out_rank = HF's index of the running beam that lives in the slot; out_done [groups].  Waits for the stream. */
+int ze_op_beam_step(ze_engine* e, const int32_t* seqs, int groups, const ze_beam_params* p, int begin, const float* logits, int vocab,
+                    int ld, int32_t* out_parent, int32_t* out_token, float* out_score, int32_t* out_rank, int32_t* out_done, void* stream);
+/* The finished pools of the last ze_op_beam_step / ze_beam_search, all num_beams entries per group by rank: the outputs of
+ * ze_beam_search with num_return_sequences = num_beams, and out_finished [groups, num_beams] = HF's is_sent_finished.  Any may be NULL. */
+int ze_op_beam_finished(ze_engine* e, int groups, int32_t* out_tokens, int32_t* out_len, float* out_scores, int32_t* out_beam_indices,
+                        int32_t* out_finished, void* stream);
+/* Unit entry of k_beam_reorder: cached rows [row0, row0 + rows) of every layer of chain src_seqs[i] become those of chain dst_seqs[i],
+ * n host pairs in one launch; nothing else of a chain moves (the call keeps tables of its own: a beam call in progress is not
+ * disturbed, though its hypotheses' rows are what the caller makes of them).  ZE_ERR_INVALID, with nothing changed: a destination that is also a
+ * source or is named twice, rows outside [0, max_ctx]. */
+int ze_op_kv_reorder(ze_engine* e, const int32_t* src_seqs, const int32_t* dst_seqs, int n, int row0, int rows, void* stream);
+
+/* Measurement entry (tools/bench_beam_search.py): HIP-event microseconds per launch of one beam kernel (which: 0 k_beam_rows, 1
+ * k_beam_select, 2 k_beam_reorder) on `groups` groups of num_beams beams in slots 0 .. groups * num_beams - 1; logits device f32
+ * [groups * num_beams, vocab]; the reorder moves gen_rows generated rows into every slot but a group's first.  Overwrites the slots'
+ * chain states: for an engine that serves nothing else. */
+int ze_profile_beam_kernel(ze_engine* e, int which, int groups, int num_beams, int gen_rows, const float* logits, int iters, float* out_us,
+                           void* stream);
 /* Per-phase device time (ms) accumulated by HIP events since the last reset: [0] front-end, [1] ViT,
  * [2] prefill, [3] decode, [4] sampling.  Only recorded while enabled. */
 int ze_phase_timers(ze_engine* e, int enable, int reset, float out_ms[5]);

@@ -40,6 +40,12 @@ class ZeGenParams(C.Structure):
                 ("temperature", C.c_float), ("seed", C.c_uint64)]
 
 
+class ZeBeamParams(C.Structure):
+    _fields_ = [("num_beams", C.c_int32), ("num_return_sequences", C.c_int32), ("max_new_tokens", C.c_int32),
+                ("length_penalty", C.c_float), ("early_stopping", C.c_int32), ("repetition_penalty", C.c_float),
+                ("use_graph", C.c_int32), ("sync_every", C.c_int32)]
+
+
 class ZoomEarthError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libzoomearth_hip error {code}: {msg}")
@@ -116,6 +122,15 @@ _SIGS = {
     "ze_seq_len": (C.c_int, [_P, C.c_int]),
     "ze_seq_copy_prefix": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "ze_seq_fork": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_int, _P]),
+    "ze_beam_search": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.POINTER(ZeBeamParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                C.POINTER(C.c_float), C.POINTER(C.c_int32), _P]),
+    "ze_op_beam_step": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.POINTER(ZeBeamParams), C.c_int, _P, C.c_int, C.c_int,
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32), _P]),
+    "ze_op_beam_finished": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "ze_profile_beam_kernel": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_float), _P]),
+    "ze_op_kv_reorder": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, _P]),
     "ze_prefix_pool_create": (C.c_int, [_P, C.c_int, C.c_int]),
     "ze_prefix_pool_destroy": (C.c_int, [_P]),
     "ze_prefix_pool_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]),

@@ -241,6 +241,23 @@ struct ze_spec {
     bool on(int seq) const { return !host.empty() && host[seq].k > 0; }
 };
 
+// Beam search (ze_beam.hip): everything a beam call keeps between two forwards, device-resident, allocated by the first call (all or
+// none) and grown when a call asks for more generated tokens per hypothesis than `cap`.  Rows are indexed g * B + j (group g, slot
+// position j); tables marked "by slot" by the chain slot.  seqs: the call's slots; glist: the groups still stepping; gstate:
+// ZE_BM_GWORDS ints per group (steps done, done word, heuristic bit, prompt rows, token budget, float bits of budget ** length_penalty);
+// run_score / brank: running score and HF beam index of the hypothesis in a row; cand_*: k_beam_rows' table, B + n_eos per row;
+// parent (by slot): the slot whose hypothesis moves here; seen_prev (by slot): the seen byte select overwrote; bidx (by slot) [cap]:
+// the running beam indices; fin_*: the finished pool of a group (B entries, fin_order = rank -> entry); divs[n] = n ** length_penalty.
+enum { ZE_BM_GWORDS = 8, ZE_BM_MAX_BEAMS = 16 };
+struct ze_beam {
+    int cap = 0, rows = 0;      // generated tokens a hypothesis row holds; rows (= max_seqs)
+    int B = 0, groups = 0, max_new = 0;   // of the last call (ze_op_beam_finished reads with them)
+    int *seqs = nullptr, *glist = nullptr, *gstate = nullptr, *brank = nullptr, *cand_tok = nullptr, *parent = nullptr, *seen_prev = nullptr;
+    int *bidx = nullptr, *fin_len = nullptr, *fin_is = nullptr, *fin_order = nullptr, *fin_tok = nullptr, *fin_bidx = nullptr;
+    float *run_score = nullptr, *cand_score = nullptr, *fin_score = nullptr, *divs = nullptr;
+    int *u_seqs = nullptr, *u_parent = nullptr;   // ze_op_kv_reorder's own slot and parent tables (a beam call in progress keeps its own)
+};
+
 struct ze_engine {
     ze_config cfg{};
     int device = 0;
@@ -317,6 +334,7 @@ struct ze_engine {
     bool prefix_hints = true;      // the hint fits its 16 + 16 bits (ze_tune knob 17 = 1: every chain reads its own rows)
     ze_requests req;  // per-chain requests (above)
     ze_spec spec;     // speculative decoding (above)
+    ze_beam* beam = nullptr;  // beam search (above; null until the first beam call)
     const int* brow_off = nullptr;  // set while a speculative step is enqueued: its rows' offsets (batch_qkv, batch_attention)
     // prefix cache: the pool (null = none) and the generation of the weights -- bumped by whatever changes what a K/V row of given
     // tokens would be (ze_prefix_weights_changed), so that a block saved under another generation is never loaded
@@ -478,6 +496,12 @@ struct ze_spec_step {
 void ze_launch_spec_draft(const ze_spec_step& a, hipStream_t s);
 void ze_launch_spec_accept(const ze_spec_step& a, int first_chain, hipStream_t s);
 void ze_launch_spec_embed(const int* row_tok, int n, const bf16_t* embed, bf16_t* out, int hidden, hipStream_t s);
+
+// ---- beam search (ze_beam.hip)
+void ze_beam_free(ze_engine* e);   // (ze_engine_destroy)
+// one teacher-forced batched step of the chains `seqs` (ze_forward.hip): the forward of ze_decode_batch on the tokens their chain
+// states hold -- the cache grows by one row per chain, the logits rows stay in e->blogits, nothing is drawn
+int ze_beam_forward(ze_engine* e, const int32_t* seqs, int n, int use_graph, hipStream_t s);
 
 // ---- the launch sites of the forward passes (ze_forward.hip) that the profilers (ze_profile.hip) time: a projection's launcher is
 // chosen in these functions only, so a profiler cannot launch anything but what the pass launches

@@ -464,6 +464,7 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
         if (p) hipFree(p);
     ze_requests_free(e);
     ze_spec_free(e);
+    ze_beam_free(e);
     ze_prefix_pool_free(e);
     ze_lora_free(e);
     if (e->pfx_dev) hipFree(e->pfx_dev);

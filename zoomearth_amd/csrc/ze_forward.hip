@@ -1829,6 +1829,37 @@ static int batch_step_graph(ze_engine* e, int na, float pen, int ign, const ze_s
     return ZE_OK;
 }
 
+// The forward of a beam step (ze_beam.hip): the batched step without its sampler -- teacher forcing on the tokens the chain states
+// hold, as ze_decode_batch runs it; captured, it is the same linear chain of launches under a key of its own
+int ze_beam_forward(ze_engine* e, const int32_t* seqs, int n, int use_graph, hipStream_t s) {
+    ZE_TRY(upload_batch(e, seqs, n, s));
+    set_live_parts(e, seqs, n, 1);
+    const ze_sample_opts so{};
+    hipGraphExec_t gx = nullptr;
+    if (use_graph) {
+        ze_step_key key = ze_step_key_of(e, n, 0, 1.0f, 1, so);
+        key.n = n | 1 << 29;   // (no sampler: not the step ze_decode_burst captures for n chains)
+        if (e->bgraph_epoch != ze_tune_epoch) {
+            for (auto& kv : e->bgraphs) hipGraphExecDestroy(kv.second);
+            e->bgraphs.clear();
+            e->bgraph_epoch = ze_tune_epoch;
+        }
+        auto it = e->bgraphs.find(key);
+        if (it == e->bgraphs.end()) {
+            hipGraphExec_t ex = nullptr;
+            ZE_TRY(capture_step(e, [&](hipStream_t cs) { return enqueue_decode_batch(e, n, 1.0f, 1, 0, so, cs); }, &ex));
+            it = e->bgraphs.emplace(key, ex).first;
+        }
+        gx = it->second;
+    }
+    if (gx)
+        ZE_HIP(hipGraphLaunch(gx, s));
+    else
+        ZE_TRY(enqueue_decode_batch(e, n, 1.0f, 1, 0, so, s));
+    for (int i = 0; i < n; ++i) e->ctx_host[seqs[i]] += 1, e->logits_fresh[seqs[i]] = 0;
+    return ZE_OK;
+}
+
 // `steps` sampled decode steps for the chains in `active` (all with room for them)
 static int run_burst(ze_engine* e, const std::vector<int>& active, int steps, const ze_gen_params* p, float pen, int ign,
                      const ze_sample_opts& bso, hipStream_t s) {

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "ze_host.h"
@@ -163,4 +164,58 @@ int ze_rope_index_impl(const int32_t* ids, int len, const int32_t* grid_thw, int
     }
     *rope_delta = maxpos + 1 - len;
     return 0;
+}
+
+// ---- beam search: the host-only checks (ze_host.h)
+int ze_beam_check_impl(const int32_t* seqs, int groups, int num_beams, int num_return_sequences, int max_new_tokens, int early_stopping,
+                       float length_penalty, float repetition_penalty, int max_seqs, int max_ctx, const char** why) {
+    const char* sink;
+    if (!why) why = &sink;
+    if (!seqs) return *why = "null argument", -1;
+    if (groups <= 0 || num_beams < 1 || num_beams > 16) return *why = "beam search: groups >= 1 and 1 <= num_beams <= 16", -1;
+    if (num_return_sequences < 1 || num_return_sequences > num_beams) return *why = "beam search: 1 <= num_return_sequences <= num_beams", -1;
+    if (max_new_tokens < 1 || max_new_tokens > max_ctx) return *why = "beam search: 1 <= max_new_tokens <= max_ctx", -1;
+    if (early_stopping < 0 || early_stopping > 2) return *why = "beam search: early_stopping is 0, 1 or 2 (never)", -1;
+    if (!std::isfinite(length_penalty) || !std::isfinite(repetition_penalty) || repetition_penalty < 0.f)
+        return *why = "beam search: length_penalty and repetition_penalty must be finite (repetition_penalty > 0, 0 = off)", -1;
+    if ((long long)groups * num_beams > max_seqs) return *why = "beam search: groups * num_beams exceeds max_seqs", -1;
+    const int n = groups * num_beams;
+    std::vector<char> named(std::max(max_seqs, 0), 0);
+    for (int i = 0; i < n; ++i) {
+        if (seqs[i] < 0 || seqs[i] >= max_seqs) return *why = "sequence id out of range", -4;
+        if (named[seqs[i]]) return *why = "beam search: a slot is named twice", -1;
+        named[seqs[i]] = 1;
+    }
+    return 0;
+}
+
+int ze_kv_reorder_check_impl(const int32_t* src_seqs, const int32_t* dst_seqs, int n, int row0, int rows, int max_seqs, int max_ctx,
+                             const char** why) {
+    const char* sink;
+    if (!why) why = &sink;
+    if (n < 0 || (n > 0 && (!src_seqs || !dst_seqs))) return *why = "null argument", -1;
+    if (n > max_seqs) return *why = "kv reorder: more pairs than slots", -1;
+    if (row0 < 0 || rows < 0 || (long long)row0 + rows > max_ctx) return *why = "kv reorder: rows outside [0, max_ctx]", -1;
+    std::vector<char> is_src(std::max(max_seqs, 0), 0), is_dst(std::max(max_seqs, 0), 0);
+    for (int i = 0; i < n; ++i) {
+        if (src_seqs[i] < 0 || src_seqs[i] >= max_seqs || dst_seqs[i] < 0 || dst_seqs[i] >= max_seqs) return *why = "sequence id out of range", -4;
+        is_src[src_seqs[i]] = 1;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (is_src[dst_seqs[i]]) return *why = "kv reorder: a destination is also a source", -1;
+        if (is_dst[dst_seqs[i]]) return *why = "kv reorder: a destination is named twice", -1;
+        is_dst[dst_seqs[i]] = 1;
+    }
+    return 0;
+}
+
+void ze_beam_divs_impl(float length_penalty, int max_new_tokens, std::vector<float>& divs) {
+    divs.assign((size_t)std::max(max_new_tokens, 0) + 1, 1.0f);
+    for (int n = 0; n <= max_new_tokens; ++n) divs[n] = (float)pow((double)std::max(n, 1), (double)length_penalty);
+}
+
+void ze_beam_live_impl(const std::vector<int>& live, const std::vector<char>& done, const std::vector<int>& budget, int t, std::vector<int>& still) {
+    still.clear();
+    for (int g : live)
+        if (g >= 0 && (size_t)g < done.size() && (size_t)g < budget.size() && !done[g] && t < budget[g]) still.push_back(g);
 }

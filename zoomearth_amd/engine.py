@@ -720,6 +720,76 @@ class Engine:
         a, p = _i32(list(dsts))
         self._check(self.lib.ze_seq_fork(self.h, int(src), p, len(a), self._stream()))
 
+    # -- beam search (csrc/ze_beam.hip)
+    EARLY_STOPPING = {False: 0, True: 1, "never": 2}
+
+    def _beam_params(self, num_beams, num_return_sequences, max_new_tokens, length_penalty, early_stopping, repetition_penalty,
+                     use_graph=True, sync_every=8):
+        if early_stopping not in self.EARLY_STOPPING:
+            raise ValueError(f"early_stopping must be False, True or 'never', not {early_stopping!r}")
+        return _lib.ZeBeamParams(int(num_beams), int(num_return_sequences), int(max_new_tokens), float(length_penalty),
+                                 self.EARLY_STOPPING[early_stopping], float(repetition_penalty), int(bool(use_graph)), int(sync_every))
+
+    def beam_search(self, seqs, groups: int, num_beams: int, max_new_tokens: int, num_return_sequences: int = 1,
+                    length_penalty: float = 1.0, early_stopping=False, repetition_penalty: float = 1.0, use_graph: bool = True,
+                    sync_every: int = 8):
+        """Beam search over `groups` prompts (ze_beam_search): seqs[g * num_beams] is the prefilled, unstepped chain of group g, the
+        other slots of the group are taken by the call.  Returns (tokens, scores, beam_indices): per group a list of
+        num_return_sequences id lists, best first; HF's sequences_scores [groups, n]; and the beam indices per returned sequence."""
+        sq, sp = _i32(list(seqs))
+        if len(sq) != groups * num_beams:
+            raise ValueError("seqs must name groups * num_beams slots")
+        p = self._beam_params(num_beams, num_return_sequences, max_new_tokens, length_penalty, early_stopping, repetition_penalty,
+                              use_graph, sync_every)
+        n = groups * num_return_sequences
+        tok = np.zeros((max(n, 1), max(max_new_tokens, 1)), np.int32)
+        bix = np.zeros_like(tok)
+        ln = np.zeros(max(n, 1), np.int32)
+        sc = np.zeros(max(n, 1), np.float32)
+        self._check(self.lib.ze_beam_search(self.h, sp, int(groups), C.byref(p), tok.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            ln.ctypes.data_as(C.POINTER(C.c_int32)), sc.ctypes.data_as(C.POINTER(C.c_float)),
+                                            bix.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()))
+        R = num_return_sequences
+        tokens = [[tok[g * R + r, :ln[g * R + r]].tolist() for r in range(R)] for g in range(groups)]
+        indices = [[bix[g * R + r, :ln[g * R + r]].tolist() for r in range(R)] for g in range(groups)]
+        return tokens, sc[:n].reshape(groups, R).copy(), indices
+
+    def op_beam_step(self, seqs, groups: int, logits: torch.Tensor, begin: bool, num_beams: int, max_new_tokens: int,
+                     length_penalty: float = 1.0, early_stopping=False, repetition_penalty: float = 1.0, vocab: Optional[int] = None):
+        """One beam step on the caller's logits rows [groups * num_beams, ld] (ze_op_beam_step); returns a dict of host arrays:
+        parent, token, score, rank per row and done per group."""
+        sq, sp = _i32(list(seqs))
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == len(sq)
+        p = self._beam_params(num_beams, 1, max_new_tokens, length_penalty, early_stopping, repetition_penalty)
+        n = len(sq)
+        par, tok, rank = (np.zeros(n, np.int32) for _ in range(3))
+        sc = np.zeros(n, np.float32)
+        done = np.zeros(groups, np.int32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self.lib.ze_op_beam_step(self.h, sp, int(groups), C.byref(p), int(bool(begin)), _ptr(logits),
+                                             int(vocab if vocab is not None else logits.shape[1]), int(logits.stride(0)), ip(par), ip(tok),
+                                             sc.ctypes.data_as(C.POINTER(C.c_float)), ip(rank), ip(done), self._stream()))
+        return dict(parent=par, token=tok, score=sc, rank=rank, done=done)
+
+    def op_beam_finished(self, groups: int, num_beams: int, max_new_tokens: int):
+        """The finished pools of the last beam call, by rank: dict of tokens (lists), scores, beam_indices (lists), finished."""
+        n = groups * num_beams
+        tok = np.zeros((n, max_new_tokens), np.int32)
+        bix = np.zeros_like(tok)
+        ln, fin = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        sc = np.zeros(n, np.float32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self.lib.ze_op_beam_finished(self.h, int(groups), ip(tok), ip(ln), sc.ctypes.data_as(C.POINTER(C.c_float)), ip(bix),
+                                                 ip(fin), self._stream()))
+        return dict(tokens=[tok[i, :ln[i]].tolist() for i in range(n)], scores=sc, beam_indices=[bix[i, :ln[i]].tolist() for i in range(n)],
+                    finished=fin)
+
+    def op_kv_reorder(self, pairs, row0: int, rows: int):
+        """Cached rows [row0, row0 + rows) of every layer: chain dst takes chain src's, for every (src, dst) of `pairs` (ze_op_kv_reorder)."""
+        src, sp = _i32([a for a, _ in pairs])
+        dst, dp = _i32([b for _, b in pairs])
+        self._check(self.lib.ze_op_kv_reorder(self.h, sp, dp, len(src), int(row0), int(rows), self._stream()))
+
     # -- prefix cache: the engine's pool of K/V blocks (zoomearth_amd/prefix_cache.py decides what is in them)
     def prefix_pool_create(self, n_blocks: int, block_rows: int) -> None:
         self._check(self.lib.ze_prefix_pool_create(self.h, int(n_blocks), int(block_rows)))

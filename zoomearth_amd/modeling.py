@@ -47,6 +47,16 @@ class GenerateOutput:
     top_logprobs: torch.Tensor
 
 
+@dataclass
+class BeamSearchOutput:
+    """What beam_search(return_dict_in_generate=True) returns, HF's GenerateBeamDecoderOnlyOutput in the fields this path fills:
+    sequences [rows * num_return_sequences, prompt + new]; sequences_scores f32 (None without output_scores); beam_indices int32
+    [.., new]: per generated token the running beam it extended, the row's offset row * num_beams included, -1 behind a row's end."""
+    sequences: torch.Tensor
+    sequences_scores: Optional[torch.Tensor]
+    beam_indices: torch.Tensor
+
+
 class ScoreItem(NamedTuple):
     """One sequence of `score_sequences`: its ids; its images in order -- grids (t, h, w), ViT features bf16 [merged rows,
     hidden] and identity keys (None: never shared); and the first position whose next-token log-probability is wanted."""
@@ -685,6 +695,87 @@ class ZoomEarthForConditionalGeneration:
                     if self.engine.chain_grammar_state(slot)[0] >= 0:
                         self.engine.set_grammar(slot, None)
                 self.engine.grammar_destroy(gid)
+
+    @torch.no_grad()
+    def beam_search(self, input_ids=None, attention_mask=None, pixel_values=None, image_grid_thw=None, mm_token_type_ids=None,
+                    image_keys=None, num_beams: int = 2, max_new_tokens: int = 20, length_penalty: float = 1.0, early_stopping=False,
+                    num_return_sequences: int = 1, repetition_penalty=None, return_dict_in_generate: bool = False,
+                    output_scores: bool = False, **kw):
+        """Beam search on the device (Engine.beam_search; HF's `generate(num_beams=B, do_sample=False)`, which `generate` itself keeps
+        refusing).  Takes the inputs of `generate` and returns what it returns: prompt + ids, right-padded, rows (b0 r0, b0 r1, ...,
+        b1 r0, ...) for `num_return_sequences` = r per input row -- or, with `return_dict_in_generate`, a BeamSearchOutput with
+        `sequences`, `sequences_scores` (with `output_scores`) and `beam_indices`.  Beside the beam parameters only
+        `repetition_penalty` and the config's EOS ids apply; any other generation keyword is an error."""
+        B, R = num_beams, num_return_sequences
+        if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or B < 2:
+            raise ValueError(f"`num_beams` has to be an integer strictly greater than 1 for beam search, but is {B}")
+        if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or R < 1:
+            raise ValueError(f"`num_return_sequences` has to be a strictly positive integer, but is {R}")
+        if R > B:
+            raise ValueError(f"`num_return_sequences` ({R}) has to be smaller or equal to `num_beams` ({B}).")
+        if B > 16:
+            raise ValueError(f"`num_beams` is at most 16 on the device, but is {B}")
+        if kw.get("do_sample"):
+            raise ValueError("beam search is greedy here: `do_sample` with beams is not supported")
+        extra = sorted(k for k, v in kw.items() if k != "do_sample" and v is not None)
+        if extra:
+            raise ValueError(f"beam search takes the beam parameters and `repetition_penalty` only, not {extra}")
+        e, cfg = self.engine, self.config
+        ids_cpu = input_ids.cpu().numpy()
+        mask = attention_mask.cpu().numpy().astype(bool) if attention_mask is not None else np.ones_like(ids_cpu, bool)
+        grids = image_grid_thw.cpu().numpy().tolist() if image_grid_thw is not None else []
+        keys = list(image_keys) if image_keys is not None else [None] * len(grids)
+        offs = np.concatenate([[0], np.cumsum([g[0] * g[1] * g[2] for g in grids])]).astype(int)
+        pen = repetition_penalty if repetition_penalty is not None else getattr(self.generation_config, "repetition_penalty", 1.0) or 1.0
+        nrows = ids_cpu.shape[0]
+        if nrows * B > e.max_seqs:
+            raise ValueError(f"{nrows} rows of {B} beams need max_seqs >= {nrows * B} (engine has {e.max_seqs})")
+        self._chains.clear()   # every group takes B slots from slot b * B on
+        self._next_slot = 0
+        # (the decode family stays as it is -- a scheduler may have pinned it, and a change moves the weight generation; an engine
+        #  pinned to family 0 refuses more than 64 rows)
+        gi, pending = 0, []
+        for b in range(nrows):
+            ids = ids_cpu[b][mask[b]].astype(np.int64).tolist()
+            is_img = np.asarray(ids) == cfg.image_token_id
+            n_img = int((is_img & ~np.concatenate([[False], is_img[:-1]])).sum())
+            my = list(range(gi, gi + n_img))
+            gi += n_img
+            if gi > len(grids):
+                raise ValueError("Image features and image tokens do not match")
+            feats = [self._features(pixel_values[offs[i]:offs[i + 1]], grids[i], keys[i]) for i in my]
+            emb = (torch.cat(feats) if len(feats) > 1 else feats[0]) if feats else None
+            pos, delta = e.rope_index(ids, [grids[i] for i in my])
+            for j in range(B):
+                e.seq_reset(b * B + j)
+            pending.append((b * B, ids, emb, pos, delta))
+        group, rows = [], 0
+        for item in pending + [None]:
+            if group and (item is None or rows + len(item[1]) > e.max_prefill_rows):
+                e.prefill_batch([g[0] for g in group], [g[1] for g in group], [g[2] for g in group], [g[3] for g in group],
+                                [g[4] for g in group])
+                group, rows = [], 0
+            if item is not None:
+                group.append(item)
+                rows += len(item[1])
+        if pen != 1.0:   # (HF's RepetitionPenaltyLogitsProcessor sees the prompt's ids; the marks travel with the fork)
+            for slot, ids, _, _, _ in pending:
+                e.mark_seen(slot, ids)
+        tokens, scores, indices = e.beam_search(list(range(nrows * B)), nrows, B, max_new_tokens, num_return_sequences=R,
+                                                length_penalty=length_penalty, early_stopping=early_stopping, repetition_penalty=float(pen))
+        outs = [t for g in tokens for t in g]
+        width = max(len(t) for t in outs)
+        rep = np.repeat(ids_cpu, R, axis=0)
+        res = torch.full((rep.shape[0], rep.shape[1] + width), cfg.pad_token_id, dtype=torch.long)
+        res[:, : rep.shape[1]] = torch.from_numpy(rep)
+        bix = torch.full((rep.shape[0], width), -1, dtype=torch.int32)
+        for i, (t, x) in enumerate(zip(outs, (x for g in indices for x in g))):
+            res[i, rep.shape[1]: rep.shape[1] + len(t)] = torch.tensor(t, dtype=torch.long)
+            bix[i, : len(x)] = torch.tensor(x, dtype=torch.int32)
+        if not return_dict_in_generate:
+            return res.to(input_ids.device)
+        return BeamSearchOutput(sequences=res.to(input_ids.device),
+                                sequences_scores=torch.from_numpy(scores.reshape(-1).copy()) if output_scores else None, beam_indices=bix)
 
     def _generate_rows(self, rows: _Rows, chain: ChainRequest, gid, max_new_tokens, ignore_eos, sample_kw, stop_strings, tokenizer,
                        k: int = 1):

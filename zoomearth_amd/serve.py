@@ -9,6 +9,10 @@ base64,..."}}` items, plus `max_tokens`, `temperature`, `seed`, `top_p` and the 
 `min_p` (`stream` is not offered); the three filters apply to sampled requests, each request its own.  So do HF's `typical_p`,
 `epsilon_cutoff` and `eta_cutoff` (in (0, 1); 1.0 / 0.0 / 0.0 = off; anything else is a 400), behind the three on the device.
 `n` in [1, 16]: that many completions of the prompt, sampled requests only (n > 1 at temperature 0 / absent is a 400, vLLM's rule).
+vLLM's `use_beam_search: true`: beam search on the device (`model.beam_search`) with `n` (2 .. 16) as the beam width AND the number
+of choices, best first, and `length_penalty` (default 1.0); `repetition_penalty` applies; together with `temperature > 0`,
+`logprobs` / `prompt_logprobs`, the guided fields or any logit adjustment / stop field it is a 400.  It runs while no other request's
+chain is alive (it takes the engine's first n slots); requests that arrive behind it wait for it.
 The prompt is prefilled once and forked on the device (`ze_seq_fork`); the response carries `n` choices with `index` 0 .. n-1, each
 with its own `finish_reason`, `logprobs` and stop-string cut; choice i draws from random stream i of the request's `seed` (choice 0
 is what n = 1 returns); `usage.completion_tokens` sums the choices, `prompt_tokens` counts once, `prompt_logprobs` appears once.
@@ -131,6 +135,8 @@ class _Parsed:
     guided_regex: Optional[str] = None
     guided_choice: Optional[list] = None
     n: int = 1
+    use_beam_search: bool = False
+    length_penalty: float = 1.0
     future: Any = None
 
     def guided(self) -> bool:
@@ -207,7 +213,23 @@ class ChatServer:
         p.temperature = float(t) if p.sample else None
         if p.n > self.max_batch:
             raise BadRequest(f"n = {p.n} exceeds the engine's {self.max_batch} chain slots")
-        if p.n > 1 and not p.sample:
+        # vLLM's `use_beam_search`: `n` is the beam width AND the number of choices, `length_penalty` HF's; greedy only
+        ub = req.get("use_beam_search")
+        if ub is not None and not isinstance(ub, bool):
+            raise BadRequest(f"use_beam_search must be a boolean, got {ub!r}")
+        p.use_beam_search = bool(ub)
+        if p.use_beam_search:
+            if p.sample:
+                raise BadRequest("use_beam_search is greedy: it cannot be combined with temperature > 0")
+            if p.n < 2:
+                raise BadRequest("use_beam_search needs n >= 2: n is the beam width and the number of choices")
+            lpen = req.get("length_penalty")
+            if lpen is not None and (isinstance(lpen, bool) or not isinstance(lpen, (int, float)) or not math.isfinite(float(lpen))):
+                raise BadRequest(f"length_penalty must be a finite number, got {lpen!r}")
+            p.length_penalty = 1.0 if lpen is None else float(lpen)
+        elif req.get("length_penalty") is not None:
+            raise BadRequest("length_penalty needs use_beam_search = true")
+        if p.n > 1 and not p.sample and not p.use_beam_search:
             raise BadRequest(f"n = {p.n} needs temperature > 0: greedy completions would all be the same")
         p.seed = int(req.get("seed") or 0)
         # vLLM's `repetition_penalty`: None = the model's own (generation_config)
@@ -347,6 +369,14 @@ class ChatServer:
             except ValueError as ex:
                 raise BadRequest(f"guided decoding: {ex}") from ex
         p.guided_regex, p.guided_choice = gr, gc
+        if p.use_beam_search:   # the beam step serves the repetition penalty and the EOS ids only (ze_beam_search refuses the rest)
+            if p.logprobs is not None or p.prompt_logprobs is not None:
+                raise BadRequest("use_beam_search cannot be combined with logprobs / prompt_logprobs")
+            if p.guided():
+                raise BadRequest("use_beam_search cannot be combined with guided_regex / guided_choice")
+            if p.adjusts():
+                raise BadRequest("use_beam_search cannot be combined with presence_penalty / frequency_penalty / logit_bias / min_tokens / "
+                                 "stop / stop_token_ids / no_repeat_ngram_size")
         return p
 
     def _logprobs_block(self, p: _Parsed, ids, lp) -> dict:
@@ -465,9 +495,33 @@ class ChatServer:
                    for b in range(len(batch))]
         return [self._response(p, row, int(n), lp) for p, row, n, lp in zip(batch, out, n_in, lps)]
 
+    def _run_beam(self, p: _Parsed) -> dict:
+        """A `use_beam_search` request through model.beam_search: n beams, the n best finished hypotheses as n indexed choices, best
+        first.  The call takes the engine's first n slots, so the caller runs it while no scheduler chain is alive, under the lock."""
+        from .image import DeviceImage
+
+        images = [DeviceImage.from_pil(im, self.model.engine) for im in p.pil_images]
+        inputs = self.processor(text=[p.prompt], images=images or None, return_tensors="pt").to(self.model.device)
+        width, n_in = int(inputs["input_ids"].shape[1]), int(inputs["attention_mask"].sum())
+        kw = dict(num_beams=p.n, num_return_sequences=p.n, max_new_tokens=max(1, min(p.max_tokens, self.model.engine.max_ctx)),
+                  length_penalty=p.length_penalty)
+        if p.repetition_penalty is not None:
+            kw.update(repetition_penalty=p.repetition_penalty)
+        try:
+            out = self.model.beam_search(**inputs, **kw)[:, width:].tolist()
+        finally:
+            for slot in range(p.n):   # the slots go back empty
+                self.model.engine.seq_reset(slot)
+        return self._merge_choices([self._response(p, row, n_in) for row in out], n_in)
+
     # ------------------------------------------------------------------ entry points
     def complete(self, req: dict) -> dict:
         p = self._parse(req)
+        if p.use_beam_search:
+            if self._worker is not None:   # a dispatcher owns the chain slots: it runs the request while none of its chains is alive
+                return self.submit(req).result()
+            with self._lock:
+                return self._run_beam(p)
         if p.prompt_logprobs is not None or p.n > 1:   # the scheduler's work: the scoring prefill pass, the fork of n completions
             return self.submit(req).result()
         return self._run([p])[0]
@@ -484,8 +538,8 @@ class ChatServer:
                              "no_repeat_ngram_size / guided_regex / guided_choice are not batched")
         if len(batch) > self.max_batch:
             raise BadRequest(f"batch of {len(batch)} exceeds max_seqs = {self.max_batch}")
-        if any(p.prompt_logprobs is not None or p.n > 1 for p in batch):
-            raise BadRequest("requests with prompt_logprobs or n > 1 go through submit() / complete()")
+        if any(p.prompt_logprobs is not None or p.n > 1 or p.use_beam_search for p in batch):
+            raise BadRequest("requests with prompt_logprobs or n > 1 go through submit() / complete()")   # (use_beam_search has n > 1)
         return self._run(batch)
 
     def submit(self, req: dict):
@@ -558,13 +612,16 @@ class ChatServer:
         from .scheduler import ChainScheduler
 
         sched = None
+        beams, held = [], []   # beam requests wait for the running chains to end; what arrives behind them waits for the beams
         while True:
             with self._cv:
-                while not self._queue and not self._stop and not (sched is not None and sched.busy()):
+                # (a beam request that waits for the running chains to end is work too, and so is what waits behind it: neither
+                #  the wait nor the stop may pass them by)
+                while not self._queue and not self._stop and not beams and not (sched is not None and sched.busy()):
                     self._cv.wait()
-                if self._stop and not self._queue and not (sched is not None and sched.busy()):
+                if self._stop and not self._queue and not beams and not (sched is not None and sched.busy()):
                     return
-                if sched is None or not sched.busy():  # idle: give concurrent arrivals a moment to share the first prefill
+                if not beams and (sched is None or not sched.busy()):  # idle: give concurrent arrivals a moment to share the first prefill
                     deadline = time.monotonic() + self.batch_window_s
                     while len(self._queue) < self.max_batch and not self._stop:
                         left = deadline - time.monotonic()
@@ -584,12 +641,26 @@ class ChatServer:
                         kw["speculative_tokens"] = self.speculative_ngram
                     sched = ChainScheduler(self.model, self.processor, do_sample=False, max_batch=self.max_batch, burst=8, **kw)
                     self.scheduler = sched
+                def admit(reqs):
+                    for p in reqs:
+                        try:
+                            sched.submit(self._request(p))
+                        except Exception as ex:
+                            if not p.future.done():
+                                p.future.set_exception(ex)
+
+                ahead = []   # arrivals in front of the first waiting beam request go to the scheduler as ever
                 for p in new:
-                    try:
-                        sched.submit(self._request(p))
-                    except Exception as ex:
-                        if not p.future.done():
+                    (beams if p.use_beam_search else held if beams else ahead).append(p)
+                admit(ahead)
+                if beams and not sched.busy():   # model.beam_search takes the first n slots: only while no chain is alive
+                    for p in beams:
+                        try:
+                            p.future.set_result(self._run_beam(p))
+                        except Exception as ex:
                             p.future.set_exception(ex)
+                    waiting, beams, held = held, [], []
+                    admit(waiting)
                 if sched.busy():
                     try:
                         sched.step()
