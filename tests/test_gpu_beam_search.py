@@ -513,3 +513,28 @@ def test_server_runs_a_beam_request_that_waited_for_running_chains(stack):
     assert res[0]["choices"] == res[2]["choices"] and res[1]["choices"] == res[3]["choices"]
     alone = serve.ChatServer(model, proc, "ZoomEarth")
     assert alone.complete(beam)["choices"] == res[1]["choices"] and alone.complete(plain)["choices"] == res[0]["choices"]
+
+
+# ---------------------------------------------------------------- f. the captured forward of a beam step is the eager one
+@pytest.mark.parametrize("regime", [0, 1])
+def test_captured_beam_search_equals_eager(eng, regime):
+    """2 groups x 3 beams, 8 new tokens, a host check every 3 steps: the call whose forwards replay a captured step (the unsampled
+    kind of the engine's one step cache) against the call that enqueues every forward.  The same launches on the same rows, so
+    tokens and beam indices are equal and the scores are the same float32 bits -- no tolerance."""
+    e, G, B, N = eng, 2, 3, 8
+    prompts = (text_ids(31, 23), text_ids(32, 31))
+    slots = list(range(G * B))
+    e.set_decode_regime(regime)
+    try:
+        runs = []
+        for use_graph in (True, False):
+            for g in range(G):
+                prefill_text(e, slots[g * B], prompts[g])
+                e.mark_seen(slots[g * B], prompts[g])
+            runs.append(e.beam_search(slots, G, B, N, num_return_sequences=B, repetition_penalty=1.3, use_graph=use_graph, sync_every=3))
+        (tok_c, sc_c, ix_c), (tok_e, sc_e, ix_e) = runs
+        assert all(len(t) == N for g in tok_c for t in g), "the comparison is for hypotheses of full length"
+        assert tok_c == tok_e and ix_c == ix_e
+        assert np.array_equal(sc_c.view(np.uint32), sc_e.view(np.uint32)), (sc_c, sc_e)
+    finally:
+        e.set_decode_regime(-1)

@@ -405,3 +405,93 @@ def e_generate_family0(model, rows, n, pen):
     if len(rows) > 1:
         return e.generate_batch(list(range(len(rows))), n, repetition_penalty=pen, ignore_eos=True)
     return e.generate_speculative([0], n, repetition_penalty=pen, ignore_eos=True)     # (no request set: plain family-0 bursts)
+
+
+# ---------------------------------------------------------------- 7. the captured step is the eager step; no step leaks into the next
+LONG = [repeating(378), repeating(186, shift=2), repeating(25, shift=4)]   # 24 new tokens: chain 0 crosses key 384, chain 1 key 192
+
+
+def burst_run(e, prompts, spec_k, lookup, n_new, use_graph):
+    """generate_speculative over chains 0 .. of `prompts` (spec_k[i] = 0: a plain chain); returns (ids per chain, stats per chain)."""
+    seqs = list(range(len(prompts)))
+    for s, ids in zip(seqs, prompts):
+        prefill_text(e, s, ids)
+        if spec_k[s]:
+            e.set_speculation(s, spec_k[s], lookup[s], 1, 3)
+    toks = e.generate_speculative(seqs, n_new, repetition_penalty=1.3, ignore_eos=True, use_graph=use_graph)
+    return toks, [e.spec_stats(s) for s in seqs]
+
+
+def test_captured_speculative_bursts_equal_eager_ones(eng):
+    """Two speculating chains (k = 3) and a plain one through the same bursts, 24 new tokens, once with every step replayed from the
+    engine's step cache and once with every step enqueued: the same launches on the same rows, so the ids and the counters are equal.
+    The lookup texts hold (part of) the plain continuation, so that drafts are accepted across the part boundaries."""
+    plain, _ = burst_run(eng, LONG, [0, 0, 0], None, 24, True)
+    lookup = [LONG[0] + plain[0], LONG[1] + plain[1][:14], None]
+    captured = burst_run(eng, LONG, [3, 3, 0], lookup, 24, True)
+    eager = burst_run(eng, LONG, [3, 3, 0], lookup, 24, False)
+    print("stats", captured[1], eager[1])
+    assert captured[0] == eager[0] and captured[1] == eager[1]
+    assert captured[0] == plain and all(len(t) == 24 for t in plain)
+    assert captured[1][0][2] > 0 and captured[1][1][2] > 0 and captured[1][2] == (0, 0, 0)   # a run that never speculated fails here
+
+
+SHORT = [repeating(40), repeating(33, shift=2), repeating(25, shift=4)]
+
+
+def step_calls(plain_ids):
+    """The kinds of batched step by name, each a function of an engine that prefills its own chains and returns what the call gave."""
+    def f32_bits(t):
+        return t.cpu().numpy().view(np.uint32)
+
+    def plain(e):
+        return burst_run(e, SHORT, [0, 0, 0], None, 9, True)[0]
+
+    def spec(e):
+        return burst_run(e, SHORT, [3, 2, 0], [SHORT[0] + plain_ids[0], SHORT[1] + plain_ids[1], None], 9, True)
+
+    def rows(e):
+        prefill_text(e, 1, SHORT[1])
+        return f32_bits(e.decode_rows(1, [21, 22, 23, 24, 25])).tolist()
+
+    def beam(e):
+        prefill_text(e, 0, SHORT[2])
+        tokens, scores, indices = e.beam_search([0, 1, 2], 1, 3, 6, num_return_sequences=3, repetition_penalty=1.3, sync_every=2)
+        return tokens, scores.view(np.uint32).tolist(), indices
+
+    def decode_batch(e):
+        for s, ids in enumerate(SHORT):
+            prefill_text(e, s, ids)
+        return f32_bits(e.decode_batch([2, 0, 1], [31, 32, 33])).tolist()
+
+    return dict(plain=plain, spec=spec, rows=rows, beam=beam, decode_batch=decode_batch)
+
+
+def test_no_step_leaks_into_the_next(eng):
+    """Every kind of batched step in a row on ONE engine -- a plain captured burst of 3 chains, a speculative burst, decode_rows of 5
+    rows, a beam search, decode_batch, the plain burst again -- each against the same call made first on an engine of its own.  A step
+    takes its rows from the ze_step_rows it is handed and no engine member changes while it is enqueued (there is no guard that swaps
+    the engine's buffers and puts them back), so this holds by construction: a step that read another step's row table, logits,
+    partials or tickets fails here."""
+    from zoomearth_amd.config import ModelConfig
+    from zoomearth_amd.engine import Engine
+
+    def first_on_a_fresh_engine(call):
+        e = Engine(ModelConfig.tiny(), device=0, max_seqs=3, max_ctx=MAX_CTX, max_patches=64, max_tile_side=64)
+        try:
+            e.fill_synthetic(**CHAIN_W)
+            e.set_decode_regime(0)
+            return call(e)
+        finally:
+            e.close()
+
+    plain_ids = first_on_a_fresh_engine(step_calls(None)["plain"])
+    calls = step_calls(plain_ids)
+    want = {name: first_on_a_fresh_engine(call) for name, call in calls.items() if name != "plain"}
+    want["plain"] = plain_ids
+    assert want["spec"][1][0][2] > 0 and want["spec"][0][2] == plain_ids[2]      # drafts were accepted; the plain chain is the plain chain
+    order = ["plain", "spec", "rows", "beam", "decode_batch", "plain"]
+    got = [calls[name](eng) for name in order]
+    for name, g in zip(order, got):
+        assert g == want[name], name
+    assert got[0] == got[-1]

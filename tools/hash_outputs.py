@@ -48,5 +48,28 @@ for label, cfg in (("tiny", ModelConfig.tiny()),
         e.seq_reset(s)
         e.prefill(s, tid, None, p2, d2, want_logits=False)
     h(label + " decode_batch", e.decode_batch([1, 2], [11, 12]))
+    # every kind of batched step (plain burst captured and eager, speculative burst, rows of one chain, beam search)
+    texts = [uniform_ints(20 + s, n, 10, vocab - 100).tolist() for s, n in ((0, 190), (1, 150), (2, 97))]
+    def chains(spec=None):
+        for s, tid in enumerate(texts):
+            p2, d2 = e.rope_index(tid, [])
+            e.seq_reset(s)
+            e.prefill(s, tid, None, p2, d2, want_logits=False)
+            e.mark_seen(s, tid)
+            if spec and spec[s]:
+                e.set_speculation(s, spec[s], tid + plain[s])
+    chains()
+    plain = e.generate_speculative([0, 1, 2], 12, repetition_penalty=1.1, ignore_eos=True, use_graph=True)
+    chains()
+    eager = e.generate_speculative([0, 1, 2], 12, repetition_penalty=1.1, ignore_eos=True, use_graph=False)
+    print(label, "burst captured", plain, "eager", eager)
+    chains(spec=(3, 2, 0))
+    print(label, "speculative burst", e.generate_speculative([0, 1, 2], 12, repetition_penalty=1.1, ignore_eos=True),
+          [e.spec_stats(s) for s in range(3)])
+    chains()
+    h(label + " decode_rows", e.decode_rows(0, uniform_ints(8, 5, 10, vocab - 100).tolist()))
+    chains()
+    tokens, scores, indices = e.beam_search([1, 0, 2], 1, 3, 6, num_return_sequences=3, repetition_penalty=1.1, sync_every=2)
+    print(label, "beam search", tokens, scores.view(np.uint32).tolist(), indices)
     e.close()
     torch.cuda.empty_cache()

@@ -13,6 +13,7 @@
 //   workspaces    ViT activations for max_patches rows; prefill activations for max_ctx rows; decode vectors
 #pragma once
 #include <algorithm>
+#include <functional>
 #include <map>
 #include <tuple>
 #include <set>
@@ -59,8 +60,11 @@ struct ze_dest {
 
 // What a captured decode step was captured under: every value its launch sequence or a kernel argument depends on.  Built in one
 // place, ze_step_key_of (ze_requests.hip); a request kind that changes what a step launches adds its mode here and there.
+enum { ZE_STEP_SAMPLED = 0, ZE_STEP_UNSAMPLED = 1, ZE_STEP_SPEC = 2 };
 struct ze_step_key {
-    int n = 0;  // chains of a batched step; 0 = the single-chain step
+    int n = 0;  // rows of a batched step; 0 = the single-chain step
+    int kind = ZE_STEP_SAMPLED;     // batched step: with its sampler, without it (beam search), or speculative (draft .. accept)
+    int n_plain = 0, n_chains = 0;  // speculative step only: the rows the sampler takes, the chains the drafter and the accept pass walk
     float penalty = 0.f;
     int ignore_eos = 0;
     float temperature = 0.f;
@@ -70,7 +74,7 @@ struct ze_step_key {
     int sampling_bits = 0;                     // bit 0 = sampling filters, bit 1 = per-chain sampling table, bit 2 = ... with a draw, bit 3 = entropy filters
     int lp_mode = 0, la_mode = 0, tr_mode = 0, gr_mode = 0;
     auto tied() const {
-        return std::tie(n, penalty, ignore_eos, temperature, seed, tune_epoch, live_parts, live_parts_long, sampling_bits, lp_mode, la_mode,
+        return std::tie(n, kind, n_plain, n_chains, penalty, ignore_eos, temperature, seed, tune_epoch, live_parts, live_parts_long, sampling_bits, lp_mode, la_mode,
                         tr_mode, gr_mode);
     }
     bool operator==(const ze_step_key& o) const { return tied() == o.tied(); }
@@ -220,7 +224,7 @@ struct ze_lora {
     size_t store_bytes = 0;
 };
 
-// Speculative decoding by prompt lookup (ze_spec.hip; the steps themselves: ze_forward.hip).  host: the truth per slot (k = 0: off);
+// Speculative decoding by prompt lookup (ze_spec.hip; the steps themselves: ze_decode_batch.hip).  host: the truth per slot (k = 0: off);
 // table: the per-slot device words the drafter and the accept pass read (ZE_SP_WORDS ints: k, min_ngram, max_ngram, prompt ids, then
 // the counters steps / drafted / accepted), written in stream order by the setter; n_spec = slots with a request.  While it is 0 no
 // burst launches anything for it.  The prompt ids live in the context history of the token rules (ze_requests::tr_ctx: the two
@@ -320,12 +324,12 @@ struct ze_engine {
     // token those passes pushed into the chain state (the prompt's last id)
     std::vector<char> logits_fresh;
     std::vector<int> tok_host;
-    int* bmate = nullptr;          // [max_seqs] per row of the batched step: the row it shares its prefix parts with, or -1 (upload_batch)
+    int* bmate = nullptr;          // [max_seqs] per row of the batched step: the row it shares its prefix parts with, or -1 (upload_mates)
     int live_parts_long = 0;       // 384-key parts of the batch's longest chain under its split (the pipelined attention's grid extent)
     // Shared-prefix hints, (source chain << 16) | P per chain slot.  pfx_host is the truth, kept by whatever call changes it
     // (ze_seq_copy_prefix on the admission stream, ze_seq_retire, ...); the device copy pfx_dev -- what the decode attention
     // reads -- is written by ONE stream only: the stream of the batched decode step, which pushes the words that differ from
-    // pfx_pushed for ITS chains before it enqueues the step (sync_prefix, ze_forward.hip).  A chain state pushed from another
+    // pfx_pushed for ITS chains before it enqueues the step (sync_prefix, ze_forward.hip; called from ze_decode_batch.hip).  A chain state pushed from another
     // stream can therefore never bring a stale hint back.  pfx_copy_ev[seq]: recorded behind the chain's last
     // ze_seq_copy_prefix (null = none): only a chain whose copy has COMPLETED may become the holder other chains read from.
     std::vector<int> pfx_host, pfx_pushed;
@@ -335,7 +339,6 @@ struct ze_engine {
     ze_requests req;  // per-chain requests (above)
     ze_spec spec;     // speculative decoding (above)
     ze_beam* beam = nullptr;  // beam search (above; null until the first beam call)
-    const int* brow_off = nullptr;  // set while a speculative step is enqueued: its rows' offsets (batch_qkv, batch_attention)
     // prefix cache: the pool (null = none) and the generation of the weights -- bumped by whatever changes what a K/V row of given
     // tokens would be (ze_prefix_weights_changed), so that a block saved under another generation is never loaded
     ze_prefix_pool* prefix_pool = nullptr;
@@ -475,8 +478,9 @@ int ze_check_entropy_filter(ze_engine* e, float typical_p, float epsilon_cutoff,
 void ze_attach_filters(ze_engine* e, ze_sample_opts& so, bool batch);
 float ze_penalty_of(const ze_engine* e, const ze_gen_params* p, int seq);
 ze_sample_opts ze_sample_opts_of(ze_engine* e, const ze_gen_params* p, int slot, bool batch = false);
-// n = 0: the single-chain step of chain `seq`; else the batched step of n chains
-ze_step_key ze_step_key_of(const ze_engine* e, int n, int seq, float penalty, int ignore_eos, const ze_sample_opts& so);
+// n = 0: the single-chain step of chain `seq`; else the batched step of n rows, of `kind` (a speculative one with its layout)
+ze_step_key ze_step_key_of(const ze_engine* e, int n, int seq, float penalty, int ignore_eos, const ze_sample_opts& so,
+                           int kind = ZE_STEP_SAMPLED, int n_plain = 0, int n_chains = 0);
 
 // ---- speculative decoding (ze_spec.hip)
 void ze_spec_free(ze_engine* e);
@@ -499,11 +503,11 @@ void ze_launch_spec_embed(const int* row_tok, int n, const bf16_t* embed, bf16_t
 
 // ---- beam search (ze_beam.hip)
 void ze_beam_free(ze_engine* e);   // (ze_engine_destroy)
-// one teacher-forced batched step of the chains `seqs` (ze_forward.hip): the forward of ze_decode_batch on the tokens their chain
+// one teacher-forced batched step of the chains `seqs` (ze_decode_batch.hip): the forward of ze_decode_batch on the tokens their chain
 // states hold -- the cache grows by one row per chain, the logits rows stay in e->blogits, nothing is drawn
 int ze_beam_forward(ze_engine* e, const int32_t* seqs, int n, int use_graph, hipStream_t s);
 
-// ---- the launch sites of the forward passes (ze_forward.hip) that the profilers (ze_profile.hip) time: a projection's launcher is
+// ---- the launch sites of the forward passes (ze_forward.hip, ze_decode_batch.hip) that the profilers (ze_profile.hip) time: a projection's launcher is
 // chosen in these functions only, so a profiler cannot launch anything but what the pass launches
 enum { ZE_PROJ_QKV = 0, ZE_PROJ_O = 1, ZE_PROJ_GATE_UP = 2, ZE_PROJ_DOWN = 3 };
 enum { ZE_NORM_IN = 0, ZE_NORM_POST = 1, ZE_NORM_FINAL = 2 };
@@ -512,14 +516,31 @@ void prefill_projection(ze_engine* e, const ze_text_layer& L, int which, int row
 // single-chain decode: the cleared GEMV arguments with the weight (the FP8 copy too on a quantised engine), N, K, x and D set
 ze_gemv_args gemv_args_of(const ze_engine* e, const ze_linear& lin, int N, int K, const bf16_t* x);
 ze_linear lm_head_linear(const ze_engine* e, bool decode);
-// batched decode: one launch kind each for the n chains of e->bseq; a projection returns whether it streamed FP8 weights
-void batch_norm(ze_engine* e, int li, int n, int which, hipStream_t s);
-bool batch_qkv(ze_engine* e, int li, int n, hipStream_t s);  // with the rope / KV-append launch where that is not fused
-void batch_attention(ze_engine* e, int li, int n, hipStream_t s);
-bool batch_o(ze_engine* e, int li, int n, hipStream_t s);
-bool batch_gate_up(ze_engine* e, int li, int n, hipStream_t s);
-bool batch_down(ze_engine* e, int li, int n, hipStream_t s);
-bool batch_lm_head(ze_engine* e, int li, int n, hipStream_t s);
+// The rows of one batched decode step (ze_decode_batch.hip): what its launches read or write per row that differs between the
+// kinds of step.  A launch takes its rows from this struct and from nowhere else; no engine member changes while a step is enqueued.
+struct ze_step_rows {
+    const int* seq;      // row -> chain slot
+    const int* off;      // row -> its offset behind the chain's context; null = one row per chain, at the chain's own ctx
+    const int* mate;     // row -> the row it shares its prefix parts with (upload_mates); null = no pairing
+    const bf16_t* q;     // the qkv rows the attention reads ...
+    bf16_t* out;         // ... and the rows it writes
+    float* logits;       // [rows, vocab]
+    float* partial;      // attention partials
+    unsigned* tickets;   // arrival tickets of the attention's merge
+};
+ze_step_rows ze_rows_own(const ze_engine* e);   // the engine's own step buffers: the plain step, beam, ze_decode_batch, the profiler
+ze_step_rows ze_rows_spec(const ze_engine* e);  // the speculative row table (ze_spec): spec_burst, ze_op_decode_rows
+ze_step_rows ze_rows_caller(const ze_engine* e, const bf16_t* q, bf16_t* out);   // the engine's chains, the caller's q / out rows: ze_op_attn_decode
+// batched decode: one launch kind each for the n rows of `rows`; a projection returns whether it streamed FP8 weights
+void batch_norm(ze_engine* e, const ze_step_rows& rows, int li, int n, int which, hipStream_t s);
+bool batch_qkv(ze_engine* e, const ze_step_rows& rows, int li, int n, hipStream_t s);  // with the rope / KV-append launch where that is not fused
+void batch_attention(ze_engine* e, const ze_step_rows& rows, int li, int n, hipStream_t s);
+bool batch_o(ze_engine* e, const ze_step_rows& rows, int li, int n, hipStream_t s);
+bool batch_gate_up(ze_engine* e, const ze_step_rows& rows, int li, int n, hipStream_t s);
+bool batch_down(ze_engine* e, const ze_step_rows& rows, int li, int n, hipStream_t s);
+bool batch_lm_head(ze_engine* e, const ze_step_rows& rows, int li, int n, hipStream_t s);
+// the decode attention of a step alone (frag_out: its output in the fragment layout the o projection of family 0 reads)
+void launch_batch_attention(ze_engine* e, const ze_step_rows& rows, int li, int n, bool frag_out, hipStream_t s);
 // the scored-row path of a scoring pass (ze_score.hip): final norm of the n hidden rows e->tscore lists, lm_head in chunks of the
 // MLP workspace, log-softmax pick of their targets into out (device f32 [n]); n = 0 launches nothing
 void ze_launch_rmsnorm_gather(const bf16_t* x, int ldx, const int* src_rows, const bf16_t* w, bf16_t* y, int ldy, int rows, int cols,
@@ -539,8 +560,14 @@ int ze_score_rows(ze_engine* e, int n, float* out, const ze_score_detail_out* de
 // what a batched step sets up before its launches
 int ensure_fragments(ze_engine* e, hipStream_t s);
 void sync_prefix(ze_engine* e, const int32_t* seqs, int n, hipStream_t s);
-void upload_mates(ze_engine* e, const int32_t* seqs, int n, hipStream_t s);
 void set_live_parts(ze_engine* e, const int32_t* seqs, int n, int steps);
+// ... all of it for `steps` steps of the (valid) chains `seqs`: e->bseq, the prefix hints, the mates, the attention grids' extents
+void stage_batch(ze_engine* e, const int32_t* seqs, int n, int steps, hipStream_t s);
+// helpers of ze_forward.hip that the batched paths (ze_decode_batch.hip) share with the single-chain ones
+int capture_step(ze_engine* e, const std::function<int(hipStream_t)>& enqueue, hipGraphExec_t* exec);
+int first_token(ze_engine* e, int q, float pen, int ign, const ze_sample_opts& so, hipStream_t s);
+int trim_at_eos(const ze_config& c, const int32_t* tokens, int n);
+int xfer_reserve(ze_engine* e, int*& host, int*& dev, size_t& cap, size_t need, hipEvent_t staged, hipStream_t s);
 // chain bookkeeping shared with ze_prefix.hip: the readers of rows >= keep of chain `seq` move to another holder; the chain state
 // of `seq` goes to the device in stream order
 void prefix_source_gone(ze_engine* e, int seq, int keep);

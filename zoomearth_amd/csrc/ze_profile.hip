@@ -1,6 +1,6 @@
 // Measurement entries: the kernels of the forward passes, alone, between HIP events on the caller's stream.  Nothing here chooses
-// a launcher: every projection goes through the function the pass itself calls (ze_forward.hip: gemv_args_of, the batch_* launches,
-// prefill_projection), so a profiler times what the pass runs.
+// a launcher: every projection goes through the function the pass itself calls (ze_forward.hip: gemv_args_of, prefill_projection;
+// ze_decode_batch.hip: the batch_* launches), so a profiler times what the pass runs.
 #include <string.h>
 
 #include <vector>
@@ -116,29 +116,27 @@ extern "C" int ze_profile_batch_kernel(ze_engine* e, int which, int n, int iters
         seqs[i] = i;
         kv_bytes += (double)(std::min(e->ctx_host[i] + 1, c.max_ctx)) * nkv * 2 * 2;
     }
-    ze_launch_set_ints(e->bseq, seqs.data(), n, s);
-    sync_prefix(e, seqs.data(), n, s);
-    upload_mates(e, seqs.data(), n, s);
-    set_live_parts(e, seqs.data(), n, 1);  // (the grid a decode step of these chains would launch)
+    stage_batch(e, seqs.data(), n, 1, s);  // (the row table, the hints, the mates and the grid a decode step of these chains would launch)
+    const ze_step_rows rows = ze_rows_own(e);
     double bytes = 0;
     auto launch = [&](int it) {
         const int li = it % c.layers;
         switch (which) {
-            case 0: bytes = weight_bytes(nqkv, H, batch_qkv(e, li, n, s)); break;
-            case 1: bytes = weight_bytes(H, nq, batch_o(e, li, n, s)); break;
-            case 2: bytes = weight_bytes(2.0 * c.intermediate, H, batch_gate_up(e, li, n, s)); break;
-            case 3: bytes = weight_bytes(H, c.intermediate, batch_down(e, li, n, s)); break;
-            case 4: bytes = weight_bytes(c.vocab, H, batch_lm_head(e, li, n, s)); break;
+            case 0: bytes = weight_bytes(nqkv, H, batch_qkv(e, rows, li, n, s)); break;
+            case 1: bytes = weight_bytes(H, nq, batch_o(e, rows, li, n, s)); break;
+            case 2: bytes = weight_bytes(2.0 * c.intermediate, H, batch_gate_up(e, rows, li, n, s)); break;
+            case 3: bytes = weight_bytes(H, c.intermediate, batch_down(e, rows, li, n, s)); break;
+            case 4: bytes = weight_bytes(c.vocab, H, batch_lm_head(e, rows, li, n, s)); break;
             case 5:
-                batch_attention(e, li, n, s);
+                batch_attention(e, rows, li, n, s);
                 bytes = kv_bytes;
                 break;
             case 6:
-                batch_norm(e, li, n, ZE_NORM_IN, s);
+                batch_norm(e, rows, li, n, ZE_NORM_IN, s);
                 bytes = (double)n * H * 2 * 2;
                 break;
             default:
-                ze_launch_rope_kv_batch(e->bqkv, n, c.heads, c.kv_heads, hd, e->cosT, e->sinT, e->st_dev, e->bseq, e->kc(li, 0),
+                ze_launch_rope_kv_batch(e->bqkv, n, c.heads, c.kv_heads, hd, e->cosT, e->sinT, e->st_dev, rows.seq, e->kc(li, 0),
                                         e->vc(li, 0), (size_t)c.kv_heads * c.max_ctx * hd, c.max_ctx, s);
                 bytes = (double)n * nqkv * 2 * 2;
                 break;

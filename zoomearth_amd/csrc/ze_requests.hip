@@ -598,10 +598,14 @@ ze_sample_opts ze_sample_opts_of(ze_engine* e, const ze_gen_params* p, int slot,
 
 // The key of a captured step: the effective values of the launch (a new request re-captures), and per request kind what the step
 // launches for it -- of a single-chain step by THAT chain's request, of a batched step by the engine's.  Never a request's values.
-ze_step_key ze_step_key_of(const ze_engine* e, int n, int seq, float penalty, int ignore_eos, const ze_sample_opts& so) {
+ze_step_key ze_step_key_of(const ze_engine* e, int n, int seq, float penalty, int ignore_eos, const ze_sample_opts& so, int kind, int n_plain,
+                           int n_chains) {
     const ze_requests& q = e->req;
     ze_step_key k;
     k.n = n;
+    k.kind = kind;
+    k.n_plain = n_plain;
+    k.n_chains = n_chains;
     k.penalty = penalty;
     k.ignore_eos = ignore_eos;
     k.temperature = so.temperature;

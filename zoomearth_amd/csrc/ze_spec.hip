@@ -1,6 +1,6 @@
 // Speculative decoding by prompt lookup (HF: generate(prompt_lookup_num_tokens=, max_matching_ngram_size=); vLLM: the `ngram`
 // speculative method): the drafter, the accept pass, the row table of a speculative step, their unit entries and the setter.
-// The step itself -- draft -> rows -> the fragment family's launches -> accept -- is enqueued by ze_forward.hip (spec_burst).
+// The step itself -- draft -> rows -> the fragment family's launches -> accept -- is enqueued by ze_decode_batch.hip (spec_burst).
 //
 // Drafter (normative: tests/spec_ref.py restates it).  The history of a chain is its prompt ids followed by its generated ids, n
 // ids in all.  For g = max_ngram down to min_ngram with g < n: among the starts p in [0, n - g - 1] with
