@@ -736,8 +736,8 @@ int ze_op_linear_mx(ze_engine* e, const void* a8, const void* sa, const void* w8
  * bf16(code * 2^e) is exact.  4.25 bits per weight.
  * ze_weights_quantize_mxfp4 quantises the tensors ze_weights_quantize_fp8 does (the decoder's projections, an untied lm_head),
  * REPLACES their bf16 values by the dequantised ones and makes the batch-1 decode GEMVs (ze_decode_step, ze_generate, a single-chain
- * burst) read the 4-bit stream; prefill, scoring, both batched decode families, the ViT and the fragment-major copies compute from
- * the dequantised bf16 arena: one model whichever kernel serves a token.  A tensor whose K is not a multiple of 32 keeps its bf16
+ * burst) read the 4-bit stream; prefill, scoring, both batched decode families, the ViT compute from
+ * the dequantised bf16 arena (the fragment kernels of family 0: see below): one model whichever kernel serves a token.  A tensor whose K is not a multiple of 32 keeps its bf16
  * stream (none of the 3B / 7B decoder tensors: K = 2048 / 11008 and 3584 / 18944).  Life cycle as the FP8 switch: captured graphs
  * and fragment copies are dropped, the prefix pool's generation moves; any base-weight write (load, fill, arena hand-out, broadcast)
  * and any adapter switch drops the stream -- quantise again, from the merged arena after a switch (the base store keeps the values
@@ -749,7 +749,26 @@ int ze_op_linear_mx(ze_engine* e, const void* a8, const void* sa, const void* w8
  * ze_op_gemv4: ze_op_gemv with the MXFP4 stream as W (q4 / scale_e8m0 in the canonical layout, fp32 accumulation, every prologue
  * and epilogue of ze_op_gemv; there are no FP8 activations on this stream).  K % 32 != 0 is ZE_ERR_INVALID, an x that does not
  * fit the LDS stage ZE_ERR_NOMEM: outputs untouched, no other kernel runs in its place.
- * ze_weight_format: which stream the batch-1 decode reads now. */
+ * ze_weight_format: which stream the batch-1 decode reads now.
+ * The 2 .. 64-chain step of decode family 0 (the fragment kernels; the speculative step included) streams 4-bit copies too: its qkv,
+ * o, gate/up and untied lm_head launches read fragment-major MXFP4 copies of q / scale (below) and dequantise in registers right
+ * before the MFMA -- code * 2^e is exact in bf16, so every row is BIT-IDENTICAL to the one the dequantised bf16 fragments give
+ * (ze_tune knob 24 = 1 runs those, for the A/B and the bit-equality test).  The down projection of that step (the split-K ring, no
+ * fragment kernel), decode family 1, prefill, scoring and the ViT keep computing from the dequantised arena.
+ * Fragment-major MXFP4 copy (ze_gemm.hip / ze_gemm_oneshot.hip W4, packed by k_pack_fragments4 in ze_quant.hip), for W [N, K],
+ * N % 16 == 0, K % 32 == 0, nb = row / 16, ks = k / 32, S = K / 32:
+ *   codes  u8 [N / 16][S][64 lanes][4]: lane = (k % 32) / 8 * 16 + row % 16 holds the 8 codes of k = 32 ks + 8 (lane / 16) .. + 7 of
+ *          its row, the four bytes q[row][k / 2 .. + 3] unchanged (even k in the low nibble): 256 B per 16 x 32 fragment, in the
+ *          fragment order of the bf16 and FP8 copies (the qkv copy with the same per-head row permutation);
+ *   scales u8 [N / 16][S][16]: byte (nb, ks, r) = scale[row r of block nb][ks] -- one 32-k MFMA slice of a row is one MX block, so
+ *          the four lane groups of a row read the same byte, and the scales of a wave's prefetch chunk (consecutive ks of one
+ *          block) are 16 x chunk contiguous bytes.
+ * ze_op_gemm4: the unit entry of those kernels.  launcher 5 / 6 and epi as ze_op_gemm (the fragment-major skinny / one-shot
+ * kernels; none + bias, residual, SwiGLU and fp32 on 5, none + bias and residual on 6), a bf16 [M, lda], q4 / scale_e8m0 in the
+ * canonical row-major layout (packed inside the call), the limits of ze_op_gemm's fragment path.  ZE_ERR_INVALID, nothing launched:
+ * any other launcher (none has a 4-bit form), K % 32 != 0, and whatever ze_op_gemm refuses for the launcher.
+ * ze_fragment_bytes: the device bytes the fragment copies of decode family 0 hold now (bf16 + FP8 + MXFP4 copies); 0 before the
+ * first batched step and after anything that drops them. */
 #define ZE_WEIGHTS_BF16 0
 #define ZE_WEIGHTS_FP8 1
 #define ZE_WEIGHTS_MXFP4 2
@@ -759,6 +778,9 @@ int ze_op_gemv4(ze_engine* e, int epi, const void* q4, const void* scale_e8m0, c
                 const void* bias_bf16, int N, int K, void* out_bf16, float* out_f32, const uint8_t* seen, float penalty,
                 int32_t* out_token, int seq, int layer, const void* embed, int token, void* embed_out, void* stream);
 int ze_weight_format(ze_engine* e);
+int ze_op_gemm4(ze_engine* e, int launcher, int epi, const void* a_bf16, int lda, const void* q4, const void* scale_e8m0,
+                const void* bias_bf16, const void* r_bf16, int ldr, void* c, int ldc, int M, int N, int K, void* stream);
+int ze_fragment_bytes(ze_engine* e, size_t* bytes);
 
 /* ------------------------------------------------------------------ unit ops for parity tests (K3-K22) */
 /* C[M,N] = A[M,K] * W[N,K]^T (+bias[N]) ; bf16 in, fp32 accumulate, bf16 out (one rounding).  act: 0 none, 1 exact GELU,
@@ -949,7 +971,7 @@ int ze_profile_prefill_kernel(ze_engine* e, int which, int rows, int iters, floa
  * `top_kernel_by_gpu_time` quotes next to the rocprofv3 figure of the replayed pass.  avg_us / flops: [0] qkv [1] o [2] gate/up [3] down. */
 int ze_profile_prefill_layer(ze_engine* e, int rows, int layers_run, float avg_us[4], double flops[4], void* stream);
 /* Measurement-only kernel-configuration override (A/B of kernels and launch shapes inside one process; value 0 is always
- * the shipped default, every alternative computes the same function -- bit for bit unless noted).  Knobs (0..23; round 4 re-used
+ * the shipped default, every alternative computes the same function -- bit for bit unless noted).  Knobs (0..24; round 4 re-used
  * knobs 3 and 4, which until round 3 switched the removed one-launch-per-layer kernels: an old `3:1` / `4:1` habit now changes GEMM
  * tiling / launch form -- same results, different speed):
  *   0, 1  variants of the single-chain down / gate-up GEMVs          2   grid cap of the GEMV family
@@ -975,6 +997,7 @@ int ze_profile_prefill_layer(ze_engine* e, int rows, int layers_run, float avg_u
  *            them; the M-RoPE kernel then writes K and V only; same bits)
  *   23    batched decode attention, round 6 (built, measured slower, off): 2 = a chain's parts cut at its split row, 3 = that + two chains
  *            of a tile per workgroup on the prefix parts (2 and 3: the same bits; against 0 -- parts of the whole context -- within rounding)
+ *   24    1: dequantised bf16 fragments in the 2 .. 64-chain step of an MXFP4 engine (default: the 4-bit fragment stream; same bits)
  * Changing a knob invalidates captured decode graphs (they are re-captured on the next step).
  * PROCESS-WIDE, by design: there is no engine argument, every engine of the process sees the value at its next launch, and nothing in
  * the product path (Engine, scheduler, entry points, clone_lane) calls it -- a knob is for A/B measurements and the bit-equality tests,

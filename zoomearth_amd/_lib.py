@@ -211,6 +211,8 @@ _SIGS = {
     "ze_op_linear": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ze_op_gemm": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int,
                              C.c_int, _P]),
+    "ze_op_gemm4": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ze_fragment_bytes": (C.c_int, [_P, C.POINTER(C.c_size_t)]),
     "ze_op_rmsnorm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P]),
     "ze_op_attention": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
                                   C.c_int, C.c_int, _P]),

@@ -804,7 +804,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
     }
 }
 
-extern int ze_gemv_knobs[24];
+extern int ze_gemv_knobs[25];
 
 #ifdef ZE_ATTN_ROWS_UNIT
 // the pipelined kernel's ROWS form over the n rows of a step; `parts`: the 384-key parts the longest row can have (the grid's extent)

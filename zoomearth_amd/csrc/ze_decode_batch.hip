@@ -8,7 +8,7 @@
 
 #include "ze_engine.h"
 
-extern int ze_gemv_knobs[24];
+extern int ze_gemv_knobs[25];
 
 // ================================================================== batched decode (BASELINE configs[2])
 // One token for each of n chains per step: the weights are streamed ONCE for the whole batch through the MFMA GEMM
@@ -17,8 +17,12 @@ extern int ze_gemv_knobs[24];
 // depend on which other chains share its steps.
 // Fragment-major copies of the wide, short-K decode projections for the batched step (see ze_engine.h).  Shapes the
 // fragment kernel does not cover (rows % 16, K % 32, K > 4096) keep wf = null and stay on the row-major launchers.
+// MXFP4 engine: the 4-bit fragment stream of the 2 .. 64-chain step (ze_tune knob 24 = 1: dequantised bf16 fragments, the form before
+// the W4 kernels -- same bits; kept for the A/B and the bit-equality test)
+static bool want_frag4(const ze_engine* e) { return e->mx4_ready && ze_gemv_knobs[24] != 1; }
+
 int ensure_fragments(ze_engine* e, hipStream_t s) {
-    if (e->frag_ready) return ZE_OK;
+    if (e->frag_ready && e->frag_w4 == want_frag4(e)) return ZE_OK;
     const ze_config& c = e->cfg;
     const int H = c.hidden, hd = e->head_dim, nq = c.heads * hd, nqkv = nq + 2 * c.kv_heads * hd, ip = e->text_ipad;
     const bool ok = H % 32 == 0 && H <= 4096 && nq % 32 == 0 && nq <= 4096 && nqkv % 16 == 0 && (2 * ip) % 32 == 0 && c.vocab % 16 == 0;
@@ -26,23 +30,30 @@ int ensure_fragments(ze_engine* e, hipStream_t s) {
         ze_text_layer& L = e->tl[li];
         L.qkv.wf = L.o.wf = L.gate_up.wf = nullptr;
         L.qkv.wf8 = L.o.wf8 = L.gate_up.wf8 = nullptr;   // (these stayed stale in the row-streaming regime)
+        L.qkv.wf4 = L.o.wf4 = L.gate_up.wf4 = nullptr;
+        L.qkv.sf4 = L.o.sf4 = L.gate_up.sf4 = nullptr;
         L.qkv.wp = L.qkv.bias_p = nullptr;
     }
     e->lm_head_f = nullptr;
     e->lm_head8.wf8 = nullptr;
+    e->lm_head8.wf4 = e->lm_head8.sf4 = nullptr;
+    e->frag_ready = false;
     // Each kernel family gets only the copies it reads: the row-streaming regime the permuted qkv rows (0.38 GB at the
     // 3B shape), the fragment family the fragment-major arena (4.5 GB) -- an engine of 64 slots never runs the first, one of 768
     // never the second.  ze_set_decode_regime clears frag_ready, so a regime change rebuilds what the new family needs.
     const bool wide = e->wide_regime();
     // ... and the OTHER family's copies are given back (after ze_set_decode_regime the 4.5-GB fragment arena, its FP8 twin
     // and the permuted qkv rows all stayed allocated).  A regime change is rare and never concurrent with a step: wait for the device.
-    if (wide ? (e->arena_f || e->arena_f8) : (e->arena_p != nullptr)) {
+    if (wide ? (e->arena_f || e->arena_f8 || e->arena_f4) : (e->arena_p != nullptr)) {
         ZE_HIP(hipDeviceSynchronize());
         if (wide) {
             if (e->arena_f) hipFree(e->arena_f);
             if (e->arena_f8) hipFree(e->arena_f8);
+            if (e->arena_f4) hipFree(e->arena_f4);
             e->arena_f = nullptr;
             e->arena_f8 = nullptr;
+            e->arena_f4 = nullptr;
+            e->arena_f_bytes = e->arena_f8_bytes = e->arena_f4_bytes = 0;
         } else {
             hipFree(e->arena_p);
             e->arena_p = nullptr;
@@ -79,23 +90,60 @@ int ensure_fragments(ze_engine* e, hipStream_t s) {
         ZE_KCHECK();
     }
     if (ok && !wide) {
-        const size_t per_layer = (size_t)(nqkv + 2 * ip) * H + (size_t)H * nq;
-        const size_t total = per_layer * c.layers + (size_t)c.vocab * H;
-        if (!e->arena_f) ZE_HIP(hipMalloc((void**)&e->arena_f, total * sizeof(bf16_t)));
+        // MXFP4 engine (want_frag4): a tensor the quantiser took (w4: K % 32 == 0) gets the 4-bit fragment copy INSTEAD of the bf16 one --
+        // codes + fragment-major scales, 4.25 bits per weight; every other tensor (a tied lm_head: the embedding table) bf16 fragments
+        const bool f4 = want_frag4(e);
+        struct item {
+            ze_linear* l;
+            int rows, cols, rope_dim;
+        };
+        std::vector<item> items;
+        for (int li = 0; li < c.layers; ++li) {
+            ze_text_layer& L = e->tl[li];
+            items.push_back({&L.qkv, nqkv, H, hd});  // rows permuted per head for the fused M-RoPE epilogue (ze_gemm_oneshot.hip)
+            items.push_back({&L.o, H, nq, 0});
+            items.push_back({&L.gate_up, 2 * ip, H, 0});
+        }
+        const bool head4 = f4 && e->lm_head8.w4 != nullptr;
+        size_t elems16 = head4 ? 0 : (size_t)c.vocab * H, bytes4 = head4 ? (size_t)c.vocab * H / 2 + (size_t)c.vocab * H / 32 : 0;
+        for (const item& it : items) {
+            if (f4 && it.l->w4) bytes4 += (size_t)it.rows * it.cols / 2 + (size_t)it.rows * it.cols / 32;
+            else elems16 += (size_t)it.rows * it.cols;
+        }
+        // (the two arenas are sized for the format in force: a format or knob change is rare and never concurrent with a step)
+        if (e->arena_f_bytes != elems16 * sizeof(bf16_t) || e->arena_f4_bytes != bytes4) {
+            ZE_HIP(hipDeviceSynchronize());
+            if (e->arena_f) hipFree(e->arena_f);
+            if (e->arena_f4) hipFree(e->arena_f4);
+            e->arena_f = nullptr;
+            e->arena_f4 = nullptr;
+            e->arena_f_bytes = e->arena_f4_bytes = 0;
+            if (elems16) ZE_HIP(hipMalloc((void**)&e->arena_f, elems16 * sizeof(bf16_t)));
+            e->arena_f_bytes = elems16 * sizeof(bf16_t);
+            if (bytes4) ZE_HIP(hipMalloc((void**)&e->arena_f4, bytes4));
+            e->arena_f4_bytes = bytes4;
+        }
         bf16_t* cur = e->arena_f;
+        uint8_t* cur4 = e->arena_f4;
         auto pack = [&](ze_linear& l, int rows, int cols, int rope_dim) {
+            if (f4 && l.w4) {
+                l.wf4 = cur4;
+                l.sf4 = cur4 + (size_t)rows * cols / 2;
+                ze_launch_pack_fragments4(l.w4, l.scale4, rows, cols, l.wf4, l.sf4, s, rope_dim);
+                cur4 = l.sf4 + (size_t)rows * cols / 32;
+                return;
+            }
             ze_launch_pack_fragments(l.w, l.ld, rows, cols, cur, s, rope_dim);
             l.wf = cur;
             cur += (size_t)rows * cols;
         };
-        for (int li = 0; li < c.layers; ++li) {
-            ze_text_layer& L = e->tl[li];
-            pack(L.qkv, nqkv, H, hd);  // rows permuted per head for the fused M-RoPE epilogue (ze_gemm_oneshot.hip)
-            pack(L.o, H, nq, 0);
-            pack(L.gate_up, 2 * ip, H, 0);
+        for (const item& it : items) pack(*it.l, it.rows, it.cols, it.rope_dim);
+        if (head4) {
+            pack(e->lm_head8, c.vocab, H, 0);
+        } else {
+            ze_launch_pack_fragments(e->lm_head, H, c.vocab, H, cur, s);
+            e->lm_head_f = cur;
         }
-        ze_launch_pack_fragments(e->lm_head, H, c.vocab, H, cur, s);
-        e->lm_head_f = cur;
         // FP8 engine: the same fragments at one byte per weight (qkv, o, gate/up, an untied lm_head); the batched step
         // streams these and dequantises in registers -- identical values, half the weight bytes
         for (int li = 0; li < c.layers; ++li) {
@@ -107,6 +155,7 @@ int ensure_fragments(ze_engine* e, hipStream_t s) {
             const bool head8 = e->lm_head8.w8 != nullptr;
             const size_t bytes = ((size_t)(nqkv + 2 * ip) * H + (size_t)H * nq) * c.layers + (head8 ? (size_t)c.vocab * H : 0);
             if (!e->arena_f8) ZE_HIP(hipMalloc((void**)&e->arena_f8, bytes));
+            e->arena_f8_bytes = bytes;
             uint8_t* c8 = e->arena_f8;
             auto pack8 = [&](ze_linear& l, int rows, int cols, int rope_dim) {
                 ze_launch_pack_fragments8(l.w8, l.ld8, rows, cols, c8, s, rope_dim);
@@ -124,6 +173,7 @@ int ensure_fragments(ze_engine* e, hipStream_t s) {
         ZE_KCHECK();
     }
     e->frag_ready = true;
+    e->frag_w4 = want_frag4(e);
     return ZE_OK;
 }
 
@@ -275,14 +325,27 @@ struct batch_regime {
 };
 // the FP8 fragment stream of a projection (quantised engine; ze_tune knob 10 = 1: the bf16 fragments)
 static bool frag8(const ze_linear& l) { return l.wf8 && ze_gemv_knobs[10] != 1; }
+// the weight operand of a fragment launch: the MXFP4 copy where ensure_fragments built one (there is no bf16 copy then), else the
+// FP8 copy of a quantised engine, else bf16 fragments
+struct frag_w {
+    const bf16_t* wf;
+    const float* scale8;
+    const uint8_t* scale4;
+    bool w8;
+};
+static frag_w frag_of(const ze_linear& l, const bf16_t* wf16) {
+    if (l.wf4) return frag_w{(const bf16_t*)l.wf4, nullptr, l.sf4, false};
+    if (frag8(l)) return frag_w{(const bf16_t*)l.wf8, l.scale8, nullptr, true};
+    return frag_w{wf16, nullptr, nullptr, false};
+}
 static batch_regime regime_of(const ze_engine* e, int li) {
     const ze_text_layer& L = e->tl[li];
     batch_regime r;
-    r.fr = L.qkv.wf && !e->wide_regime() && ze_gemv_knobs[5] != 1;
+    r.fr = L.qkv.has_frag() && !e->wide_regime() && ze_gemv_knobs[5] != 1;
     r.tiled = e->wide_regime() && ze_gemv_knobs[13] != 1;
     r.a8q = e->fp8_act && r.fr && frag8(L.qkv);
     r.a8g = e->fp8_act && r.fr && frag8(L.gate_up);
-    r.fl = e->lm_head_f && !e->wide_regime() && ze_gemv_knobs[5] != 1;
+    r.fl = (e->lm_head_f || e->lm_head8.wf4) && !e->wide_regime() && ze_gemv_knobs[5] != 1;
     return r;
 }
 
@@ -309,12 +372,12 @@ bool batch_qkv(ze_engine* e, const ze_step_rows& rows, int li, int n, hipStream_
     const batch_regime r = regime_of(e, li);
     const ze_gemm_ws ws = e->gemm_ws();
     if (r.fr) {  // projection + M-RoPE + KV append in one launch (the fragment copy of qkv is packed for it)
-        const bool w8 = frag8(L.qkv);
-        ze_launch_qkv_rope_oneshot(r.a8q ? (const bf16_t*)e->ty8 : e->by, w8 ? (const bf16_t*)L.qkv.wf8 : L.qkv.wf, L.qkv.bias,
+        const frag_w w = frag_of(L.qkv, L.qkv.wf);
+        ze_launch_qkv_rope_oneshot(r.a8q ? (const bf16_t*)e->ty8 : e->by, w.wf, L.qkv.bias,
                                    e->bqkv, nqkv, n, H, c.heads, c.kv_heads, e->cosT, e->sinT, e->st_dev, rows.seq,
-                                   e->kc(li, 0), e->vc(li, 0), seq_stride, c.max_ctx, s, w8 ? L.qkv.scale8 : nullptr,
-                                   r.a8q ? e->ty8_scale : nullptr, rows.off);
-        return w8;
+                                   e->kc(li, 0), e->vc(li, 0), seq_stride, c.max_ctx, s, w.scale8,
+                                   r.a8q ? e->ty8_scale : nullptr, rows.off, w.scale4);
+        return w.w8;
     }
     // row streaming: projection + M-RoPE + KV append in ONE launch on the permuted rows (same bits as the pair of
     // launches below; knob 13 = 2 keeps the pair, for A/B runs and the bit-equality test); its chain ids are e->bseq's (ze_rows_spec)
@@ -338,12 +401,13 @@ bool batch_o(ze_engine* e, const ze_step_rows& rows, int li, int n, hipStream_t 
     const ze_text_layer& L = e->tl[li];
     const batch_regime r = regime_of(e, li);
     if (r.fr && ze_gemv_knobs[9] != 1) {
-        const bool w8 = frag8(L.o);
-        ze_launch_gemm_oneshot(ZE_EPI_RESIDUAL, rows.out, w8 ? (const bf16_t*)L.o.wf8 : L.o.wf, nullptr, e->bh, H, e->bh, H, n, H, nq, s,
-                               w8 ? L.o.scale8 : nullptr);
-        return w8;
+        const frag_w w = frag_of(L.o, L.o.wf);
+        ze_launch_gemm_oneshot(ZE_EPI_RESIDUAL, rows.out, w.wf, nullptr, e->bh, H, e->bh, H, n, H, nq, s, w.scale8, nullptr, w.scale4);
+        return w.w8;
     }
-    if (r.fr) ze_launch_gemm_frag(ZE_EPI_RESIDUAL, rows.out, L.o.wf, nullptr, e->bh, H, e->bh, H, n, H, nq, s);
+    if (r.fr)  // (knob 9: bf16 fragments, or the MXFP4 ones where they are the only copy)
+        ze_launch_gemm_frag(ZE_EPI_RESIDUAL, rows.out, L.o.wf4 ? (const bf16_t*)L.o.wf4 : L.o.wf, nullptr, e->bh, H, e->bh, H, n, H, nq, s, nullptr,
+                            nullptr, L.o.wf4 ? L.o.sf4 : nullptr);
     else if (r.tiled) ze_launch_gemm_wide(ZE_EPI_RESIDUAL, rows.out, nq, L.o.w, L.o.ld, nullptr, e->bh, H, e->bh, H, n, H, nq, e->gemm_ws(), s);
     else ze_launch_gemm_stream(ZE_EPI_RESIDUAL, rows.out, nq, L.o.w, L.o.ld, nullptr, e->bh, H, e->bh, H, n, H, nq, e->gemm_ws(), s);
     return false;
@@ -354,10 +418,10 @@ bool batch_gate_up(ze_engine* e, const ze_step_rows& rows, int li, int n, hipStr
     const ze_text_layer& L = e->tl[li];
     const batch_regime r = regime_of(e, li);
     if (r.fr) {
-        const bool w8 = frag8(L.gate_up);
-        ze_launch_gemm_frag(ZE_EPI_SWIGLU, r.a8g ? (const bf16_t*)e->ty8 : e->by, w8 ? (const bf16_t*)L.gate_up.wf8 : L.gate_up.wf, nullptr,
-                            nullptr, 0, e->ba, ip, n, 2 * ip, H, s, w8 ? L.gate_up.scale8 : nullptr, r.a8g ? e->ty8_scale : nullptr);
-        return w8;
+        const frag_w w = frag_of(L.gate_up, L.gate_up.wf);
+        ze_launch_gemm_frag(ZE_EPI_SWIGLU, r.a8g ? (const bf16_t*)e->ty8 : e->by, w.wf, nullptr, nullptr, 0, e->ba, ip, n, 2 * ip, H, s,
+                            w.scale8, r.a8g ? e->ty8_scale : nullptr, w.scale4);
+        return w.w8;
     }
     if (r.tiled) ze_launch_gemm_wide(ZE_EPI_SWIGLU, e->by, H, L.gate_up.w, L.gate_up.ld, nullptr, nullptr, 0, e->ba, ip, n, 2 * ip, H, e->gemm_ws(), s);
     else ze_launch_gemm_stream(ZE_EPI_SWIGLU, e->by, H, L.gate_up.w, L.gate_up.ld, nullptr, nullptr, 0, e->ba, ip, n, 2 * ip, H, e->gemm_ws(), s);
@@ -380,10 +444,10 @@ bool batch_lm_head(ze_engine* e, const ze_step_rows& rows, int li, int n, hipStr
     const int H = c.hidden;
     const batch_regime r = regime_of(e, li);
     if (r.fl) {
-        const bool w8 = frag8(e->lm_head8);
-        ze_launch_gemm_frag(ZE_EPI_F32, e->by, w8 ? (const bf16_t*)e->lm_head8.wf8 : e->lm_head_f, nullptr, nullptr, 0,
-                            (bf16_t*)rows.logits, c.vocab, n, c.vocab, H, s, w8 ? e->lm_head8.scale8 : nullptr);
-        return w8;
+        const frag_w w = frag_of(e->lm_head8, e->lm_head_f);
+        ze_launch_gemm_frag(ZE_EPI_F32, e->by, w.wf, nullptr, nullptr, 0, (bf16_t*)rows.logits, c.vocab, n, c.vocab, H, s, w.scale8, nullptr,
+                            w.scale4);
+        return w.w8;
     }
     if (r.tiled)  // (one pass over K whatever the row count: batch invariance)
         ze_launch_gemm_wide(ZE_EPI_F32, e->by, H, e->lm_head, H, nullptr, nullptr, 0, (bf16_t*)rows.logits, c.vocab, n, c.vocab, H, e->gemm_ws(), s);

@@ -42,6 +42,11 @@ struct ze_linear {
     bf16_t* bias_p = nullptr;
     // the same in FP8 (ze_launch_pack_fragments8 of w8), streamed with scale8 when the engine is quantised, null = none
     uint8_t* wf8 = nullptr;
+    // the same in MXFP4 (ze_launch_pack_fragments4 of w4 / scale4): codes and fragment-major block scales, streamed by the W4 kernels
+    // of the 2 .. 64-chain step on an MXFP4 engine (such a tensor then has no bf16 fragments: wf stays null), null = none
+    uint8_t* wf4 = nullptr;
+    uint8_t* sf4 = nullptr;
+    bool has_frag() const { return wf || wf4; }
 };
 struct ze_vit_block {
     bf16_t *norm1 = nullptr, *norm2 = nullptr;
@@ -295,6 +300,9 @@ struct ze_engine {
     // the first batched step, rebuilt after any weight change (the 288 GB of HBM make the extra 4.2 GB free)
     bf16_t* arena_f = nullptr;
     uint8_t* arena_f8 = nullptr;  // FP8 fragment copies (fp8_ready only)
+    uint8_t* arena_f4 = nullptr;  // MXFP4 fragment copies: codes, then scales, per tensor (mx4_ready, ze_tune knob 24 = 0)
+    size_t arena_f_bytes = 0, arena_f8_bytes = 0, arena_f4_bytes = 0;  // what the three hold (ze_fragment_bytes)
+    bool frag_w4 = false;         // the copies were built for the 4-bit stream (a change of knob 24 rebuilds them)
     bf16_t* lm_head_f = nullptr;
     bool frag_ready = false;
     bf16_t* arena_p = nullptr;        // permuted qkv rows + biases of every layer (row-streaming regime, head_dim 128)

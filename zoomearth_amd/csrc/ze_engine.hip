@@ -36,9 +36,11 @@ void ze_weights_changed(ze_engine* e) {
             for (ze_linear* l : {&L.qkv, &L.o, &L.gate_up, &L.down}) {
                 l->w4 = nullptr;
                 l->scale4 = nullptr;
+                l->wf4 = l->sf4 = nullptr;
             }
         e->lm_head8.w4 = nullptr;
         e->lm_head8.scale4 = nullptr;
+        e->lm_head8.wf4 = e->lm_head8.sf4 = nullptr;
     }
     ++ze_tune_epoch;
 }
@@ -415,7 +417,7 @@ extern "C" int ze_engine_create(const ze_config* cfg, int device_id, ze_engine**
     return ZE_OK;
 }
 
-extern int ze_gemv_knobs[24];
+extern int ze_gemv_knobs[25];
 // prefill split-K slabs: 3 slices x (rows of the largest pass, padded to a 256-row tile) x (hidden, padded to a 256-column tile) floats --
 // the same whatever tile a row count selects -- and a zeroed ticket per 64 x 64 tile (the smallest).  Only with knob 20 = 3.
 ze_gemm_ws ze_engine::prefill_ws() {
@@ -458,7 +460,7 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
                    e->st_dev, e->seen, e->out_tokens, e->fe_tmp, e->fe_img, e->fe_coef, e->vx, e->vh, e->vy, e->vqkv,
                    e->vo, e->va, e->vz, e->vz2, e->vcos, e->vsin, e->vperm, e->vinv, e->vtiles_win, e->vtiles_full,
                    e->th, e->ty, e->tqkv, e->to, e->ta, e->tsrc, e->tpos, e->ttiles, e->ttile_aux, e->trow_aux, e->tscore, e->dh, e->dq, e->dattn, e->dact,
-                   e->dlogits, e->dpartial, e->dsample, e->atickets, e->gslab, e->gtickets, e->pslab, e->ptickets, e->bh, e->by, e->bqkv, e->bo, e->ba, e->bseq, e->bmate, e->blogits, e->bpartial, e->bsample, e->arena8, e->arena4, e->arena_f, e->arena_f8,
+                   e->dlogits, e->dpartial, e->dsample, e->atickets, e->gslab, e->gtickets, e->pslab, e->ptickets, e->bh, e->by, e->bqkv, e->bo, e->ba, e->bseq, e->bmate, e->blogits, e->bpartial, e->bsample, e->arena8, e->arena4, e->arena_f, e->arena_f8, e->arena_f4,
                    e->ty8, e->ty8_scale, e->damax, e->ty8p, e->ty8p_scale, e->xl_dev};
     for (void* p : dev)
         if (p) hipFree(p);

@@ -8,7 +8,7 @@
 
 #include "ze_engine.h"
 
-extern int ze_gemv_knobs[24];
+extern int ze_gemv_knobs[25];
 
 // ================================================================== front-end
 // dst = crop(src, box).resize((dst_w, dst_h), BICUBIC), Pillow-exact (two passes, u8 intermediate).
@@ -1483,7 +1483,7 @@ extern "C" int ze_op_linear(ze_engine* e, const void* a, const void* w, const vo
     } else if (act == 3 || act == 5) {  // the fragment-major kernels of the batched decode step, operands packed here
         if (M > 64 || N % 16 || K % 32 || K > 4096) return ze_fail(e, ZE_ERR_INVALID, "fragment path: M <= 64, N % 16, K % 32, K <= 4096");
         bf16_t *wf = nullptr, *xf = nullptr;
-        const size_t mp = (size_t)(M + 15) / 16 * 16;
+        const size_t mp = M <= 16 ? 16 : M <= 32 ? 32 : 64;  // the kernels read whole 16-row tiles: 1, 2 or 4 of them (dispatch_mt)
         ZE_HIP(hipMalloc((void**)&wf, ((size_t)N * K + mp * K) * sizeof(bf16_t)));
         xf = wf + (size_t)N * K;
         ze_launch_pack_fragments((const bf16_t*)w, K, N, K, wf, s);
@@ -1551,7 +1551,7 @@ extern "C" int ze_op_gemm(ze_engine* e, int launcher, int epi, const void* a, in
     bf16_t* C = (bf16_t*)cmat;
     if (frag) {  // operands packed here, as ze_op_linear act 3 / 5 does
         bf16_t *wf = nullptr, *xf = nullptr;
-        const size_t mp = (size_t)(M + 15) / 16 * 16;
+        const size_t mp = M <= 16 ? 16 : M <= 32 ? 32 : 64;  // the kernels read whole 16-row tiles: 1, 2 or 4 of them (dispatch_mt)
         ZE_HIP(hipMalloc((void**)&wf, ((size_t)N * K + mp * K) * sizeof(bf16_t)));
         xf = wf + (size_t)N * K;
         ze_launch_pack_fragments(W, ldw, N, K, wf, s);
@@ -1572,6 +1572,53 @@ extern "C" int ze_op_gemm(ze_engine* e, int launcher, int epi, const void* a, in
         default: ze_launch_gemm_wide(epi, A, lda, W, ldw, B, R, ldr, C, ldc, M, N, K, e->gemm_ws(), s); break;
     }
     ZE_KCHECK();
+    return ZE_OK;
+}
+
+// The W4 forms of the fragment launchers on one matrix: ze_op_gemm's launchers 5 / 6 with the MXFP4 stream as W (row-major q4 / scale
+// as ze_op_quantize_mxfp4 writes them, packed here by ze_launch_pack_fragments4).  tests/test_gpu_gemm4.py holds it against
+// ze_op_gemm on the dequantised bf16 weights, bit for bit.
+extern "C" int ze_op_gemm4(ze_engine* e, int launcher, int epi, const void* a, int lda, const void* q4, const void* scale_e8m0,
+                           const void* bias, const void* r, int ldr, void* cmat, int ldc, int M, int N, int K, void* stream) {
+    if (!e || !a || !q4 || !scale_e8m0 || !cmat) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    if (launcher != 5 && launcher != 6) return ze_fail(e, ZE_ERR_INVALID, "only launchers 5 and 6 (the fragment kernels) have an MXFP4 form");
+    if (M <= 0 || N <= 0 || K <= 0) return ze_fail(e, ZE_ERR_INVALID, "M, N, K > 0");
+    if (K % 32) return ze_fail(e, ZE_ERR_INVALID, "MXFP4: K must be a multiple of 32");
+    bool epi_ok = epi == ZE_EPI_NONE || epi == ZE_EPI_RESIDUAL;
+    if (launcher == 5) epi_ok = epi_ok || epi == ZE_EPI_SWIGLU || epi == ZE_EPI_F32;
+    if (!epi_ok) return ze_fail(e, ZE_ERR_INVALID, "the launcher has no kernel with this epilogue");
+    if (epi == ZE_EPI_RESIDUAL && !r) return ze_fail(e, ZE_ERR_INVALID, "RESIDUAL needs r");
+    if (epi == ZE_EPI_SWIGLU && N % 32) return ze_fail(e, ZE_ERR_INVALID, "SwiGLU: N = 2 * width with width % 16 == 0");
+    if (lda < K || ldc < (epi == ZE_EPI_SWIGLU ? N / 2 : N) || (epi == ZE_EPI_RESIDUAL && ldr < N))
+        return ze_fail(e, ZE_ERR_INVALID, "a leading dimension is below its extent");
+    if (lda % 8 || (size_t)a % 16 || (size_t)q4 % 4) return ze_fail(e, ZE_ERR_INVALID, "the rows of a start on 16-byte boundaries, q4 on a 4-byte one");
+    if (M > 64 || N % 16 || (launcher == 5 && K > 4096)) return ze_fail(e, ZE_ERR_INVALID, "fragment path: M <= 64, N % 16, K % 32, K <= 4096");
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    const bf16_t *A = (const bf16_t*)a, *B = (const bf16_t*)bias;
+    const bf16_t* R = epi == ZE_EPI_RESIDUAL ? (const bf16_t*)r : nullptr;
+    if (!R) ldr = 0;
+    bf16_t* C = (bf16_t*)cmat;
+    const size_t mp = M <= 16 ? 16 : M <= 32 ? 32 : 64;  // the kernels read whole 16-row tiles: 1, 2 or 4 of them (dispatch_mt)
+    const size_t codes = (size_t)N * K / 2, scales = (size_t)N * K / 32;
+    uint8_t* buf = nullptr;  // activation fragments, then the codes, then the scales
+    ZE_HIP(hipMalloc((void**)&buf, mp * K * sizeof(bf16_t) + codes + scales));
+    bf16_t* xf = (bf16_t*)buf;
+    uint8_t *wf4 = buf + mp * K * sizeof(bf16_t), *sf4 = wf4 + codes;
+    ze_launch_pack_fragments(A, lda, M, K, xf, s);
+    ze_launch_pack_fragments4((const uint8_t*)q4, (const uint8_t*)scale_e8m0, N, K, wf4, sf4, s);
+    if (launcher == 6) ze_launch_gemm_oneshot(epi, xf, (const bf16_t*)wf4, B, R, ldr, C, ldc, M, N, K, s, nullptr, nullptr, sf4);
+    else ze_launch_gemm_frag(epi, xf, (const bf16_t*)wf4, B, R, ldr, C, ldc, M, N, K, s, nullptr, nullptr, sf4);
+    hipError_t le = hipGetLastError();
+    hipStreamSynchronize(s);
+    hipFree(buf);
+    if (le != hipSuccess) return ze_fail(e, ZE_ERR_HIP, hipGetErrorString(le));
+    return ZE_OK;
+}
+
+extern "C" int ze_fragment_bytes(ze_engine* e, size_t* bytes) {
+    if (!e || !bytes) return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    *bytes = (e->frag_ready && !e->wide_regime()) ? e->arena_f_bytes + (e->fp8_ready ? e->arena_f8_bytes : 0) + e->arena_f4_bytes : 0;
     return ZE_OK;
 }
 
@@ -2136,7 +2183,7 @@ extern "C" int ze_set_decode_regime(ze_engine* e, int regime) {
 
 // ================================================================== measurement
 extern "C" int ze_tune(int knob, int value) {
-    if (knob < 0 || knob >= 24) return ze_fail(nullptr, ZE_ERR_INVALID, "unknown knob");
+    if (knob < 0 || knob >= 25) return ze_fail(nullptr, ZE_ERR_INVALID, "unknown knob");
     ze_gemv_knobs[knob] = value;
     ++ze_tune_epoch;  // captured decode steps bake the launch policy in: engines drop their graphs on the next use
     return ZE_OK;

@@ -21,7 +21,7 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 #define GEMM_BK 64
 
 extern int ze_live_engines;    // ze_gemv.hip: engines alive in this process
-extern int ze_gemv_knobs[24];  // [5]: 1 = no skinny kernel in the weight-streaming launcher; [6]: 0 = shipped policy, 1 = register-staged kernel everywhere, 2 = ring wherever it applies
+extern int ze_gemv_knobs[25];  // [5]: 1 = no skinny kernel in the weight-streaming launcher; [6]: 0 = shipped policy, 1 = register-staged kernel everywhere, 2 = ring wherever it applies
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
@@ -1651,10 +1651,11 @@ bool ze_launch_gemm_mx(int epi, const uint8_t* A, int lda, const float* sa, cons
 // down projection) then go through the slab / ticket reduction of gemm_finish.  The order of every sum is a function
 // of (K, ksplit) alone, so a chain's result does not depend on how many chains share the step.
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;  // an FP8 weight fragment of one lane: 8 bytes
-template <int TN, int CH, int MT, bool W8 = false, bool A8 = false>
+template <int TN, int CH, int MT, bool W8 = false, bool A8 = false, bool W4 = false>
 struct skinny_frag {
     typename std::conditional<A8, u32x2_t, bf16x8>::type a[CH][MT];
-    typename std::conditional<W8, u32x2_t, bf16x8>::type b[CH][TN];
+    typename std::conditional<W4, uint32_t, typename std::conditional<W8, u32x2_t, bf16x8>::type>::type b[CH][TN];
+    uint32_t e[W4 ? CH : 1][W4 ? TN : 1];  // W4: the E8M0 scale byte of each weight fragment's (row, 32-k block)
 };
 
 // FP8 (E4M3) weight fragment -> bf16 MFMA operand: 8 bytes per lane, all of ONE weight row, times that row's
@@ -1673,6 +1674,23 @@ __device__ __forceinline__ bf16x8 deq_fp8x8(u32x2_t w, float scale) {
     return u.v;
 }
 
+// MXFP4 weight fragment -> bf16 MFMA operand: 4 bytes per lane, the 8 codes of 8 consecutive k of ONE weight row (even k in the
+// low nibble), times 2^e of that row's 32-k block -- e8 = e + 127 is the exponent field of the float 2^e (the quantiser's clamp keeps
+// it in [2, 252]).  v_cvt_scalef32_pk_bf16_fp4: two values per instruction.  code * 2^e is one mantissa bit times a power of two, a
+// normal bf16, so the operand is the dequantised bf16 copy's, bit for bit, at 4.25 bits per weight.
+__device__ __forceinline__ bf16x8 deq_fp4x8(uint32_t w, uint32_t e8) {
+    const float scale = __uint_as_float(e8 << 23);
+    union {
+        bf16x2_t h[4];
+        bf16x8 v;
+    } u;
+    u.h[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0);
+    u.h[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1);
+    u.h[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2);
+    u.h[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3);
+    return u.v;
+}
+
 // FRAG: both operands are stored MFMA-fragment-major (k_pack_fragments / k_rmsnorm(frag)), so every fragment load
 // of a wave is one contiguous 1-KiB read (the row-major form reads 16 rows x 64 B per load, which the vector memory
 // path serves at a fraction of that rate: it is why the row-major kernel only pays on the narrow projections).
@@ -1687,7 +1705,10 @@ __device__ __forceinline__ bf16x8 deq_fp8x8(u32x2_t w, float scale) {
 // A8 (with W8): the activations are FP8 fragments as well (k_rmsnorm_row act8 = 2) and the product runs on
 // v_mfma_f32_16x16x32_fp8_fp8; `ascale` holds one power-of-two scale per activation row, applied with the weight row's to
 // the fp32 sums before the epilogue.
-template <int TN, int EPI, bool FRAG = false, int MT = 4, bool BAL = false, bool W8 = false, bool A8 = false>
+// W4: the fragment-major weights are MXFP4 (4 B per lane per fragment, k_pack_fragments4) and `wscale` points at their fragment-major
+// E8M0 block scales (bytes: 16 per fragment, the slices of a block back to back, so a prefetch chunk's scales are contiguous); a lane
+// loads its row's byte beside each weight fragment and dequantises in registers (deq_fp4x8) right before the MFMA.
+template <int TN, int EPI, bool FRAG = false, int MT = 4, bool BAL = false, bool W8 = false, bool A8 = false, bool W4 = false>
 __global__ void __launch_bounds__(256) k_gemm_skinny(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W,
                                                      int ldw, const bf16_t* __restrict__ bias,
                                                      const bf16_t* __restrict__ R, int ldr, bf16_t* __restrict__ C,
@@ -1697,6 +1718,7 @@ __global__ void __launch_bounds__(256) k_gemm_skinny(const bf16_t* __restrict__ 
                                                      const float* __restrict__ ascale = nullptr) {
     static_assert(!W8 || FRAG, "fp8 weights come fragment-major");
     static_assert(!A8 || W8, "fp8 activations go with fp8 weights");
+    static_assert(!W4 || (FRAG && !W8), "MXFP4 weights come fragment-major, one weight format per instantiation");
     constexpr int BN = 16 * TN, CH = (TN == 1) ? 4 : 2;  // MFMA slices per prefetch chunk
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     int nwg = (N + BN - 1) / BN;
@@ -1722,11 +1744,12 @@ __global__ void __launch_bounds__(256) k_gemm_skinny(const bf16_t* __restrict__ 
 
     // per-slice stride of a fragment pointer, in elements: 32 columns of a row (row-major) or one 1-KiB fragment
     constexpr int SSTR = FRAG ? 512 : 32;
-    constexpr int WSTR = W8 ? 256 : SSTR;  // an fp8 fragment is 512 B = 256 bf16-sized elements
+    constexpr int WSTR = W4 ? 128 : W8 ? 256 : SSTR;  // an fp8 fragment is 512 B = 256 bf16-sized elements, an MXFP4 one 256 B
     constexpr int ASTR = A8 ? 256 : SSTR;
     const bf16_t* wp[TN];
     const bf16_t* ap[4];
     float wsc[TN];
+    const uint8_t* sp4[TN];  // W4: this lane's row in the scale bytes of block j, 16 bytes per slice
 #pragma unroll
     for (int j = 0; j < TN; ++j) wsc[j] = 1.0f;
     if (FRAG) {
@@ -1734,8 +1757,9 @@ __global__ void __launch_bounds__(256) k_gemm_skinny(const bf16_t* __restrict__ 
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int blk = min((bn0 >> 4) + j, nb_last);
-            wp[j] = W + ((size_t)blk * ns_all * 64 + lane) * (W8 ? 4 : 8);
+            wp[j] = W + ((size_t)blk * ns_all * 64 + lane) * (W4 ? 2 : W8 ? 4 : 8);
             if (W8) wsc[j] = wscale[blk * 16 + fr];
+            if (W4) sp4[j] = reinterpret_cast<const uint8_t*>(wscale) + (size_t)blk * ns_all * 16 + fr;
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) ap[i] = A + ((size_t)min(i, mt - 1) * ns_all * 64 + lane) * (A8 ? 4 : 8);
@@ -1752,21 +1776,25 @@ __global__ void __launch_bounds__(256) k_gemm_skinny(const bf16_t* __restrict__ 
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    typedef typename std::conditional<W8, u32x2_t, bf16x8>::type wfrag_t;
+    typedef typename std::conditional<W4, uint32_t, typename std::conditional<W8, u32x2_t, bf16x8>::type>::type wfrag_t;
     typedef typename std::conditional<A8, u32x2_t, bf16x8>::type afrag_t;
-    auto load = [&](skinny_frag<TN, CH, MT, W8, A8>& f, int s) {
+    auto load = [&](skinny_frag<TN, CH, MT, W8, A8, W4>& f, int s) {
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             const int k = (s + c) * ASTR, kw = (s + c) * WSTR;
 #pragma unroll
             for (int j = 0; j < TN; ++j)  // streamed once: non-temporal
                 f.b[c][j] = __builtin_nontemporal_load(reinterpret_cast<const wfrag_t*>(wp[j] + kw));
+            if constexpr (W4) {
+#pragma unroll
+                for (int j = 0; j < TN; ++j) f.e[c][j] = sp4[j][(s + c) * 16];
+            }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 if (i < mt) f.a[c][i] = *reinterpret_cast<const afrag_t*>(ap[i] + k);
         }
     };
-    auto mac = [&](const skinny_frag<TN, CH, MT, W8, A8>& f) {
+    auto mac = [&](const skinny_frag<TN, CH, MT, W8, A8, W4>& f) {
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             if constexpr (A8) {  // both operands as they came from memory
@@ -1783,7 +1811,8 @@ __global__ void __launch_bounds__(256) k_gemm_skinny(const bf16_t* __restrict__ 
                 bf16x8 fb[TN];
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-                    if constexpr (W8) fb[j] = deq_fp8x8(f.b[c][j], wsc[j]);
+                    if constexpr (W4) fb[j] = deq_fp4x8(f.b[c][j], f.e[c][j]);
+                    else if constexpr (W8) fb[j] = deq_fp8x8(f.b[c][j], wsc[j]);
                     else fb[j] = f.b[c][j];
                 }
 #pragma unroll
@@ -1798,7 +1827,7 @@ __global__ void __launch_bounds__(256) k_gemm_skinny(const bf16_t* __restrict__ 
     };
     const int nch = ns / CH;
     {
-        skinny_frag<TN, CH, MT, W8, A8> f0, f1;
+        skinny_frag<TN, CH, MT, W8, A8, W4> f0, f1;
         if (nch > 0) load(f0, s0);
         int c = 0;
         for (; c + 2 <= nch; c += 2) {
@@ -1816,7 +1845,8 @@ __global__ void __launch_bounds__(256) k_gemm_skinny(const bf16_t* __restrict__ 
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             raw[j] = __builtin_nontemporal_load(reinterpret_cast<const wfrag_t*>(wp[j] + kw));
-            if constexpr (W8 && !A8) fb[j] = deq_fp8x8(raw[j], wsc[j]);
+            if constexpr (W4) fb[j] = deq_fp4x8(raw[j], sp4[j][s * 16]);
+            else if constexpr (W8 && !A8) fb[j] = deq_fp8x8(raw[j], wsc[j]);
             else if constexpr (!W8) fb[j] = raw[j];
         }
 #pragma unroll
@@ -2065,8 +2095,9 @@ struct gemm_frag_call {
     int M, N, K;
     hipStream_t s;
     const float *wscale, *ascale;  // FP8 weight fragments / FP8 activation fragments: the scales per row; null = bf16
+    const uint8_t* wscale4;        // MXFP4 weight fragments: their fragment-major block scales; null = not MXFP4
 };
-template <int TN, int MT, bool W8 = false, bool A8 = false>
+template <int TN, int MT, bool W8 = false, bool A8 = false, bool W4 = false>
 static void launch_frag_mt(const gemm_frag_call& c) {
     const int ksplit = 1;  // (no split-K: no workspace)
     const int grid = ze_cdiv(c.N, 16 * TN) * ksplit;
@@ -2075,9 +2106,10 @@ static void launch_frag_mt(const gemm_frag_call& c) {
     const size_t lds = (grid <= ze_cu_count()) ? (size_t)96 * 1024 : (size_t)16 * TN * 1024;
     const size_t lds_max = (size_t)96 * 1024;
     auto go = [&](auto E) {
-        launch_lds<k_gemm_skinny<TN, E, true, MT, false, W8, A8>>(dim3(grid), dim3(256), lds, lds_max, c.s, c.Xf, 0, c.Wf, 0, c.bias, c.R, c.ldr,
-                                                                  c.C, c.ldc, c.M, c.N, c.K, ksplit, nullptr, nullptr, W8 ? c.wscale : nullptr,
-                                                                  A8 ? c.ascale : nullptr);
+        launch_lds<k_gemm_skinny<TN, E, true, MT, false, W8, A8, W4>>(dim3(grid), dim3(256), lds, lds_max, c.s, c.Xf, 0, c.Wf, 0, c.bias, c.R,
+                                                                      c.ldr, c.C, c.ldc, c.M, c.N, c.K, ksplit, nullptr, nullptr,
+                                                                      W4 ? reinterpret_cast<const float*>(c.wscale4) : W8 ? c.wscale : nullptr,
+                                                                      A8 ? c.ascale : nullptr);
     };
     if constexpr (TN % 2 == 0) {
         if (dispatch_epi<ZE_EPI_SWIGLU>(c.epi, go)) return;
@@ -2095,33 +2127,38 @@ static void launch_frag(const gemm_frag_call& c) {
                 return;
             }
         }
-        if (c.wscale) launch_frag_mt<TN, MT, true>(c);  // fp8 fragment stream
+        if (c.wscale4) launch_frag_mt<TN, MT, false, false, true>(c);  // MXFP4 fragment stream
+        else if (c.wscale) launch_frag_mt<TN, MT, true>(c);  // fp8 fragment stream
         else launch_frag_mt<TN, MT>(c);
     });
 }
 
 // gate/up (SwiGLU, wide): one workgroup per CU (or a multiple), each with a balanced range of at most three 32-row
 // pairs and ONE pass over the activations
-template <int MT, bool W8 = false, bool A8 = false>
+template <int MT, bool W8 = false, bool A8 = false, bool W4 = false>
 static void launch_frag_balanced(const gemm_frag_call& c, int grid) {
     const size_t lds = (size_t)16 * 6 * 1024;
-    launch_lds<k_gemm_skinny<6, ZE_EPI_SWIGLU, true, MT, true, W8, A8>>(dim3(grid), dim3(256), lds, lds, c.s, c.Xf, 0, c.Wf, 0, c.bias,
-                                                                        nullptr, 0, c.C, c.ldc, c.M, c.N, c.K, 1, nullptr, nullptr,
-                                                                        W8 ? c.wscale : nullptr, A8 ? c.ascale : nullptr);
+    launch_lds<k_gemm_skinny<6, ZE_EPI_SWIGLU, true, MT, true, W8, A8, W4>>(
+        dim3(grid), dim3(256), lds, lds, c.s, c.Xf, 0, c.Wf, 0, c.bias, nullptr, 0, c.C, c.ldc, c.M, c.N, c.K, 1, nullptr, nullptr,
+        W4 ? reinterpret_cast<const float*>(c.wscale4) : W8 ? c.wscale : nullptr, A8 ? c.ascale : nullptr);
 }
 
 void ze_launch_gemm_frag(int epi, const bf16_t* Xf, const bf16_t* Wf, const bf16_t* bias, const bf16_t* R, int ldr,
-                         bf16_t* C, int ldc, int M, int N, int K, hipStream_t s, const float* wscale, const float* ascale) {
+                         bf16_t* C, int ldc, int M, int N, int K, hipStream_t s, const float* wscale, const float* ascale,
+                         const uint8_t* wscale4) {
     if (M <= 0 || N <= 0) return;
-    const gemm_frag_call c{epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, wscale, ascale};
+    const gemm_frag_call c{epi, Xf, Wf, bias, R, ldr, C, ldc, M, N, K, s, wscale, ascale, wscale4};
     // (more than 32 chains only: below that the activation pass is small and the finer 32-row grid wins, 2.84 against
     //  2.91 ms per step at 8 chains; at 64 chains 3.86 against 3.95.  Both forms add an output's K quarters in the same
     //  order, so the choice does not change a chain's result.)
     if (epi == ZE_EPI_SWIGLU && N > 4096 && N % 32 == 0 && M > 32 && ze_gemv_knobs[5] != 2) {
         const int cus = ze_cu_count();
         const int P = N / 32;
-        const int grid = cus * ze_cdiv(P, 3 * cus);  // at most three pairs per workgroup
-        if (wscale && ascale) launch_frag_balanced<4, true, true>(c, grid);
+        // at most three pairs per workgroup, and never more workgroups than pairs: a workgroup with an empty range would address
+        // block -1 of the weights
+        const int grid = std::min(cus * ze_cdiv(P, 3 * cus), P);
+        if (wscale4) launch_frag_balanced<4, false, false, true>(c, grid);
+        else if (wscale && ascale) launch_frag_balanced<4, true, true>(c, grid);
         else if (wscale) launch_frag_balanced<4, true>(c, grid);
         else launch_frag_balanced<4>(c, grid);
         return;

@@ -33,6 +33,7 @@ struct ze_oneshot_args {
     const bf16_t* bias;    // [N] in ORIGINAL row order, or null
     const float* wscale;   // W8: per-row power-of-two scales of the FP8 fragment copy, ORIGINAL row order
     const float* ascale;   // A8: Xf holds FP8 fragments (k_rmsnorm_row act8 = 2), one power-of-two scale per activation row
+    const uint8_t* wscale4;  // W4: the fragment-major E8M0 block scales of the MXFP4 fragment copy (k_pack_fragments4)
     const bf16_t* R;       // residual rows (OS_EPI_RESIDUAL)
     bf16_t* C;             // output rows (BIAS / RESIDUAL: [M, ldc]; QKV: the q buffer, row stride ldc)
     int ldr, ldc, M, N, K;
@@ -60,13 +61,32 @@ __device__ __forceinline__ os_bf16x8 os_deq_fp8x8(os_u32x2 w, float scale) {  //
     return u.v;
 }
 
+// MXFP4 weight fragment -> bf16 MFMA operand: 4 bytes per lane, the 8 codes of 8 consecutive k of ONE weight row (even k in the
+// low nibble), times 2^e of the row's block (e8 = e + 127, never 0 or 255: E8M0 is the exponent field of the float).  code * 2^e is
+// a normal bf16 (ze_quant.hip), so the operand is the dequantised bf16 copy's, bit for bit, at 4.25 bits per weight.
+__device__ __forceinline__ os_bf16x8 os_deq_fp4x8(uint32_t w, uint32_t e8) {  // see deq_fp4x8 (ze_gemm.hip)
+    const float scale = __uint_as_float(e8 << 23);
+    union {
+        os_bf16x2 h[4];
+        os_bf16x8 v;
+    } u;
+    u.h[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0);
+    u.h[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1);
+    u.h[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2);
+    u.h[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3);
+    return u.v;
+}
+
 // W8: Wf is the FP8 fragment copy (8 B per lane per fragment), dequantised in registers with the row's scale.
 // A8 (with W8): the activations are FP8 fragments too and the product runs on v_mfma_f32_16x16x32_fp8_fp8 -- both
 // operands straight from memory into the matrix cores, half the bytes of each; the row and column scales (powers of two)
 // multiply the fp32 sums in the epilogue, exactly.
-template <int EPI, int MT, bool W8 = false, bool A8 = false>
+// W4: Wf is the MXFP4 fragment copy (4 B per lane per fragment) and every fragment comes with its row's block scale, one byte per
+// lane from a.wscale4 (16 contiguous bytes per fragment, the slices of a chunk back to back); dequantised in registers (os_deq_fp4x8).
+template <int EPI, int MT, bool W8 = false, bool A8 = false, bool W4 = false>
 __global__ void __launch_bounds__(1024) k_gemm_oneshot(const ze_oneshot_args a) {
     static_assert(!A8 || W8, "fp8 activations go with fp8 weights");
+    static_assert(!W4 || !W8, "one weight format per instantiation");
     constexpr int D = 128;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -105,7 +125,8 @@ __global__ void __launch_bounds__(1024) k_gemm_oneshot(const ze_oneshot_args a) 
     os_f32x4 acc[MT];
 #pragma unroll
     for (int i = 0; i < MT; ++i) acc[i] = os_f32x4{0.f, 0.f, 0.f, 0.f};
-    const bf16_t* wp = a.Wf + ((size_t)nb * ns_all * 64 + lane) * (W8 ? 4 : 8);
+    const bf16_t* wp = a.Wf + ((size_t)nb * ns_all * 64 + lane) * (W4 ? 2 : W8 ? 4 : 8);
+    const uint8_t* sp4 = W4 ? a.wscale4 + (size_t)nb * ns_all * 16 + fr : nullptr;
     const float wsc = W8 ? a.wscale[col] : 1.0f;  // fragment row fr of this block IS output column `col`
     const bf16_t* ap[MT];
 #pragma unroll
@@ -113,10 +134,14 @@ __global__ void __launch_bounds__(1024) k_gemm_oneshot(const ze_oneshot_args a) 
     for (int c0 = 0; c0 < ns; c0 += 4) {
         os_bf16x8 fb[4], fa[4][MT];
         os_u32x2 fb8[4], fa8[4][MT];
+        uint32_t fb4[4], fs4[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const size_t k = (size_t)(s0 + min(c0 + c, ns - 1)) * 512;  // slices past the share re-read its last one
-            if constexpr (W8) fb8[c] = __builtin_nontemporal_load(reinterpret_cast<const os_u32x2*>(wp + (k >> 1)));
+            if constexpr (W4) {
+                fb4[c] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(wp + (k >> 2)));
+                fs4[c] = sp4[k >> 5];  // 16 scale bytes per slice
+            } else if constexpr (W8) fb8[c] = __builtin_nontemporal_load(reinterpret_cast<const os_u32x2*>(wp + (k >> 1)));
             else fb[c] = __builtin_nontemporal_load(reinterpret_cast<const os_bf16x8*>(wp + k));
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
@@ -127,6 +152,10 @@ __global__ void __launch_bounds__(1024) k_gemm_oneshot(const ze_oneshot_args a) 
         if constexpr (W8 && !A8) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) fb[c] = os_deq_fp8x8(fb8[c], wsc);
+        }
+        if constexpr (W4) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) fb[c] = os_deq_fp4x8(fb4[c], fs4[c]);
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -228,7 +257,7 @@ __global__ void __launch_bounds__(1024) k_gemm_oneshot(const ze_oneshot_args a) 
     }
 }
 
-template <int EPI, bool W8, bool A8>
+template <int EPI, bool W8, bool A8, bool W4 = false>
 static void launch_oneshot_w(const ze_oneshot_args& a, hipStream_t s) {
     const int grid = a.N / 16;
 #define ZE_OS_LAUNCH(MT)                                                                                              \
@@ -236,11 +265,11 @@ static void launch_oneshot_w(const ze_oneshot_args& a, hipStream_t s) {
         const size_t lds = (size_t)(16 + 4) * MT * 64 * 16;                                                           \
         static bool attr_set = false;                                                                                 \
         if (!attr_set) {                                                                                              \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_oneshot<EPI, MT, W8, A8>),                      \
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_oneshot<EPI, MT, W8, A8, W4>),                      \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
             attr_set = true;                                                                                          \
         }                                                                                                             \
-        hipLaunchKernelGGL((k_gemm_oneshot<EPI, MT, W8, A8>), dim3(grid), dim3(1024), lds, s, a);                     \
+        hipLaunchKernelGGL((k_gemm_oneshot<EPI, MT, W8, A8, W4>), dim3(grid), dim3(1024), lds, s, a);                     \
     } while (0)
     if (a.M <= 16) ZE_OS_LAUNCH(1);
     else if (a.M <= 32) ZE_OS_LAUNCH(2);
@@ -249,17 +278,20 @@ static void launch_oneshot_w(const ze_oneshot_args& a, hipStream_t s) {
 }
 template <int EPI>
 static void launch_oneshot(const ze_oneshot_args& a, hipStream_t s) {
-    if (a.wscale && a.ascale) launch_oneshot_w<EPI, true, true>(a, s);
+    if (a.wscale4) launch_oneshot_w<EPI, false, false, true>(a, s);
+    else if (a.wscale && a.ascale) launch_oneshot_w<EPI, true, true>(a, s);
     else if (a.wscale) launch_oneshot_w<EPI, true, false>(a, s);
     else launch_oneshot_w<EPI, false, false>(a, s);
 }
 
 // C = X W^T (+ bias) (+ residual): M <= 64, N % 16 == 0, K % 32 == 0
 void ze_launch_gemm_oneshot(int epi, const bf16_t* Xf, const bf16_t* Wf, const bf16_t* bias, const bf16_t* R, int ldr,
-                            bf16_t* C, int ldc, int M, int N, int K, hipStream_t s, const float* wscale, const float* ascale) {
+                            bf16_t* C, int ldc, int M, int N, int K, hipStream_t s, const float* wscale, const float* ascale,
+                            const uint8_t* wscale4) {
     if (M <= 0 || N <= 0) return;
     ze_oneshot_args a;
     memset(&a, 0, sizeof(a));
+    a.wscale4 = wscale4;
     a.wscale = wscale;
     a.ascale = ascale;
     a.Xf = Xf; a.Wf = Wf; a.bias = bias; a.R = R; a.ldr = ldr; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
@@ -272,10 +304,11 @@ void ze_launch_qkv_rope_oneshot(const bf16_t* Xf, const bf16_t* Wf_perm, const b
                                 int K, int heads, int kv_heads, const bf16_t* cosT, const bf16_t* sinT,
                                 const ze_seq_dev* st, const int* seq_ids, bf16_t* kcache, bf16_t* vcache,
                                 size_t cache_seq_stride, int max_ctx, hipStream_t s, const float* wscale, const float* ascale,
-                                const int* row_off) {
+                                const int* row_off, const uint8_t* wscale4) {
     if (M <= 0) return;
     ze_oneshot_args a;
     memset(&a, 0, sizeof(a));
+    a.wscale4 = wscale4;
     a.wscale = wscale;
     a.ascale = ascale;
     a.Xf = Xf; a.Wf = Wf_perm; a.bias = bias; a.C = q_out; a.ldc = ldq; a.M = M; a.N = (heads + 2 * kv_heads) * 128; a.K = K;

@@ -110,7 +110,8 @@ void ze_launch_pack_fragments(const bf16_t* W, int ldw, int n, int k, bf16_t* Wf
 // trip per launch.  epi: ZE_EPI_NONE (+bias) or ZE_EPI_RESIDUAL; M <= 64, N % 16 == 0, K % 32 == 0.
 void ze_launch_gemm_oneshot(int epi, const bf16_t* Xf, const bf16_t* Wf, const bf16_t* bias, const bf16_t* R, int ldr,
                             bf16_t* C, int ldc, int M, int N, int K, hipStream_t s, const float* wscale = nullptr,
-                            const float* ascale = nullptr);  // ascale: Xf is FP8 fragments (fp8 x fp8 MFMA)
+                            const float* ascale = nullptr,  // ascale: Xf is FP8 fragments (fp8 x fp8 MFMA)
+                            const uint8_t* wscale4 = nullptr);  // Wf is the MXFP4 fragment copy, wscale4 its fragment-major scales
 // qkv projection + M-RoPE + KV append in one launch; Wf_perm = ze_launch_pack_fragments(..., rope_dim = 128); q heads go
 // to q_out rows (stride ldq, original column order), k / v rows into the caches at each chain's position.
 void ze_launch_qkv_rope_oneshot(const bf16_t* Xf, const bf16_t* Wf_perm, const bf16_t* bias, bf16_t* q_out, int ldq, int M,
@@ -120,7 +121,8 @@ void ze_launch_qkv_rope_oneshot(const bf16_t* Xf, const bf16_t* Wf_perm, const b
                                 const float* ascale = nullptr,
                                 // a step whose rows may name a chain more than once (ze_spec.hip): row r sits row_off[r] positions
                                 // behind its chain's context; row_off[r] < 0: a dead row, which appends no K/V row
-                                const int* row_off = nullptr);
+                                const int* row_off = nullptr,
+                                const uint8_t* wscale4 = nullptr);  // Wf_perm is the MXFP4 fragment copy (ze_launch_pack_fragments4)
 // block-scaled FP8 GEMM (k_gemm_ring_mx): A8 [M, K] / W8 [N, K] E4M3 bytes with one power-of-two scale per row each; epi
 // ZE_EPI_NONE or ZE_EPI_SWIGLU; false when the shape does not qualify (K % 128, leading dimensions % 16)
 bool ze_launch_gemm_mx(int epi, const uint8_t* A, int lda, const float* sa, const uint8_t* W, int ldw, const float* sw,
@@ -130,10 +132,16 @@ bool ze_launch_gemm_mx(int epi, const uint8_t* A, int lda, const float* sa, cons
 // wscale != null: Wf is the FP8 fragment copy (ze_launch_pack_fragments8) and wscale the per-row power-of-two scales
 void ze_launch_gemm_frag(int epi, const bf16_t* Xf, const bf16_t* Wf, const bf16_t* bias, const bf16_t* R, int ldr,
                          bf16_t* C, int ldc, int M, int N, int K, hipStream_t s, const float* wscale = nullptr,
-                         const float* ascale = nullptr);  // ascale (gate/up at > 32 chains only): Xf is FP8 fragments
+                         const float* ascale = nullptr,  // ascale (gate/up at > 32 chains only): Xf is FP8 fragments
+                         const uint8_t* wscale4 = nullptr);  // Wf is the MXFP4 fragment copy, wscale4 its fragment-major scales
 // FP8 weights [n, ld8] row-major (ze_launch_quantize_rows) -> fragment-major: fragment (nb, ks) = 64 lanes x 8 B,
 // lane = (col % 32) / 8 * 16 + row % 16 holds columns 8 (lane / 16) .. +7 of its row; rope_dim as ze_launch_pack_fragments
 void ze_launch_pack_fragments8(const uint8_t* W8, int ld8, int n, int k, uint8_t* Wf8, hipStream_t s, int rope_dim = 0);
+// MXFP4 weights (q [n, k / 2] + scale [n, k / 32], ze_launch_quantize_mxfp4) -> fragment-major (ze_quant.hip; layout: zoomearth.h):
+// codes Wf4 [n / 16][k / 32][64 lanes][4 B] (n k / 2 bytes), scales Sf4 [n / 16][k / 32][16] (n k / 32 bytes); n % 16 == 0, k % 32 == 0;
+// rope_dim as ze_launch_pack_fragments (codes and scales of a block follow the same row permutation)
+void ze_launch_pack_fragments4(const uint8_t* q4, const uint8_t* scale, int n, int k, uint8_t* Wf4, uint8_t* Sf4, hipStream_t s,
+                               int rope_dim = 0);
 void ze_launch_gather_cast_rows(const float* src, int k, const int* perm, bf16_t* dst, int kp, int rows,
                                 hipStream_t s);
 void ze_launch_vision_rope(bf16_t* qkv, const float* cosT, const float* sinT, int n, int heads, int D, hipStream_t s);

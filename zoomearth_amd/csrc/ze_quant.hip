@@ -106,6 +106,33 @@ __global__ void __launch_bounds__(256) k_quantize_mxfp4(bf16_t* __restrict__ w, 
     scale[(size_t)r * bpr + b] = (uint8_t)E;
 }
 
+// Row-major MXFP4 (q [n, k / 2], scale [n, k / 32]) -> the fragment-major copy the W4 kernels of the batched decode step stream
+// (ze_gemm.hip, ze_gemm_oneshot.hip; the layout is written down in zoomearth.h next to the format, restated by tests/gemm4_ref.py).
+// One wave per 16 x 32 fragment (nb, ks), as k_pack_fragments8: lane = fq * 16 + fr moves the four bytes q[row][16 ks + 4 fq .. + 3]
+// -- its 8 codes, nibble order untouched -- to codes[((nb S + ks) * 64 + lane) * 4], and the lanes fq == 0 move the row's scale byte of
+// block ks to scales[(nb S + ks) * 16 + fr].  rope_dim: the row permutation of k_pack_fragments (qkv), for codes and scales alike.
+__global__ void __launch_bounds__(256) k_pack_fragments4(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scale, int n, int k,
+                                                         uint8_t* __restrict__ Wf, uint8_t* __restrict__ Sf, int rope_dim) {
+    const size_t frag = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int ns = k >> 5;
+    if (frag >= (size_t)(n >> 4) * ns) return;
+    const int lane = threadIdx.x & 63, nb = (int)(frag / ns), ks = (int)(frag % ns);
+    int row = nb * 16 + (lane & 15);
+    if (rope_dim > 0) {
+        const int bph = rope_dim >> 4, h = nb / bph, j = nb % bph, r = lane & 15;
+        row = h * rope_dim + (r < 8 ? 8 * j + r : (rope_dim >> 1) + 8 * j + (r - 8));
+    }
+    const uint32_t v = *reinterpret_cast<const uint32_t*>(q + (size_t)row * (k >> 1) + ks * 16 + (lane >> 4) * 4);
+    *reinterpret_cast<uint32_t*>(Wf + (frag * 64 + lane) * 4) = v;
+    if (lane < 16) Sf[frag * 16 + lane] = scale[(size_t)row * ns + ks];
+}
+// n % 16 == 0 and k % 32 == 0 (the callers check)
+void ze_launch_pack_fragments4(const uint8_t* q4, const uint8_t* scale, int n, int k, uint8_t* Wf4, uint8_t* Sf4, hipStream_t s, int rope_dim) {
+    const size_t frags = (size_t)(n >> 4) * (k >> 5);
+    if (frags == 0) return;
+    k_pack_fragments4<<<(unsigned)((frags + 3) / 4), 256, 0, s>>>(q4, scale, n, k, Wf4, Sf4, rope_dim);
+}
+
 // cols % 32 == 0, ld % 8 == 0 and w 16-byte aligned (the callers check): a thread owns one block
 void ze_launch_quantize_mxfp4(bf16_t* w, int rows, int cols, int ld, uint8_t* q, uint8_t* scale, hipStream_t s) {
     if (rows <= 0 || cols <= 0) return;

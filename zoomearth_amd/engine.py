@@ -1177,7 +1177,8 @@ class Engine:
 
     def quantize_mxfp4(self):
         """Switch the decoder's linear layers to MXFP4 (E2M1 codes, one E8M0 scale per 32 weights; reduced precision, opt-in): the
-        batch-1 decode reads the 4-bit stream, every other path the dequantised bf16 values.  See ze_weights_quantize_mxfp4."""
+        batch-1 decode reads the 4-bit stream, the 2 .. 64-chain step of decode family 0 the 4-bit fragment copies (bit-identical to the
+        dequantised form), every other path the dequantised bf16 values.  See ze_weights_quantize_mxfp4."""
         self._check(self.lib.ze_weights_quantize_mxfp4(self.h, self._stream()))
 
     WEIGHT_FORMATS = ("bf16", "fp8", "mxfp4")
@@ -1187,6 +1188,13 @@ class Engine:
         """The weight stream the batch-1 decode reads now: "bf16", "fp8" or "mxfp4" (the engine's state: a weight write or an
         adapter switch returns it to "bf16")."""
         return self.WEIGHT_FORMATS[self._check(self.lib.ze_weight_format(self.h))]
+
+    def fragment_bytes(self) -> int:
+        """Device bytes the fragment-major weight copies of the 2 .. 64-chain decode step hold now (ze_fragment_bytes): 0 before the
+        first batched step; on an MXFP4 engine the 4-bit copies, 4.25 bits per quantised weight."""
+        b = C.c_size_t()
+        self._check(self.lib.ze_fragment_bytes(self.h, C.byref(b)))
+        return int(b.value)
 
     def set_weight_format(self, fmt) -> None:
         """Quantise the loaded weights to `fmt` ("fp8" / "mxfp4"; None or "bf16": leave them).  The formats exclude each other."""
@@ -1368,6 +1376,12 @@ class Engine:
         Returns the status code without raising, so that a test can see ZE_ERR_INVALID (-1)."""
         return int(self.lib.ze_op_gemm(self.h, launcher, epi, _ptr(a), lda, _ptr(w), ldw, _ptr(bias), _ptr(r), ldr, _ptr(c), ldc,
                                        _ptr(c_rows), m, n, k, self._stream()))
+
+    def op_gemm4(self, launcher: int, epi: int, a, lda: int, q4, scale4, bias, r, ldr: int, c, ldc: int, m: int, n: int, k: int) -> int:
+        """ze_op_gemm4: op_gemm's fragment launchers (5 skinny, 6 one-shot) with the MXFP4 stream as W -- q4 u8 [N, K / 2], scale4 u8
+        [N, K / 32] as op_quantize_mxfp4 returns them.  Returns the status code without raising (ZE_ERR_INVALID is -1)."""
+        return int(self.lib.ze_op_gemm4(self.h, launcher, epi, _ptr(a), lda, _ptr(q4), _ptr(scale4), _ptr(bias), _ptr(r), ldr, _ptr(c), ldc,
+                                        m, n, k, self._stream()))
 
     def op_rmsnorm(self, x, w, eps: float):
         out = torch.empty_like(x)
