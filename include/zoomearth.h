@@ -873,8 +873,9 @@ int ze_op_kv_read(ze_engine* e, int seq, int layer, int start, int n, void* out_
  * accept; chains without speculation ride along with one row and their usual sampler.  A burst of `steps` steps emits up to
  * steps x (k + 1) tokens per speculating chain (n_generated reports it; a caller with a token budget trims).  How far a speculating
  * chain came is known on the device alone until ze_decode_burst_end has read it back: between ze_decode_burst_begin and its _end
- * ze_seq_len reports the length before the burst, and a second ze_decode_burst_begin that names the chain is ZE_ERR_INVALID.  Greedy only: a
- * speculating chain may carry a repetition penalty (the call's, or its own ze_seq_set_sampling mode 0) and nothing else.
+ * ze_seq_len reports the length before the burst, and a second ze_decode_burst_begin that names the chain is ZE_ERR_INVALID.  Greedy only
+ * as set by this entry: the chain may carry a repetition penalty (the call's, or its own ze_seq_set_sampling mode 0) and nothing else;
+ * a chain that samples speculates through ze_seq_set_speculation_mode (mode 1, below).
  * ze_seq_set_speculation: k = 0 clears; 1 <= k <= 8 and 1 <= min_ngram <= max_ngram <= 8, n_prompt in [0, max_ctx], ids inside the
  * vocabulary -- anything else is ZE_ERR_INVALID.  ZE_ERR_INVALID too, and nothing changes: the engine runs the row-streaming family
  * (decode family 1 has no multi-row kernels); the chain has a sampled request, a sampling filter, a logit adjust, token rules, a
@@ -883,6 +884,23 @@ int ze_op_kv_read(ze_engine* e, int seq, int layer, int start, int n, void* out_
  * the sampling filter is (ze_seq_reset, ze_seq_truncate, ze_seq_copy_prefix / ze_seq_fork / ze_prefix_load into the slot).  The
  * buffers come with the first request (64 logits rows among them); ZE_ERR_NOMEM if that fails, and the engine stays usable. */
 int ze_seq_set_speculation(ze_engine* e, int seq, int k, int min_ngram, int max_ngram, const int32_t* prompt_ids, int n_prompt, void* stream);
+/* ze_seq_set_speculation with the accept pass chosen (replaces: HF generate(prompt_lookup_num_tokens=k, do_sample=True), whose
+ * _speculative_sampling needs a rejection step because torch's generator is sequential; vLLM's ngram method under a sampled request).
+ * mode 0 is ze_seq_set_speculation.  mode 1 is the SAMPLED mode: the chain's effective request -- its own (ze_seq_set_sampling,
+ * ze_seq_set_sampling_filter) or the call's ze_gen_params -- may be greedy or temperature sampling with any seed, any repetition
+ * penalty and any top-k / top-p / min-p filter.  The draw of this engine is counter-based (u = f(seed, stream of the chain, index of
+ * the generated token)) and the drafter is deterministic, so no rejection sampling is needed: row j draws exactly the token a plain
+ * step at that position draws -- the plain step's sampler (the arithmetic of ze_op_sample_rows / ze_op_sample_filter) on row j's
+ * logits, at draw index n_gen + j, under the seen-set of the chain plus draft ids 0 .. j - 1 -- and the walk keeps rows while the drawn
+ * token equals the draft id (stop rules, commit and counters as the greedy pass).  Ids, n_gen, the finished flag, the seen-set and
+ * the K/V rows 0 .. ctx - 1 are bit for bit those of the chain under plain family-0 bursts with the same values.  Row contract,
+ * drafter, row table and step are ze_seq_set_speculation's; validation, allocation and clearing too, except that a sampled request or
+ * a sampling filter is not refused and that ze_seq_set_sampling / ze_seq_set_sampling_filter do not refuse the chain.  Still refused
+ * both ways (ZE_ERR_INVALID, nothing changes): entropy filters, logit adjust, token rules, grammar, log-probabilities, and the
+ * row-streaming family.  Any other mode is ZE_ERR_INVALID.  The first request of mode 1 allocates the per-row shadows (64 x vocab
+ * bytes of seen-sets among them), all or none: ZE_ERR_NOMEM, and the engine stays usable. */
+int ze_seq_set_speculation_mode(ze_engine* e, int seq, int k, int min_ngram, int max_ngram, const int32_t* prompt_ids, int n_prompt, int mode,
+                                void* stream);
 /* The chain's counters since its request was set: speculative steps it took part in, draft ids proposed, draft ids accepted (tokens
  * emitted = steps + accepted).  All zero for a chain without a request.  Any out pointer may be NULL.  Waits for `stream`. */
 int ze_chain_spec_stats(ze_engine* e, int seq, int* steps, int* drafted, int* accepted, void* stream);
@@ -899,6 +917,16 @@ int ze_op_spec_draft(ze_engine* e, const int32_t* hist_ids, const int32_t* hist_
 int ze_op_spec_accept(ze_engine* e, const float* logits, int n_chains, int vocab, int ld, int k, const int32_t* draft,
                       const int32_t* draft_len, uint8_t* seen, const float* repetition_penalty, const int32_t* room, int ignore_eos,
                       int32_t* out_tokens, int32_t* out_count, int32_t* out_finished, void* stream);
+/* The accept pass of the sampled mode alone (replaces: ze_op_spec_accept where the chain samples; HF: _speculative_sampling): the
+ * arguments of ze_op_spec_accept (seen NULL: no penalty, repetition_penalty may then be NULL) plus HOST arrays of length n_chains:
+ * temperature (0 = greedy), seed, sample_stream, index0 (the draw index of row 0: the chain's n_gen) and top_k / top_p / min_p (all
+ * three NULL = no filter).  Row j of chain c is drawn as ze_op_sample_rows draws a row with those values at index0[c] + j, under
+ * seen[c] plus draft ids 0 .. j - 1.  Same outputs; waits for `stream`. */
+int ze_op_spec_accept_sampled(ze_engine* e, const float* logits, int n_chains, int vocab, int ld, int k, const int32_t* draft,
+                              const int32_t* draft_len, uint8_t* seen, const float* repetition_penalty, const int32_t* room, int ignore_eos,
+                              const float* temperature, const uint64_t* seed, const int32_t* sample_stream, const int32_t* index0,
+                              const int32_t* top_k, const float* top_p, const float* min_p, int32_t* out_tokens, int32_t* out_count,
+                              int32_t* out_finished, void* stream);
 /* The row contract alone (HF / vLLM: the verification forward of a speculative step): chain `seq` is fed tokens[0 .. r) (host) at r
  * consecutive positions in ONE family-0 step -- teacher forcing as ze_decode_batch, the cache grows by r rows; out_logits f32
  * [r, vocab] device or NULL.  r <= 64. */

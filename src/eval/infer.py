@@ -72,9 +72,25 @@ def done_question_ids_all(exp_name, world):
     return ids
 
 
+def speculative_kwargs(speculative_ngram, batch_size):
+    """The scheduler arguments of --speculative-ngram K (0: none, today's steps): up to K draft ids per step by prompt lookup, in
+    the sampled mode -- this entry samples at T = 0.01 -- which draws what the plain steps draw, so the records do not change.
+    Refused where the lane would run the row-streaming decode family (more than 64 chains), which has no multi-row kernels."""
+    k = int(speculative_ngram or 0)
+    if k == 0:
+        return {}
+    if not (1 <= k <= 8):
+        raise ValueError(f"--speculative-ngram has to be in [0, 8], but is {k}")
+    if batch_size > 64:
+        raise ValueError(f"--speculative-ngram needs the fragment decode kernels: --batch_size {batch_size} runs the row-streaming "
+                         "family (more than 64 chains per lane); use --batch_size <= 64 or --speculative-ngram 0")
+    return dict(speculative_tokens=k, speculative_sampling=True)
+
+
 def eval_model_lora(model_name, exp_name, ds_path="./LRS_GRO/test", image_dir="./image/", max_new_tokens=1024,
                     batch_size=BATCH_SIZE, max_ctx=4096, do_sample=True, resume=False, decode_workers=3, decode_ahead=6, lanes=1,
-                    steal=False, hold=0, admit_rows=0):
+                    steal=False, hold=0, admit_rows=0, speculative_ngram=0):
+    spec_kw = speculative_kwargs(speculative_ngram, batch_size)   # (refused before anything is loaded)
     # capacity: the stage-2 prompt holds the stage-1 prompt, its output and a second image (<= ~3200 tokens at the
     # default budgets); prefill passes of up to 16 prompts share their GEMMs
     # one rank per GPU (torchrun / accelerate launch): rank 0 reads the checkpoint, the others receive the packed weight
@@ -189,7 +205,8 @@ def eval_model_lora(model_name, exp_name, ds_path="./LRS_GRO/test", image_dir=".
         # the lane's questions arrive grouped by tile: decode the next tiles while the current one is being questioned
         tiles = TilePrefetcher([tile_path(name) for _, name, _items in todo], m.engine, depth=decode_ahead, workers=decode_workers)
         sched = ChainScheduler(m, proc, do_sample=do_sample, temperature=0.01 if do_sample else None, burst=8,
-                               min_admit=max(1, batch_size // 2), max_wait_bursts=12, hold_below=hold, admit_chunk_rows=admit_rows)
+                               min_admit=max(1, batch_size // 2), max_wait_bursts=12, hold_below=hold, admit_chunk_rows=admit_rows,
+                               **spec_kw)
 
         def finish(idx, sample, r):
             with lock:
@@ -335,6 +352,8 @@ if __name__ == "__main__":
                                                                            "batch; 256 gives about 1.5x the questions/s, DESIGN.md 7b)")
     parser.add_argument("--max_ctx", type=int, default=4096, help="tokens per chain (KV capacity)")
     parser.add_argument("--greedy", action="store_true", help="arg-max instead of the reference's T=0.01 sampling")
+    parser.add_argument("--speculative-ngram", type=int, default=0, help="speculative decoding by prompt lookup, up to K draft ids per step "
+                        "(sampled mode: the same records; 0 = off; needs --batch_size <= 64)")
     parser.add_argument("--resume", action="store_true", help="keep the records results/{exp_name}{rank}.jsonl already holds and "
                                                               "run only the questions that are missing")
     parser.add_argument("--lanes", type=int, default=1, help="engines per GPU, each with its own scheduler thread and --batch_size "
@@ -355,4 +374,5 @@ if __name__ == "__main__":
     args = parser.parse_args()
     eval_model_lora(args.model_name, args.exp_name, args.dataset, args.image_dir, args.max_new_tokens, args.batch_size,
                     args.max_ctx, do_sample=not args.greedy, resume=args.resume, decode_workers=args.decode_workers,
-                    decode_ahead=args.decode_ahead, lanes=args.lanes, steal=args.steal, hold=args.hold, admit_rows=args.admit_rows)
+                    decode_ahead=args.decode_ahead, lanes=args.lanes, steal=args.steal, hold=args.hold, admit_rows=args.admit_rows,
+                    speculative_ngram=args.speculative_ngram)

@@ -228,6 +228,10 @@ _SIGS = {
     "ze_seq_set_speculation": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _P]),
     "ze_chain_spec_stats": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
     "ze_op_spec_draft": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "ze_seq_set_speculation_mode": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, _P]),
+    "ze_op_spec_accept_sampled": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_float),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P]),
     "ze_op_spec_accept": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "ze_op_decode_rows": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_int, _P, _P]),
     "ze_op_gemv": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_float,

@@ -43,6 +43,9 @@ class ChainRequest:
     speculative_tokens: int = 0
     ngram_min: int = 1
     ngram_max: int = 3
+    # the sampled mode of speculation (Engine.set_speculation(sampled=True)): the chain may sample and carry a top-k / top-p / min-p
+    # filter; every row draws what a plain step would, so it stays lossless.  Opt-in: without it the rule above holds
+    speculative_sampling: bool = False
 
     @property
     def wants_logprobs(self) -> bool:
@@ -54,8 +57,10 @@ class ChainRequest:
 
     def speculation_conflict(self, grammar: bool = False) -> Optional[str]:
         """What of this request speculation excludes (the engine's rule, ze_seq_set_speculation), or None."""
-        if self.sampled:
+        if self.sampled and not self.speculative_sampling:
             return "sampling"
+        if self.sampled and (self.typical_p < 1.0 or self.epsilon_cutoff > 0.0 or self.eta_cutoff > 0.0):
+            return "entropy filters"
         if self.logprobs is not None:
             return "logprobs"
         if self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or self.logit_bias or self.min_new_tokens > 0:
@@ -85,4 +90,7 @@ class ChainRequest:
         if grammar is not None:
             engine.set_grammar(slot, grammar)
         if self.speculative_tokens > 0:   # (last: the engine checks the slot's other requests)
-            engine.set_speculation(slot, self.speculative_tokens, list(prompt_ids), self.ngram_min, self.ngram_max)
+            if self.speculative_sampling:
+                engine.set_speculation(slot, self.speculative_tokens, list(prompt_ids), self.ngram_min, self.ngram_max, sampled=True)
+            else:
+                engine.set_speculation(slot, self.speculative_tokens, list(prompt_ids), self.ngram_min, self.ngram_max)

@@ -580,6 +580,8 @@ static int run_burst(ze_engine* e, const std::vector<int>& active, int steps, co
 // (enqueue_forward) on the row set of the speculative table (ze_rows_spec).
 struct spec_layout {
     int rows = 0, n_plain = 0, n_chains = 0;
+    // the chains that speculate in sampled mode come last: n_drawn of them, the last n_drawn_rows rows
+    int n_drawn = 0, n_drawn_rows = 0;
 };
 
 // the multi-row forms exist for the fragment kernels and the pipelined attention alone
@@ -602,7 +604,14 @@ static int enqueue_spec_step(ze_engine* e, const spec_layout& L, float penalty, 
     ze_launch_spec_embed(q.row_tok, L.rows, e->embed, e->bh, c.hidden, s);
     enqueue_forward(e, rows, L.rows, s);
     if (L.n_plain > 0) enqueue_sampler(e, rows, L.n_plain, penalty, ign, 1, so, s);  // rows 0 .. n_plain - 1: one chain each, and their usual sampler
-    ze_launch_spec_accept(a, L.n_plain, s);
+    ze_spec_step g = a;  // the greedy-mode chains: [n_plain, n_chains - n_drawn)
+    g.n_chains = L.n_chains - L.n_drawn;
+    ze_launch_spec_accept(g, L.n_plain, s);
+    // the sampled-mode chains behind them: their rows drawn by the plain step's sampler kernels, then the walk (a burst without such a
+    // chain launches nothing here)
+    if (L.n_drawn > 0)
+        ze_launch_spec_accept_sampled(a, q.draw, L.n_chains - L.n_drawn, L.rows - L.n_drawn_rows, L.n_drawn_rows, so.temperature, so.seed, so.draws(), so.samp,
+                                      so.filt, s);
     ZE_KCHECK();
     return ZE_OK;
 }
@@ -622,24 +631,29 @@ static int spec_burst(ze_engine* e, const std::vector<int>& chains, int steps, c
         if (!q.on(chains[i]) && e->ctx_host[chains[i]] > c.max_ctx) return ze_fail(e, ZE_ERR_NOMEM, "sequence exceeds max_ctx");
     }
     const bool call_draws = p->do_sample && p->temperature > 0.f;
-    // the row table: the chains without speculation first (one row each: the sampler's rows), then k + 1 rows per speculating chain
+    // the row table: the chains without speculation first (one row each: the sampler's rows), then k + 1 rows per speculating chain --
+    // the greedy-mode ones, then the sampled-mode ones, so that each accept launch covers one contiguous range
     std::vector<int> order;
-    for (int pass = 0; pass < 2; ++pass)
+    for (int pass = 0; pass < 3; ++pass)
         for (int ch : chains)
-            if ((int)q.on(ch) == pass) order.push_back(ch);
+            if ((int)q.on(ch) + (int)q.sampled(ch) == pass) order.push_back(ch);
     spec_layout L;
     std::vector<int> row_seq, tab;
     int mx = 0;
     for (int ch : order) {
         const int k = q.on(ch) ? q.host[ch].k : 0;
         const ze_chain_sampling& own = e->req.samp_host[ch];
-        if (k > 0 && (own.penalty > 0.f ? own.temperature > 0.f : call_draws))
+        if (k > 0 && !q.sampled(ch) && (own.penalty > 0.f ? own.temperature > 0.f : call_draws))
             return ze_fail(e, ZE_ERR_INVALID, "speculation is greedy only: the burst samples a speculating chain");
         if (k == 0) steps = std::min(steps, c.max_ctx - e->ctx_host[ch]);  // (a speculating chain out of room rides along with dead rows)
         const float cp = own.penalty > 0.f ? own.penalty : pen;
         int bits;
         memcpy(&bits, &cp, sizeof(bits));
         tab.insert(tab.end(), {ch, L.rows, k + 1, bits});
+        if (q.sampled(ch)) {
+            L.n_drawn += 1;
+            L.n_drawn_rows += k + 1;
+        }
         for (int j = 0; j <= k; ++j) row_seq.push_back(ch);
         L.rows += k + 1;
         L.n_chains += 1;
@@ -656,7 +670,7 @@ static int spec_burst(ze_engine* e, const std::vector<int>& chains, int steps, c
     const auto step = [&](hipStream_t cs) { return enqueue_spec_step(e, L, pen, ign, bso, cs); };
     hipGraphExec_t gx = nullptr;
     // the key of a plain step over `rows` rows, and the layout: nothing else decides what the step launches
-    if (p->use_graph) ZE_TRY(step_graph(e, ze_step_key_of(e, L.rows, 0, pen, ign, bso, ZE_STEP_SPEC, L.n_plain, L.n_chains), step, &gx));
+    if (p->use_graph) ZE_TRY(step_graph(e, ze_step_key_of(e, L.rows, 0, pen, ign, bso, ZE_STEP_SPEC, L.n_plain, L.n_chains, L.n_drawn, L.n_drawn_rows), step, &gx));
     ZE_TRY(run_steps(e, gx, step, steps, s));
     // a speculating chain's length is the device's to know until ze_decode_burst_end reads it back
     for (int ch : chains) {

@@ -70,6 +70,7 @@ struct ze_step_key {
     int n = 0;  // rows of a batched step; 0 = the single-chain step
     int kind = ZE_STEP_SAMPLED;     // batched step: with its sampler, without it (beam search), or speculative (draft .. accept)
     int n_plain = 0, n_chains = 0;  // speculative step only: the rows the sampler takes, the chains the drafter and the accept pass walk
+    int n_drawn = 0, n_drawn_rows = 0;  // ... the last of those chains that speculate in sampled mode, and their rows (the step's last): the drawn accept pass
     float penalty = 0.f;
     int ignore_eos = 0;
     float temperature = 0.f;
@@ -79,7 +80,7 @@ struct ze_step_key {
     int sampling_bits = 0;                     // bit 0 = sampling filters, bit 1 = per-chain sampling table, bit 2 = ... with a draw, bit 3 = entropy filters
     int lp_mode = 0, la_mode = 0, tr_mode = 0, gr_mode = 0;
     auto tied() const {
-        return std::tie(n, kind, n_plain, n_chains, penalty, ignore_eos, temperature, seed, tune_epoch, live_parts, live_parts_long, sampling_bits, lp_mode, la_mode,
+        return std::tie(n, kind, n_plain, n_chains, n_drawn, n_drawn_rows, penalty, ignore_eos, temperature, seed, tune_epoch, live_parts, live_parts_long, sampling_bits, lp_mode, la_mode,
                         tr_mode, gr_mode);
     }
     bool operator==(const ze_step_key& o) const { return tied() == o.tied(); }
@@ -237,9 +238,23 @@ struct ze_lora {
 // row_seq / row_off / row_tok [64]: the chain slot of a row, its offset behind the chain's context (< 0: a dead row) and the id it
 // is fed -- the burst's chains (ZE_SP_CHAIN_WORDS ints each: slot, first row, rows, penalty bits), their draft lengths, and the
 // step's own logits rows, attention partials and tickets (a step may have more rows than the engine has slots).
+// Sampled mode (ze_seq_set_speculation_mode, mode 1; chain_host::mode): the chain's rows are drawn by the per-chain sampling kernels
+// of the plain step with row = slot, on per-row shadows the prepare pass lays down (ze_spec_draw below).  The shadows come with the
+// first request of that mode, all or none: the scratch seen-sets are ZE_SP_MAX_ROWS x vocab bytes.
 enum { ZE_SP_WORDS = 8, ZE_SP_CHAIN_WORDS = 4, ZE_SP_MAX_ROWS = 64, ZE_SP_MAX_K = 8 };
+// the shadows of n rows: entry r of every table belongs to row r (ids[r] = r): the request, the chain state (stream, draw index),
+// the filter, the seen-set as of that row ([n, vocab]), then the draw's workspaces (cuts n, part 2 * 128 * n, sums 128 * n) and tokens
+struct ze_spec_draw {
+    ze_chain_sampling* samp = nullptr;
+    ze_seq_dev* st = nullptr;
+    float* filt = nullptr;
+    int* ids = nullptr;
+    uint8_t* seen = nullptr;
+    float *cuts = nullptr, *part = nullptr, *sums = nullptr;
+    int32_t* tok = nullptr;
+};
 struct ze_spec {
-    struct chain_host { int k = 0, min_ngram = 0, max_ngram = 0, n_prompt = 0; };
+    struct chain_host { int k = 0, min_ngram = 0, max_ngram = 0, n_prompt = 0, mode = 0; };
     std::vector<chain_host> host;
     std::vector<char> pending;   // the chain took part in a ze_decode_burst_begin whose _end has not read its length back yet
     int n_spec = 0;
@@ -247,7 +262,9 @@ struct ze_spec {
     int *row_seq = nullptr, *row_off = nullptr, *row_tok = nullptr, *chains = nullptr, *dlen = nullptr;
     float *logits = nullptr, *partial = nullptr;
     unsigned* tickets = nullptr;
+    ze_spec_draw draw;           // sampled mode only (null until its first request)
     bool on(int seq) const { return !host.empty() && host[seq].k > 0; }
+    bool sampled(int seq) const { return on(seq) && host[seq].mode == 1; }
 };
 
 // Beam search (ze_beam.hip): everything a beam call keeps between two forwards, device-resident, allocated by the first call (all or
@@ -488,7 +505,7 @@ float ze_penalty_of(const ze_engine* e, const ze_gen_params* p, int seq);
 ze_sample_opts ze_sample_opts_of(ze_engine* e, const ze_gen_params* p, int slot, bool batch = false);
 // n = 0: the single-chain step of chain `seq`; else the batched step of n rows, of `kind` (a speculative one with its layout)
 ze_step_key ze_step_key_of(const ze_engine* e, int n, int seq, float penalty, int ignore_eos, const ze_sample_opts& so,
-                           int kind = ZE_STEP_SAMPLED, int n_plain = 0, int n_chains = 0);
+                           int kind = ZE_STEP_SAMPLED, int n_plain = 0, int n_chains = 0, int n_drawn = 0, int n_drawn_rows = 0);
 
 // ---- speculative decoding (ze_spec.hip)
 void ze_spec_free(ze_engine* e);
@@ -507,6 +524,12 @@ struct ze_spec_step {
 };
 void ze_launch_spec_draft(const ze_spec_step& a, hipStream_t s);
 void ze_launch_spec_accept(const ze_spec_step& a, int first_chain, hipStream_t s);
+// The accept pass of the sampled-mode chains [first_chain, a.n_chains) of the list, whose rows are [first_row, first_row + n_rows) of
+// the step: prepare (the rows' shadows) -> the per-chain sampling kernels over the rows -> the walk.  temperature / seed: the call's
+// (a chain without a request of its own follows them, its penalty is in its chain words); draws: some row may have a temperature;
+// samp / filt: the per-slot tables or null.
+void ze_launch_spec_accept_sampled(const ze_spec_step& a, const ze_spec_draw& d, int first_chain, int first_row, int n_rows, float temperature,
+                                   unsigned long long seed, bool draws, const ze_chain_sampling* samp, const float* filt, hipStream_t s);
 void ze_launch_spec_embed(const int* row_tok, int n, const bf16_t* embed, bf16_t* out, int hidden, hipStream_t s);
 
 // ---- beam search (ze_beam.hip)

@@ -88,7 +88,7 @@ static void write_filter(ze_engine* e, int seq, int top_k, float top_p, float mi
 extern "C" int ze_seq_set_sampling_filter(ze_engine* e, int seq, int top_k, float top_p, float min_p, void* stream) {
     ZE_TRY(check_seq(e, seq));
     ZE_TRY(ze_check_filter(e, top_k, top_p, min_p));
-    if ((top_k > 0 || top_p < 1.f || min_p > 0.f) && e->spec.on(seq)) return ze_fail(e, ZE_ERR_INVALID, "the chain speculates (ze_seq_set_speculation): greedy only, no sampling filter");
+    if ((top_k > 0 || top_p < 1.f || min_p > 0.f) && e->spec.on(seq) && !e->spec.sampled(seq)) return ze_fail(e, ZE_ERR_INVALID, "the chain speculates (ze_seq_set_speculation): greedy only, no sampling filter");
     hipSetDevice(e->device);
     write_filter(e, seq, top_k, top_p, min_p, (hipStream_t)stream);
     ZE_KCHECK();
@@ -144,7 +144,7 @@ extern "C" int ze_seq_set_sampling(ze_engine* e, int seq, int mode, float temper
         return ze_fail(e, ZE_ERR_INVALID, "temperature must be finite and > 0");
     if (mode >= 0 && !(std::isfinite(repetition_penalty) && repetition_penalty > 0.f))
         return ze_fail(e, ZE_ERR_INVALID, "repetition_penalty must be finite and > 0 (1 = off)");
-    if (mode == 1 && e->spec.on(seq)) return ze_fail(e, ZE_ERR_INVALID, "the chain speculates (ze_seq_set_speculation): greedy only");
+    if (mode == 1 && e->spec.on(seq) && !e->spec.sampled(seq)) return ze_fail(e, ZE_ERR_INVALID, "the chain speculates (ze_seq_set_speculation): greedy only");
     hipSetDevice(e->device);
     hipStream_t s = (hipStream_t)stream;
     if (mode >= 0 && !e->req.samp_dev) {
@@ -599,13 +599,15 @@ ze_sample_opts ze_sample_opts_of(ze_engine* e, const ze_gen_params* p, int slot,
 // The key of a captured step: the effective values of the launch (a new request re-captures), and per request kind what the step
 // launches for it -- of a single-chain step by THAT chain's request, of a batched step by the engine's.  Never a request's values.
 ze_step_key ze_step_key_of(const ze_engine* e, int n, int seq, float penalty, int ignore_eos, const ze_sample_opts& so, int kind, int n_plain,
-                           int n_chains) {
+                           int n_chains, int n_drawn, int n_drawn_rows) {
     const ze_requests& q = e->req;
     ze_step_key k;
     k.n = n;
     k.kind = kind;
     k.n_plain = n_plain;
     k.n_chains = n_chains;
+    k.n_drawn = n_drawn;
+    k.n_drawn_rows = n_drawn_rows;
     k.penalty = penalty;
     k.ignore_eos = ignore_eos;
     k.temperature = so.temperature;

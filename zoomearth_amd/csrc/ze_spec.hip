@@ -15,6 +15,7 @@
 // emitted and marked seen; the walk ends behind the last row, behind a token that is not draft id j, behind an EOS id, or when the
 // chain's room is used up.  Plain C++ stores from vector lanes only; nothing waits for the host.
 #include <cmath>
+#include <cstring>
 
 #include "ze_engine.h"
 
@@ -218,6 +219,138 @@ __global__ void __launch_bounds__(SP_THREADS) k_spec_accept_rows(const float* __
     out_finished[c] = s_fin;
 }
 
+// ------------------------------------------------------------------ sampled mode (ze_seq_set_speculation_mode, mode 1)
+// The token of row j is what the plain step's sampler gives on that row: the chain's request (greedy | temperature, seed, penalty,
+// filter), the draw index n_gen + j on the chain's own stream, and the seen-set as of row j -- the chain's plus draft ids 0 .. j - 1,
+// which ARE the tokens of rows 0 .. j - 1 whenever row j is reached.  Every row's inputs are therefore known before any row is drawn:
+// the prepare pass lays them down as per-row shadows (ze_spec_draw), the per-chain sampling kernels of ze_sample.hip draw all rows at
+// once with row = slot (ze_launch_sample_rows, as ze_op_sample_rows runs them: the same device functions as the plain step, so the
+// same bits), and the walk compares tokens with the draft and commits as k_spec_accept does.
+
+// the seen-set of row j: the chain's bytes, then draft ids 0 .. j - 1 (workgroup-wide; ids outside the vocabulary are skipped)
+__device__ __forceinline__ void spec_seen_row(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int vocab, const int* __restrict__ draft,
+                                              int j) {
+    if ((vocab & 15) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
+        for (int i = threadIdx.x; i < (vocab >> 4); i += blockDim.x) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
+    } else {
+        for (int i = threadIdx.x; i < vocab; i += blockDim.x) dst[i] = src[i];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < j && (unsigned)draft[threadIdx.x] < (unsigned)vocab) dst[draft[threadIdx.x]] = 1;
+}
+
+// chain form: workgroup (j, b) lays down the shadow of row j of chain first_chain + b
+__global__ void __launch_bounds__(256) k_spec_prepare(const ze_spec_step a, const ze_spec_draw d, int first_chain, int first_row, float temperature,
+                                                      unsigned long long seed, const ze_chain_sampling* __restrict__ samp,
+                                                      const float4* __restrict__ filt) {
+    const int c = first_chain + blockIdx.y, j = blockIdx.x;
+    const int slot = a.chains[ZE_SP_CHAIN_WORDS * c], row0 = a.chains[ZE_SP_CHAIN_WORDS * c + 1], rows = a.chains[ZE_SP_CHAIN_WORDS * c + 2];
+    if (j >= rows) return;
+    const int sh = row0 + j - first_row;
+    const bool live = j <= a.dlen[c];  // (a dead chain: -1)
+    // the chain's own request, else the call's values (chain_sampling_of of ze_sample.hip; the penalty was resolved by the host)
+    ze_chain_sampling r{temperature, __int_as_float(a.chains[ZE_SP_CHAIN_WORDS * c + 3]), seed};
+    if (samp) {
+        const ze_chain_sampling own = samp[slot];
+        if (own.penalty > 0.f) r = own;
+    }
+    if (!live) r = ze_chain_sampling{0.f, 1.0f, 0ull};  // a row the walk never reaches: the cheapest draw there is
+    if (threadIdx.x == 0) {
+        const ze_seq_dev cs = a.st[slot];
+        ze_seq_dev st = {};
+        st.n_gen = cs.n_gen + j;
+        st.stream = cs.stream;
+        d.samp[sh] = r;
+        d.st[sh] = st;
+        d.ids[sh] = sh;
+        reinterpret_cast<float4*>(d.filt)[sh] = filt && live ? filt[slot] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (!live || r.penalty == 1.0f) return;  // (the sampler reads a seen-set under a penalty alone)
+    spec_seen_row(a.seen + (size_t)slot * a.vocab, d.seen + (size_t)sh * a.vocab, a.vocab, a.row_tok + row0 + 1, j);
+}
+
+// unit form: the tables come from the host; row c * (k + 1) + j gets the seen-set of chain c as of row j
+__global__ void __launch_bounds__(256) k_spec_prepare_rows(const uint8_t* __restrict__ seen, uint8_t* __restrict__ scratch, int vocab, int k,
+                                                           const int* __restrict__ draft, const int* __restrict__ draft_len) {
+    const int c = blockIdx.y, j = blockIdx.x;
+    const int L = min(max(draft_len[c], 0), k);
+    spec_seen_row(seen + (size_t)c * vocab, scratch + ((size_t)c * (k + 1) + j) * vocab, vocab, draft + (size_t)c * k, min(j, L));
+}
+
+// The walk over the drawn tokens of one chain (one thread): tok[0 .. L], draft[0 .. L), room >= 1 tokens may be emitted.  Returns the
+// number emitted; *fin = an EOS id was emitted.
+__device__ __forceinline__ int spec_walk_drawn(const int* __restrict__ tok, const int* __restrict__ draft, int L, int room,
+                                               const int* __restrict__ eos_ids, int n_eos, int ignore_eos, int* fin) {
+    *fin = 0;
+    int m = 0;
+    for (int j = 0; j <= L; ++j) {
+        const int t = tok[j];
+        bool eos = false;
+        if (!ignore_eos)
+            for (int e = 0; e < n_eos; ++e) eos = eos || t == eos_ids[e];
+        if (eos) *fin = 1;
+        m = j + 1;
+        if (j == L || t != draft[j] || eos || j + 1 >= room) break;
+    }
+    return m;
+}
+
+// chain form: workgroup b (one wave, one thread at work) serves chain first_chain + b; the commit is k_spec_accept's
+__global__ void __launch_bounds__(64) k_spec_accept_drawn(const ze_spec_step a, const int32_t* __restrict__ tok, int first_chain, int first_row) {
+    if (threadIdx.x != 0) return;
+    const int c = first_chain + blockIdx.x;
+    const int slot = a.chains[ZE_SP_CHAIN_WORDS * c], row0 = a.chains[ZE_SP_CHAIN_WORDS * c + 1];
+    const int L = a.dlen[c];
+    if (L < 0) return;  // a dead chain: finished, or out of room
+    const int32_t* mine = tok + row0 - first_row;
+    int fin;
+    const int m = spec_walk_drawn(mine, a.row_tok + row0 + 1, L, L + 1, a.eos_ids, a.n_eos, a.ignore_eos, &fin);
+    uint8_t* seen = a.seen + (size_t)slot * a.vocab;
+    ze_seq_dev* st = a.st + slot;
+    const int n_gen = st->n_gen;
+    for (int q = 0; q < m; ++q) {
+        if (n_gen + q < st->max_gen) a.out_tokens[(size_t)slot * a.max_ctx + n_gen + q] = mine[q];
+        seen[mine[q]] = 1;
+    }
+    st->ctx += m;
+    st->n_gen = n_gen + m;
+    st->token = mine[m - 1];
+    if (fin) st->finished = 1;
+    int* t = const_cast<int*>(a.table) + (size_t)slot * ZE_SP_WORDS;
+    t[4] += 1;
+    t[5] += L;
+    t[6] += m - 1;
+}
+
+// unit form: the outputs of k_spec_accept_rows
+__global__ void __launch_bounds__(64) k_spec_accept_drawn_rows(const int32_t* __restrict__ tok, int vocab, int k, const int* __restrict__ draft,
+                                                               const int* __restrict__ draft_len, uint8_t* __restrict__ seen,
+                                                               const int* __restrict__ room, const int* __restrict__ eos_ids, int n_eos,
+                                                               int ignore_eos, int* __restrict__ out_tokens, int* __restrict__ out_count,
+                                                               int* __restrict__ out_finished) {
+    if (threadIdx.x != 0) return;
+    const int c = blockIdx.x;
+    const int L = min(max(draft_len[c], 0), k);
+    const int32_t* mine = tok + (size_t)c * (k + 1);
+    int fin;
+    const int m = spec_walk_drawn(mine, draft + (size_t)c * k, L, max(room[c], 1), eos_ids, n_eos, ignore_eos, &fin);
+    for (int q = 0; q <= k; ++q) out_tokens[(size_t)c * (k + 1) + q] = q < m ? mine[q] : -1;
+    if (seen)
+        for (int q = 0; q < m; ++q) seen[(size_t)c * vocab + mine[q]] = 1;
+    out_count[c] = m;
+    out_finished[c] = fin;
+}
+
+void ze_launch_spec_accept_sampled(const ze_spec_step& a, const ze_spec_draw& d, int first_chain, int first_row, int n_rows, float temperature,
+                                   unsigned long long seed, bool draws, const ze_chain_sampling* samp, const float* filt, hipStream_t s) {
+    const int n = a.n_chains - first_chain;
+    if (n <= 0 || n_rows <= 0) return;
+    k_spec_prepare<<<dim3(ZE_SP_MAX_K + 1, n), 256, 0, s>>>(a, d, first_chain, first_row, temperature, seed, samp, reinterpret_cast<const float4*>(filt));
+    ze_launch_sample_rows(a.logits + (size_t)first_row * a.vocab, a.vocab, a.vocab, d.seen, d.st, d.ids, n_rows, d.samp, draws,
+                          filt ? d.filt : nullptr, d.cuts, nullptr, d.part, d.sums, d.tok, s);
+    k_spec_accept_drawn<<<n, 64, 0, s>>>(a, d.tok, first_chain, first_row);
+}
+
 // the rows' input embeddings (k_embed_tokens_batch with the ids of the row table)
 __global__ void __launch_bounds__(256) k_spec_embed(const int* __restrict__ row_tok, int n, const bf16_t* __restrict__ embed,
                                                     bf16_t* __restrict__ out, int hidden) {
@@ -241,7 +374,9 @@ void ze_launch_spec_embed(const int* row_tok, int n, const bf16_t* embed, bf16_t
 // ------------------------------------------------------------------ host
 void ze_spec_free(ze_engine* e) {
     const ze_spec& q = e->spec;
-    void* dev[] = {q.table, q.row_seq, q.row_off, q.row_tok, q.chains, q.dlen, q.logits, q.partial, q.tickets};
+    const ze_spec_draw& d = q.draw;
+    void* dev[] = {q.table, q.row_seq, q.row_off, q.row_tok, q.chains, q.dlen, q.logits, q.partial, q.tickets,
+                   d.samp,  d.st,      d.filt,    d.ids,     d.seen,   d.cuts, d.part,   d.sums,    d.tok};
     for (void* p : dev)
         if (p) hipFree(p);
 }
@@ -261,18 +396,41 @@ void ze_spec_clear(ze_engine* e, int seq, hipStream_t s) {
     if (e->spec.on(seq)) write_spec(e, seq, ze_spec::chain_host{}, s);
 }
 
-// the buffers of the first request, all or none (the engine stays usable without them)
+// buffers that come with a first request, all or none (the engine stays usable without them)
+struct sp_item {
+    void** p;
+    size_t bytes;
+    bool zero;
+};
+static int alloc_all_or_none(ze_engine* e, const sp_item* items, int n, const char* msg) {
+    void* got[16] = {};
+    int k = 0;
+    bool ok = true;
+    for (; k < n; ++k) {
+        if (hipMalloc(&got[k], items[k].bytes) != hipSuccess || (items[k].zero && hipMemset(got[k], 0, items[k].bytes) != hipSuccess)) {
+            ok = false;
+            break;
+        }
+    }
+    // once per engine, and waited for: setters on other streams may write their entries at once
+    if (ok && hipStreamSynchronize(nullptr) != hipSuccess) ok = false;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (void* p : got)
+            if (p) hipFree(p);
+        return ze_fail(e, ZE_ERR_NOMEM, msg);
+    }
+    for (k = 0; k < n; ++k) *items[k].p = got[k];
+    return ZE_OK;
+}
+
 int ze_spec_alloc(ze_engine* e) {
     ze_spec& q = e->spec;
     const ze_config& c = e->cfg;
     if (q.table) return ZE_OK;
     if (q.host.empty()) q.host.assign(c.max_seqs, ze_spec::chain_host{}), q.pending.assign(c.max_seqs, 0);
     const int wparts = (c.max_ctx + 191) / 192;
-    struct item {
-        void** p;
-        size_t bytes;
-        bool zero;
-    } items[] = {
+    const sp_item items[] = {
         {(void**)&q.table, (size_t)c.max_seqs * ZE_SP_WORDS * sizeof(int), true},
         {(void**)&q.row_seq, ZE_SP_MAX_ROWS * sizeof(int), true},
         {(void**)&q.row_off, ZE_SP_MAX_ROWS * sizeof(int), true},
@@ -283,32 +441,28 @@ int ze_spec_alloc(ze_engine* e) {
         {(void**)&q.partial, (size_t)ZE_SP_MAX_ROWS * std::max(std::max(e->max_splits, 8), wparts) * c.heads * 132 * sizeof(float), false},
         {(void**)&q.tickets, (size_t)ZE_SP_MAX_ROWS * c.kv_heads * sizeof(unsigned), true},
     };
-    void* got[sizeof(items) / sizeof(items[0])] = {};
-    int k = 0;
-    bool ok = true;
-    for (const item& it : items) {
-        if (hipMalloc(&got[k], it.bytes) != hipSuccess || (it.zero && hipMemset(got[k], 0, it.bytes) != hipSuccess)) {
-            ok = false;
-            break;
-        }
-        ++k;
-    }
-    // once per engine, and waited for: setters on other streams may write their entries at once
-    if (ok && hipStreamSynchronize(nullptr) != hipSuccess) ok = false;
-    if (!ok) {
-        (void)hipGetLastError();
-        for (void* p : got)
-            if (p) hipFree(p);
-        return ze_fail(e, ZE_ERR_NOMEM, "hipMalloc of the speculation buffers failed");
-    }
-    k = 0;
-    for (const item& it : items) *it.p = got[k++];
-    return ZE_OK;
+    return alloc_all_or_none(e, items, (int)(sizeof(items) / sizeof(items[0])), "hipMalloc of the speculation buffers failed");
 }
 
-extern "C" int ze_seq_set_speculation(ze_engine* e, int seq, int k, int min_ngram, int max_ngram, const int32_t* prompt_ids, int n_prompt,
-                                      void* stream) {
+// the per-row shadows of the sampled mode, with its first request
+static int spec_alloc_draw(ze_engine* e) {
+    ze_spec_draw& d = e->spec.draw;
+    if (d.samp) return ZE_OK;
+    const size_t R = ZE_SP_MAX_ROWS;
+    const sp_item items[] = {
+        {(void**)&d.samp, R * sizeof(ze_chain_sampling), true}, {(void**)&d.st, R * sizeof(ze_seq_dev), true},
+        {(void**)&d.filt, R * 4 * sizeof(float), true},         {(void**)&d.ids, R * sizeof(int), true},
+        {(void**)&d.seen, R * (size_t)e->cfg.vocab, true},      {(void**)&d.cuts, R * sizeof(float), true},
+        {(void**)&d.part, R * 2 * 128 * sizeof(float), true},   {(void**)&d.sums, R * 128 * sizeof(float), true},
+        {(void**)&d.tok, R * sizeof(int32_t), true},
+    };
+    return alloc_all_or_none(e, items, (int)(sizeof(items) / sizeof(items[0])), "hipMalloc of the sampled-speculation buffers failed");
+}
+
+static int set_speculation(ze_engine* e, int seq, int k, int min_ngram, int max_ngram, const int32_t* prompt_ids, int n_prompt, int mode,
+                           void* stream) {
     ZE_TRY(check_seq(e, seq));
+    if (mode != 0 && mode != 1) return ze_fail(e, ZE_ERR_INVALID, "mode must be 0 (greedy) or 1 (sampled)");
     const ze_config& c = e->cfg;
     hipSetDevice(e->device);
     hipStream_t s = (hipStream_t)stream;
@@ -326,15 +480,17 @@ extern "C" int ze_seq_set_speculation(ze_engine* e, int seq, int k, int min_ngra
     if (e->wide_regime())
         return ze_fail(e, ZE_ERR_INVALID, "speculation needs the fragment kernels: this engine runs the row-streaming family (ze_set_decode_regime)");
     const ze_requests& r = e->req;
-    if (r.samp_host[seq].penalty > 0.f && r.samp_host[seq].temperature > 0.f)
+    if (mode == 0 && r.samp_host[seq].penalty > 0.f && r.samp_host[seq].temperature > 0.f)
         return ze_fail(e, ZE_ERR_INVALID, "speculation is greedy only: the chain has a sampled request (ze_seq_set_sampling)");
-    if (r.filt_host[seq].on()) return ze_fail(e, ZE_ERR_INVALID, "speculation is greedy only: the chain has a sampling filter");
-    if (r.ent_host[seq].on()) return ze_fail(e, ZE_ERR_INVALID, "speculation is greedy only: the chain has an entropy filter");
+    if (mode == 0 && r.filt_host[seq].on()) return ze_fail(e, ZE_ERR_INVALID, "speculation is greedy only: the chain has a sampling filter");
+    if (r.ent_host[seq].on())
+        return ze_fail(e, ZE_ERR_INVALID, mode ? "speculation excludes an entropy filter on the same chain" : "speculation is greedy only: the chain has an entropy filter");
     if (r.la_host[seq].on()) return ze_fail(e, ZE_ERR_INVALID, "speculation excludes a logit adjust on the same chain");
     if (r.tr_host[seq].on()) return ze_fail(e, ZE_ERR_INVALID, "speculation excludes token rules on the same chain");
     if (r.gr_host[seq] >= 0) return ze_fail(e, ZE_ERR_INVALID, "speculation excludes a grammar on the same chain");
     if (r.lp_host[seq] >= 0) return ze_fail(e, ZE_ERR_INVALID, "speculation excludes log-probabilities on the same chain");
     ZE_TRY(ze_spec_alloc(e));
+    if (mode == 1) ZE_TRY(spec_alloc_draw(e));
     if (!e->req.tr_ctx) {  // the context history of the token rules holds the prompt ids (a chain has rules or speculation, never both)
         int* ctx = nullptr;
         if (hipMalloc((void**)&ctx, (size_t)c.max_seqs * c.max_ctx * sizeof(int)) != hipSuccess) {
@@ -347,10 +503,20 @@ extern "C" int ze_seq_set_speculation(ze_engine* e, int seq, int k, int min_ngra
     if (n_prompt > 0)
         ZE_HIP(hipMemcpyAsync(e->req.tr_ctx + (size_t)seq * c.max_ctx, prompt_ids, (size_t)n_prompt * sizeof(int), hipMemcpyHostToDevice, s));
     ze_spec::chain_host h;
-    h.k = k, h.min_ngram = min_ngram, h.max_ngram = max_ngram, h.n_prompt = n_prompt;
+    h.k = k, h.min_ngram = min_ngram, h.max_ngram = max_ngram, h.n_prompt = n_prompt, h.mode = mode;
     write_spec(e, seq, h, s);
     ZE_KCHECK();
     return ZE_OK;
+}
+
+extern "C" int ze_seq_set_speculation(ze_engine* e, int seq, int k, int min_ngram, int max_ngram, const int32_t* prompt_ids, int n_prompt,
+                                      void* stream) {
+    return set_speculation(e, seq, k, min_ngram, max_ngram, prompt_ids, n_prompt, 0, stream);
+}
+
+extern "C" int ze_seq_set_speculation_mode(ze_engine* e, int seq, int k, int min_ngram, int max_ngram, const int32_t* prompt_ids, int n_prompt,
+                                           int mode, void* stream) {
+    return set_speculation(e, seq, k, min_ngram, max_ngram, prompt_ids, n_prompt, mode, stream);
 }
 
 extern "C" int ze_chain_spec_stats(ze_engine* e, int seq, int* steps, int* drafted, int* accepted, void* stream) {
@@ -394,4 +560,74 @@ extern "C" int ze_op_spec_accept(ze_engine* e, const float* logits, int n_chains
                                                                         e->eos_dev, e->cfg.n_eos, ignore_eos, out_tokens, out_count, out_finished);
     ZE_KCHECK();
     return ZE_OK;
+}
+
+// The sampled accept pass alone: the shadows of the n_chains x (k + 1) rows on tables built for the call (the requests, draw indices
+// and filters by the host, the seen-sets by k_spec_prepare_rows), the per-chain sampling kernels over them, the walk.
+extern "C" int ze_op_spec_accept_sampled(ze_engine* e, const float* logits, int n_chains, int vocab, int ld, int k, const int32_t* draft,
+                                         const int32_t* draft_len, uint8_t* seen, const float* repetition_penalty, const int32_t* room,
+                                         int ignore_eos, const float* temperature, const uint64_t* seed, const int32_t* sample_stream,
+                                         const int32_t* index0, const int32_t* top_k, const float* top_p, const float* min_p,
+                                         int32_t* out_tokens, int32_t* out_count, int32_t* out_finished, void* stream) {
+    if (!e || !logits || !draft || !draft_len || !room || !out_tokens || !out_count || !out_finished || !temperature || !seed || !sample_stream || !index0)
+        return ze_fail(e, ZE_ERR_INVALID, "null argument");
+    if (seen && !repetition_penalty) return ze_fail(e, ZE_ERR_INVALID, "a seen-set needs the penalties");
+    if (n_chains < 0 || vocab <= 0 || ld < vocab) return ze_fail(e, ZE_ERR_INVALID, "n_chains >= 0, vocab > 0 and ld >= vocab");
+    if (k < 1 || k > ZE_SP_MAX_K) return ze_fail(e, ZE_ERR_INVALID, "k must be in [1, 8]");
+    const bool filters = top_k || top_p || min_p;
+    if (filters && !(top_k && top_p && min_p)) return ze_fail(e, ZE_ERR_INVALID, "top_k, top_p and min_p come together or not at all");
+    if (n_chains == 0) return ZE_OK;
+    const size_t rows = (size_t)n_chains * (k + 1);
+    // one block of 4-byte words: requests (4 per row) | chain states (8) | filters (4) | row ids | cuts | tokens | arg-max partials
+    // (256) | chunk sums (128), then the seen-sets as of every row (bytes); the host fills the words before the partials
+    static_assert(sizeof(ze_chain_sampling) == 16 && sizeof(ze_seq_dev) == 32, "table strides");
+    const size_t o_samp = 0, o_st = o_samp + 4 * rows, o_filt = o_st + 8 * rows, o_ids = o_filt + 4 * rows, o_cut = o_ids + rows, o_tok = o_cut + rows,
+                 o_part = o_tok + rows, o_sum = o_part + 256 * rows, o_seen = o_sum + 128 * rows, words = o_seen + (seen ? (rows * vocab + 3) / 4 : 0);
+    std::vector<int32_t> host(o_part, 0);
+    bool draws = false;
+    for (int c = 0; c < n_chains; ++c) {
+        if (!(std::isfinite(temperature[c]) && temperature[c] >= 0.f)) return ze_fail(e, ZE_ERR_INVALID, "temperature must be finite and >= 0 (0 = greedy)");
+        const float pen = seen ? repetition_penalty[c] : 1.0f;
+        if (!(std::isfinite(pen) && pen > 0.f)) return ze_fail(e, ZE_ERR_INVALID, "repetition_penalty must be finite and > 0 (1 = off)");
+        if (index0[c] < 0) return ze_fail(e, ZE_ERR_INVALID, "index0 must be >= 0");
+        if (filters) ZE_TRY(ze_check_filter(e, top_k[c], top_p[c], min_p[c]));
+        draws |= temperature[c] > 0.f;
+        for (int j = 0; j <= k; ++j) {
+            const size_t r = (size_t)c * (k + 1) + j;
+            const ze_chain_sampling req{temperature[c], pen, temperature[c] > 0.f ? (unsigned long long)seed[c] : 0ull};
+            memcpy(&host[o_samp + 4 * r], &req, sizeof(req));
+            ze_seq_dev st;
+            memset(&st, 0, sizeof(st));
+            st.n_gen = index0[c] + j;
+            st.stream = sample_stream[c];
+            memcpy(&host[o_st + 8 * r], &st, sizeof(st));
+            host[o_ids + r] = (int32_t)r;
+            if (filters) {
+                host[o_filt + 4 * r] = top_k[c];
+                memcpy(&host[o_filt + 4 * r + 1], &top_p[c], sizeof(float));
+                memcpy(&host[o_filt + 4 * r + 2], &min_p[c], sizeof(float));
+            }
+        }
+    }
+    hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    int32_t* dev = nullptr;
+    ZE_HIP(hipMalloc((void**)&dev, words * sizeof(int32_t)));
+    int r = ZE_OK;
+    if (hipMemcpyAsync(dev, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess)
+        r = ze_fail(e, ZE_ERR_HIP, "hipMemcpyAsync failed");
+    if (r == ZE_OK) {
+        uint8_t* scratch = seen ? reinterpret_cast<uint8_t*>(dev + o_seen) : nullptr;
+        if (seen) k_spec_prepare_rows<<<dim3(k + 1, n_chains), 256, 0, s>>>(seen, scratch, vocab, k, draft, draft_len);
+        ze_launch_sample_rows(logits, vocab, ld, scratch, reinterpret_cast<const ze_seq_dev*>(dev + o_st), dev + o_ids, (int)rows,
+                              reinterpret_cast<const ze_chain_sampling*>(dev + o_samp), draws,
+                              filters ? reinterpret_cast<const float*>(dev + o_filt) : nullptr, reinterpret_cast<float*>(dev + o_cut), nullptr,
+                              reinterpret_cast<float*>(dev + o_part), reinterpret_cast<float*>(dev + o_sum), dev + o_tok, s);
+        k_spec_accept_drawn_rows<<<n_chains, 64, 0, s>>>(dev + o_tok, vocab, k, draft, draft_len, seen, room, e->eos_dev, e->cfg.n_eos, ignore_eos,
+                                                        out_tokens, out_count, out_finished);
+    }
+    if (r == ZE_OK && hipGetLastError() != hipSuccess) r = ze_fail(e, ZE_ERR_HIP, "sampled accept launch failed");
+    if (hipStreamSynchronize(s) != hipSuccess && r == ZE_OK) r = ze_fail(e, ZE_ERR_HIP, "hipStreamSynchronize failed");
+    hipFree(dev);
+    return r;
 }

@@ -985,23 +985,34 @@ class Engine:
         self._check(self.lib.ze_generate(self.h, seq, C.byref(p), out, C.byref(n), self._stream()))
         return [int(out[i]) for i in range(n.value)]
 
-    def set_speculation(self, seq: int, k: int, prompt_ids=(), ngram_min: int = 1, ngram_max: int = 3):
+    def set_speculation(self, seq: int, k: int, prompt_ids=(), ngram_min: int = 1, ngram_max: int = 3, sampled: bool = False):
         """Speculative decoding by prompt lookup for chain `seq` (ze_seq_set_speculation; HF's prompt_lookup_num_tokens, vLLM's
         ngram method): up to `k` draft ids per step, looked up in prompt_ids + the generated ids by the most recent earlier
         occurrence of the last ngram_max .. ngram_min ids, verified in the same family-0 step.  Lossless and greedy only; k = 0
-        clears.  Set after the chain's prefill; held until the slot is reset, truncated or copied into."""
+        clears.  Set after the chain's prefill; held until the slot is reset, truncated or copied into.
+        sampled=True (ze_seq_set_speculation_mode, mode 1): the chain may sample -- temperature, seed, penalty, top-k / top-p /
+        min-p, its own or the call's; every row draws the token a plain step at its position draws, so the answer is still bit for
+        bit the plain one."""
         ids, ip = _i32(list(prompt_ids) if k else [])
+        if sampled:
+            self._check(self.lib.ze_seq_set_speculation_mode(self.h, int(seq), int(k), int(ngram_min), int(ngram_max), ip, len(ids), 1,
+                                                             self._stream()))
+            return
         self._check(self.lib.ze_seq_set_speculation(self.h, int(seq), int(k), int(ngram_min), int(ngram_max), ip, len(ids), self._stream()))
 
     def generate_speculative(self, seqs, max_new_tokens: int, repetition_penalty: float = 1.0, ignore_eos: bool = False,
-                             use_graph: bool = True, burst: int = 8):
-        """Greedy generation for prefilled chains through family-0 bursts (chain_begin + decode_burst), the path chains with
+                             use_graph: bool = True, burst: int = 8, do_sample: bool = False, temperature: float = 1.0, seed: int = 0,
+                             sample_streams=None):
+        """Generation for prefilled chains through family-0 bursts (chain_begin + decode_burst), the path chains with
         set_speculation take: a step emits up to k + 1 tokens per speculating chain.  Returns one id list per chain, trimmed to
-        max_new_tokens -- bit for bit what the same bursts give without speculation."""
+        max_new_tokens -- bit for bit what the same bursts give without speculation.  do_sample / temperature / seed: the call's
+        sampling (chains that speculate then need set_speculation(sampled=True)); sample_streams: the random stream per chain
+        (default: its position in `seqs`)."""
         seqs = [int(s) for s in seqs]
-        p = self.gen_params(repetition_penalty=repetition_penalty, ignore_eos=ignore_eos, use_graph=use_graph)
+        p = self.gen_params(repetition_penalty=repetition_penalty, ignore_eos=ignore_eos, use_graph=use_graph, do_sample=do_sample,
+                            temperature=temperature, seed=seed)
         for i, s in enumerate(seqs):
-            self.chain_begin(s, p, i)
+            self.chain_begin(s, p, i if sample_streams is None else int(sample_streams[i]))
         n_gen, fin, live = {s: 1 for s in seqs}, {s: False for s in seqs}, list(seqs)
         while live:
             live = [s for s in live if n_gen[s] < max_new_tokens and not fin[s] and self.seq_len(s) < self.max_ctx]
@@ -1056,6 +1067,48 @@ class Engine:
         self._check(self.lib.ze_op_spec_accept(self.h, _ptr(logits), n, int(logits.shape[1]), int(logits.stride(0)), k, _ptr(dd), _ptr(dl),
                                                _ptr(seen), _ptr(pen), _ptr(rm), int(bool(ignore_eos)), _ptr(out), _ptr(cnt), _ptr(fin),
                                                self._stream()))
+        o, m, f = out.cpu().numpy(), cnt.cpu().numpy(), fin.cpu().numpy()
+        return [[int(t) for t in o[c, :m[c]]] for c in range(n)], [bool(x) for x in f]
+
+    def op_spec_accept_sampled(self, logits: torch.Tensor, drafts, k: int, temperature, seed=0, sample_stream=0, index0=0,
+                               seen: Optional[torch.Tensor] = None, repetition_penalty=1.0, room=None, ignore_eos: bool = False,
+                               top_k=None, top_p=None, min_p=None):
+        """The accept pass of the sampled mode alone (ze_op_spec_accept_sampled): op_spec_accept's arguments (logits f32
+        [n * (k + 1), vocab], row stride >= vocab) plus, per chain (scalars broadcast), temperature (0 = greedy), seed,
+        sample_stream, index0 (the draw index of row 0) and top_k / top_p / min_p (or all None).  Returns (emitted ids per chain,
+        finished flags); seen is updated in place."""
+        n, k = len(drafts), int(k)
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == n * (k + 1)
+        vocab = int(logits.shape[1])
+        if seen is not None:
+            assert seen.dtype == torch.uint8 and seen.is_contiguous() and tuple(seen.shape) == (n, vocab)
+        d = np.full((n, k), -1, dtype=np.int32)
+        for c, dr in enumerate(drafts):
+            d[c, :len(dr)] = dr
+        dd = torch.from_numpy(d).to(self.device)
+        dl = torch.tensor([len(dr) for dr in drafts], dtype=torch.int32, device=self.device)
+
+        def per_chain(v, dtype):
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (n,)))
+        pen = torch.tensor(per_chain(repetition_penalty, np.float32).copy(), device=self.device)
+        rm = torch.tensor(per_chain(k + 1 if room is None else room, np.int32).copy(), device=self.device)
+        t, sd = per_chain(temperature, np.float32), per_chain(seed, np.uint64)
+        strm, idx = per_chain(sample_stream, np.int32), per_chain(index0, np.int32)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        filt = (None, None, None)
+        if top_k is not None or top_p is not None or min_p is not None:
+            filt = (per_chain(0 if top_k is None else top_k, np.int32), per_chain(1.0 if top_p is None else top_p, np.float32),
+                    per_chain(0.0 if min_p is None else min_p, np.float32))
+        out = torch.empty((n, k + 1), dtype=torch.int32, device=self.device)
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device)
+        fin = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._use(logits)
+        self._check(self.lib.ze_op_spec_accept_sampled(
+            self.h, _ptr(logits), n, vocab, int(logits.stride(0)), k, _ptr(dd), _ptr(dl), _ptr(seen) if seen is not None else None,
+            _ptr(pen), _ptr(rm), int(bool(ignore_eos)), t.ctypes.data_as(fp), sd.ctypes.data_as(C.POINTER(C.c_uint64)),
+            strm.ctypes.data_as(ip), idx.ctypes.data_as(ip), filt[0].ctypes.data_as(ip) if filt[0] is not None else None,
+            filt[1].ctypes.data_as(fp) if filt[1] is not None else None, filt[2].ctypes.data_as(fp) if filt[2] is not None else None,
+            _ptr(out), _ptr(cnt), _ptr(fin), self._stream()))
         o, m, f = out.cpu().numpy(), cnt.cpu().numpy(), fin.cpu().numpy()
         return [[int(t) for t in o[c, :m[c]]] for c in range(n)], [bool(x) for x in f]
 

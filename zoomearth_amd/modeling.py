@@ -569,6 +569,8 @@ class ZoomEarthForConditionalGeneration:
         g = 3 if g is None else g
         if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not (1 <= g <= 8):
             raise ValueError(f"`max_matching_ngram_size` has to be an integer in [1, 8], but is {g!r}")
+        if kw.get("prompt_lookup_sampling"):   # the sampled mode (Engine.set_speculation(sampled=True)): opt-in, rows budgeted by the caller
+            return int(k), int(g)
         if do_sample or num_return_sequences != 1:
             raise ValueError("`prompt_lookup_num_tokens` is greedy speculative decoding here: it is not supported with "
                              "`do_sample=True` or `num_return_sequences` > 1.")
@@ -624,7 +626,10 @@ class ZoomEarthForConditionalGeneration:
         `prompt_lookup_num_tokens` = k (HF's; 1 .. 8) with `max_matching_ngram_size` (default 3, as HF's is 2 .. here up to 8):
         speculative decoding by prompt lookup on the device (Engine.set_speculation), greedy only.  The call goes through the
         family-0 bursts (Engine.generate_speculative) and returns bit for bit what those bursts return without it -- the batched
-        family's sequence, which agrees with the single-chain path's within bf16 rounding."""
+        family's sequence, which agrees with the single-chain path's within bf16 rounding.
+        `prompt_lookup_sampling=True` with it: the sampled mode -- `do_sample=True` with temperature, seed and top-k / top-p / min-p
+        (and `num_return_sequences` > 1 while two rows per completion fit a step's 64) speculate too; every row draws the token the
+        plain family-0 bursts draw with the same seed, so the result is still theirs bit for bit."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not part of the ZoomEarth path (num_beams=1 everywhere)")
         k = num_return_sequences
@@ -671,8 +676,12 @@ class ZoomEarthForConditionalGeneration:
         presence, frequency, min_new, bias = self._logit_adjust_request(kw)
         ngram, stop, bad, stop_strings = self._token_rules_request(kw)
         spec_k, spec_g = self._speculation_request(kw, do_sample, k)
+        spec_sampling = bool(spec_k and kw.get("prompt_lookup_sampling"))
+        if spec_sampling and k > 1 and ids_cpu.shape[0] * k * 2 > 64:   # (1 + k_eff rows per completion, k_eff >= 1: generate_speculative's budget)
+            raise ValueError("`prompt_lookup_num_tokens` is greedy speculative decoding here: it is not supported with "
+                             "`do_sample=True` or `num_return_sequences` > 1.")
         # generate's sampling goes through gen_params and Engine.generate(**sample_kw): the chain carries none of its own, no filter
-        chain = ChainRequest(speculative_tokens=spec_k, ngram_max=spec_g, ngram_min=1, effective_penalty=float(pen), logprobs=logprobs, presence_penalty=presence, frequency_penalty=frequency,
+        chain = ChainRequest(speculative_tokens=spec_k, ngram_max=spec_g, ngram_min=1, speculative_sampling=spec_sampling, effective_penalty=float(pen), logprobs=logprobs, presence_penalty=presence, frequency_penalty=frequency,
                              min_new_tokens=min_new, logit_bias=bias, no_repeat_ngram_size=ngram, stop_ids=stop, bad_words_ids=bad)
         guided = None
         if kw.get("guided_regex") is not None or kw.get("guided_choice") is not None:
@@ -777,6 +786,15 @@ class ZoomEarthForConditionalGeneration:
         return BeamSearchOutput(sequences=res.to(input_ids.device),
                                 sequences_scores=torch.from_numpy(scores.reshape(-1).copy()) if output_scores else None, beam_indices=bix)
 
+    @staticmethod
+    def _speculative_sampling_kw(e, slots, chain: ChainRequest, sample_kw) -> dict:
+        """What generate_speculative gets of the call's sampling: nothing in greedy mode (today's call); in sampled mode the call's
+        do_sample / temperature / seed, behind its top-k / top-p / min-p written to the slots as generate_batch writes them."""
+        if not (chain.speculative_sampling and sample_kw.get("do_sample")):
+            return {}
+        e._apply_filter(slots, sample_kw.get("top_k"), sample_kw.get("top_p"), sample_kw.get("min_p"))
+        return dict(do_sample=True, temperature=sample_kw["temperature"], seed=sample_kw["seed"])
+
     def _generate_rows(self, rows: _Rows, chain: ChainRequest, gid, max_new_tokens, ignore_eos, sample_kw, stop_strings, tokenizer,
                        k: int = 1):
         e, cfg = self.engine, self.config
@@ -836,7 +854,8 @@ class ZoomEarthForConditionalGeneration:
                 self._chains.move_to_end(slot)
                 chain.install(e, slot, ids, gid)  # (the reset / truncate above cleared the slot's previous request)
                 if spec:
-                    outs.append(e.generate_speculative([slot], max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos)[0])
+                    outs.append(e.generate_speculative([slot], max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos,
+                                                       **self._speculative_sampling_kw(e, [slot], chain, sample_kw))[0])
                 else:
                     outs.append(e.generate(slot, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw))
                 if logprobs is not None:
@@ -867,8 +886,9 @@ class ZoomEarthForConditionalGeneration:
                 k_eff = min(chain.speculative_tokens, 64 // len(slots) - 1)
                 if k_eff < chain.speculative_tokens:
                     for slot, _, _, _, _, ids in pending:
-                        e.set_speculation(slot, k_eff, ids, chain.ngram_min, chain.ngram_max)
-                outs = e.generate_speculative(slots, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos)
+                        e.set_speculation(slot, k_eff, ids, chain.ngram_min, chain.ngram_max, **(dict(sampled=True) if chain.speculative_sampling else {}))
+                outs = e.generate_speculative(slots, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos,
+                                              **self._speculative_sampling_kw(e, slots, chain, sample_kw))
             else:
                 outs = e.generate_batch(slots, max_new_tokens, repetition_penalty=pen, ignore_eos=ignore_eos, **sample_kw)
             if logprobs is not None:

@@ -91,6 +91,9 @@ class Request:
     # request that names it together with sampling, log-probabilities, logit adjustments, token rules or a grammar is refused.
     # Init-only like prompt_logprobs, and for the same reason
     speculative_tokens: InitVar[Optional[int]] = None
+    # the sampled mode of speculation for this request (None = the scheduler's default): a sampled request, with its top-k / top-p /
+    # min-p, speculates too -- every row draws what a plain step draws (Engine.set_speculation(sampled=True)).  Init-only likewise
+    speculative_sampling: InitVar[Optional[bool]] = None
     # HF's typical_p / epsilon_cutoff / eta_cutoff of this request (None = the scheduler's default; 1.0 / 0.0 / 0.0 = off), resolved
     # like min_p and written with the sampling filter.  Init-only like prompt_logprobs, and for the same reason
     typical_p: InitVar[Optional[float]] = None
@@ -108,10 +111,12 @@ class Request:
     # with `prompt_logprobs`: one entry per prompt token, there before on_done runs -- the token's log-probability given the ids in
     # front of it, its 0-based rank, and the best alternatives at its place as (id, logprob), best first.  None at position 0 and
     # wherever the predicting row was not computed by the request's own pass (a cached prefix of its slot)
-    def __post_init__(self, prompt_logprobs, n=1, speculative_tokens=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
+    def __post_init__(self, prompt_logprobs, n=1, speculative_tokens=None, speculative_sampling=None, typical_p=None, epsilon_cutoff=None,
+                      eta_cutoff=None):
         self.typical_p, self.epsilon_cutoff, self.eta_cutoff = typical_p, epsilon_cutoff, eta_cutoff
         self.prompt_logprobs = prompt_logprobs
         self.speculative_tokens = speculative_tokens
+        self.speculative_sampling = speculative_sampling
         self.n, self.index, self.parent = n, 0, None
         self.prompt_token_logprobs, self.prompt_ranks, self.prompt_top_logprobs = [], [], []
 
@@ -189,8 +194,10 @@ class ChainScheduler:
                  frequency_penalty: Optional[float] = None, logit_bias: Optional[dict] = None, min_new_tokens: Optional[int] = None,
                  prefix_cache_rows: int = 0, prefix_cache_block_rows: int = 32, prefix_cache=None, adapter=KEEP_ADAPTER,
                  speculative_tokens: int = 0, ngram_min: int = 1, ngram_max: int = 3, typical_p: Optional[float] = None,
-                 epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None):
+                 epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, speculative_sampling: bool = False):
         self.model, self.processor, self.engine = model, processor, model.engine
+        # the sampled mode of speculation, the default of requests that name none: off -- a sampled request then rides with one row
+        self.speculative_sampling = bool(speculative_sampling)
         self.typical_p, self.epsilon_cutoff, self.eta_cutoff = typical_p, epsilon_cutoff, eta_cutoff
         # Speculative decoding by prompt lookup: the default of requests that name none (0 = off).  A step of the fragment family
         # holds 64 rows, one per chain and one more per draft id: a chain's k is lowered when it joins so that the live chains' rows,
@@ -909,6 +916,9 @@ class ChainScheduler:
             raise ValueError(f"`speculative_tokens` has to be an integer in [0, 8], but is {k!r}")
         if not k:
             return chain
+        sampling = getattr(req, "speculative_sampling", None)
+        sampling = self.speculative_sampling if sampling is None else bool(sampling)
+        chain = dataclasses.replace(chain, speculative_sampling=sampling)
         what = chain.speculation_conflict(grammar=self._grammar_key(req) is not None)
         if what is not None:
             if own is None:

@@ -177,11 +177,14 @@ class ChatServer:
     (`complete`), as an explicit batch (`complete_many`) or through the batching dispatcher (`submit`)."""
 
     def __init__(self, model, processor, model_id: str = "ZoomEarth", batch_window_s: float = 0.01, max_batch=None,
-                 prefix_cache_rows: int = 0, speculative_ngram: int = 0):
+                 prefix_cache_rows: int = 0, speculative_ngram: int = 0, speculative_sampling: bool = False):
         self.model, self.processor, self.model_id = model, processor, model_id
         # --speculative-ngram K: greedy requests without log-probabilities, adjustments, rules or a grammar draft up to K ids per
         # step by prompt lookup (vLLM's ngram method; ChainScheduler(speculative_tokens=)); lossless.  0: off, today's steps.
         self.speculative_ngram = int(speculative_ngram or 0)
+        # --speculative-sampling: sampled requests (temperature, seed, top_p) speculate too, in the sampled mode
+        # (ChainScheduler(speculative_sampling=True)): every row draws what a plain step draws.  Off: they ride with one row.
+        self.speculative_sampling = bool(speculative_sampling)
         # --prefix-cache-rows N: the K/V rows of finished requests stay in a pool of N rows (zoomearth_amd/prefix_cache.py), and a
         # later request whose prompt starts with them -- stage 2 of a question, the next question of a tile -- prefills only its
         # tail; `usage.prompt_tokens_details.cached_tokens` reports the rows it did not compute.  0: no pool, today's responses.
@@ -639,6 +642,8 @@ class ChatServer:
                         kw["prefix_cache"] = self.prefix_cache
                     if self.speculative_ngram > 0:
                         kw["speculative_tokens"] = self.speculative_ngram
+                        if self.speculative_sampling:
+                            kw["speculative_sampling"] = True
                     sched = ChainScheduler(self.model, self.processor, do_sample=False, max_batch=self.max_batch, burst=8, **kw)
                     self.scheduler = sched
                 def admit(reqs):
@@ -692,6 +697,7 @@ def create_app(server: ChatServer):
             card["weight_format"] = engine.weight_format   # "bf16", or the reduced-precision decode stream: "fp8" / "mxfp4"
         if getattr(server, "speculative_ngram", 0) > 0:
             card["speculative_ngram"] = server.speculative_ngram   # draft ids per step by prompt lookup (lossless)
+            card["speculative_sampling"] = bool(getattr(server, "speculative_sampling", False))   # sampled requests speculate too
         return {"object": "list", "data": [card]}
 
     @app.post("/v1/chat/completions")
@@ -729,6 +735,9 @@ def main():  # pragma: no cover
     ap.add_argument("--speculative-ngram", type=int, default=0,
                     help="speculative decoding by prompt lookup: up to K draft ids per step for greedy requests (vLLM's ngram method; "
                          "lossless; 0 = off; needs at most 64 chain slots; reported by /v1/models)")
+    ap.add_argument("--speculative-sampling", action="store_true",
+                    help="with --speculative-ngram: sampled requests (temperature / seed / top_p) speculate too, each row drawing "
+                         "what a plain step draws (lossless; reported by /v1/models)")
     ap.add_argument("--lora", default=None, help="a PEFT LoRA adapter directory: loaded and activated at start (listed by /v1/models)")
     ap.add_argument("--weight-format", default="bf16", choices=["bf16", "fp8", "mxfp4"],
                     help="decode weight stream: fp8 / mxfp4 quantise the decoder's linear layers (reduced precision, opt-in; "
@@ -740,7 +749,7 @@ def main():  # pragma: no cover
     processor = ZoomEarthProcessor.from_pretrained(args.model_name, trust_remote_code=True, max_pixels=128 * 128 * 28 * 28)
     processor.tokenizer.padding_side = "left"
     uvicorn.run(create_app(ChatServer(model, processor, args.served_model_name, prefix_cache_rows=args.prefix_cache_rows,
-                                     speculative_ngram=args.speculative_ngram)),
+                                     speculative_ngram=args.speculative_ngram, speculative_sampling=args.speculative_sampling)),
                 host=args.host, port=args.port)
 
 
