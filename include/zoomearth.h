@@ -1001,31 +1001,40 @@ int ze_profile_prefill_layer(ze_engine* e, int rows, int layers_run, float avg_u
 /* Measurement-only kernel-configuration override (A/B of kernels and launch shapes inside one process; value 0 is always
  * the shipped default, every alternative computes the same function -- bit for bit unless noted).  Knobs (0..24; round 4 re-used
  * knobs 3 and 4, which until round 3 switched the removed one-launch-per-layer kernels: an old `3:1` / `4:1` habit now changes GEMM
- * tiling / launch form -- same results, different speed):
- *   0, 1  variants of the single-chain down / gate-up GEMVs          2   grid cap of the GEMV family
- *   3     first row count of the 320 x 192 decode tiles (measurements) 5   1: no fragment / skinny kernels in the batched step
- *   4     launch form of the eight-phase GEMM: 0 = by the number of engines alive in this process (one: persistent workgroups;
- *         several -- lanes sharing the GPU --: one tile per workgroup, so that the other engine's kernels get CUs at tile boundaries;
- *         the library counts its engines itself, no caller sets this), 1 = always one tile per workgroup, 2 = always persistent
+ * tiling / launch form -- same results, different speed); one row per knob, with its name in zoomearth_amd/csrc/ze_knobs.h, which also
+ * names the values the launch rules compare against:
+ *   0  ZE_KNOB_GEMV_DOWN           variants of the single-chain down GEMV (1 .. 3)
+ *   1  ZE_KNOB_GATE_UP_FLASH       variants of the single-chain gate/up GEMV (1, 2); 7 / 9: the prefill flash attention on its register-
+ *                                  staged form / on 64-row query tiles (9: the ViT's full-attention blocks too) -- the same bits
+ *   2  ZE_KNOB_GEMV_GRID_CAP       grid cap of the GEMV family
+ *   3  ZE_KNOB_RING32_FROM         first row count of the 320 x 192 decode tiles (measurements)
+ *   4  ZE_KNOB_P8_LAUNCH           launch form of the eight-phase GEMM: 0 = by the number of engines alive in this process (one: persistent
+ *         workgroups; several -- lanes sharing the GPU --: one tile per workgroup, so that the other engine's kernels get CUs at tile
+ *         boundaries; the library counts its engines itself, no caller sets this), 1 = always one tile per workgroup, 2 = always persistent
  *         (same bits in every form)
- *   6, 7  GEMM policy (register-staged vs LDS-DMA ring; forced tile) 8   batched decode attention: 2 = ring kernel,
- *                                                                        1 = 64-key slice kernel (agree within rounding)
- *   9     1: skinny instead of one-shot o projection                 10  1: bf16 fragments on a quantised engine
- *   12    1: bf16 GEMMs instead of the block-scaled FP8 MFMA in a prefill with FP8 activations (agree within rounding)
- *   11    fixed part size (keys) of the ring attention kernel        13  1: streaming launcher beyond 64 chains
- *   14    1: separate arg-max pass in single-chain greedy decode
- *   15    tile family of the row-streaming decode GEMMs (measurements)  16  grid rotation step | shift << 4 of the decode attention
- *   17    1: no shared-prefix hints (every chain reads its own K/V rows: same bits, more HBM traffic)
- *   18    1: round 4's K loop on the 513 .. 768-row decode tiles (K-steps of 32 in four stages; default: 64 in two; same bits)
- *   19    4: the tall qkv / o decode tiles on a plain four-stage ring, one barrier per K-step (default: six stages in groups of two)
- *   20    3: the long-K projection of a prefill pass (K > 4096: down) in three K slices on every prefill kernel (round 6: built, slower --
- *            down 469 -> 725 us at 12.8 K rows, the stream 86.4 -> 82.4 questions/s -- kept for its bit-equality test; other bits than 0)
- *   21    1: column walk of the eight-phase GEMM's tile grid (default: 8 x 4 blocks; > 1: R << 8 | C blocks)
- *   22    1: the prefill's queries rotated in place by the M-RoPE kernel (default at head_dim 128: inside the flash kernel, as it loads
- *            them; the M-RoPE kernel then writes K and V only; same bits)
- *   23    batched decode attention, round 6 (built, measured slower, off): 2 = a chain's parts cut at its split row, 3 = that + two chains
- *            of a tile per workgroup on the prefix parts (2 and 3: the same bits; against 0 -- parts of the whole context -- within rounding)
- *   24    1: dequantised bf16 fragments in the 2 .. 64-chain step of an MXFP4 engine (default: the 4-bit fragment stream; same bits)
+ *   5  ZE_KNOB_SKINNY              1: no fragment / skinny kernels in the batched step
+ *   6  ZE_KNOB_GEMM_STAGING        GEMM policy: register-staged (1) vs LDS-DMA ring (2)
+ *   7  ZE_KNOB_GEMM_TILE           GEMM policy: forced tile / kernel form
+ *   8  ZE_KNOB_BATCH_ATTN          batched decode attention: 2 = ring kernel, 1 = 64-key slice kernel (agree within rounding)
+ *   9  ZE_KNOB_O_SKINNY            1: skinny instead of one-shot o projection
+ *   10 ZE_KNOB_BF16_FRAGMENTS      1: bf16 fragments on a quantised engine
+ *   11 ZE_KNOB_RING_ATTN_PART      fixed part size (keys) of the ring attention kernel
+ *   12 ZE_KNOB_PREFILL_BF16_GEMM   1: bf16 GEMMs instead of the block-scaled FP8 MFMA in a prefill with FP8 activations (agree within rounding)
+ *   13 ZE_KNOB_WIDE_DECODE         1: streaming launcher beyond 64 chains
+ *   14 ZE_KNOB_SEPARATE_ARGMAX     1: separate arg-max pass in single-chain greedy decode
+ *   15 ZE_KNOB_WIDE_TILES          tile family of the row-streaming decode GEMMs (measurements)
+ *   16 ZE_KNOB_ATTN_ROTATION       grid rotation step | shift << 4 of the decode attention
+ *   17 ZE_KNOB_NO_PREFIX_HINTS     1: no shared-prefix hints (every chain reads its own K/V rows: same bits, more HBM traffic)
+ *   18 ZE_KNOB_KSTEP32             1: round 4's K loop on the 513 .. 768-row decode tiles (K-steps of 32 in four stages; default: 64 in two; same bits)
+ *   19 ZE_KNOB_TALL_RING           4: the tall qkv / o decode tiles on a plain four-stage ring, one barrier per K-step (default: six stages in groups of two)
+ *   20 ZE_KNOB_PREFILL_KSPLIT      3: the long-K projection of a prefill pass (K > 4096: down) in three K slices on every prefill kernel (round 6:
+ *            built, slower -- down 469 -> 725 us at 12.8 K rows, the stream 86.4 -> 82.4 questions/s -- kept for its bit-equality test; other bits than 0)
+ *   21 ZE_KNOB_P8_WALK             1: column walk of the eight-phase GEMM's tile grid (default: 8 x 4 blocks; > 1: R << 8 | C blocks)
+ *   22 ZE_KNOB_MROPE_Q_IN_PLACE    1: the prefill's queries rotated in place by the M-RoPE kernel (default at head_dim 128: inside the flash kernel, as
+ *            it loads them; the M-RoPE kernel then writes K and V only; same bits)
+ *   23 ZE_KNOB_ATTN_SPLIT          batched decode attention, round 6 (built, measured slower, off): 2 = a chain's parts cut at its split row, 3 = that + two
+ *            chains of a tile per workgroup on the prefix parts (2 and 3: the same bits; against 0 -- parts of the whole context -- within rounding)
+ *   24 ZE_KNOB_MX4_BF16_FRAGMENTS  1: dequantised bf16 fragments in the 2 .. 64-chain step of an MXFP4 engine (default: the 4-bit fragment stream; same bits)
  * Changing a knob invalidates captured decode graphs (they are re-captured on the next step).
  * PROCESS-WIDE, by design: there is no engine argument, every engine of the process sees the value at its next launch, and nothing in
  * the product path (Engine, scheduler, entry points, clone_lane) calls it -- a knob is for A/B measurements and the bit-equality tests,

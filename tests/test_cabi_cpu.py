@@ -147,3 +147,21 @@ def test_the_committed_counter_profile_names_the_kernel_sources_it_was_taken_on(
         tj = json.load(f)
     assert tj.get("round", 0) >= 6 and len(tj.get("kernel_sources_sha16", "")) == 16
     assert tj["stream_shared"]["attention"]["ratio"] < tj["stream"]["attention"]["ratio"]
+
+
+def test_ze_tune_bounds_and_the_knob_table_of_the_header(lib):
+    """ze_tune takes the knobs 0 .. 24 and refuses the numbers beside them; the table of include/zoomearth.h names every enumerator of
+    csrc/ze_knobs.h exactly once, with the same number (both files read as text)."""
+    for k in range(25):
+        assert lib.ze_tune(k, 0) == 0, k
+    for k in (-1, 25):
+        assert lib.ze_tune(k, 0) == -1, k   # ZE_ERR_INVALID
+        assert b"unknown knob" in lib.ze_last_error(None)
+    knobs_h = open(os.path.join(ROOT, "zoomearth_amd", "csrc", "ze_knobs.h")).read()
+    enum = dict((name, int(num)) for name, num in re.findall(r"^\s+(ZE_KNOB_[A-Z0-9_]+) = (\d+),?", knobs_h, flags=re.M))
+    assert enum.pop("ZE_KNOB_COUNT") == 25 and sorted(enum.values()) == list(range(25))
+    hdr = open(os.path.join(ROOT, "include", "zoomearth.h")).read()
+    rows = re.findall(r"^ \*\s+(\d+)\s+(ZE_KNOB_[A-Z0-9_]+)\b", hdr, flags=re.M)
+    assert sorted((name, int(num)) for num, name in rows) == sorted(enum.items())
+    for name in enum:
+        assert len(re.findall(r"\b%s\b" % name, hdr)) == 1, name

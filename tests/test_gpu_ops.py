@@ -355,3 +355,26 @@ def test_prefill_split_k_is_one_sum_order_on_every_kernel(tiny_engine):
     want = a.astype(np.float64) @ w.astype(np.float64).T
     for got in (p8, one_run):
         close_bf16(got.float().cpu().numpy(), want, scale=0.05 * np.sqrt(k) * 0.05)
+
+
+# ze_op_linear's `act` is an older spelling of ze_op_gemm's (launcher, epilogue) pair: act -> (launcher, epi)
+LINEAR_ACT_FORMS = {0: (0, 0), 1: (0, 1), 4: (0, 3), 8: (2, 0), 9: (2, 3), 2: (3, 0), 6: (4, 0), 7: (4, 3), 10: (4, 4), 3: (5, 0), 5: (6, 0)}
+
+
+@pytest.mark.parametrize("act", sorted(LINEAR_ACT_FORMS))
+def test_linear_act_is_a_launcher_and_an_epilogue_of_op_gemm(tiny_engine, act):
+    """op_linear(a, w, bias, act) and op_gemm with the pair of the table above give the same bits on the same operands: M = 5 (a ragged
+    tail below one 16-row tile; more than one row, so that act 0 is on its GEMM), N = K = 64 (K % 64 for the eight-phase kernel, K % 32
+    for the fragment kernels, N % 32 for SwiGLU), bias present.  act 10 (fp32 logits) takes no bias: op_linear drops it, so op_gemm gets none."""
+    m, n, k = 5, 64, 64
+    launcher, epi = LINEAR_ACT_FORMS[act]
+    a, w = to_dev_bf16(rnd(31, (m, k))), to_dev_bf16(rnd(32, (n, k), 0.05))
+    b = None if act == 10 else to_dev_bf16(rnd(33, (n,), 0.5))
+    got = tiny_engine.op_linear(a, w, b, act)
+    want = torch.full_like(got, float("nan"))
+    assert got.shape == (m, n // 2 if epi == 3 else n) and got.dtype == (torch.float32 if epi == 4 else torch.bfloat16)
+    st = tiny_engine.op_gemm(launcher, epi, a, k, w, k, b, None, 0, want, want.shape[1], None, m, n, k)
+    assert st == 0, (st, tiny_engine.lib.ze_last_error(tiny_engine.h))
+    torch.cuda.synchronize()
+    view = torch.int32 if epi == 4 else torch.int16
+    assert torch.equal(got.view(view), want.view(view)), (act, launcher, epi)

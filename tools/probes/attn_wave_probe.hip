@@ -12,7 +12,7 @@
 
 #include "ze_kernels.h"
 
-int ze_gemv_knobs[25] = {0};
+int ze_knobs[ZE_KNOB_COUNT] = {0};
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); exit(1);} } while (0)
 
 static bf16_t f2b(float f) {
@@ -100,7 +100,7 @@ int main(int argc, char** argv) {
         std::vector<bf16_t> base(heads * D), got(heads * D);
         const int live = (ctx + 1 + 191) / 192;
         for (int knob : {0, 4}) {  // 0: k_attn_decode_wave_long (384-key parts), 4: k_attn_decode_wave (192-key parts)
-            ze_gemv_knobs[8] = knob;
+            ze_knobs[ZE_KNOB_BATCH_ATTN] = knob;
             CHECK(hipMemset(out, 0xff, heads * D * 2));
             ze_launch_attn_decode_stream(q, heads * D, k, v, (size_t)kvh * max_ctx * D, out, heads * D, st, ids, 1, heads, kvh, max_ctx, scale, ws,
                                          wparts, tickets, 0, 0, live, nullptr);

@@ -386,8 +386,7 @@ void ze_launch_flash_attn(int D, int causal, const bf16_t* q, int q_rs, int q_hs
 #define FA_LAUNCH(DD, CC, QQ) FA_LAUNCH_(DD, CC, QQ, false)
     // D = 128 causal (the prefill: K / V rows are whole 256-byte cache rows, 16-byte aligned): the LDS-DMA staging form;
     // ze_tune knob 1 = 7 keeps the register-staged form for A/B runs and the bit-equality test
-    extern int ze_gemv_knobs[25];
-    if (D == 128 && causal && ZE_FA_CAUSAL_BKV == 64 && ze_gemv_knobs[1] != 7 && k_rs % 8 == 0 && v_rs % 8 == 0 && k_hs % 8 == 0 &&
+    if (D == 128 && causal && ZE_FA_CAUSAL_BKV == 64 && ze_knobs[ZE_KNOB_GATE_UP_FLASH] != ZE_FLASH_REG_STAGED && k_rs % 8 == 0 && v_rs % 8 == 0 && k_hs % 8 == 0 &&
         v_hs % 8 == 0 && ((size_t)k % 16) == 0 && ((size_t)v % 16) == 0 && kv_seq_stride % 8 == 0) {
         if (q_tile > 64) FA_LAUNCH_(128, 1, 2, true);
         else FA_LAUNCH_(128, 1, 1, true);

@@ -804,8 +804,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
     }
 }
 
-extern int ze_gemv_knobs[25];
-
 #ifdef ZE_ATTN_ROWS_UNIT
 // the pipelined kernel's ROWS form over the n rows of a step; `parts`: the 384-key parts the longest row can have (the grid's extent)
 void ze_launch_attn_decode_rows(const bf16_t* q, int q_row_stride, const bf16_t* kcache, const bf16_t* vcache, size_t cache_seq_stride,
@@ -816,7 +814,7 @@ void ze_launch_attn_decode_rows(const bf16_t* q, int q_row_stride, const bf16_t*
     const int wparts = (max_ctx + AW_PART - 1) / AW_PART;   // slots per row of the partial buffer, as the plain launch lays it out
     const int lparts = (max_ctx + rounds * AW_TOK - 1) / (rounds * AW_TOK);
     const int lg = std::min(lparts, std::max(1, parts));
-    const int xrot = ze_gemv_knobs[16] > 0 ? ze_gemv_knobs[16] : (3 | (2 << 4));
+    const int xrot = ze_knobs[ZE_KNOB_ATTN_ROTATION] > 0 ? ze_knobs[ZE_KNOB_ATTN_ROTATION] : (3 | (2 << 4));
     k_attn_decode_wave_long<8, rounds, false, true><<<dim3(kv_heads * lg, n), 256, 4 * 3 * AW_VSTAGE, s>>>(
         q, q_row_stride, kcache, vcache, cache_seq_stride, st, seq_ids, heads, kv_heads, max_ctx, scale * 1.4426950408889634f, ws_partial, wparts,
         tickets, out, out_row_stride, xrot, prefix, row_off, 0);
@@ -824,7 +822,7 @@ void ze_launch_attn_decode_rows(const bf16_t* q, int q_row_stride, const bf16_t*
 #else
 
 // (measurements: ze_tune knob 16 = step | shift << 4 overrides the grid rotation of the pipelined kernel; 0 = the shipped 3 | 2 << 4)
-static int xrot_knob() { return ze_gemv_knobs[16] > 0 ? ze_gemv_knobs[16] : (3 | (2 << 4)); }
+static int xrot_knob() { return ze_knobs[ZE_KNOB_ATTN_ROTATION] > 0 ? ze_knobs[ZE_KNOB_ATTN_ROTATION] : (3 | (2 << 4)); }
 
 void ze_launch_attn_decode_stream(const bf16_t* q, int q_row_stride, const bf16_t* kcache, const bf16_t* vcache,
                                   size_t cache_seq_stride, bf16_t* out, int out_row_stride, const ze_seq_dev* st,
@@ -844,12 +842,12 @@ void ze_launch_attn_decode_stream(const bf16_t* q, int q_row_stride, const bf16_
         // for parts no chain has would only look their chain up and leave -- 22 parts instead of 11 per chain and kv head
         // (max_ctx 4096 against 2048, contexts of ~1100) cost the launch 9 %
         // (knob 8 = 3, for A/B runs: every part of max_ctx in the grid, no rotation)
-        const bool plain = ze_gemv_knobs[8] == 3;
+        const bool plain = ze_knobs[ZE_KNOB_BATCH_ATTN] == ZE_ATTN_PLAIN_GRID;
         const int gparts = plain ? wparts : std::min(wparts, std::max(1, per_wave));
         // Round 4: 384-key parts on the pipelined form (k_attn_decode_wave_long<8, 6>: 4.4 -> 4.7-4.9 TB/s on independent chains at
         // 410-768 of them, 5.5 -> 6.1-6.4 with the stream's shared prefixes; 320-key parts 4.70 / 5.92 at 410, 512-key 4.54 / 5.41,
         // 256-key 4.51 / 5.49).  knob 8 = 4: the 192-key kernel (A/B runs and the agreement test); 3: every part of max_ctx in the grid, no rotation
-        if (ze_gemv_knobs[8] != 4) {
+        if (ze_knobs[ZE_KNOB_BATCH_ATTN] != ZE_ATTN_PART192) {
             constexpr int rounds = AW_LONG_ROUNDS;
             const int lparts = (max_ctx + rounds * AW_TOK - 1) / (rounds * AW_TOK);
             // (the split adds at most one part to a chain: with it on the grid covers lparts + 1, or the caller's exact count; the
@@ -859,13 +857,13 @@ void ze_launch_attn_decode_stream(const bf16_t* q, int q_row_stride, const bf16_
             // split (a chain of 1127 rows has four parts instead of three), 100.5 with the pairing on top -- the prefix rows a pair no longer
             // loads twice were L2 hits already (0.856 x algorithmic bytes at the HBM interface), while the leader's workgroup now publishes two
             // sets of partials, draws two tickets and may merge two chains; the stream does not move (85.9-87.0 in every form).
-            const int split_on = (use_split && (ze_gemv_knobs[23] == 2 || ze_gemv_knobs[23] == 3) && lparts + 1 <= wparts) ? 1 : 0;
+            const int split_on = (use_split && (ze_knobs[ZE_KNOB_ATTN_SPLIT] == ZE_SPLIT_ROWS || ze_knobs[ZE_KNOB_ATTN_SPLIT] == ZE_SPLIT_PAIRED) && lparts + 1 <= wparts) ? 1 : 0;
             int lg = plain ? lparts : std::min(lparts, std::max(1, (per_wave * AW_PART + rounds * AW_TOK - 1) / (rounds * AW_TOK)));
             if (split_on) lg = (plain || long_parts <= 0) ? std::min(lparts + 1, lg + 1) : std::min(lparts + 1, long_parts);
             if (split_on)
                 k_attn_decode_wave_long<8, rounds, true><<<dim3(kv_heads * lg, n), 256, 4 * 3 * AW_VSTAGE, s>>>(
                     q, q_row_stride, kcache, vcache, cache_seq_stride, st, seq_ids, heads, kv_heads, max_ctx, sl, ws_partial, wparts, tickets, out,
-                    out_row_stride, plain ? 0 : xrot_knob(), prefix, ze_gemv_knobs[23] == 3 ? mate : nullptr, 1);
+                    out_row_stride, plain ? 0 : xrot_knob(), prefix, ze_knobs[ZE_KNOB_ATTN_SPLIT] == ZE_SPLIT_PAIRED ? mate : nullptr, 1);
             else
                 k_attn_decode_wave_long<8, rounds, false><<<dim3(kv_heads * lg, n), 256, 4 * 3 * AW_VSTAGE, s>>>(
                     q, q_row_stride, kcache, vcache, cache_seq_stride, st, seq_ids, heads, kv_heads, max_ctx, sl, ws_partial, wparts, tickets, out,

@@ -8,8 +8,6 @@
 
 #include "ze_engine.h"
 
-extern int ze_gemv_knobs[25];
-
 // ================================================================== batched decode (BASELINE configs[2])
 // One token for each of n chains per step: the weights are streamed ONCE for the whole batch through the MFMA GEMM
 // path (rows = chains), each chain keeps its own KV cache / position / seen-set.  Rows are computed independently of
@@ -19,7 +17,7 @@ extern int ze_gemv_knobs[25];
 // fragment kernel does not cover (rows % 16, K % 32, K > 4096) keep wf = null and stay on the row-major launchers.
 // MXFP4 engine: the 4-bit fragment stream of the 2 .. 64-chain step (ze_tune knob 24 = 1: dequantised bf16 fragments, the form before
 // the W4 kernels -- same bits; kept for the A/B and the bit-equality test)
-static bool want_frag4(const ze_engine* e) { return e->mx4_ready && ze_gemv_knobs[24] != 1; }
+static bool want_frag4(const ze_engine* e) { return e->mx4_ready && ze_knobs[ZE_KNOB_MX4_BF16_FRAGMENTS] != ZE_KNOB_ON; }
 
 int ensure_fragments(ze_engine* e, hipStream_t s) {
     if (e->frag_ready && e->frag_w4 == want_frag4(e)) return ZE_OK;
@@ -204,7 +202,7 @@ static void set_live_parts_reach(ze_engine* e, int mx) {
 // -1 = alone.  A pairing changes who computes a partial, never its bits.
 static void upload_mates(ze_engine* e, const int32_t* seqs, int n, hipStream_t s) {
     std::vector<int> mate(n, -1);
-    if (e->prefix_hints && ze_gemv_knobs[17] != 1) {
+    if (e->prefix_hints && ze_knobs[ZE_KNOB_NO_PREFIX_HINTS] != ZE_KNOB_ON) {
         std::map<long long, int> open;   // (holder, split) -> the row waiting for a partner
         for (int i = 0; i < n; ++i) {
             const int q = seqs[i], sp = e->split_host[q];
@@ -275,7 +273,7 @@ ze_step_rows ze_rows_caller(const ze_engine* e, const bf16_t* q, bf16_t* out) {
 static bool attn_per_wave(const ze_engine* e) {
     const ze_config& c = e->cfg;
     const int wparts = (c.max_ctx + 191) / 192;
-    return ze_gemv_knobs[8] != 2 && ze_gemv_knobs[11] == 0 && wparts <= std::max(e->max_splits, 8) && wparts <= 64 && e->head_dim == 128 &&
+    return ze_knobs[ZE_KNOB_BATCH_ATTN] != ZE_ATTN_RING && ze_knobs[ZE_KNOB_RING_ATTN_PART] == 0 && wparts <= std::max(e->max_splits, 8) && wparts <= 64 && e->head_dim == 128 &&
            c.heads / c.kv_heads <= 16;
 }
 
@@ -292,7 +290,7 @@ void launch_batch_attention(ze_engine* e, const ze_step_rows& rows, int li, int 
                                    rows.off, n, c.heads, c.kv_heads, c.max_ctx, scale, rows.partial, rows.tickets, e->live_parts_long, e->pfx_dev, s);
         return;
     }
-    if (ze_gemv_knobs[8] == 1)
+    if (ze_knobs[ZE_KNOB_BATCH_ATTN] == ZE_ATTN_SLICE)
         ze_launch_attn_decode(rows.q, nqkv, e->kc(li, 0), e->vc(li, 0), seq_stride, rows.out, frag_out ? -(nq / 32) : nq, e->st_dev,
                               rows.seq, n, c.heads, c.kv_heads, hd, c.max_ctx, scale, rows.partial, e->max_splits, rows.tickets, s);
     else {
@@ -302,7 +300,7 @@ void launch_batch_attention(ze_engine* e, const ze_step_rows& rows, int li, int 
         // (max(max_splits, 8) parts per chain) and the merge's 64 lanes
         const int wparts = (c.max_ctx + 191) / 192;
         const bool per_wave = attn_per_wave(e);
-        const int chunk = ze_gemv_knobs[11] >= 64 ? ze_gemv_knobs[11] / 32 * 32 : 0;  // 0: a sixth of the chain's context
+        const int chunk = ze_knobs[ZE_KNOB_RING_ATTN_PART] >= 64 ? ze_knobs[ZE_KNOB_RING_ATTN_PART] / 32 * 32 : 0;  // 0: a sixth of the chain's context
         const int max_parts = chunk ? (c.max_ctx + chunk - 1) / chunk : 8;           // (at most 8 parts: 128-token floor)
         ze_launch_attn_decode_stream(rows.q, nqkv, e->kc(li, 0), e->vc(li, 0), seq_stride, rows.out, frag_out ? -(nq / 32) : nq,
                                      e->st_dev, rows.seq, n, c.heads, c.kv_heads, c.max_ctx, scale, rows.partial, max_parts,
@@ -324,7 +322,7 @@ struct batch_regime {
     bool fr, tiled, a8q, a8g, fl;
 };
 // the FP8 fragment stream of a projection (quantised engine; ze_tune knob 10 = 1: the bf16 fragments)
-static bool frag8(const ze_linear& l) { return l.wf8 && ze_gemv_knobs[10] != 1; }
+static bool frag8(const ze_linear& l) { return l.wf8 && ze_knobs[ZE_KNOB_BF16_FRAGMENTS] != ZE_KNOB_ON; }
 // the weight operand of a fragment launch: the MXFP4 copy where ensure_fragments built one (there is no bf16 copy then), else the
 // FP8 copy of a quantised engine, else bf16 fragments
 struct frag_w {
@@ -341,11 +339,11 @@ static frag_w frag_of(const ze_linear& l, const bf16_t* wf16) {
 static batch_regime regime_of(const ze_engine* e, int li) {
     const ze_text_layer& L = e->tl[li];
     batch_regime r;
-    r.fr = L.qkv.has_frag() && !e->wide_regime() && ze_gemv_knobs[5] != 1;
-    r.tiled = e->wide_regime() && ze_gemv_knobs[13] != 1;
+    r.fr = L.qkv.has_frag() && !e->wide_regime() && ze_knobs[ZE_KNOB_SKINNY] != ZE_SKINNY_OFF;
+    r.tiled = e->wide_regime() && ze_knobs[ZE_KNOB_WIDE_DECODE] != ZE_WIDE_STREAM;
     r.a8q = e->fp8_act && r.fr && frag8(L.qkv);
     r.a8g = e->fp8_act && r.fr && frag8(L.gate_up);
-    r.fl = (e->lm_head_f || e->lm_head8.wf4) && !e->wide_regime() && ze_gemv_knobs[5] != 1;
+    r.fl = (e->lm_head_f || e->lm_head8.wf4) && !e->wide_regime() && ze_knobs[ZE_KNOB_SKINNY] != ZE_SKINNY_OFF;
     return r;
 }
 
@@ -381,7 +379,7 @@ bool batch_qkv(ze_engine* e, const ze_step_rows& rows, int li, int n, hipStream_
     }
     // row streaming: projection + M-RoPE + KV append in ONE launch on the permuted rows (same bits as the pair of
     // launches below; knob 13 = 2 keeps the pair, for A/B runs and the bit-equality test); its chain ids are e->bseq's (ze_rows_spec)
-    if (r.tiled && L.qkv.wp && ze_gemv_knobs[13] != 2) {
+    if (r.tiled && L.qkv.wp && ze_knobs[ZE_KNOB_WIDE_DECODE] != ZE_WIDE_QKV_PAIR) {
         ze_launch_gemm_qkv_rope(e->by, H, L.qkv.wp, H, L.qkv.bias_p, e->qkv_epi_dev + li, e->bqkv, nqkv, n, nqkv, H, s);
         return false;
     }
@@ -400,7 +398,7 @@ bool batch_o(ze_engine* e, const ze_step_rows& rows, int li, int n, hipStream_t 
     const int H = e->cfg.hidden, nq = e->cfg.heads * e->head_dim;
     const ze_text_layer& L = e->tl[li];
     const batch_regime r = regime_of(e, li);
-    if (r.fr && ze_gemv_knobs[9] != 1) {
+    if (r.fr && ze_knobs[ZE_KNOB_O_SKINNY] != ZE_KNOB_ON) {
         const frag_w w = frag_of(L.o, L.o.wf);
         ze_launch_gemm_oneshot(ZE_EPI_RESIDUAL, rows.out, w.wf, nullptr, e->bh, H, e->bh, H, n, H, nq, s, w.scale8, nullptr, w.scale4);
         return w.w8;
@@ -587,9 +585,9 @@ struct spec_layout {
 // the multi-row forms exist for the fragment kernels and the pipelined attention alone
 static bool spec_step_ok(const ze_engine* e) {
     const batch_regime r = regime_of(e, 0);
-    const int k8 = ze_gemv_knobs[8], k23 = ze_gemv_knobs[23];
+    const int k8 = ze_knobs[ZE_KNOB_BATCH_ATTN], k23 = ze_knobs[ZE_KNOB_ATTN_SPLIT];
     // the plain step must be on the very kernel the ROWS form instantiates: per-wave, 384-key parts (knob 8 not 1 / 4), no split rows
-    return r.fr && r.fl && attn_per_wave(e) && k8 != 1 && k8 != 4 && k23 != 2 && k23 != 3;
+    return r.fr && r.fl && attn_per_wave(e) && k8 != ZE_ATTN_SLICE && k8 != ZE_ATTN_PART192 && k23 != ZE_SPLIT_ROWS && k23 != ZE_SPLIT_PAIRED;
 }
 
 static int enqueue_spec_step(ze_engine* e, const spec_layout& L, float penalty, int ign, const ze_sample_opts& so, hipStream_t s) {

@@ -354,7 +354,7 @@ struct ze_engine {
     // Shared-prefix hints, (source chain << 16) | P per chain slot.  pfx_host is the truth, kept by whatever call changes it
     // (ze_seq_copy_prefix on the admission stream, ze_seq_retire, ...); the device copy pfx_dev -- what the decode attention
     // reads -- is written by ONE stream only: the stream of the batched decode step, which pushes the words that differ from
-    // pfx_pushed for ITS chains before it enqueues the step (sync_prefix, ze_forward.hip; called from ze_decode_batch.hip).  A chain state pushed from another
+    // pfx_pushed for ITS chains before it enqueues the step (sync_prefix, ze_seq.hip; called from ze_decode_batch.hip).  A chain state pushed from another
     // stream can therefore never bring a stale hint back.  pfx_copy_ev[seq]: recorded behind the chain's last
     // ze_seq_copy_prefix (null = none): only a chain whose copy has COMPLETED may become the holder other chains read from.
     std::vector<int> pfx_host, pfx_pushed;
@@ -594,12 +594,18 @@ void sync_prefix(ze_engine* e, const int32_t* seqs, int n, hipStream_t s);
 void set_live_parts(ze_engine* e, const int32_t* seqs, int n, int steps);
 // ... all of it for `steps` steps of the (valid) chains `seqs`: e->bseq, the prefix hints, the mates, the attention grids' extents
 void stage_batch(ze_engine* e, const int32_t* seqs, int n, int steps, hipStream_t s);
+// the attention tile list of n_seg segments (ze_vision.hip; ze_op_attention): the tile count, -1 when cap_tiles do not hold it
+int build_tiles(const int32_t* cu, int n_seg, int* out /* int4 rows */, int cap_tiles, int bq = 64);
+int stage_acquire(ze_engine* e, hipEvent_t& ev);   // wait for / record the event behind the last reader of a staging buffer (ze_forward.hip)
+int stage_release(ze_engine* e, hipEvent_t& ev, hipStream_t s);
+// the decode attention of the single-chain step (ze_forward.hip) on its own q / out rows, or the caller's: ze_op_attn_decode_single
+void launch_step_attention(ze_engine* e, int li, int seq, hipStream_t s, const bf16_t* q_row = nullptr, bf16_t* out_row = nullptr);
 // helpers of ze_forward.hip that the batched paths (ze_decode_batch.hip) share with the single-chain ones
 int capture_step(ze_engine* e, const std::function<int(hipStream_t)>& enqueue, hipGraphExec_t* exec);
 int first_token(ze_engine* e, int q, float pen, int ign, const ze_sample_opts& so, hipStream_t s);
 int trim_at_eos(const ze_config& c, const int32_t* tokens, int n);
-int xfer_reserve(ze_engine* e, int*& host, int*& dev, size_t& cap, size_t need, hipEvent_t staged, hipStream_t s);
-// chain bookkeeping shared with ze_prefix.hip: the readers of rows >= keep of chain `seq` move to another holder; the chain state
+int xfer_reserve(ze_engine* e, int*& host, int*& dev, size_t& cap, size_t need, hipEvent_t staged, hipStream_t s);   // (ze_seq.hip)
+// chain bookkeeping (ze_seq.hip) shared with ze_prefix.hip: the readers of rows >= keep of chain `seq` move to another holder; the chain state
 // of `seq` goes to the device in stream order
 void prefix_source_gone(ze_engine* e, int seq, int keep);
 int push_state(ze_engine* e, int seq, hipStream_t s, int token, int n_gen, int finished);

@@ -417,11 +417,10 @@ extern "C" int ze_engine_create(const ze_config* cfg, int device_id, ze_engine**
     return ZE_OK;
 }
 
-extern int ze_gemv_knobs[25];
 // prefill split-K slabs: 3 slices x (rows of the largest pass, padded to a 256-row tile) x (hidden, padded to a 256-column tile) floats --
 // the same whatever tile a row count selects -- and a zeroed ticket per 64 x 64 tile (the smallest).  Only with knob 20 = 3.
 ze_gemm_ws ze_engine::prefill_ws() {
-    if (!pslab && ze_gemv_knobs[20] == 3) {
+    if (!pslab && ze_knobs[ZE_KNOB_PREFILL_KSPLIT] == ZE_PREFILL_KSPLIT_3) {
         const size_t rows_pad = ((size_t)prefill_rows + 255) / 256 * 256, cols_pad = ((size_t)cfg.hidden + 255) / 256 * 256;
         const size_t floats = 3 * rows_pad * cols_pad;
         const int cap = (int)((rows_pad / 64) * (cols_pad / 64)) + 64;

@@ -21,7 +21,6 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 #define GEMM_BK 64
 
 extern int ze_live_engines;    // ze_gemv.hip: engines alive in this process
-extern int ze_gemv_knobs[25];  // [5]: 1 = no skinny kernel in the weight-streaming launcher; [6]: 0 = shipped policy, 1 = register-staged kernel everywhere, 2 = ring wherever it applies
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
@@ -1242,19 +1241,19 @@ static void launch_p8(const gemm_call& c, int ksplit = 1) {
     // Round 6: the library knows how many engines are alive (ze_live_engines), so the form follows that by itself -- knob 4 = 0: tile-
     // granular iff more than one engine exists; 1: always tile-granular; 2: always persistent (measurements).  No caller flips a
     // process-wide switch on behalf of engines it does not own any more.
-    const bool shared_gpu = ze_gemv_knobs[4] == 1 || (ze_gemv_knobs[4] == 0 && ze_live_engines > 1);
+    const bool shared_gpu = ze_knobs[ZE_KNOB_P8_LAUNCH] == ZE_P8_TILE_PER_WG || (ze_knobs[ZE_KNOB_P8_LAUNCH] == 0 && ze_live_engines > 1);
     const int units = tiles * std::max(1, ksplit);   // (split K: a unit = a K slice of a tile)
-    const int grid = (ze_gemv_knobs[7] == 9 || shared_gpu) ? units : std::min(units, cus);
+    const int grid = (ze_knobs[ZE_KNOB_GEMM_TILE] == ZE_TILE_P8_PER_TILE || shared_gpu) ? units : std::min(units, cus);
     // the wide-store epilogue (p8_finish_wide: 16-byte row pieces through 4 KB of LDS per wave) wherever rows are 16-byte
     // aligned; knob 7 = 10: the plain two-byte epilogue, for A/B runs and tests/test_gpu_gemm_operands.py (both tails against the
     // same expected bits)
     const bool sw = c.epi == ZE_EPI_SWIGLU;
-    const bool wide = ze_gemv_knobs[7] != 10 && (c.ldc % 8) == 0 && ((size_t)c.C % 16) == 0 && ((sw ? c.N / 2 : c.N) % 8) == 0 &&
+    const bool wide = ze_knobs[ZE_KNOB_GEMM_TILE] != ZE_TILE_PLAIN_EPILOGUE && (c.ldc % 8) == 0 && ((size_t)c.C % 16) == 0 && ((sw ? c.N / 2 : c.N) % 8) == 0 &&
                       (c.epi != ZE_EPI_RESIDUAL || ((c.ldr % 8) == 0 && ((size_t)c.R % 16) == 0));
     const size_t lds = wide ? (128 + 32) * 1024 : (128 + 1) * 1024;   // (+ 1 KB: the split-K flag lives behind the K-tile buffers)
     // the blocked walk of the tile grid (k_gemm_p8: `place`): 8 x 4 blocks; knob 21 = 1: the column walk of rounds 3-4, any other
     // value v > 1: blocks of (v >> 8) x (v & 255)
-    const int blk = ze_gemv_knobs[21] == 1 ? 0 : (ze_gemv_knobs[21] > 1 ? ze_gemv_knobs[21] : ((8 << 8) | 4));
+    const int blk = ze_knobs[ZE_KNOB_P8_WALK] == ZE_KNOB_ON ? 0 : (ze_knobs[ZE_KNOB_P8_WALK] > 1 ? ze_knobs[ZE_KNOB_P8_WALK] : ((8 << 8) | 4));
     auto go = [&](auto E, auto WD) {
         launch_lds<k_gemm_p8<E, WD>>(dim3(grid), dim3(512), lds, lds, c.s, c.A, c.lda, c.W, c.ldw, c.bias, c.R, c.ldr, c.C, c.ldc, c.c_rows,
                                      c.M, c.N, c.K, blk, std::max(1, ksplit), c.ws.slab, c.ws.tickets);
@@ -1921,7 +1920,7 @@ static void launch_ring_variant(const gemm_call& c, int ksplit = 1) {
             // launches (no epilogue runs) and not where the staged tile would not fit the ring's LDS.
             const bool sw = c.epi == ZE_EPI_SWIGLU, f32 = c.epi == ZE_EPI_F32;
             const size_t stage_b = (size_t)BM * ((sw ? BN / 2 : BN) * (f32 ? 4 : 2) + 16);
-            const bool wide_ok = ze_gemv_knobs[7] != 10 && c.c_rows == nullptr && !(ksplit > 1 && c.ws.tickets == nullptr) && stage_b <= lds &&
+            const bool wide_ok = ze_knobs[ZE_KNOB_GEMM_TILE] != ZE_TILE_PLAIN_EPILOGUE && c.c_rows == nullptr && !(ksplit > 1 && c.ws.tickets == nullptr) && stage_b <= lds &&
                                  (c.ldc % 8) == 0 && ((size_t)c.C % 16) == 0 && ((sw ? c.N / 2 : c.N) % 8) == 0 && (!sw || BN % 32 == 0) &&
                                  (c.epi != ZE_EPI_RESIDUAL || ((c.ldr % 8) == 0 && ((size_t)c.R % 16) == 0)) && c.epi != ZE_EPI_QKV_ROPE;
             if (wide_ok) {
@@ -1946,7 +1945,7 @@ static void launch_ring_variant(const gemm_call& c, int ksplit = 1) {
 // r06_prefill_by_shape.csv): down 469 -> 725 us at 12,832 rows, 217 -> 284 at 5,280; the question stream, same box, two runs each:
 // 86.75 / 86.1 unsplit, 82.2 / 82.6 split.  The grid's idle tail is cheaper than the slabs.  Needs the engine's prefill slabs (ze_gemm_ws).
 static int ze_prefill_ksplit(int K, bool have_slab) {
-    return (have_slab && ze_gemv_knobs[20] == 3 && K > 4096 && K % GEMM_BK == 0 && K / GEMM_BK >= 3 * 8) ? 3 : 1;
+    return (have_slab && ze_knobs[ZE_KNOB_PREFILL_KSPLIT] == ZE_PREFILL_KSPLIT_3 && K > 4096 && K % GEMM_BK == 0 && K / GEMM_BK >= 3 * 8) ? 3 : 1;
 }
 static int ze_prefill_split_dropped(int M, int N, int K, int ksplit) {
     static bool told = false;
@@ -2014,8 +2013,8 @@ static void launch_cfg(const gemm_call& c, bool stream_mode) {
     //     matrix load (zero-filled operands run 15-20 % faster than random ones: MI355X_MICROARCH.md).
     // All of them accumulate an output element in the same K order: results are bit-identical across the choices.
     // knob 7: 3 = register-staged only, 4 = always 256 x 256, 6 = always 128 x 256.
-    if (BM == 128 && BN == 128 && (ksplit == 1 || !stream_mode) && K % GEMM_BK == 0 && K / GEMM_BK >= 4 && ze_gemv_knobs[7] != 3 &&
-        ze_gemv_knobs[6] == 0) {
+    if (BM == 128 && BN == 128 && (ksplit == 1 || !stream_mode) && K % GEMM_BK == 0 && K / GEMM_BK >= 4 && ze_knobs[ZE_KNOB_GEMM_TILE] != ZE_TILE_REG_ONLY &&
+        ze_knobs[ZE_KNOB_GEMM_STAGING] == 0) {
         const int grid4 = ze_cdiv(M, 256) * ze_cdiv(N, 256);
         const bool big = (2 * grid4 >= 3 * cus) || (grid4 <= cus && 10 * grid4 >= 9 * cus);
         // (the 256 x 256 tile runs on the eight-phase kernel; knob 7 = 4: on the two-stage ring, 8: eight-phase at every grid)
@@ -2029,9 +2028,9 @@ static void launch_cfg(const gemm_call& c, bool stream_mode) {
         //  tiles need their own share of the capacity check above, which was made for BM x BN = 128 x 128)
         const bool fits256 = ksplit == 1 || ((size_t)ksplit * grid4 * 256 * 256 <= ws.slab_floats && grid4 <= ws.ticket_cap);
         const bool fits128x256 = ksplit == 1 || ((size_t)ksplit * ze_cdiv(M, 128) * ze_cdiv(N, 256) * 128 * 256 <= ws.slab_floats);
-        if (fits256 && p8_ok && (ze_gemv_knobs[7] == 8 || ((ze_gemv_knobs[7] == 0 || ze_gemv_knobs[7] == 9) && p8_wins)))
+        if (fits256 && p8_ok && (ze_knobs[ZE_KNOB_GEMM_TILE] == ZE_TILE_P8 || ((ze_knobs[ZE_KNOB_GEMM_TILE] == 0 || ze_knobs[ZE_KNOB_GEMM_TILE] == ZE_TILE_P8_PER_TILE) && p8_wins)))
             launch_p8(c, ksplit);
-        else if (fits256 && (ze_gemv_knobs[7] == 4 || (ze_gemv_knobs[7] != 6 && big)))
+        else if (fits256 && (ze_knobs[ZE_KNOB_GEMM_TILE] == ZE_TILE_256 || (ze_knobs[ZE_KNOB_GEMM_TILE] != ZE_TILE_128X256 && big)))
             launch_ring_variant<256, 256, 2, 2, 4, true>(c, ksplit);
         else if (fits128x256)
             launch_ring_variant<128, 256, 3, 2, 4, true>(c, ksplit);
@@ -2039,7 +2038,7 @@ static void launch_cfg(const gemm_call& c, bool stream_mode) {
             launch_ring_variant<128, 128, 4, 2, 4, true>(c, ksplit);
         return;
     }
-    const bool ring = ze_gemv_knobs[6] == 2 || (ze_gemv_knobs[6] == 0 && (grid <= cus || stream_mode));
+    const bool ring = ze_knobs[ZE_KNOB_GEMM_STAGING] == ZE_STAGING_RING || (ze_knobs[ZE_KNOB_GEMM_STAGING] == 0 && (grid <= cus || stream_mode));
     if (K % GEMM_BK == 0 && K / GEMM_BK / ksplit >= 4 && ring) {
         // LDS-DMA ring: four stages when they fit beside nothing else (one workgroup per CU), else three
         constexpr int STAGES = ((BM + BN) * 128 * 4 <= 128 * 1024) ? 4 : 3;
@@ -2048,14 +2047,14 @@ static void launch_cfg(const gemm_call& c, bool stream_mode) {
         // 64 x 128 tiles of a one-round grid: eight waves (2 x 4, 32 x 32 per wave), two per SIMD, hide each other's DMA
         // issue and LDS latency: o 20.4 -> 16.9 us, down 73.4 -> 62.7 (M = 802), 72.7 -> 58.4 (M = 518), ViT proj
         // 15.6 -> 12.4, ViT down 27.3 -> 22.9, merger 37.9 -> 31.4 (1 x 8 waves and the spread refill are 2-8 % behind)
-        if (BM == 64 && BN == 128 && (ksplit == 1 || !stream_mode) && ze_gemv_knobs[7] != 3) {
+        if (BM == 64 && BN == 128 && (ksplit == 1 || !stream_mode) && ze_knobs[ZE_KNOB_GEMM_TILE] != ZE_TILE_REG_ONLY) {
             launch_ring_variant<64, 128, 4, 2, 4, false>(c, ksplit);
             return;
         }
         // the same on 64 x 64 tiles (4 x 2 waves, 16 x 32 per wave: the SwiGLU epilogue pairs two 16-column tiles of a
         // wave), split-K included: merger 26.8 -> 23.3 us; the weight-streaming
         // GEMMs of the batched decode step 4.48 -> 4.33 ms per 64-chain step, 3.27 -> 3.14 at 8 chains
-        if (BM == 64 && BN == 64 && ze_gemv_knobs[7] != 3) {
+        if (BM == 64 && BN == 64 && ze_knobs[ZE_KNOB_GEMM_TILE] != ZE_TILE_REG_ONLY) {
             // (round 3, the split-K stream of the down projection, us at 64 / 256 rows: this tile 17.4 / 35.2; eight or six
             //  stages 17.8 / 44.1 and 17.7 / 42.9; 128 x 64 tiles 21.3 / 36.7; 256 x 64 tiles, three stages 32.8 / 39.1)
             // (qkv / o of a decode step -- 128-240 tiles of 32 K-steps, at most one workgroup per CU -- with EIGHT stages, 112 KB in
@@ -2151,7 +2150,7 @@ void ze_launch_gemm_frag(int epi, const bf16_t* Xf, const bf16_t* Wf, const bf16
     // (more than 32 chains only: below that the activation pass is small and the finer 32-row grid wins, 2.84 against
     //  2.91 ms per step at 8 chains; at 64 chains 3.86 against 3.95.  Both forms add an output's K quarters in the same
     //  order, so the choice does not change a chain's result.)
-    if (epi == ZE_EPI_SWIGLU && N > 4096 && N % 32 == 0 && M > 32 && ze_gemv_knobs[5] != 2) {
+    if (epi == ZE_EPI_SWIGLU && N > 4096 && N % 32 == 0 && M > 32 && ze_knobs[ZE_KNOB_SKINNY] != ZE_SKINNY_GRID32) {
         const int cus = ze_cu_count();
         const int P = N / 32;
         // at most three pairs per workgroup, and never more workgroups than pairs: a workgroup with an empty range would address
@@ -2284,14 +2283,14 @@ void ze_launch_permute_qkv(const bf16_t* W, int ldw, const bf16_t* bias, int n_h
 template <bool QKV>
 static bool launch_tall(const gemm_call& c) {
     const int M = c.M, K = c.K, nct = ze_cdiv(c.N, 64);
-    if (ze_gemv_knobs[13] == 4 || K % GEMM_BK != 0 || K / GEMM_BK < 4 || M <= 64 || M > 768) return false;
+    if (ze_knobs[ZE_KNOB_WIDE_DECODE] == ZE_WIDE_NO_TALL || K % GEMM_BK != 0 || K / GEMM_BK < 4 || M <= 64 || M > 768) return false;
     if (!QKV && c.epi != ZE_EPI_NONE && c.epi != ZE_EPI_RESIDUAL) return false;
     // one workgroup per CU.  Default: six stages in three groups of two K-steps (one barrier per 128 of K; two groups in flight: 16.0 /
     // 11.5 us for qkv / o at 399 rows against 16.4 / 12.1 on the plain four-stage ring, knob 19 = 4; eight stages in four groups of two:
     // level; in two groups of four: 17.8 / 13.6; a plain ring of six or eight stages: 18.9 / 18.2 -- what bounds these launches is what
     // a CU takes in per microsecond, not the depth of its ring)
     auto tall = [&](auto BM) {  // (one run over K: the callers pass no workspace)
-        if (ze_gemv_knobs[19] == 4 || (K / GEMM_BK) % 2) launch_ring_variant<BM, 64, 4, BM / 16, 2, false, false, QKV, GEMM_BK, 1>(c);
+        if (ze_knobs[ZE_KNOB_TALL_RING] == ZE_TALL_PLAIN_RING || (K / GEMM_BK) % 2) launch_ring_variant<BM, 64, 4, BM / 16, 2, false, false, QKV, GEMM_BK, 1>(c);
         else launch_ring_variant<BM, 64, 6, BM / 16, 2, false, false, QKV, GEMM_BK, 2>(c);
     };
     if (ze_cdiv(M, 64) * nct <= 256) tall(int_c<64>());
@@ -2320,7 +2319,7 @@ void ze_launch_gemm_qkv_rope(const bf16_t* A, int lda, const bf16_t* Wp, int ldw
     }
     // (two 64-KB workgroups share a CU: up to 512 tiles stay on 64 x 64 -- 16.4 against 20.8 us at 410 rows, 19.9 / 21.0 at 580, 20.9 /
     //  22.7 at 768; knob 13 = 3: 64 x 128 from 257 tiles on, the rule before)
-    if (b64 <= (ze_gemv_knobs[13] == 3 ? 256 : 512))
+    if (b64 <= (ze_knobs[ZE_KNOB_WIDE_DECODE] == ZE_WIDE_TILES_257 ? 256 : 512))
         launch_ring_variant<64, 64, 4, 4, 2, false, false, true>(c);
     else
         launch_ring_variant<64, 128, 4, 2, 4, false, false, true>(c);
@@ -2342,7 +2341,7 @@ static void launch_stream(const gemm_call& c) {
     // (gate/up 43.9 against 27.5 us at 64 chains: its 16-row x 64-B fragment loads use the vector memory path at a
     // fraction of what the LDS-DMA's 128-B rows do), so wide or long matrices stay on the ring.  The choice is a
     // function of (N, K, epilogue) alone: batch-composition invariance.
-    if (c.M <= 64 && c.K % 32 == 0 && c.K <= 4096 && c.N <= 4096 && c.epi != ZE_EPI_SWIGLU && ze_gemv_knobs[5] != 1 &&
+    if (c.M <= 64 && c.K % 32 == 0 && c.K <= 4096 && c.N <= 4096 && c.epi != ZE_EPI_SWIGLU && ze_knobs[ZE_KNOB_SKINNY] != ZE_SKINNY_OFF &&
         (c.lda % 8) == 0 && (c.ldw % 8) == 0) {
         dispatch_mt(c.M, [&](auto MT) { launch_skinny_mt<1, MT>(c, 1); });
         return;
@@ -2360,7 +2359,7 @@ void ze_launch_gemm_stream(int epi, const bf16_t* A, int lda, const bf16_t* W, i
 
 static void launch_policy(const gemm_call& c);  // the prefill / ViT policy (ze_launch_gemm, below)
 // knob 3: first row count (exclusive) of the 320 x 192 tiles
-static int ze_ring32_from() { return ze_gemv_knobs[3] > 0 ? ze_gemv_knobs[3] : 512; }
+static int ze_ring32_from() { return ze_knobs[ZE_KNOB_RING32_FROM] > 0 ? ze_knobs[ZE_KNOB_RING32_FROM] : 512; }
 void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, const bf16_t* R,
                          int ldr, bf16_t* C, int ldc, int M, int N, int K, const ze_gemm_ws& ws, hipStream_t s) {
     if (M <= 0 || N <= 0) return;
@@ -2379,19 +2378,19 @@ void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int
         // 20.9 / 25.7 / 27.0 / 31.2 / 35.4 / 36.9 / 37.4 / 40.4 against 22.5 / 31.2 / 33.8 / 37.2 / 43.2 / 45.3 / 50.4 / 57.0 in one
         // launch on 64 x 64 tiles (with 128 x 256 tiles at 217 / 256 rows: 32.9 / 34.4 -- 128 workgroups, half the chip).  Same
         // slices, same order of additions: the same bits whatever the form.  knob 15 = 6: one launch at every row count
-        if (ze_gemv_knobs[15] != 6) {
+        if (ze_knobs[ZE_KNOB_WIDE_TILES] != ZE_WT_ONE_LAUNCH) {
             // 257 .. 384 rows: 192 x 128 tiles -- two row tiles instead of three of 128 (no wasted third), 256 workgroups
             // instead of 192 (every CU), 17 % fewer bytes staged per workgroup; knob 15 = 4: the 128 x 256 tiles there too
-            if (M > 256 && M <= 384 && ze_gemv_knobs[15] != 4 && launch_splitk_two<192, 128, 3, false, 4, 2>(c)) return;
+            if (M > 256 && M <= 384 && ze_knobs[ZE_KNOB_WIDE_TILES] != ZE_WT_WSTREAM_TILES && launch_splitk_two<192, 128, 3, false, 4, 2>(c)) return;
             // 513 .. 640 / 641 .. 768 rows: 320 x 128 / 384 x 128 tiles with K-steps of 32 (four stages): two row tiles x 16
             // column tiles x 8 slices = 256 workgroups, one round, where five or six row tiles of 128 x 256 are 320 / 384
             // workgroups -- a second round for a quarter / half of the chip.  knob 15 = 7: off
             // (knob 18, as for gate/up: 0 K-steps of 64 in two stages -- 56.3 -> 53.3 us at 704 rows, level at 576 --, 1 round 4's form)
             auto two_bm = [&](auto BM) {
-                return ze_gemv_knobs[18] == 1 ? launch_splitk_two<BM, 128, 4, true, 4, 2, 32>(c) : launch_splitk_two<BM, 128, 2, false, 4, 2>(c);
+                return ze_knobs[ZE_KNOB_KSTEP32] == ZE_KNOB_ON ? launch_splitk_two<BM, 128, 4, true, 4, 2, 32>(c) : launch_splitk_two<BM, 128, 2, false, 4, 2>(c);
             };
-            if (M > 512 && M <= 640 && ze_gemv_knobs[15] != 7 && two_bm(int_c<320>())) return;
-            if (M > 640 && M <= 768 && ze_gemv_knobs[15] != 7 && two_bm(int_c<384>())) return;
+            if (M > 512 && M <= 640 && ze_knobs[ZE_KNOB_WIDE_TILES] != ZE_WT_NO_TWO_ROW_TILES && two_bm(int_c<320>())) return;
+            if (M > 640 && M <= 768 && ze_knobs[ZE_KNOB_WIDE_TILES] != ZE_WT_NO_TWO_ROW_TILES && two_bm(int_c<384>())) return;
             // (round 5: 128 x 256 without the spread refill 35.7 against 35.1 us at 399 rows, in two stages 43.8)
             if (M > 256 && launch_splitk_two<128, 256, 3, true>(c)) return;
             if (M > 128 && M <= 256 && launch_splitk_two<128, 128, 4, true>(c)) return;
@@ -2409,14 +2408,14 @@ void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int
     // cut for at most 768 rows -- beyond, the row count is a small prefill pass's and its policy serves it best (3B shape at 1152 rows:
     // qkv 21.7 us, o 21.1, gate/up 101.7 on the prefill policy against 38.1 / 22.3 / 129.9 on two blocks of the decode tiles).  K in
     // sequence on every tile: the same bits, so the choice may follow the row count.
-    if (M > 768 && epi != ZE_EPI_F32 && ze_gemv_knobs[15] != 9) {
+    if (M > 768 && epi != ZE_EPI_F32 && ze_knobs[ZE_KNOB_WIDE_TILES] != ZE_WT_PLAIN) {
         launch_policy(p);
         return;
     }
     const bool ok = K % GEMM_BK == 0 && (lda % 8) == 0 && (ldw % 8) == 0 && (size_t)N * ldw * sizeof(bf16_t) < ((size_t)1 << 31) &&
                     N % 32 == 0 && (ldc % 8) == 0 && ((size_t)A % 16) == 0 && ((size_t)C % 16) == 0;
-    const int v = ze_gemv_knobs[15];
-    const bool want = v == 1 || (v != 9 && ((epi == ZE_EPI_SWIGLU && M > 96) || (epi == ZE_EPI_F32 && M <= 160)));
+    const int v = ze_knobs[ZE_KNOB_WIDE_TILES];
+    const bool want = v == ZE_WT_WSTREAM || (v != ZE_WT_PLAIN && ((epi == ZE_EPI_SWIGLU && M > 96) || (epi == ZE_EPI_F32 && M <= 160)));
     bool done = false;
     if (ok && want && N >= 8192) {
         // more than 256 rows (engines with up to 512 chain slots): blocks of 256 rows, one launch each -- the second pass over
@@ -2429,7 +2428,7 @@ void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int
         // the ring with K-steps of 32 -- four 32-KB stages, two row tiles x 115 column tiles = 230 workgroups in ONE round, 512
         // staged rows per 320 x 192 outputs -- instead of a 512-row and a 128-row weight-streaming pass.  knob 15 = 7: off
         // 641 .. 768 rows: 384 x 192 tiles the same way (four 36-KB stages, 96 x 96 outputs per wave)
-        if (epi == ZE_EPI_SWIGLU && ((M > ze_ring32_from() && M <= 640) || (M > 640 && M <= 768)) && v != 7 && v != 4) {
+        if (epi == ZE_EPI_SWIGLU && ((M > ze_ring32_from() && M <= 640) || (M > 640 && M <= 768)) && v != ZE_WT_NO_TWO_ROW_TILES && v != ZE_WT_WSTREAM_TILES) {
             // (round 5: the two-phase loop -- the waves of a SIMD in opposite phases; knob 18 = 1: the plain loop with the spread refill)
             // Round 5.  The launch is bound by what its workgroups take in through LDS-DMA -- with the MFMAs AND the fragment reads compiled
             // out (tools/probes/ring_ablate.sh) it still takes 57.6 of 63.1 us at 576 rows: 230 workgroups x 2 MB = 460 MB at 8 TB/s, the
@@ -2439,7 +2438,7 @@ void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int
             // the same K order on every form: the same bits.  knob 18: 0 this default, 1 round 4's form (K-steps of 32, four stages,
             // spread refill).
             auto ring_bm = [&](auto BM) {
-                if (ze_gemv_knobs[18] == 1) launch_ring_variant<BM, 192, 4, 4, 2, true, true, false, 32>(p);
+                if (ze_knobs[ZE_KNOB_KSTEP32] == ZE_KNOB_ON) launch_ring_variant<BM, 192, 4, 4, 2, true, true, false, 32>(p);
                 else launch_ring_variant<BM, 192, 2, 4, 2, false, true>(p);
             };
             if (M <= 640) ring_bm(int_c<320>());
@@ -2449,11 +2448,11 @@ void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int
         // 385 .. 512 rows (round 5): 256 x 192 tiles on K-steps of 64 in two stages WITHOUT the spread refill -- two row tiles x 115
         // column tiles = 230 workgroups staging 1.8 MB each, against 2.4 MB for the 512 x 96 weight-streaming tile (round 4 had tried
         // this tile with the spread refill: 61.9 against 57.4 us at 440 rows).  knob 15 = 8: the weight-streaming tile
-        if (epi == ZE_EPI_SWIGLU && M > 384 && M <= 512 && v != 8 && v != 4 && v != 7) {
+        if (epi == ZE_EPI_SWIGLU && M > 384 && M <= 512 && v != ZE_WT_WSTREAM_385_512 && v != ZE_WT_WSTREAM_TILES && v != ZE_WT_NO_TWO_ROW_TILES) {
             launch_ring_variant<256, 192, 2, 4, 2, false, true>(p);
             return;
         }
-        const int blk = (epi == ZE_EPI_SWIGLU && K / GEMM_BK == 32 && v != 5) ? 512 : 256;
+        const int blk = (epi == ZE_EPI_SWIGLU && K / GEMM_BK == 32 && v != ZE_WT_BLOCKS_256) ? 512 : 256;
         for (int r0 = 0; r0 < M && done; r0 += blk) {
             const int mb = std::min(blk, M - r0);
             gemm_call b = c;  // this block of rows
@@ -2468,7 +2467,7 @@ void ze_launch_gemm_wide(int epi, const bf16_t* A, int lda, const bf16_t* W, int
             // workgroup stages (192 + 192) rows per K-step for 192 x 192 outputs -- 96 FLOP per staged byte against 77 for
             // the 384 x 96 weight-streaming tile, which re-reads ALL the activations in every workgroup.  Same K order per
             // output element: the same bits.  knob 15 = 4: the weight-streaming tile there too
-            if (mb > 256 && mb <= 384 && epi == ZE_EPI_SWIGLU && v != 4 && r0 == 0 && M <= 384) {
+            if (mb > 256 && mb <= 384 && epi == ZE_EPI_SWIGLU && v != ZE_WT_WSTREAM_TILES && r0 == 0 && M <= 384) {
                 // (the refill DMAs spread between the rows of MFMAs: 40.6 against 41.6 us at 344 rows)
                 // (round 5: without the spread refill 41.4 us, in two stages 46.9, against 40.3 as is at 344 rows)
                 launch_ring_variant<192, 192, 3, 4, 2, true, true>(no_ws(b));
@@ -2502,8 +2501,8 @@ static void launch_policy(const gemm_call& c) {
     // the LLM qkv projection at M = 802: 260 / 140 tiles): one round of 128 x 128 tiles on the eight-wave ring with the
     // spread refill, 23.6 us against 33.7 register-staged on 64 x 128 (30.4 / 25.7 for the 64 x 128 ring in two rounds /
     // the unspread 128 x 128 ring).
-    if (ringable && K / GEMM_BK >= 4 && b128 < 200 && b128 >= 96 && b64x128 > 256 && ze_gemv_knobs[6] == 0 &&
-        ze_gemv_knobs[7] != 3) {
+    if (ringable && K / GEMM_BK >= 4 && b128 < 200 && b128 >= 96 && b64x128 > 256 && ze_knobs[ZE_KNOB_GEMM_STAGING] == 0 &&
+        ze_knobs[ZE_KNOB_GEMM_TILE] != ZE_TILE_REG_ONLY) {
         int ks_ = ze_prefill_ksplit(K, ws.slab != nullptr);
         if (ks_ > 1 && ((size_t)ks_ * b128 * 128 * 128 > ws.slab_floats || b128 > ws.ticket_cap)) ks_ = ze_prefill_split_dropped(M, N, K, ks_);
         launch_ring_variant<128, 128, 4, 2, 4, true>(c, ks_);

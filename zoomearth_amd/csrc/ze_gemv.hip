@@ -14,8 +14,8 @@
 bool ze_launch_gemv8(int epi, const ze_gemv_args& a, hipStream_t s);
 bool ze_launch_gemv4(int epi, const ze_gemv_args& a, hipStream_t s);
 
-// overrides set through ze_tune(): [0] down variant, [1] gate_up variant, [2] grid cap, [3] fused attention block
-int ze_gemv_knobs[25] = {0};
+// overrides set through ze_tune(), named in ze_knobs.h
+int ze_knobs[ZE_KNOB_COUNT] = {0};
 int ze_live_engines = 0;  // engines alive in this process (one GPU per process): counted by ze_engine_create / ze_engine_destroy
 
 bool ze_launch_gemv(int epi, const ze_gemv_args& a, hipStream_t s) {
@@ -32,13 +32,13 @@ bool ze_launch_gemv(int epi, const ze_gemv_args& a, hipStream_t s) {
         //  pays the x-staging prologue)
         case ZE_GV_QKV_ROPE: launch_gemv_cfg<ZE_GV_QKV_ROPE, 1, 1, 4>(a, s); break;
         case ZE_GV_SWIGLU:
-            if (many_rows && ze_gemv_knobs[1] == 1) launch_gemv_cfg<ZE_GV_SWIGLU, 2, 1, 4>(a, s);
+            if (many_rows && ze_knobs[ZE_KNOB_GATE_UP_FLASH] == ZE_GATE_UP_TWO_PAIRS) launch_gemv_cfg<ZE_GV_SWIGLU, 2, 1, 4>(a, s);
             else launch_gemv_cfg<ZE_GV_SWIGLU, 1, 1, 4>(a, s);
             break;
         case ZE_GV_RESIDUAL:
-            if (long_k && ze_gemv_knobs[0] == 1) launch_gemv_cfg<ZE_GV_RESIDUAL, 2, 4, 6>(a, s);
-            else if (long_k && ze_gemv_knobs[0] == 2) launch_gemv_cfg<ZE_GV_RESIDUAL, 1, 4, 4>(a, s);
-            else if (long_k && ze_gemv_knobs[0] == 3) launch_gemv_cfg<ZE_GV_RESIDUAL, 1, 1, 4>(a, s);
+            if (long_k && ze_knobs[ZE_KNOB_GEMV_DOWN] == ZE_DOWN_TWO_PAIRS) launch_gemv_cfg<ZE_GV_RESIDUAL, 2, 4, 6>(a, s);
+            else if (long_k && ze_knobs[ZE_KNOB_GEMV_DOWN] == ZE_DOWN_FOUR_CHUNKS) launch_gemv_cfg<ZE_GV_RESIDUAL, 1, 4, 4>(a, s);
+            else if (long_k && ze_knobs[ZE_KNOB_GEMV_DOWN] == ZE_DOWN_NO_KSPLIT) launch_gemv_cfg<ZE_GV_RESIDUAL, 1, 1, 4>(a, s);
             else if (long_k) launch_gemv_cfg<ZE_GV_RESIDUAL, 1, 4, 6>(a, s);
             else launch_gemv_cfg<ZE_GV_RESIDUAL, 1, 1, 4>(a, s);
             break;

@@ -11,8 +11,8 @@ bool ze_launch_gemv4(int epi, const ze_gemv_args& a, hipStream_t s) {
     // whatever N: two pairs make hipcc unroll the pair-set loop to 185 VGPRs (2 waves per SIMD against the family's 4) and measured
     // 9.46 us against 8.62 on the 3B gate/up.  Long K (the down projection) splits K over the four waves as the family does.
     const bool long_k = a.K > 4096;
-    const bool many_rows = a.N >= 8192 && ze_gemv_knobs[1] != 2;  // (knob 1 = 2: one pair per wave, as for the fp8 stream)
-    const bool wide_one = many_rows && ze_gemv_knobs[1] == 1;      // (knob 1 = 1: the measured-and-rejected two pairs at one chunk)
+    const bool many_rows = a.N >= 8192 && ze_knobs[ZE_KNOB_GATE_UP_FLASH] != ZE_GATE_UP_ONE_PAIR;  // (knob 1 = 2: one pair per wave, as for the fp8 stream)
+    const bool wide_one = many_rows && ze_knobs[ZE_KNOB_GATE_UP_FLASH] == ZE_GATE_UP_TWO_PAIRS;      // (knob 1 = 1: the measured-and-rejected two pairs at one chunk)
     const bool one_chunk = a.K <= 2048;
 #define ZE_GV4(EPI, P1, PM1, P2, PM2)                                                   \
     if (one_chunk) {                                                                    \

@@ -11,7 +11,7 @@ bool ze_launch_gemv8(int epi, const ze_gemv_args& a, hipStream_t s) {
         // two row pairs per wave-iteration where there are many rows: the f32 widening of x is shared by four rows
         case ZE_GV_QKV_ROPE: launch_gemv_cfg<ZE_GV_QKV_ROPE, 1, 1, 4, 8>(a, s); break;
         case ZE_GV_SWIGLU:
-            if (many_rows && ze_gemv_knobs[1] != 2) launch_gemv_cfg<ZE_GV_SWIGLU, 2, 1, 4, 8>(a, s);
+            if (many_rows && ze_knobs[ZE_KNOB_GATE_UP_FLASH] != ZE_GATE_UP_ONE_PAIR) launch_gemv_cfg<ZE_GV_SWIGLU, 2, 1, 4, 8>(a, s);
             else launch_gemv_cfg<ZE_GV_SWIGLU, 1, 1, 4, 8>(a, s);
             break;
         case ZE_GV_RESIDUAL:

@@ -493,8 +493,6 @@ __global__ void __launch_bounds__(256) k_gemv(const ze_gemv_args a) {
     }
 }
 
-extern int ze_gemv_knobs[25];
-
 template <int EPI, int PAIRS, int KSPLIT, int CH, int WB = 16>
 static void launch_gemv_cfg(const ze_gemv_args& a, hipStream_t s) {
     const int P = a.N / 2;
@@ -518,7 +516,7 @@ static void launch_gemv_cfg(const ze_gemv_args& a, hipStream_t s) {
         // one-set workgroups and 768 + 256 (10.4 vs 10.9 us)
         if (KSPLIT > 1 && natural > 2 * cus && natural <= 4 * cus) grid = ze_cdiv(natural, 2);
     }
-    if (ze_gemv_knobs[2] > 0) grid = std::min(ze_cdiv(P, PAIRS * (KSPLIT == 1 ? 4 : 1)), ze_gemv_knobs[2]);
+    if (ze_knobs[ZE_KNOB_GEMV_GRID_CAP] > 0) grid = std::min(ze_cdiv(P, PAIRS * (KSPLIT == 1 ? 4 : 1)), ze_knobs[ZE_KNOB_GEMV_GRID_CAP]);
     if (EPI == ZE_GV_LOGITS && a.amax_ws && grid > 2048) grid = 2048;  // one arg-max slot per workgroup (k_argmax_final_folded)
     hipLaunchKernelGGL((k_gemv<EPI, PAIRS, KSPLIT, CH, WB>), dim3(grid), dim3(256), lds, s, a);
 }

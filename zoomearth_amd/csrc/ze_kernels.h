@@ -1,6 +1,7 @@
 // Launcher declarations for the HIP kernels of libzoomearth_hip.so (internal C++ interface).
 #pragma once
 #include "ze_common.h"
+#include "ze_knobs.h"  // the launchers' policies read the ze_tune knobs
 
 // GEMM epilogues
 enum { ZE_EPI_NONE = 0, ZE_EPI_GELU = 1, ZE_EPI_RESIDUAL = 2, ZE_EPI_SWIGLU = 3, ZE_EPI_F32 = 4, ZE_EPI_QKV_ROPE = 5 };
