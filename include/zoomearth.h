@@ -160,6 +160,30 @@ int ze_op_lora_merge(ze_engine* e, const void* base_bf16, int rows, int cols, co
  * device buffer on `stream`.  The copy is asynchronous when host_rgb is pinned; the tile is uploaded ONCE per tile and
  * every view / crop of every question about it reads it in place. */
 int ze_tile_upload(ze_engine* e, const uint8_t* host_rgb, int h, int w, uint8_t* dev_rgb, void* stream);
+/* replaces: `Image.open(image_fp).convert("RGB")` + ze_tile_upload for an LZW (compression 5) or PackBits (32773) 8-bit RGB TIFF,
+ * predictor 1 or 2, in strips or tiles: the COMPRESSED chunks travel and the device decodes them into dev_rgb, u8 [h, w, 3]
+ * (zoomearth_amd.image.tiff_plan reads the tags and builds the arguments; it returns None for every file this entry does not take).
+ * host_bytes (pinned for an asynchronous copy): the chunks one behind the other, each starting on a 16-byte boundary; n_bytes, a
+ * multiple of 16, covers them all.  host_table: int32 [n_chunks, 8] = {offset in host_bytes, byte count, x0, y0, w, h of the chunk's
+ * rectangle in the image, stored w, stored h}.  tiled = 0: strips -- full width, stored = destination rectangle, at most chunk_h rows,
+ * chunk_w = w -- decoded in place.  tiled = 1: every chunk stores chunk_w x chunk_h pixels (edge tiles padded, as TIFF stores them) and
+ * is clipped when it is placed.  A chunk stores at most 1 MiB (ZE_ERR_INVALID beyond: such a file stays on the host path).
+ * dev_status: int32 [n_chunks] on the device, one word per chunk: 0 = decoded exactly the stored rectangle's bytes; else the first
+ * defect: 1 input exhausted, 2 a code above the next free code, 3 the output would pass the chunk's end, 4 output short (EOI early),
+ * 5 a table row that does not fit the image, the input or the limits.  No stream of bytes makes a chunk read outside its own input,
+ * write outside its own output or run longer than its byte count allows.  A chunk with a non-zero status leaves its rectangle
+ * undefined: the caller reads the status words where it waits for the upload and decodes such a tile on the host.
+ * Asynchronous like ze_tile_upload: both arrays are copied and the kernels launched on `stream`.  The device staging is the engine's,
+ * sized by the request; an event behind the last kernel guards its reuse, so calls on different streams are ordered by the library. */
+int ze_tile_upload_tiff(ze_engine* e, const uint8_t* host_bytes, size_t n_bytes, const int32_t* host_table, int n_chunks, int h, int w,
+                        int compression, int predictor, int tiled, int chunk_w, int chunk_h, uint8_t* dev_rgb, int32_t* dev_status,
+                        void* stream);
+/* The decode of ze_tile_upload_tiff alone, on compressed bytes (16-byte aligned) and a chunk table that are on the device already:
+ * k_tiff_lzw or k_tiff_packbits, one wave per chunk, then k_tiff_unpredict (predictor 2: the running sum mod 256 per channel along
+ * every stored row; tiles: the placement of the padded tiles).  The table is checked on the device, row by row (status 5). */
+int ze_op_tiff_decode(ze_engine* e, const uint8_t* dev_bytes, size_t n_bytes, const int32_t* dev_table, int n_chunks, int h, int w,
+                      int compression, int predictor, int tiled, int chunk_w, int chunk_h, uint8_t* dev_rgb, int32_t* dev_status,
+                      void* stream);
 /* replaces: PIL `image.crop(box).resize((dst_w, dst_h), Image.BICUBIC)` on RGB u8 as used by cut_image /
  * resize_image (src/eval/infer.py:41-85, src/demo.py:30-93) and by the HF image processor
  * (HF:models/qwen2_vl/image_processing_pil_qwen2_vl.py:126-150).  Bit-exact with Pillow.

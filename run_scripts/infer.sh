@@ -17,6 +17,10 @@ NGPU="${NGPU:-1}"
 if [ "${ZE_THROUGHPUT:-0}" = "1" ]; then
   EXTRA_ARGS="--batch_size 512 --lanes 2 --hold 384 ${EXTRA_ARGS:-}"
 fi
+# ZE_DEVICE_TIFF=1: LZW / PackBits TIFF tiles are decoded on the GPU (--device_tiff_decode); other files keep the host decoder
+if [ "${ZE_DEVICE_TIFF:-0}" = "1" ]; then
+  EXTRA_ARGS="--device_tiff_decode ${EXTRA_ARGS:-}"
+fi
 echo "Infering model: $model_name on LRS-GRO!"
 echo "Experiment name: $exp_name!"
 if [ "$NGPU" -gt 1 ]; then

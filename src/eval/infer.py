@@ -89,7 +89,7 @@ def speculative_kwargs(speculative_ngram, batch_size):
 
 def eval_model_lora(model_name, exp_name, ds_path="./LRS_GRO/test", image_dir="./image/", max_new_tokens=1024,
                     batch_size=BATCH_SIZE, max_ctx=4096, do_sample=True, resume=False, decode_workers=3, decode_ahead=6, lanes=1,
-                    steal=False, hold=0, admit_rows=0, speculative_ngram=0):
+                    steal=False, hold=0, admit_rows=0, speculative_ngram=0, device_tiff_decode=False):
     spec_kw = speculative_kwargs(speculative_ngram, batch_size)   # (refused before anything is loaded)
     # capacity: the stage-2 prompt holds the stage-1 prompt, its output and a second image (<= ~3200 tokens at the
     # default budgets); prefill passes of up to 16 prompts share their GEMMs
@@ -203,7 +203,8 @@ def eval_model_lora(model_name, exp_name, ds_path="./LRS_GRO/test", image_dir=".
     def run_lane(ln):
         m, proc, todo = models[ln], procs[ln], work[ln]
         # the lane's questions arrive grouped by tile: decode the next tiles while the current one is being questioned
-        tiles = TilePrefetcher([tile_path(name) for _, name, _items in todo], m.engine, depth=decode_ahead, workers=decode_workers)
+        tiles = TilePrefetcher([tile_path(name) for _, name, _items in todo], m.engine, depth=decode_ahead, workers=decode_workers,
+                               device_decode=device_tiff_decode)
         sched = ChainScheduler(m, proc, do_sample=do_sample, temperature=0.01 if do_sample else None, burst=8,
                                min_admit=max(1, batch_size // 2), max_wait_bursts=12, hold_below=hold, admit_chunk_rows=admit_rows,
                                **spec_kw)
@@ -255,7 +256,7 @@ def eval_model_lora(model_name, exp_name, ds_path="./LRS_GRO/test", image_dir=".
             name, idxs = claims.lists[took[0]][took[1]]
             try:
                 from zoomearth_amd.image import DeviceImage
-                tile = DeviceImage.open(tile_path(name), m.engine)
+                tile = DeviceImage.open(tile_path(name), m.engine, device_decode=device_tiff_decode)
                 view = tuple(H.resize_image(tile))
             except Exception as ex:
                 tile, view, err = None, None, ex
@@ -276,7 +277,8 @@ def eval_model_lora(model_name, exp_name, ds_path="./LRS_GRO/test", image_dir=".
             sched.step()
             flush()
         st = dict(sched.stats)
-        st.update(tile_decodes=tiles.decodes, tile_decode_s=round(tiles.decode_s, 3), tile_wait_s=round(tiles.wait_s, 3))
+        st.update(tile_decodes=tiles.decodes, tile_decode_s=round(tiles.decode_s, 3), tile_wait_s=round(tiles.wait_s, 3),
+                  tile_device_decodes=tiles.device_decodes, tile_fallbacks=tiles.fallbacks)
         all_stats[ln] = st
 
     def lane_thread(ln):
@@ -371,8 +373,11 @@ if __name__ == "__main__":
                              "costs almost the same at 60 chains as at 400); 0 = never hold")
     parser.add_argument("--decode_workers", type=int, default=3, help="tile decode threads per lane")
     parser.add_argument("--decode_ahead", type=int, default=6, help="tiles decoded ahead of the one in use (75 MB pinned each)")
+    parser.add_argument("--device_tiff_decode", action="store_true", default=os.environ.get("ZE_DEVICE_TIFF") == "1",
+                        help="LZW / PackBits RGB TIFF tiles travel compressed and are decoded on the GPU (zoomearth_amd.image.tiff_plan says "
+                             "which files); every other tile, and a tile with a defective chunk, is decoded on the host as without the flag")
     args = parser.parse_args()
     eval_model_lora(args.model_name, args.exp_name, args.dataset, args.image_dir, args.max_new_tokens, args.batch_size,
                     args.max_ctx, do_sample=not args.greedy, resume=args.resume, decode_workers=args.decode_workers,
                     decode_ahead=args.decode_ahead, lanes=args.lanes, steal=args.steal, hold=args.hold, admit_rows=args.admit_rows,
-                    speculative_ngram=args.speculative_ngram)
+                    speculative_ngram=args.speculative_ngram, device_tiff_decode=args.device_tiff_decode)

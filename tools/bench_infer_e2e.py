@@ -32,7 +32,7 @@ def word(i: int) -> str:
     return f"w{i}"
 
 
-def build(d, n_questions, tile_side, n_pool):
+def build(d, n_questions, tile_side, n_pool, tile_compression="none"):
     from datasets import Dataset
     from PIL import Image
     from tokenizers import AddedToken, Tokenizer
@@ -72,7 +72,11 @@ def build(d, n_questions, tile_side, n_pool):
     while len(rows) < n_questions:
         c = min(3 + int(uniform_ints(424_242 + t, 1, 0, 16)[0]), n_questions - len(rows))
         arr = np.roll(pool[t % n_pool], shift=(37 * t) % tile_side, axis=1)  # distinct bytes per tile at memcpy cost
-        Image.fromarray(arr).save(os.path.join(d, "image", f"tile{t:04d}.tif"))
+        # --tile_compression: none (uncompressed, the default), lzw, lzw2 (LZW + horizontal predictor: what gdal_translate -co COMPRESS=LZW
+        # -co PREDICTOR=2 writes) or packbits, through Pillow + libtiff
+        kw = {"none": {}, "lzw": {"compression": "tiff_lzw"}, "lzw2": {"compression": "tiff_lzw", "tiffinfo": {317: 2}},
+              "packbits": {"compression": "packbits"}}[tile_compression]
+        Image.fromarray(arr).save(os.path.join(d, "image", f"tile{t:04d}.tif"), **kw)
         for k in range(c):
             q = len(rows)
             rows.append({"question": " ".join(word(int(v)) for v in uniform_ints(500 + q, 12 + q % 9, 0, 151000)),
@@ -96,9 +100,11 @@ def main():
     ap.add_argument("--hold", type=int, default=0)
     ap.add_argument("--admit_rows", type=int, default=0)
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--tile_compression", choices=("none", "lzw", "lzw2", "packbits"), default="none", help="how the tiles on disk are stored")
+    ap.add_argument("--device_tiff_decode", action="store_true", help="the entry point's --device_tiff_decode: compressed tiles are decoded on the GPU")
     args = ap.parse_args()
     d = args.workdir or tempfile.mkdtemp(prefix="ze_e2e_")
-    n_tiles, build_s = build(d, args.questions, args.tile, 4)
+    n_tiles, build_s = build(d, args.questions, args.tile, 4, args.tile_compression)
     os.chdir(d)
     import torch
     from zoomearth_amd.image import TilePrefetcher, decode_rgb
@@ -108,8 +114,9 @@ def main():
         device = torch.device("cuda", 0)
 
     # TilePrefetcher alone: decode (+ pinning) + upload of every tile, no model
-    out = {"questions": args.questions, "tiles": n_tiles, "tile_side": args.tile, "files": "uncompressed TIFF, %.0f MB each" %
-           (os.path.getsize(paths[0]) / 1e6), "build_s": round(build_s, 1)}
+    out = {"questions": args.questions, "tiles": n_tiles, "tile_side": args.tile, "files": "%s TIFF, %.0f MB each" %
+           ({"none": "uncompressed"}.get(args.tile_compression, args.tile_compression), os.path.getsize(paths[0]) / 1e6),
+           "device_tiff_decode": bool(args.device_tiff_decode), "build_s": round(build_s, 1)}
     for workers, ahead in ((1, 1), (args.decode_workers, args.decode_ahead), (4, 6)):
         sub = paths[: min(len(paths), 24)]
         t0 = time.perf_counter()
@@ -143,7 +150,8 @@ def main():
         prof = cProfile.Profile()
         prof.enable()
     stats = infer.eval_model_lora("ckpt", "e2e_", "./LRS_GRO/test", "./image/", args.max_new_tokens, args.batch_size, 2048,
-                                  do_sample=False, decode_workers=args.decode_workers, decode_ahead=args.decode_ahead, lanes=args.lanes, hold=args.hold, admit_rows=args.admit_rows)
+                                  do_sample=False, decode_workers=args.decode_workers, decode_ahead=args.decode_ahead, lanes=args.lanes, hold=args.hold, admit_rows=args.admit_rows,
+                                  device_tiff_decode=args.device_tiff_decode)
     if prof is not None:
         import io
         import pstats

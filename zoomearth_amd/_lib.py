@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("ZE_LIB_PATH") or os.path.join(_HERE, "libzoomearth_hi
 CSRC = os.path.join(_HERE, "csrc")
 
 ZE_F32, ZE_F16, ZE_BF16 = 0, 1, 2
+ZE_ERR_INVALID, ZE_ERR_HIP, ZE_ERR_NOMEM = -1, -2, -3   # ze_status
 ZE_MAX_FULLATT, ZE_MAX_EOS = 16, 4
 
 
@@ -102,6 +103,8 @@ _SIGS = {
     "ze_lora_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "ze_op_lora_merge": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ze_tile_upload": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "ze_tile_upload_tiff": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "ze_op_tiff_decode": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "ze_op_crop_resize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int32), _P, C.c_int, C.c_int, _P]),
     "ze_smart_resize": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int),
                                   C.POINTER(C.c_int)]),

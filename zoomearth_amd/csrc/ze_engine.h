@@ -380,6 +380,12 @@ struct ze_engine {
     hipEvent_t v_staged = nullptr, t_staged = nullptr;  // behind the last H2D copy out of v_host_* / t_host_ints (stage_acquire)
     hipEvent_t fe_done = nullptr;  // recorded behind the last kernel that reads the front-end workspace (any stream)
     bool fe_in_flight = false;
+    // TIFF tile decode (ze_tiff.hip): the compressed bytes + chunk table of ze_tile_upload_tiff on the device, and the padded tiles of a
+    // tiled file before they are placed.  Both are sized by the request and grown on demand; tiff_done is recorded behind the last kernel
+    // that reads either, and the next call's copy waits for it on its own stream
+    uint8_t *tiff_in = nullptr, *tiff_tiles = nullptr;
+    size_t tiff_in_cap = 0, tiff_tiles_cap = 0;
+    hipEvent_t tiff_done = nullptr;
 
     // ViT workspace
     bf16_t *vx = nullptr, *vh = nullptr, *vy = nullptr, *vqkv = nullptr, *vo = nullptr, *va = nullptr, *vz = nullptr,

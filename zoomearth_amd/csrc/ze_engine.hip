@@ -474,6 +474,9 @@ extern "C" int ze_engine_destroy(ze_engine* e) {
     for (hipEvent_t ev : e->pfx_copy_ev)
         if (ev) hipEventDestroy(ev);
     if (e->fe_done) hipEventDestroy(e->fe_done);
+    if (e->tiff_done) hipEventDestroy(e->tiff_done);
+    if (e->tiff_in) hipFree(e->tiff_in);
+    if (e->tiff_tiles) hipFree(e->tiff_tiles);
     if (e->v_staged) hipEventDestroy(e->v_staged);
     if (e->t_staged) hipEventDestroy(e->t_staged);
     if (e->xs_staged) hipEventDestroy(e->xs_staged);

@@ -1211,6 +1211,51 @@ class Engine:
         out._ze_host_keepalive = t  # the async copy reads the host buffer until the stream reaches it
         return out
 
+    def tile_upload_tiff(self, plan, host_bytes: torch.Tensor):
+        """ze_tile_upload_tiff: the compressed chunks of `plan` (zoomearth_amd.image.TiffPlan), read into the flat u8 tensor host_bytes
+        (pinned for an asynchronous copy), go to the device and are decoded there on the current stream.  Returns (tile u8 [H, W, 3],
+        status i32 [n_chunks]), both device tensors: the tile is valid when every status word is 0, which the caller checks where it
+        waits for the upload."""
+        assert host_bytes.dtype == torch.uint8 and host_bytes.is_contiguous() and host_bytes.numel() >= plan.n_bytes and not host_bytes.is_cuda
+        table = np.ascontiguousarray(plan.table, dtype=np.int32)
+        out = torch.empty((plan.height, plan.width, 3), dtype=torch.uint8, device=self.device)
+        status = torch.empty(plan.n_chunks, dtype=torch.int32, device=self.device)
+        self._check(self.lib.ze_tile_upload_tiff(self.h, C.c_void_p(host_bytes.data_ptr()), plan.n_bytes, C.c_void_p(table.ctypes.data),
+                                                 plan.n_chunks, plan.height, plan.width, plan.compression, plan.predictor, int(plan.tiled),
+                                                 plan.chunk_w, plan.chunk_h, _ptr(out), _ptr(status), self._stream()))
+        out._ze_host_keepalive = host_bytes  # the async copy reads the host buffer until the stream reaches it
+        return out, status
+
+    def upload_tiff(self, path_or_plan) -> torch.Tensor:
+        """`Image.open(path).convert("RGB")` on the device for an LZW / PackBits RGB TIFF: its compressed chunks are read into pinned memory
+        and decoded by the engine.  Takes a path or a TiffPlan; returns the u8 [H, W, 3] device tensor.  ValueError for a file without a plan
+        (zoomearth_amd.image.tiff_plan says which files have one), TiffChunkError when a chunk is defective -- decode_rgb is the way then."""
+        from .image import TiffChunkError, TiffPlan, tiff_plan
+        plan = path_or_plan if isinstance(path_or_plan, TiffPlan) else tiff_plan(path_or_plan)
+        if plan is None:
+            raise ValueError(f"{path_or_plan}: not a TIFF the device decodes (see zoomearth_amd.image.tiff_plan)")
+        buf = torch.empty(plan.n_bytes, dtype=torch.uint8).pin_memory()
+        if not plan.read_into(buf.numpy()):
+            raise TiffChunkError(f"{plan.path}: a chunk is old-style (pre-6.0) LZW, which the device does not decode")
+        out, status = self.tile_upload_tiff(plan, buf)
+        st = status.cpu().numpy()
+        if st.any():
+            i = int(np.flatnonzero(st)[0])
+            raise TiffChunkError(f"{plan.path}: chunk {i} is defective (status {int(st[i])})")
+        return out
+
+    def tiff_decode(self, dev_bytes: torch.Tensor, dev_table: torch.Tensor, h: int, w: int, compression: int, predictor: int, tiled: bool,
+                    chunk_w: int, chunk_h: int, out: torch.Tensor, status: torch.Tensor) -> None:
+        """ze_op_tiff_decode: the decode kernels alone on device operands -- dev_bytes u8 (16-byte aligned, a multiple of 16 long), dev_table
+        i32 [n_chunks, 8], out u8 [h, w, 3] (or a larger buffer that starts with it), status i32 [n_chunks]."""
+        assert dev_bytes.dtype == torch.uint8 and dev_table.dtype == torch.int32 and status.dtype == torch.int32 and out.dtype == torch.uint8
+        assert dev_bytes.is_cuda and dev_table.is_cuda and out.is_cuda and status.is_cuda and dev_table.is_contiguous() and out.is_contiguous()
+        n = int(dev_table.shape[0])
+        assert status.numel() >= n and out.numel() >= h * w * 3
+        self._use(dev_bytes), self._use(dev_table)
+        self._check(self.lib.ze_op_tiff_decode(self.h, _ptr(dev_bytes), int(dev_bytes.numel()), _ptr(dev_table), n, int(h), int(w), int(compression),
+                                               int(predictor), int(bool(tiled)), int(chunk_w), int(chunk_h), _ptr(out), _ptr(status), self._stream()))
+
     def sample_greedy(self, seq: int, logits: torch.Tensor, repetition_penalty: float = 1.0) -> int:
         tok = C.c_int32()
         self._check(self.lib.ze_op_sample_greedy(self.h, seq, _ptr(logits), repetition_penalty, C.byref(tok),

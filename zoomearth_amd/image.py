@@ -13,6 +13,8 @@ import itertools
 import numpy as np
 import torch
 
+from . import _lib
+
 BICUBIC = 3
 _ids = itertools.count(1)
 
@@ -40,9 +42,21 @@ class DeviceImage:
         return cls.from_numpy(np.asarray(img.convert("RGB")), engine)
 
     @classmethod
-    def open(cls, path: str, engine):
+    def open(cls, path: str, engine, device_decode: bool = False):
+        """device_decode: an LZW / PackBits TIFF (tiff_plan) travels compressed and is decoded by the engine (Engine.upload_tiff);
+        every other file, and a file with a defective chunk, is decoded on the host as without the option."""
         from PIL import Image
 
+        if device_decode:
+            plan = tiff_plan(path)
+            if plan is not None:
+                try:
+                    return cls(engine.upload_tiff(plan), engine)
+                except ValueError:   # a defective or old-style chunk (TiffChunkError): the host decodes the file, or raises as it always did
+                    pass
+                except _lib.ZoomEarthError as ex:
+                    if ex.code not in (_lib.ZE_ERR_INVALID, _lib.ZE_ERR_NOMEM):   # a shape the library refuses, no room for the staging
+                        raise
         Image.MAX_IMAGE_PIXELS = None  # 5000-px tiles (src/eval/infer.py:18)
         with Image.open(path) as im:
             return cls.from_pil(im, engine)
@@ -139,6 +153,138 @@ def _raw_rgb_strips(im):
         return None
 
 
+# ---------------------------------------------------------------------------------------------------------------- TIFF decode plan
+TIFF_LZW, TIFF_PACKBITS = 5, 32773
+TIFF_MAX_CHUNK_BYTES = 1 << 20   # what one chunk may store (ZT_MAX_CHUNK_OUT of csrc/ze_tiff_codec.h: 20 bits of offset in the string table)
+_TIFF_ALIGN = 16                 # a chunk starts on a 16-byte boundary of the upload buffer (the bit reader fetches 16 aligned bytes)
+# tags that say nothing about how the pixels are stored (names, resolution, dates, XMP / ICC / GeoTIFF / GDAL metadata); any tag outside
+# this set and the ones tiff_plan reads makes the file one the plan does not understand
+_TIFF_INERT_TAGS = frozenset((269, 270, 271, 272, 282, 283, 285, 296, 305, 306, 315, 316, 700, 33432, 33550, 33922, 34264, 34675, 34735, 34736,
+                              34737, 42112, 42113))
+_TIFF_READ_TAGS = frozenset((254, 256, 257, 258, 259, 262, 266, 273, 274, 277, 278, 279, 284, 317, 322, 323, 324, 325, 339))
+
+
+class TiffChunkError(ValueError):
+    """The device reported a defective chunk (non-zero status words): the tile is decoded on the host instead."""
+
+
+class TiffPlan:
+    """What the device needs to decode one LZW / PackBits RGB TIFF: where every chunk (strip or tile) lies in the file and in the image.
+
+    table: int32 [n_chunks, 8] = {offset in the upload buffer, byte count, x0, y0, w, h of the destination rectangle, stored w,
+    stored h} -- the chunk table of ze_tile_upload_tiff; n_bytes: the size of the upload buffer (a multiple of 16); file_offsets: where
+    read_into finds each chunk in the file.  Edge tiles are stored padded to chunk_w x chunk_h, as TIFF stores them."""
+
+    def __init__(self, path, width, height, compression, predictor, tiled, chunk_w, chunk_h, file_offsets, table, n_bytes):
+        self.path, self.width, self.height = path, int(width), int(height)
+        self.compression, self.predictor, self.tiled = int(compression), int(predictor), bool(tiled)
+        self.chunk_w, self.chunk_h = int(chunk_w), int(chunk_h)
+        self.file_offsets, self.table, self.n_bytes = file_offsets, table, int(n_bytes)
+
+    @property
+    def n_chunks(self) -> int:
+        return int(self.table.shape[0])
+
+    def read_into(self, buf) -> bool:
+        """The compressed chunks into buf (a writable u8 buffer of n_bytes, ideally pinned), each at its table offset; readinto releases
+        the interpreter lock.  False when a chunk turns out to be pre-6.0 LZW (LSB-first codes: libtiff knows it by a first byte of 0
+        and a set low bit in the second), which the device does not decode."""
+        mv = memoryview(buf).cast("B")
+        with open(self.path, "rb", buffering=0) as f:
+            for off, (o, n) in zip(self.file_offsets.tolist(), self.table[:, :2].tolist()):
+                f.seek(off)
+                got = 0
+                while got < n:
+                    k = f.readinto(mv[o + got:o + n])
+                    if not k:
+                        raise OSError(f"{self.path}: truncated image data")
+                    got += k
+                if self.compression == TIFF_LZW and n >= 2 and mv[o] == 0 and (mv[o + 1] & 1):
+                    return False
+        return True
+
+
+def tiff_plan(path: str):
+    """The TiffPlan of an LZW or PackBits 8-bit RGB TIFF, read from its tags through Pillow without decoding a pixel; None for every
+    file the device does not decode -- another compression (none included: decode_rgb reads those strips directly), palette / grey /
+    RGBA / extra samples, 16-bit, planar 2, FillOrder 2, an orientation, old-style LZW, a chunk that stores more than 1 MiB, any tag the
+    plan does not understand, no TIFF at all.  None always means: use decode_rgb as before."""
+    try:
+        from PIL import Image, TiffImagePlugin
+
+        Image.MAX_IMAGE_PIXELS = None
+        with Image.open(path) as im:
+            if not isinstance(im, TiffImagePlugin.TiffImageFile) or getattr(im, "n_frames", 1) != 1:
+                return None
+            tags = dict(im.tag_v2)
+            w, h = im.size
+        if any(t not in _TIFF_READ_TAGS and t not in _TIFF_INERT_TAGS for t in tags):
+            return None
+
+        def one(tag, default):
+            v = tags.get(tag, default)
+            return v[0] if isinstance(v, tuple) and len(v) == 1 else v
+
+        compression, predictor = one(259, 1), one(317, 1)
+        if compression not in (TIFF_LZW, TIFF_PACKBITS) or predictor not in (1, 2):
+            return None
+        if tuple(tags.get(258, ())) != (8, 8, 8) or one(277, 1) != 3 or one(262, None) != 2 or one(284, 1) != 1:
+            return None
+        if one(266, 1) != 1 or one(274, 1) != 1 or one(254, 0) != 0 or tuple(tags.get(339, (1, 1, 1))) != (1, 1, 1):
+            return None
+        if one(256, w) != w or one(257, h) != h or w < 1 or h < 1:
+            return None
+        has_strips, has_tiles = 273 in tags or 279 in tags, any(t in tags for t in (322, 323, 324, 325))
+        if has_strips == has_tiles:
+            return None
+        if has_tiles:
+            tw, th = int(one(322, 0)), int(one(323, 0))
+            if tw < 1 or th < 1:
+                return None
+            across, down = -(-w // tw), -(-h // th)
+            offs, counts = tags.get(324), tags.get(325)
+            rects = [(x * tw, y * th, min(tw, w - x * tw), min(th, h - y * th), tw, th) for y in range(down) for x in range(across)]
+            chunk_w, chunk_h = tw, th
+        else:
+            rps = min(int(one(278, h)), h)
+            if rps < 1:
+                return None
+            offs, counts = tags.get(273), tags.get(279)
+            rects = [(0, y, w, min(rps, h - y), w, min(rps, h - y)) for y in range(0, h, rps)]
+            chunk_w, chunk_h = w, rps
+        if offs is None or counts is None or len(offs) != len(rects) or len(counts) != len(rects):
+            return None
+        if chunk_w * chunk_h * 3 > TIFF_MAX_CHUNK_BYTES or min(counts) < 1 or min(offs) < 8 or max(counts) >= 1 << 30:
+            return None
+        counts = np.asarray(counts, dtype=np.int64)
+        starts = np.zeros(len(rects), dtype=np.int64)
+        padded = (counts + _TIFF_ALIGN - 1) // _TIFF_ALIGN * _TIFF_ALIGN
+        starts[1:] = np.cumsum(padded)[:-1]
+        n_bytes = int(padded.sum())
+        if n_bytes >= 1 << 31:
+            return None
+        table = np.empty((len(rects), 8), dtype=np.int32)
+        table[:, 0], table[:, 1], table[:, 2:] = starts, counts, np.asarray(rects, dtype=np.int32)
+        plan = TiffPlan(path, w, h, compression, predictor, has_tiles, chunk_w, chunk_h, np.asarray(offs, dtype=np.int64), table, n_bytes)
+        if compression == TIFF_LZW:   # the old-style header shows in the first two bytes of a chunk: look at the first one now
+            with open(path, "rb") as f:
+                f.seek(int(offs[0]))
+                head = f.read(2)
+            if len(head) == 2 and head[0] == 0 and (head[1] & 1):
+                return None
+        return plan
+    except Exception:
+        return None
+
+
+class _Compressed:
+    """A tile the worker read but did not decode: its plan and the pooled pinned buffer that holds its chunks."""
+
+    def __init__(self, plan, buf):
+        self.plan, self.buf = plan, buf
+        self._ze_pool_buffer = buf
+
+
 class TilePrefetcher:
     """One tile decode per TILE instead of two per QUESTION, and off the GPU's critical path.
 
@@ -153,9 +299,12 @@ class TilePrefetcher:
         for q in questions: tile = pf.get(q.path)
     """
 
-    def __init__(self, paths, engine, decode=decode_rgb, pin: bool = True, depth: int = 1, workers: int = 1):
+    def __init__(self, paths, engine, decode=decode_rgb, pin: bool = True, depth: int = 1, workers: int = 1, device_decode: bool = False):
         """depth: decoded tiles held ahead of the one in use (75 MB of pinned memory each at 5000 px); workers: decode
-        threads (a stream that answers 50 questions/s needs ~5 tiles/s: more than one core's worth of TIFF / PNG decode)."""
+        threads (a stream that answers 50 questions/s needs ~5 tiles/s: more than one core's worth of TIFF / PNG decode).
+        device_decode: a tile that has a tiff_plan (LZW / PackBits RGB TIFF) is only READ by the worker -- its compressed chunks, into a
+        pooled pinned buffer -- and get() has the device decode it (ze_tile_upload_tiff); a tile without a plan, or one whose status
+        words name a defect, is decoded by `decode` as without the option and counted in `fallbacks`."""
         import threading
 
         self._engine = engine
@@ -176,7 +325,11 @@ class TilePrefetcher:
         self._in_copy = []        # (event, pinned buffer) of uploads that may still be running
         self._pinned = []         # free pinned staging buffers, reused tile after tile (hipHostMalloc of 75 MB per tile costs
         #                           more than the decode itself and serialises with the GPU's work)
+        self._device_decode = bool(device_decode)
+        self._copy_stream = None
         self.decodes = 0
+        self.device_decodes = 0   # tiles the device decoded
+        self.fallbacks = 0        # tiles of a device_decode prefetcher that the host decoded after all (no plan, or a defective chunk)
         self.decode_s = 0.0       # seconds spent inside the decoder (all threads)
         self.wait_s = 0.0         # seconds get() waited for a tile that was not ready
         self._kick()
@@ -194,9 +347,8 @@ class TilePrefetcher:
                 self._busy += 1
                 threading.Thread(target=self._work, args=(path,), daemon=True).start()
 
-    def _to_pinned(self, arr):
-        """The decoded tile in a pinned buffer of the pool (allocated on first use, recycled by get() once uploaded)."""
-        n = int(arr.size)
+    def _take_pinned(self, n: int):
+        """A pinned buffer of the pool that holds n bytes (allocated on first use, recycled by get() once uploaded)."""
         buf = None
         with self._cv:
             for i, b in enumerate(self._pinned):
@@ -205,18 +357,48 @@ class TilePrefetcher:
                     break
         if buf is None:
             buf = torch.empty(n, dtype=torch.uint8).pin_memory()
+        return buf
+
+    def _to_pinned(self, arr):
+        """The decoded tile in a pinned buffer of the pool."""
+        n = int(arr.size)
+        buf = self._take_pinned(n)
         view = buf[:n].view(arr.shape)
         view.numpy()[...] = arr
         view._ze_pool_buffer = buf
         return view
 
+    def _read_compressed(self, path):
+        """The tile's compressed chunks in a pinned buffer, or None when it has no plan (the host decodes it)."""
+        plan = tiff_plan(path)
+        if plan is None:
+            return None
+        buf = self._take_pinned(plan.n_bytes)
+        ok = False
+        try:
+            ok = plan.read_into(buf[:plan.n_bytes].numpy())
+        finally:
+            if not ok:
+                with self._cv:
+                    self._pinned.append(buf)
+        return _Compressed(plan, buf) if ok else None
+
+    def _host_decode(self, path):
+        arr = self._decode(path)
+        if self._pin and torch.cuda.is_available():
+            arr = self._to_pinned(arr)
+        return arr
+
     def _work(self, path):
         import time
         t0 = time.perf_counter()
         try:
-            arr = self._decode(path)
-            if self._pin and torch.cuda.is_available():
-                arr = self._to_pinned(arr)
+            arr = self._read_compressed(path) if self._device_decode else None
+            if arr is None:
+                if self._device_decode:
+                    with self._cv:
+                        self.fallbacks += 1
+                arr = self._host_decode(path)
         except Exception as ex:  # surfaced by get()
             arr = ex
         with self._cv:
@@ -263,12 +445,49 @@ class TilePrefetcher:
                 self._cv.wait(timeout=0.05)
             arr = self._ready.pop(path, None)
         if arr is None:  # out-of-order request: decode here
-            arr = self._decode(path)
+            arr = self._read_compressed(path) if self._device_decode else None
+            if arr is None:
+                self.fallbacks += int(self._device_decode)
+                arr = self._decode(path)
             self.decodes += 1
         self.wait_s += time.perf_counter() - t0
         if isinstance(arr, Exception):
             self._kick()
             raise arr
+        if isinstance(arr, _Compressed):
+            # the compressed chunks go up and the device decodes them; the status words come back where the upload is waited for
+            # -- on a copy stream of the prefetcher's own, so that the wait is for this tile alone and not for the chains' queued steps
+            if self._copy_stream is None:
+                self._copy_stream = torch.cuda.Stream(self._engine.device)
+            try:
+                with torch.cuda.stream(self._copy_stream):
+                    dev, status = self._engine.tile_upload_tiff(arr.plan, arr.buf)
+                    bad = bool(status.any().item())   # (waits for the copy and the kernels on the copy stream)
+                dev.record_stream(torch.cuda.current_stream(self._engine.device))   # the caller's stream reads it from here on
+            except _lib.ZoomEarthError as ex:
+                if ex.code not in (_lib.ZE_ERR_INVALID, _lib.ZE_ERR_NOMEM):
+                    self._kick()
+                    raise
+                bad = True   # a shape the library refuses, no room for the staging: the host decodes this tile
+            except Exception:
+                self._kick()
+                raise
+            finally:   # the copy has run (or was never issued): the staging buffer goes back to the pool on every way out
+                with self._cv:
+                    self._pinned.append(arr.buf)
+            if bad:  # a defective chunk: the host decodes the tile as it would have without the option, or raises as it would have
+                self.fallbacks += 1
+                try:
+                    arr = self._decode(path)
+                except Exception:
+                    self._kick()
+                    raise
+            else:
+                self.device_decodes += 1
+                img = DeviceImage(dev, self._engine)
+                self._current = (path, img)
+                self._kick()
+                return img
         t = arr if isinstance(arr, torch.Tensor) else torch.from_numpy(arr)
         dev = t.to(self._engine.device, non_blocking=True)
         buf = getattr(t, "_ze_pool_buffer", None)
